@@ -15,7 +15,14 @@ A step = one pass of the hot path over the band, inputs resident in HBM.
 Algorithmic bytes per step = 4*nchan*nif*ntime read + 4*(nchan/F)*nif*(ntime/T)
 written, summed over banks.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3]
+A plain run sets up, warms up, times the K steps and prints the result line
+(metric, value, ms_per_step, ...).  --full adds every other figure and check
+of the line, each in passes of its own after the timed steps: the per-launch
+kernel time and the warm-cache figure, the integer-data self-check
+("verified"), the pure-read probe and the CPU baseline.  --dump-outputs DIR
+writes what the last timed step returned (the stitched band) to DIR/band.npy.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (N > 1)
     python bench.py --gpus N ...   (N > 1, no launcher: bench.py starts the N
                                     rank processes itself, see spawn_ranks)
@@ -171,6 +178,36 @@ def cpu_baseline(cfg, seconds, eng, torch):
                                f"{info['host_nproc']} host CPUs), {reps_all} passes in "
                                f"{el_all:.1f} s"}},
                 **info)
+
+
+DUMP_MAX_BYTES = 32 << 20  # --dump-outputs: whole outputs up to this much in all (limit: 64 MB)
+DUMP_SAMPLE_SEED = 20240229
+
+
+def dump_outputs(dirname, outputs, torch):
+    """--dump-outputs: each device tensor of ``outputs`` (name -> Julia-order
+    (c, i, t) tensor) as DIR/<name>.npy, Float32 (Float64 stays Float64), in
+    the tensor's own shape.  Outputs that together pass DUMP_MAX_BYTES are
+    written as 1-D samples instead: the same seeded draw of flat positions
+    (storage order, channel fastest) on every run, each output its equal share
+    of the budget."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(t.numel() * (8 if t.dtype == torch.float64 else 4) for t in outputs.values())
+    share = DUMP_MAX_BYTES // max(1, len(outputs))
+    for name, t in outputs.items():
+        keep = torch.float64 if t.dtype == torch.float64 else torch.float32
+        if total <= DUMP_MAX_BYTES:
+            c = t.permute(*reversed(range(t.dim()))).contiguous().to(keep).cpu().numpy()
+            a = c.transpose(*reversed(range(c.ndim)))  # back to (c, i, t)
+        else:
+            n = t.numel()
+            k = min(n, share // (8 if keep == torch.float64 else 4))
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, n, k))
+            flat = t.permute(*reversed(range(t.dim()))).reshape(-1)
+            a = flat[torch.from_numpy(idx).to(t.device)].to(keep).cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def pairwise_leaves(n):
@@ -793,7 +830,17 @@ def main():
                          "(e.g. hung in a collective) are stopped and bench.py exits 124")
     ap.add_argument("--no-verify", action="store_true",
                     help="skip the integer-data check of one step after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the passes behind the line's other "
+                         "figures: the per-launch kernel time and the warm-cache launches, the "
+                         "integer-data self-check, the pure-read probe and the CPU baseline "
+                         "(--no-verify, --no-read-probe and --no-cpu-baseline drop one each)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (the stitched band) to "
+                         "DIR/band.npy, Float32; an output over 32 MiB as a fixed seeded sample")
     args = ap.parse_args()
+    if args.dump_outputs and args.mode != "reduce":
+        raise SystemExit("--dump-outputs writes the band of --mode reduce")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher: this process only starts the N ranks (no torch, no HIP here)
         sys.exit(spawn_ranks(args.gpus, args.rank_deadline))
@@ -974,7 +1021,7 @@ def main():
     # kernel trace reports).
     HipEvent = pkg._lib.HipEvent
     evs = [(HipEvent(timing=True, fence=False), HipEvent(timing=True, fence=False))
-           for _ in range(args.steps)]
+           for _ in range(args.steps if args.full else 0)]
     sp0, sp1, sx0, sx1 = (HipEvent(timing=True, fence=False) for _ in range(4))
     K = args.steps
     if world > 1:
@@ -984,13 +1031,13 @@ def main():
     for k in range(K):
         c = k % ncopy
         if K == 1:
-            step(sp0, sp1, copy=c)
+            last = step(sp0, sp1, copy=c)
         elif k == 0:
-            step(sp0, sx1, copy=c)
+            last = step(sp0, sx1, copy=c)
         elif k == K - 1:
-            step(sx0, sp1, copy=c)
+            last = step(sx0, sp1, copy=c)
         else:
-            step(copy=c)
+            last = step(copy=c)
     host_ms = (time.perf_counter() - t0) * 1e3 / K  # enqueue cost per step
     if pipe:
         pipe.drain()
@@ -999,14 +1046,20 @@ def main():
         dist.barrier()
     el = time.perf_counter() - t0
     span_ms = sp0.elapsed_time(sp1) / K  # first kernel's start to last one's end, per launch
-    for k in range(K):  # the kernel pass
-        step(*evs[k], copy=(K + k) % ncopy)
-    if pipe:
-        pipe.drain()
-    torch.cuda.synchronize()
-    kern_ms = sum(a.elapsed_time(b) for a, b in evs) / K
-    warm_ms = kern_ms
-    if ncopy > 1:  # the same K launches on one copy: the warm (cache-resident) figure
+    if args.dump_outputs and rank == 0:  # the last timed step's band, before any later pass
+        dump_outputs(args.dump_outputs, {"band": last}, torch)
+    del last
+    # a plain run stops measuring here: its launch time is the timed steps' span
+    kern_ms = warm_ms = span_ms
+    if args.full:  # the kernel pass
+        for k in range(K):
+            step(*evs[k], copy=(K + k) % ncopy)
+        if pipe:
+            pipe.drain()
+        torch.cuda.synchronize()
+        kern_ms = sum(a.elapsed_time(b) for a, b in evs) / K
+        warm_ms = kern_ms
+    if args.full and ncopy > 1:  # the same K launches on one copy: the warm (cached) figure
         for k in range(K):
             step(*evs[k], copy=0)
         if pipe:
@@ -1019,7 +1072,7 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el, kern_ms, span_ms, warm_ms = float(t[0]), float(t[1]), float(t[2]), float(t[3])
     verified, verify_detail = None, None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         def one_step():
             res = step(copy=0)
             if pipe:
@@ -1056,7 +1109,7 @@ def main():
         # differ box to box by several percent, so the reduce is also set
         # beside what a kernel that only reads reaches on the same GPU
         probe = None
-        if not args.no_read_probe:
+        if args.full and not args.no_read_probe:
             preps.clear()
             torch.cuda.empty_cache()
             sys.path.insert(0, os.path.join(REPO, "tools"))
@@ -1064,7 +1117,7 @@ def main():
 
             probe = hbm_probe.read_probe(bytes_launch, stream=stream, pkg=pkg, copies=ncopy)
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             preps.clear()  # (they hold the banks)
             del banks, copies
             torch.cuda.empty_cache()
@@ -1086,15 +1139,17 @@ def main():
                          "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                          "traffic": traffic, "traffic_source": traffic_src,
                          "kernel": kernel_name,
-                         "kernel_ms": round(kern_ms, 4),
+                         "kernel_ms": round(kern_ms, 4) if args.full else None,
                          "kernel_ms_source": "per-launch dispatch events over K launches after "
-                                             "the timed region",
+                                             "the timed region" if args.full else
+                                             "not measured without --full: achieved and frac "
+                                             "are from span_ms_per_launch",
                          "span_ms_per_launch": round(span_ms, 4),
                          "bytes_per_launch": bytes_launch,
                          "box_read_probe": probe,
                          "frac_of_box_read": probe and round(achieved / probe["GBps"], 4),
                          "cache": cache_note(ncopy, bytes_launch),
-                         "warm": None if ncopy == 1 else {
+                         "warm": None if ncopy == 1 or not args.full else {
                              "kernel_ms": round(warm_ms, 4),
                              "achieved": round(bytes_launch / (warm_ms * 1e-3) / 1e9, 1),
                              "frac": round(bytes_launch / (warm_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,

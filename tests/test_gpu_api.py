@@ -546,7 +546,8 @@ def test_bench_pipeline_flag():
     from conftest import REPO
 
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3",
-                        "--warmup", "1", "--config", "cfg2", "--pipeline", "--no-cpu-baseline"],
+                        "--warmup", "1", "--config", "cfg2", "--pipeline", "--full",
+                        "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=300, cwd=REPO)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -912,8 +913,9 @@ def test_prepared_reduce_and_timed_launch(pkg, orc, F, T, nbank):
 
 
 def test_bench_json_contract():
-    """bench.py prints one JSON line with the keys the driver reads (a short
-    cfg1 run; the default cfg3 run is the round-end bench)."""
+    """bench.py --full prints one JSON line with the keys the driver reads and
+    every figure measured after the timed steps (a short cfg1 run; the default
+    cfg3 run is the round-end bench)."""
     import json
     import subprocess
     import sys
@@ -921,7 +923,7 @@ def test_bench_json_contract():
     from conftest import REPO
 
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3",
-                        "--warmup", "1", "--config", "cfg1", "--cpu-seconds", "0.5"],
+                        "--warmup", "1", "--config", "cfg1", "--cpu-seconds", "0.5", "--full"],
                        capture_output=True, text=True, timeout=300, cwd=REPO)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -950,6 +952,44 @@ def test_bench_json_contract():
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["value"] > 0 and cb["cores"] >= 1
     assert "workload" in d["config"]
+
+
+def test_bench_plain_run_dumps_its_band(pkg, tmp_path):
+    """bench.py without --full: the timed steps and the line only (no kernel
+    pass, self-check, read probe or CPU baseline), --steps timed steps, and
+    --dump-outputs writes the last timed step's band as Float32, bit for bit
+    the band reduce of the same synthetic bank."""
+    import json
+    import subprocess
+    import sys
+
+    from conftest import REPO
+
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps",
+                        "4", "--warmup", "1", "--config", "cfg1", "--dump-outputs",
+                        str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=300, cwd=REPO)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["n_gpus"] == 1
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "GB/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["value"] == pytest.approx(d["config"]["bytes_per_step"] / d["ms_per_step"] / 1e6,
+                                       rel=1e-2)
+    rf = d["roofline"]
+    assert rf["kernel_ms"] is None and rf["box_read_probe"] is None and rf["warm"] is None
+    assert rf["span_ms_per_launch"] > 0 and rf["frac"] > 0
+    assert d["cpu_baseline"] is None and d["verified"] is None
+    assert os.listdir(tmp_path / "out") == ["band.npy"]
+    got = np.load(tmp_path / "out" / "band.npy")
+    eng = pkg.engine
+    bank = eng.synth(65536, 1, 279, 1024, seed=2, kind=0)  # cfg1: bank 0 of product 0002
+    win = [0, 65536, 1, 0, 1, 1, 0, 272, 1]  # idxs=(:, :, 1:272)
+    want = eng.fb_to_numpy(eng.band_reduce([bank], 64, 16, "sum", win))
+    assert got.dtype == np.float32 and got.shape == (1024, 1, 17)
+    assert same_bits(got, want)
 
 
 def test_unfiltered_chunked_fbh5_on_gpu(pkg, orc, tmp_path):

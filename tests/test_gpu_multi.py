@@ -194,7 +194,7 @@ def test_getband_banks_on_several_gpus(pkg, orc, tmp_path, monkeypatch, peer_sto
 
 
 def test_bench_verifies_its_multi_gpu_band():
-    """bench.py --gpus N (N = 2, 4 or 8; ranks started by bench.py itself, one
+    """bench.py --gpus N --full (N = 2, 4 or 8; ranks started by bench.py itself, one
     RCCL rank per GPU) prints one line whose stitched band it checked bit for
     bit on integer data after the timed region ("verified": true)."""
     _need_gpus(2)
@@ -207,7 +207,7 @@ def test_bench_verifies_its_multi_gpu_band():
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     for cfg in ("cfg2", "cfg3"):
         r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(world),
-                            "--config", cfg, "--steps", "3", "--warmup", "1",
+                            "--config", cfg, "--steps", "3", "--warmup", "1", "--full",
                             "--no-cpu-baseline", "--no-read-probe", "--rank-deadline", "400"],
                            capture_output=True, text=True, timeout=480, env=env)
         assert r.returncode == 0, (cfg, r.returncode, r.stderr[-3000:])

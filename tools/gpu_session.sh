@@ -30,7 +30,7 @@ for s in $STEPS; do
   case $s in
     smoke) run smoke 300 python -c "import __graft_entry__ as e; e.smoke()" ;;
     tests) run tests 900 python -u -m pytest tests -m gpu -x -q -p no:cacheprovider --timeout 300 --timeout-method thread ;;
-    bench) run bench 600 python bench.py ;;
+    bench) run bench 600 python bench.py --full ;;
     prof)  run prof 600 rocprofv3 --kernel-trace --stats --output-format csv \
              -d "$OUT/prof" -o run -- python bench.py --steps 10 --warmup 3 --no-cpu-baseline ;;
     pmc)   run pmc_fetch 600 rocprofv3 --pmc FETCH_SIZE --output-format csv \
@@ -42,10 +42,10 @@ for s in $STEPS; do
              -d "$OUT/pmc_fetch_lb$K" -o run -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --local-banks "$K"
            run "pmc_write_lb$K" 300 rocprofv3 --pmc WRITE_SIZE --output-format csv \
              -d "$OUT/pmc_write_lb$K" -o run -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --local-banks "$K" ;;
-    benchlb_*) run "$s" 300 python bench.py --no-cpu-baseline --local-banks "${s#benchlb_}" ;;
-    bench_*) run "$s" 600 python bench.py --config "${s#bench_}" ;;
-    benchperbank) run benchperbank 600 python bench.py --band-alloc per-bank --no-cpu-baseline ;;
-    benchnocpu) run benchnocpu 600 python bench.py --no-cpu-baseline ;;
+    benchlb_*) run "$s" 300 python bench.py --full --no-cpu-baseline --local-banks "${s#benchlb_}" ;;
+    bench_*) run "$s" 600 python bench.py --full --config "${s#bench_}" ;;
+    benchperbank) run benchperbank 600 python bench.py --full --band-alloc per-bank --no-cpu-baseline ;;
+    benchnocpu) run benchnocpu 600 python bench.py --full --no-cpu-baseline ;;
     kurt_*) run "$s" 600 python bench.py --mode kurtosis --config "${s#kurt_}" ;;
     host)  run host 900 python bench.py --mode host ;;
     host2) run host2 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
@@ -80,16 +80,16 @@ for s in $STEPS; do
              -d "$OUT/pmc_write_kurt_$C" -o run -- python bench.py --mode kurtosis --config "$C" --steps 5 --warmup 2 ;;
     dist2) run dist2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
              --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 2 --dist-backend gloo \
-             --steps 10 --warmup 3 ;;
+             --steps 10 --warmup 3 --full ;;
     dist4|dist8) run "$s" 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node "${s#dist}" \
              --master-addr 127.0.0.1 --master-port 29613 bench.py --gpus "${s#dist}" --dist-backend gloo \
-             --steps 10 --warmup 3 ;;
+             --steps 10 --warmup 3 --full ;;
     dist2c2) run dist2c2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
              --master-addr 127.0.0.1 --master-port 29612 bench.py --gpus 2 --dist-backend gloo \
-             --steps 10 --warmup 3 --config cfg2 ;;
+             --steps 10 --warmup 3 --config cfg2 --full ;;
     unal_check) run unal_check 300 python tools/unaligned_check.py --variant "${UNAL_VARIANT:-unal2}" ;;
     nmix)  run nmix 300 ./build/hbm_ceiling 32 10 bldistributeddataproducts.jl_amd/libbldp_hip.so nmix ;;  # (built here: hipcc -o build/hbm_ceiling tools/hbm_ceiling.hip -ldl)
-    pipeline) run pipeline 600 python bench.py --pipeline --no-cpu-baseline ;;
+    pipeline) run pipeline 600 python bench.py --full --pipeline --no-cpu-baseline ;;
     prof_pipelb_*) run "$s" 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/$s" -o run \
              -- python bench.py --pipeline --no-cpu-baseline --local-banks "${s#prof_pipelb_}" --steps 20 --warmup 5 ;;
     stream_probe) run stream_probe 300 python tools/stream_probe.py ;;
@@ -98,7 +98,7 @@ for s in $STEPS; do
              -- python bench.py --pipeline --no-cpu-baseline --local-banks 1 --steps 20 --warmup 5 ;;
     prof_stream_probe) run prof_stream_probe 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/$s" -o run \
              -- python tools/stream_probe.py --steps 20 --warmup 5 ;;
-    pipelb_*) run "$s" 300 python bench.py --pipeline --no-cpu-baseline --local-banks "${s#pipelb_}" --steps 50 --warmup 10 ;;
+    pipelb_*) run "$s" 300 python bench.py --full --pipeline --no-cpu-baseline --local-banks "${s#pipelb_}" --steps 50 --warmup 10 ;;
     ab)    run ab 900 python tools/ab_variants.py --run --variants "${AB_VARIANTS:-base,noil}" --json "$OUT/ab.json" ;;
     ab_kurt) run ab_kurt 900 python tools/ab_variants.py --run --suite kurt --variants ${AB_VARIANTS:-base,kold,kw5,kw6} --json "$OUT/ab_kurt.json" ;;
     ab_kleaf) run ab_kleaf 600 python tools/ab_variants.py --run --suite kleaf --variants "${AB_VARIANTS:-base,kleafb2,kleafpipe2,kleafpipe2w5}" --json "$OUT/ab_kleaf.json" ;;
