@@ -14,9 +14,13 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG_DIR, "libbldp_hip.so")
 CSRC = os.path.join(PKG_DIR, "csrc")
 
-OPS = {"sum": 0, "mean": 1, "max": 2, "min": 3}
+OPS = {"sum": 0, "mean": 1, "max": 2, "min": 3, "var": 4, "std": 5, "median": 6}
+# Statistics' var (corrected) / std / median over the fqavby channels of a
+# block: Float32 on the GPU, no time integration
+STAT_OPS = ("var", "std", "median")
 PATHS = {0: "vector", 1: "narrow", 2: "scalar", 3: "tile", 4: "interleaved", 5: "row",
-         6: "narrow_mis", 7: "lane"}
+         6: "narrow_mis", 7: "lane", 8: "moments", 9: "median_sort", 10: "median_select",
+         11: "median_stream"}
 KURT_PATHS = {0: "regs", 1: "mid", 2: "leaf", 3: "twopass"}
 
 BLDP_OK, BLDP_EINVAL, BLDP_EDIM, BLDP_EHIP, BLDP_ENOMEM, BLDP_EBOUNDS = 0, -1, -2, -3, -5, -6

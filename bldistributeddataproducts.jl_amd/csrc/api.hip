@@ -286,7 +286,8 @@ bool unaligned_vec_pays(int64_t F, bool rows16) {
   return F == 1 || (F % 4 == 0 && F <= 256);
 }
 
-int valid_op(int op) { return op >= BLDP_OP_SUM && op <= BLDP_OP_MIN; }
+int valid_op(int op) { return op >= BLDP_OP_SUM && op <= BLDP_OP_MEDIAN; }
+#define BLDP_OP_NAMES "0=sum 1=mean 2=max 3=min 4=var 5=std 6=median"
 
 // Checks, window and plan of a reduce (shared by every reduce entry point and
 // by the prepared form): fills *a and *p; *empty when there is nothing to do.
@@ -296,7 +297,12 @@ int prepare_reduce(int nbank, const float *const *in, int64_t nchan, int64_t nif
                    bool query, RedArgs *ap, Plan *pp, bool *empty) {
   if (nbank < 1 || nbank > BLDP_MAX_BANKS)
     return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
-  if (!valid_op(op)) return fail(BLDP_EINVAL, "unknown op %d (0=sum 1=mean 2=max 3=min)", op);
+  if (!valid_op(op)) return fail(BLDP_EINVAL, "unknown op %d (" BLDP_OP_NAMES ")", op);
+  // Statistics' var / std / median reduce the channel blocks only: fqav on the
+  // time axis after them would not be the statistic of the F x T block
+  if (stat_op(op) && tavby > 1)
+    return fail(BLDP_EINVAL, "tavby=%lld: var/std/median have no time integration (tavby <= 1)",
+                (long long)tavby);
   Geo g;
   int rc = resolve_window(nchan, nif, ntime, win, &g);
   if (rc) return rc;
@@ -336,8 +342,13 @@ int prepare_reduce(int nbank, const float *const *in, int64_t nchan, int64_t nif
   const bool aligned = (rows16 && vec_ok(g)) ||
                        (opt(OPT_UNALIGNED_VEC) >= 1 && words && g.cs == 1 &&
                         unaligned_vec_pays(F, rows16));
-  *pp = plan_reduce(a, aligned, rows16, words && g.cs == 1, num_cus_current(),
-                    xcd_log2_current());
+  if (stat_op(op)) {
+    rc = plan_stats(a, op, words && g.cs == 1, xcd_log2_current(), pp);
+    if (rc) return rc;
+  } else {
+    *pp = plan_reduce(a, aligned, rows16, words && g.cs == 1, num_cus_current(),
+                      xcd_log2_current());
+  }
   if (!query) {
     for (int b = 0; b < nbank; ++b)
       if (!in[b] && !*empty) return fail(BLDP_EINVAL, "null input pointer (bank %d)", b);
@@ -354,7 +365,7 @@ int run_reduce(RedArgs a, const Plan &p, int op, hipStream_t s) {
     if (rc) return rc;
     a.ws = (float *)lease.ptr;
   }
-  hipError_t e = launch_reduce(a, p, op, s);
+  hipError_t e = stat_op(op) ? launch_stats(a, p, op, s) : launch_reduce(a, p, op, s);
   if (e != hipSuccess) return fail(BLDP_EHIP, "reduce launch: %s", hipGetErrorString(e));
   return BLDP_OK;
 }
@@ -611,6 +622,9 @@ int bldp_band_reduce_multi_f32(int nbank, const int *bank_dev, const float *cons
                                unsigned flags) {
   if (nbank < 1 || nbank > BLDP_MAX_BANKS || !bank_dev || !in)
     return fail(BLDP_EINVAL, "bad bank arguments");
+  if (stat_op(op))
+    return fail(BLDP_EINVAL, "var/std/median (op %d) run on one device: reduce each device's "
+                             "banks with bldp_band_reduce_f32", op);
   if (flags & ~(BLDP_BAND_STAGED | BLDP_BAND_PEER_STORE))
     return fail(BLDP_EINVAL, "unknown flags 0x%x", flags);
   if ((flags & BLDP_BAND_STAGED) && (flags & BLDP_BAND_PEER_STORE))
@@ -881,7 +895,9 @@ int typed_reduce_args(int dtype, const void *in, int64_t nchan, int64_t nif, int
                       const int64_t *win, int64_t fqavby, int64_t tavby, int op, void *out,
                       int64_t out_ld_i, int64_t out_ld_t, TypedArgs *ap, bool *empty) {
   if (!dtype_size(dtype)) return fail(BLDP_EINVAL, "unknown element type %d", dtype);
-  if (!valid_op(op)) return fail(BLDP_EINVAL, "unknown op %d (0=sum 1=mean 2=max 3=min)", op);
+  if (!valid_op(op)) return fail(BLDP_EINVAL, "unknown op %d (" BLDP_OP_NAMES ")", op);
+  if (stat_op(op))
+    return fail(BLDP_EINVAL, "median/var/std take Float32 on the GPU (element type %d)", dtype);
   Geo g;
   int rc = resolve_window(nchan, nif, ntime, win, &g);
   if (rc) return rc;

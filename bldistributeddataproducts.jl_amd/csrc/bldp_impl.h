@@ -106,11 +106,16 @@ void plan_opt_domain(int k, int64_t *lo, int64_t *hi);
 void plan_opt_set(int k, int64_t v);
 
 enum Path { PATH_VEC = 0, PATH_NARROW = 1, PATH_SCALAR = 2, PATH_TILE = 3, PATH_VEC_IL = 4,
-            PATH_VEC_ROW = 5, PATH_NARROW_MIS = 6, PATH_LANE = 7 };
+            PATH_VEC_ROW = 5, PATH_NARROW_MIS = 6, PATH_LANE = 7,
+            // median / var / std (stats.hip): the moments kernels, the bitonic
+            // sort of blocks of <= 64, the radix select with the block's keys in
+            // registers, and the radix select that re-reads the block every pass
+            PATH_MOMENTS = 8, PATH_MEDIAN_SORT = 9, PATH_MEDIAN_SELECT = 10,
+            PATH_MEDIAN_STREAM = 11 };
 
 struct Plan {
   int path;
-  int lpg;                   // lanes per output group (vector path)
+  int lpg;                   // lanes per output group (vector path; stats.hip: 256 = a workgroup)
   bool lanet;                // lane path: k_reduce_lanet (NRW rows per lane) not k_reduce_lane
   bool col3;                 // lane path at fqavby = 12: k_reduce_col3 (float4 columns)
   int64_t grid;             // blocks of 256 threads
@@ -130,6 +135,25 @@ Plan plan_reduce(RedArgs &a, bool aligned, bool rows16, bool words, int num_cus,
 hipError_t launch_reduce(const RedArgs &a, const Plan &p, int op, hipStream_t s);
 // events the next launch_reduce's dispatches carry (null, null: none)
 void set_launch_events(hipEvent_t start, hipEvent_t stop);
+// those events, for a launch outside kernels.hip that carries both on one dispatch
+void take_launch_events(hipEvent_t *start, hipEvent_t *stop);
+
+// Workgroup x of a launch of X in the per-XCD contiguous order over 2^lg
+// XCDs: x runs on XCD x % 2^lg and takes tile (x % 2^lg) * (X / 2^lg) +
+// x / 2^lg.  lg = 0 (the plan's "no"), or a grid 2^lg does not divide: x.
+__device__ __forceinline__ uint32_t xcd_order(uint32_t x, uint32_t X, int lg) {
+  const uint32_t m = (1u << lg) - 1u;
+  if (lg == 0 || (X & m)) return x;
+  return (x & m) * (X >> lg) + (x >> lg);
+}
+
+// median / var / std of the F channels of every block (stats.hip); T = 1.
+// plan_stats fills the launch geometry like plan_reduce (`words`: the channel
+// step is 1 and every bank pointer is dword-aligned) and returns BLDP_OK or,
+// with the message recorded, BLDP_EINVAL for a launch too large for one grid.
+inline bool stat_op(int op) { return op >= BLDP_OP_VAR && op <= BLDP_OP_MEDIAN; }
+int plan_stats(RedArgs &a, int op, bool words, int xcd_lg, Plan *p);
+hipError_t launch_stats(const RedArgs &a, const Plan &p, int op, hipStream_t s);
 
 hipError_t launch_stitch(int nbank, const float *g, int64_t nc, int64_t nrows, float *out,
                          hipStream_t s);

@@ -204,14 +204,7 @@ constexpr int64_t kRowXcdMinPitch = (int64_t)4 << 20;
 constexpr int64_t kIlXcdMaxPitch = (int64_t)128 << 20;
 constexpr int64_t kRowtXcdBytes = (int64_t)1 << 30;
 
-// Workgroup x of a launch of X in the per-XCD contiguous order over 2^lg
-// XCDs: x runs on XCD x % 2^lg and takes tile (x % 2^lg) * (X / 2^lg) +
-// x / 2^lg.  lg = 0 (the plan's "no"), or a grid 2^lg does not divide: x.
-__device__ __forceinline__ uint32_t xcd_order(uint32_t x, uint32_t X, int lg) {
-  const uint32_t m = (1u << lg) - 1u;
-  if (lg == 0 || (X & m)) return x;
-  return (x & m) * (X >> lg) + (x >> lg);
-}
+// (xcd_order itself: bldp_impl.h, shared with stats.hip)
 
 // The short-time-block kernels (k_reduce_rowt, k_reduce_narrowt,
 // k_reduce_lanet) also take tavby = 3 and 8, not only 1, 2, 4 (plan option
@@ -2378,6 +2371,12 @@ Plan plan_reduce(RedArgs &a, bool aligned, bool rows16, bool words, int num_cus,
 void set_launch_events(hipEvent_t start, hipEvent_t stop) {
   t_ev_start = start;
   t_ev_stop = stop;
+}
+
+void take_launch_events(hipEvent_t *start, hipEvent_t *stop) {
+  *start = t_ev_start;
+  *stop = t_ev_stop;
+  t_ev_start = nullptr;
 }
 
 hipError_t launch_reduce(const RedArgs &a, const Plan &p, int op, hipStream_t s) {

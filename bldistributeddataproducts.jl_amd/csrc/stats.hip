@@ -1,0 +1,527 @@
+// stats.hip — fqavfunc median, var and std of Float32 windows (gfx950).
+//
+// Julia's Statistics applied as f(reshape(A, (F, :, ...)); dims=1): one result
+// per block of F channels (c' F .. c' F + F - 1) of every (IF, spectrum) row.
+// No time integration (T = 1).  The window geometry is the reduce's
+// (RedArgs: any channel offset, step and direction, IF and time steps);
+// unit-step windows whose F is a multiple of 4 load float4 (16 bytes per
+// lane, at any dword alignment: f4u), the others one dword per element.
+//
+//   var / std  k_mom_lanes (F <= 1024): the 1 .. 64 lanes of a wave that share
+//              a block hold it in registers (<= 16 values per lane), the
+//              partial sums meet by xor-shuffles, then the squared deviations
+//              about the mean.  k_mom_block (F > 1024): one workgroup per
+//              block, in registers up to 4096 values, else read twice (the
+//              second read hits L2: a block is <= 256 KiB at the 0002
+//              products' F = 65536); waves meet through LDS.
+//              The mean is taken as K + sum(x - K) / F with K the block's
+//              first element: a constant block then has mean == its value and
+//              the result is exactly 0.0 whatever F does to a rounded sum, and
+//              the sum of the differences keeps more bits than the sum.
+//   median     keys are the order-preserving uint32 image of the float
+//              (isless order: -0.0 < 0.0, -Inf lowest, +Inf highest), NaN is
+//              found apart and wins.
+//              k_median_sort (F <= 64): next_pow2(F) / 4 lanes hold 4 keys
+//              each and run a bitonic network, the exchanges at distance < 4
+//              in registers and the others by xor-shuffles; missing elements
+//              are the maximal key.
+//              k_median_select (F > 64): one workgroup per block, an MSB-first
+//              radix select, 8 bits a pass, of rank (F-1)/2 and rank F/2 in
+//              the same four passes: the two ranks share a 256-bin LDS
+//              histogram while their prefixes agree and take one each after.
+//              Four passes fix all 32 bits, so ties need nothing special.
+//              Keys stay in registers up to 4096 (PATH_MEDIAN_SELECT), else
+//              every pass reads the block again (PATH_MEDIAN_STREAM).
+#include <hip/hip_ext.h>
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "bldp_impl.h"
+
+namespace bldp {
+namespace {
+
+constexpr int kBlock = 256;  // 4 waves of 64
+// a float4 on any dword boundary (kernels.hip f4u)
+typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
+
+constexpr int64_t kLaneMaxF = 1024;  // k_mom_lanes: 64 lanes x 16 values
+constexpr int64_t kRegMaxF = 4096;   // a workgroup's registers: 256 lanes x 16 values
+constexpr int64_t kSortMaxF = 64;    // k_median_sort
+
+__device__ __forceinline__ float4 ld4(const float *p) {
+  const f4u v = *reinterpret_cast<const f4u *>(p);
+  return make_float4(v.x, v.y, v.z, v.w);
+}
+
+// q = x / d, r = x % d for x >= 0 and a wave-uniform d > 0: a shift for a power
+// of two (the products' channel counts and fqavby, nif = 1), else 32-bit
+// division where both fit (a 64-bit one is ~100 instructions a lane).
+__device__ __forceinline__ void divmod(int64_t x, int64_t d, int64_t &q, int64_t &r) {
+  if ((d & (d - 1)) == 0) {
+    q = x >> __builtin_ctzll((unsigned long long)d);
+    r = x & (d - 1);
+  } else if ((((uint64_t)x | (uint64_t)d) >> 32) == 0) {
+    const uint32_t q32 = (uint32_t)x / (uint32_t)d;
+    q = q32;
+    r = (uint32_t)x - q32 * (uint32_t)d;
+  } else {
+    q = x / d;
+    r = x - q * d;
+  }
+}
+
+// Block g of bank blockIdx.y: its first element and its output; false past the end.
+__device__ __forceinline__ bool stat_group(const RedArgs &a, int64_t g, const float *&p,
+                                           float *&o) {
+  if (g >= a.nco * a.ni * a.nto) return false;
+  int64_t co, r, i, t;
+  divmod(g, a.nco, r, co);
+  divmod(r, a.ni, t, i);
+  const int64_t b = blockIdx.y;
+  p = a.in[b] + a.in_off + co * a.F * a.in_cs + i * a.in_ld_i + t * a.in_ld_t;
+  o = a.out + b * a.out_bank + co + i * a.out_ld_i + t * a.out_ld_t;
+  return true;
+}
+
+// ---------------------------------------------------------------------------
+// var / std
+
+// corrected variance (F = 1: 0/0 = NaN, as Julia), or its root
+__device__ __forceinline__ float mom_finish(float ssq, float n, int op) {
+  const float var = ssq / (n - 1.0f);
+  return op == BLDP_OP_STD ? sqrtf(var) : var;
+}
+
+template <int LPG, bool VEC>
+__global__ __launch_bounds__(kBlock) void k_mom_lanes(const RedArgs a, const int op) {
+  const int lg = threadIdx.x % LPG;
+  const int64_t tile = xcd_order(blockIdx.x, gridDim.x, a.xcd_lg);
+  const float *p = nullptr;
+  float *o = nullptr;
+  const bool ok = stat_group(a, tile * (kBlock / LPG) + threadIdx.x / LPG, p, o);
+  const int F = (int)a.F;
+  float v[16];
+  // element slot u of this lane is valid when has(u)
+  auto has = [&](int u) {
+    return ok && (VEC ? 4 * (lg + (u / 4) * LPG) < F : lg + u * LPG < F);
+  };
+  const float K = ok ? p[0] : 0.0f;  // the block's first element (the lanes' own cache line)
+  if (VEC) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (has(4 * j)) {
+        const float4 x = ld4(p + 4 * (lg + j * LPG));
+        v[4 * j] = x.x, v[4 * j + 1] = x.y, v[4 * j + 2] = x.z, v[4 * j + 3] = x.w;
+      }
+  } else {
+#pragma unroll
+    for (int u = 0; u < 16; ++u)
+      if (has(u)) v[u] = p[(int64_t)(lg + u * LPG) * a.in_cs];
+  }
+  float s = 0.0f;  // of x - K
+#pragma unroll
+  for (int u = 0; u < 16; ++u)
+    if (has(u)) s += v[u] - K;
+#pragma unroll
+  for (int w = LPG / 2; w >= 1; w /= 2) s += __shfl_xor(s, w, 64);
+  const float mean = K + s / (float)F;
+  float q = 0.0f;
+#pragma unroll
+  for (int u = 0; u < 16; ++u)
+    if (has(u)) {
+      const float d = v[u] - mean;
+      q += d * d;
+    }
+#pragma unroll
+  for (int w = LPG / 2; w >= 1; w /= 2) q += __shfl_xor(q, w, 64);
+  if (ok && lg == 0) *o = mom_finish(q, (float)F, op);
+}
+
+// sum over the workgroup, the same value in every thread (sh: 4 floats, one use)
+__device__ __forceinline__ float block_sum(float x, float *sh) {
+#pragma unroll
+  for (int w = 32; w >= 1; w /= 2) x += __shfl_xor(x, w, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
+  __syncthreads();
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(kBlock) void k_mom_block(const RedArgs a, const int op) {
+  __shared__ float sh[2][4];
+  const int tid = threadIdx.x;
+  const float *p = nullptr;
+  float *o = nullptr;
+  if (!stat_group(a, blockIdx.x, p, o)) return;  // (uniform)
+  const int64_t F = a.F, n = VEC ? F / 4 : F;    // items: float4s or values
+  const bool regs = F <= kRegMaxF;
+  float v[16];
+  auto has = [&](int u) { return (VEC ? tid + (u / 4) * kBlock : tid + u * kBlock) < n; };
+  const float K = p[0];  // the block's first element
+  float s = 0.0f;        // of x - K
+  if (regs) {
+    if (VEC) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (has(4 * j)) {
+          const float4 x = ld4(p + 4 * (tid + j * kBlock));
+          v[4 * j] = x.x, v[4 * j + 1] = x.y, v[4 * j + 2] = x.z, v[4 * j + 3] = x.w;
+        }
+    } else {
+#pragma unroll
+      for (int u = 0; u < 16; ++u)
+        if (has(u)) v[u] = p[(int64_t)(tid + u * kBlock) * a.in_cs];
+    }
+#pragma unroll
+    for (int u = 0; u < 16; ++u)
+      if (has(u)) s += v[u] - K;
+  } else {
+#pragma unroll 4
+    for (int64_t k = tid; k < n; k += kBlock) {
+      if (VEC) {
+        const float4 x = ld4(p + 4 * k);
+        s += ((x.x - K) + (x.y - K)) + ((x.z - K) + (x.w - K));
+      } else {
+        s += p[k * a.in_cs] - K;
+      }
+    }
+  }
+  const float mean = K + block_sum(s, sh[0]) / (float)F;
+  float q = 0.0f;
+  if (regs) {
+#pragma unroll
+    for (int u = 0; u < 16; ++u)
+      if (has(u)) {
+        const float d = v[u] - mean;
+        q += d * d;
+      }
+  } else {
+#pragma unroll 4
+    for (int64_t k = tid; k < n; k += kBlock) {
+      if (VEC) {
+        const float4 x = ld4(p + 4 * k);
+        const float d0 = x.x - mean, d1 = x.y - mean, d2 = x.z - mean, d3 = x.w - mean;
+        q += d0 * d0, q += d1 * d1, q += d2 * d2, q += d3 * d3;
+      } else {
+        const float d = p[k * a.in_cs] - mean;
+        q += d * d;
+      }
+    }
+  }
+  q = block_sum(q, sh[1]);
+  if (tid == 0) *o = mom_finish(q, (float)F, op);
+}
+
+// ---------------------------------------------------------------------------
+// median
+
+// isless order of Float32 as unsigned order (NaN aside)
+__device__ __forceinline__ uint32_t f2key(float x) {
+  const uint32_t u = __float_as_uint(x);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float key2f(uint32_t k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+// Statistics.middle(a, b) = a/2 + b/2 (no overflow next to floatmax), two
+// roundings: no fused multiply-add
+__device__ __forceinline__ float middle(float x, float y) {
+  return __fadd_rn(__fmul_rn(x, 0.5f), __fmul_rn(y, 0.5f));
+}
+// Ranks (F-1)/2 and F/2 of a block of F: the element itself for odd F, else
+// middle() even of two equal values (a/2 + a/2 is not a for a subnormal with
+// an odd significand).
+__device__ __forceinline__ float median_of(uint32_t k0, uint32_t k1, bool odd, bool nan) {
+  if (nan) return __uint_as_float(0x7fc00000u);
+  return odd ? key2f(k0) : middle(key2f(k0), key2f(k1));
+}
+
+constexpr uint32_t kPadKey = 0xffffffffu;  // above every non-NaN key
+
+// L = next_pow2(F) >= 4 keys over L / 4 lanes, key e = 4 * lane + r.
+template <int L, bool VEC>
+__global__ __launch_bounds__(kBlock) void k_median_sort(const RedArgs a) {
+  constexpr int LG = L / 4;
+  const int lg = threadIdx.x % LG;
+  const int64_t tile = xcd_order(blockIdx.x, gridDim.x, a.xcd_lg);
+  const float *p = nullptr;
+  float *o = nullptr;
+  const bool ok = stat_group(a, tile * (kBlock / LG) + threadIdx.x / LG, p, o);
+  const int F = (int)a.F;
+  uint32_t k[4] = {kPadKey, kPadKey, kPadKey, kPadKey};
+  bool nan = false;
+  if (VEC) {
+    if (ok && 4 * lg < F) {
+      const float4 x = ld4(p + 4 * lg);
+      nan = x.x != x.x || x.y != x.y || x.z != x.z || x.w != x.w;
+      k[0] = f2key(x.x), k[1] = f2key(x.y), k[2] = f2key(x.z), k[3] = f2key(x.w);
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (ok && 4 * lg + r < F) {
+        const float x = p[(int64_t)(4 * lg + r) * a.in_cs];
+        nan = nan || x != x;
+        k[r] = f2key(x);
+      }
+  }
+  // bitonic network: runs of kk keys, ascending where (e & kk) == 0
+#pragma unroll
+  for (int kk = 2; kk <= L; kk *= 2) {
+#pragma unroll
+    for (int j = kk / 2; j >= 1; j /= 2) {
+      if (j >= 4) {  // partner key e ^ j sits in lane ^ (j / 4), same r
+        const bool up = kk == L || ((4 * lg) & kk) == 0;
+        const bool low = (lg & (j / 4)) == 0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const uint32_t other = __shfl_xor(k[r], j / 4, 64);
+          k[r] = (low == up) ? min(k[r], other) : max(k[r], other);
+        }
+      } else {  // both keys in this lane
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if ((r & j) == 0) {
+            const bool up = kk == L || ((4 * lg + r) & kk) == 0;
+            const uint32_t lo = min(k[r], k[r | j]), hi = max(k[r], k[r | j]);
+            k[r] = up ? lo : hi;
+            k[r | j] = up ? hi : lo;
+          }
+      }
+    }
+  }
+  // ranks (F-1)/2 and F/2 (the same for odd F); the padding sorts above them
+  const int q0 = (F - 1) / 2, q1 = F / 2;
+  auto pick = [&](int q) {
+    const int r = q & 3;
+    uint32_t x = r == 0 ? k[0] : r == 1 ? k[1] : r == 2 ? k[2] : k[3];
+    if (LG > 1) x = __shfl(x, (int)(threadIdx.x & 63) - lg + q / 4, 64);
+    return x;
+  };
+  const uint32_t k0 = pick(q0), k1 = pick(q1);
+  const unsigned long long bal = __ballot(nan);
+  const unsigned long long gmask = LG == 64 ? ~0ull : ((1ull << LG) - 1ull);
+  const bool gnan = ((bal >> ((threadIdx.x & 63) - lg)) & gmask) != 0;
+  if (ok && lg == 0) *o = median_of(k0, k1, F & 1, gnan);
+}
+
+// Count digit d of the lanes with pred in the wave's histogram h.  The digits
+// of the first two leaders are counted once for the wave (spectra share their
+// exponent byte, and tied data whole keys: all 64 lanes on one LDS counter
+// otherwise); what is left goes one by one.  Called by whole waves.
+__device__ __forceinline__ void hist_add(uint32_t *h, uint32_t d, bool pred) {
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const unsigned long long act = __ballot(pred);
+    if (act == 0) return;  // (wave-uniform)
+    const int lead = __ffsll(act) - 1;
+    const uint32_t d0 = __shfl(d, lead, 64);
+    const bool eq = pred && d == d0;
+    const unsigned long long m = __ballot(eq);
+    if ((int)(threadIdx.x & 63) == lead) atomicAdd(&h[d0], (uint32_t)__popcll(m));
+    pred = pred && !eq;
+  }
+  if (pred) atomicAdd(&h[d], 1u);
+}
+
+template <bool VEC, bool REG>
+__global__ __launch_bounds__(kBlock) void k_median_select(const RedArgs a) {
+  __shared__ uint32_t hist[2][256];
+  __shared__ uint32_t wtot[2][4];
+  __shared__ uint32_t sel[2][2];  // per rank: its digit, its rank among that digit's keys
+  __shared__ int nanflag;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float *p = nullptr;
+  float *o = nullptr;
+  if (!stat_group(a, blockIdx.x, p, o)) return;  // (uniform)
+  const int64_t F = a.F, n = VEC ? F / 4 : F;    // items: float4s or values
+  // item `it` (uniform loop index) of this thread: VEC 4 keys, else 1
+  auto load = [&](int64_t it, uint32_t *k, bool &nan) {
+    const int64_t idx = it * kBlock + tid;
+    if (idx >= n) return false;
+    if (VEC) {
+      const float4 x = ld4(p + 4 * idx);
+      nan = nan || x.x != x.x || x.y != x.y || x.z != x.z || x.w != x.w;
+      k[0] = f2key(x.x), k[1] = f2key(x.y), k[2] = f2key(x.z), k[3] = f2key(x.w);
+    } else {
+      const float x = p[idx * a.in_cs];
+      nan = nan || x != x;
+      k[0] = f2key(x);
+    }
+    return true;
+  };
+  constexpr int KPI = VEC ? 4 : 1;         // keys per item
+  constexpr int NREG = VEC ? 4 : 16;       // items a lane keeps (REG)
+  const int64_t nit = (n + kBlock - 1) / kBlock;  // items per thread (uniform)
+  uint32_t keys[16];
+  bool nan = false;
+  if (REG) {
+#pragma unroll
+    for (int it = 0; it < NREG; ++it) (void)load(it, &keys[it * KPI], nan);
+  }
+  if (tid == 0) nanflag = 0;
+  uint32_t pre0 = 0, pre1 = 0;                       // key bits fixed so far
+  uint32_t r0 = (uint32_t)((F - 1) / 2), r1 = (uint32_t)(F / 2);  // rank among the prefix's keys
+  for (int pass = 0; pass < 4; ++pass) {
+    const int shift = 24 - 8 * pass;
+    const uint32_t mask = pass == 0 ? 0u : 0xffffffffu << (shift + 8);
+    const bool same = pre0 == pre1;
+    hist[0][tid] = 0;
+    hist[1][tid] = 0;
+    __syncthreads();
+    auto count = [&](uint32_t key, bool valid) {
+      const uint32_t d = (key >> shift) & 255u;
+      hist_add(hist[0], d, valid && (key & mask) == pre0);
+      if (!same) hist_add(hist[1], d, valid && (key & mask) == pre1);
+    };
+    if (REG) {
+#pragma unroll
+      for (int it = 0; it < NREG; ++it) {
+        const bool valid = (int64_t)it * kBlock + tid < n;
+#pragma unroll
+        for (int c = 0; c < KPI; ++c) count(keys[it * KPI + c], valid);
+      }
+    } else {
+      for (int64_t it = 0; it < nit; ++it) {
+        uint32_t k[4] = {0, 0, 0, 0};
+        const bool valid = load(it, k, nan);
+#pragma unroll
+        for (int c = 0; c < KPI; ++c) count(k[c], valid);
+      }
+    }
+    if (pass == 0 && nan) nanflag = 1;
+    __syncthreads();
+    // inclusive scan of the 256 bins: in the wave, then over the waves
+    const uint32_t c0 = hist[0][tid], c1 = same ? c0 : hist[1][tid];
+    uint32_t i0 = c0, i1 = c1;
+#pragma unroll
+    for (int w = 1; w < 64; w *= 2) {
+      const uint32_t u0 = __shfl_up(i0, w, 64), u1 = __shfl_up(i1, w, 64);
+      if (lane >= w) i0 += u0, i1 += u1;
+    }
+    if (lane == 63) wtot[0][wave] = i0, wtot[1][wave] = i1;
+    __syncthreads();
+    for (int w = 0; w < wave; ++w) i0 += wtot[0][w], i1 += wtot[1][w];
+    // the bin whose keys hold the rank
+    if (c0 && i0 - c0 <= r0 && r0 < i0) sel[0][0] = tid, sel[0][1] = r0 - (i0 - c0);
+    if (c1 && i1 - c1 <= r1 && r1 < i1) sel[1][0] = tid, sel[1][1] = r1 - (i1 - c1);
+    __syncthreads();
+    pre0 |= sel[0][0] << shift;
+    r0 = sel[0][1];
+    pre1 |= sel[1][0] << shift;
+    r1 = sel[1][1];
+  }
+  if (tid == 0) *o = median_of(pre0, pre1, F & 1, nanflag != 0);
+}
+
+}  // namespace
+
+int plan_stats(RedArgs &a, int op, bool words, int xcd_lg, Plan *pp) {
+  Plan p{};
+  const int64_t F = a.F;
+  p.nout = a.nco * a.ni * a.nto;
+  a.ts = 1;
+  a.tpb = 1;
+  a.tsub_log2 = 0;
+  a.rsplit = 1;
+  a.bpack = 0;
+  a.st_plain = 1;
+  a.vec_out = 0;
+  a.nchunk = 1;
+  a.rows_per_chunk = 1;
+  a.blocks_c = 1;
+  a.div = (float)F;
+  a.k4 = (words && F % 4 == 0) ? 1 : 0;  // float4 loads
+  const int64_t items = a.k4 ? F / 4 : F;
+  auto pow2_lanes = [](int64_t n) {
+    int l = 1;
+    while (l < 64 && l < n) l *= 2;
+    return l;
+  };
+  // F = 1: fqav(A, n <= 1) returns A whatever f is (src/gbtworkerfunctions.jl:17),
+  // which is what the median of one element copies
+  if (op == BLDP_OP_MEDIAN || F == 1) {
+    if (F >= ((int64_t)1 << 31))
+      return set_error(BLDP_EINVAL, "median: fqavby=%lld is beyond 2^31 - 1", (long long)F);
+    if (F <= kSortMaxF) {
+      p.path = PATH_MEDIAN_SORT;
+      p.lpg = pow2_lanes((F + 3) / 4);
+    } else {
+      p.path = F <= kRegMaxF ? PATH_MEDIAN_SELECT : PATH_MEDIAN_STREAM;
+      p.lpg = kBlock;
+    }
+  } else {
+    p.path = PATH_MOMENTS;
+    p.lpg = F <= kLaneMaxF ? pow2_lanes(items) : kBlock;
+  }
+  // one block per workgroup, or kBlock / lpg of them side by side
+  a.ntiles = p.lpg == kBlock ? p.nout : (p.nout + kBlock / p.lpg - 1) / (kBlock / p.lpg);
+  if (a.ntiles > INT32_MAX)
+    return set_error(BLDP_EINVAL, "median/var/std: %lld blocks of %lld are too many for one launch",
+                     (long long)p.nout, (long long)F);
+  p.grid = a.ntiles;
+  p.ws_bytes = 0;
+  // the per-XCD tile order where neighbouring workgroups read neighbouring
+  // memory, as k_reduce_vec (kernels.hip xcd_order_pays); a workgroup per block: off
+  a.xcd_lg = p.lpg == kBlock ? 0 : xcd_lg;
+  *pp = p;
+  return BLDP_OK;
+}
+
+
+namespace {
+// One dispatch; it carries the timing events of bldp_reduce_launch_timed when set.
+template <typename... Args>
+hipError_t launch1(void (*kn)(Args...), dim3 grid, hipStream_t s, Args... args) {
+  hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+  take_launch_events(&ev_start, &ev_stop);
+  if (ev_stop)
+    hipExtLaunchKernelGGL(kn, grid, dim3(kBlock), 0, s, ev_start, ev_stop, 0, args...);
+  else
+    hipLaunchKernelGGL(kn, grid, dim3(kBlock), 0, s, args...);
+  return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_stats(const RedArgs &a, const Plan &p, int op, hipStream_t s) {
+  if (p.grid <= 0) return hipSuccess;
+  const dim3 grid((unsigned)p.grid, (unsigned)a.nbank);
+  const bool vec = a.k4 != 0;
+#define BLDP_VECSEL(KN, N) (vec ? KN<N, true> : KN<N, false>)
+  switch (p.path) {
+    case PATH_MOMENTS:
+      switch (p.lpg) {
+        case 1: return launch1(BLDP_VECSEL(k_mom_lanes, 1), grid, s, a, op);
+        case 2: return launch1(BLDP_VECSEL(k_mom_lanes, 2), grid, s, a, op);
+        case 4: return launch1(BLDP_VECSEL(k_mom_lanes, 4), grid, s, a, op);
+        case 8: return launch1(BLDP_VECSEL(k_mom_lanes, 8), grid, s, a, op);
+        case 16: return launch1(BLDP_VECSEL(k_mom_lanes, 16), grid, s, a, op);
+        case 32: return launch1(BLDP_VECSEL(k_mom_lanes, 32), grid, s, a, op);
+        case 64: return launch1(BLDP_VECSEL(k_mom_lanes, 64), grid, s, a, op);
+        case kBlock: return launch1(vec ? k_mom_block<true> : k_mom_block<false>, grid, s, a, op);
+      }
+      break;
+    case PATH_MEDIAN_SORT:
+      switch (p.lpg) {  // lanes of 4 keys
+        case 1: return launch1(BLDP_VECSEL(k_median_sort, 4), grid, s, a);
+        case 2: return launch1(BLDP_VECSEL(k_median_sort, 8), grid, s, a);
+        case 4: return launch1(BLDP_VECSEL(k_median_sort, 16), grid, s, a);
+        case 8: return launch1(BLDP_VECSEL(k_median_sort, 32), grid, s, a);
+        case 16: return launch1(BLDP_VECSEL(k_median_sort, 64), grid, s, a);
+      }
+      break;
+#undef BLDP_VECSEL
+    case PATH_MEDIAN_SELECT:
+      return launch1(vec ? k_median_select<true, true> : k_median_select<false, true>, grid, s, a);
+    case PATH_MEDIAN_STREAM:
+      return launch1(vec ? k_median_select<true, false> : k_median_select<false, false>, grid, s,
+                     a);
+  }
+  return hipErrorInvalidValue;
+}
+
+}  // namespace bldp

@@ -209,9 +209,22 @@ def _dtype_code(dt):
     return DTYPE_CODES.get(np.dtype(dt))
 
 
+def _check_stat(op: str, tavby, dtype=None) -> None:
+    """var / std / median: no time integration, Float32 on the GPU (TypeError,
+    as Julia's MethodError for an fqavfunc the call does not fit)."""
+    if op not in _lib.STAT_OPS:
+        return
+    if int(tavby) > 1:
+        raise TypeError(f"fqavfunc {op!r} has no time integration: tavby={tavby} needs "
+                        f"sum/mean/max/min")
+    if dtype is not None and _dtype_code(dtype) != 0:
+        raise TypeError(f"fqavfunc {op!r} runs on the GPU for Float32 data only, not {dtype}")
+
+
 def out_dtype(dtype, op: str) -> np.dtype:
     """fqav's result element type for input `dtype` (Julia's; bldp_reduce_out_dtype):
-    sum widens integers to (U)Int64, mean is Float64, max / min keep the type."""
+    sum widens integers to (U)Int64, mean is Float64, max / min keep the type;
+    var / std / median are Float32 of Float32 and Float64 of anything else."""
     code = _dtype_code(dtype)
     if code is None:
         raise TypeError(f"unsupported element type {dtype}")
@@ -260,6 +273,7 @@ def reduce(x, fqavby=1, tavby=1, op="sum", win=None, out=None, stream=None):
 
     x: device filterbank tensor; win: 9-int window (see idxs.to_window) or
     None; returns a Julia-order (nc/F, ni, nt/T) device tensor."""
+    _check_stat(op, tavby, x.dtype)
     L = _lib.lib()
     shape = tuple(x.shape)
     _check_bounds(win, shape)
@@ -323,6 +337,7 @@ class PreparedReduce(_Prepared):
     ctypes call and the kernel launch.  ``out`` as ``reduce`` makes it."""
 
     def __init__(self, x, fqavby=1, tavby=1, op="sum", win=None, out=None):
+        _check_stat(op, tavby, x.dtype)
         torch = _torch()
         L = _lib.lib()
         shape = tuple(x.shape)
@@ -423,6 +438,7 @@ def _band_args(banks, fqavby, tavby, win, out):
 def band_reduce(banks, fqavby=1, tavby=1, op="sum", win=None, out=None, stream=None):
     """Reduce every bank of a band resident on ONE GPU and stitch them in bank
     order (reduce(vcat, ...), src/gbt.jl:103) in a single launch."""
+    _check_stat(op, tavby)
     L = _lib.lib()
     banks, geo, out, ptrs, (keep, wp) = _band_args(banks, fqavby, tavby, win, out)
     nchan, nif, ntime = geo
@@ -442,6 +458,7 @@ class PreparedBandReduce:
     are kept alive by the object; ``close`` releases the handle."""
 
     def __init__(self, banks, fqavby=1, tavby=1, op="sum", win=None, out=None):
+        _check_stat(op, tavby)
         L = _lib.lib()
         banks, geo, out, ptrs, (keep, wp) = _band_args(banks, fqavby, tavby, win, out)
         h = ctypes.c_void_p()
@@ -493,7 +510,11 @@ def band_reduce_multi(banks, fqavby=1, tavby=1, op="sum", win=None, root=0, out=
     (BLDP_BAND_STAGED), the root's included; ``peer_store``: devices with peer
     access store their slots over xGMI from the kernels (BLDP_BAND_PEER_STORE,
     opt-in until a multi-GPU node has run it) -- per-call arguments, not
-    process state."""
+    process state.  sum / mean / max / min only: var / std / median run on one
+    device (GBT.getband then goes bank by bank)."""
+    if op in _lib.STAT_OPS:
+        raise TypeError(f"band_reduce_multi takes sum/mean/max/min, not {op!r}: reduce each "
+                        f"device's banks with band_reduce")
     torch = _torch()
     L = _lib.lib()
     banks = list(banks)
@@ -637,6 +658,7 @@ def synth(nchan, nif, ntime, nfpc=1024, seed=0, kind=0, device=None, stream=None
 def reduce_host(a: np.ndarray, fqavby=1, tavby=1, op="sum", win=None, device=0) -> np.ndarray:
     """Host array in, host array out (bldp_reduce_host_f32): the window is
     streamed through the GPU and reduced there."""
+    _check_stat(op, tavby)
     L = _lib.lib()
     a = np.asarray(a)
     if a.dtype != np.float32 or not a.flags.f_contiguous or a.ndim != 3:
@@ -673,8 +695,9 @@ def reduce_host_typed(a: np.ndarray, fqavby=1, tavby=1, op="sum", win=None, devi
     """Host array of any supported element type in, host array of fqav's
     Julia result type out (bldp_reduce_host): e.g. UInt8 SIGPROC data summed
     into UInt64, averaged into Float64, max / min kept as UInt8."""
-    L = _lib.lib()
     a = np.asarray(a)
+    _check_stat(op, tavby, a.dtype)
+    L = _lib.lib()
     code = _dtype_code(a.dtype)
     if code is None or a.ndim != 3:
         raise TypeError(f"unsupported host filterbank {a.dtype} {a.shape}")

@@ -14,7 +14,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import readers, worker as W
+from . import _lib, readers, worker as W
 from .idxs import COLON
 
 __all__ = ["datahosts", "setupworkers", "getinventories", "getheaders", "getdata",
@@ -328,6 +328,10 @@ def _band_on_device(ws, fs, idxs, fqavby, op, tavby, nfpc, timings=None, staged=
     # filter 32008): the band's chunks read and decoded as one stream per GPU
     chunked = (not raw and all(g[0] == "h5" for g in geo) and len({g[1] for g in geo}) == 1
                and os.environ.get("BLDP_NATIVE_READ", "1") != "0")
+    # var / std / median run on one device (bldp_band_reduce_multi_f32 does not
+    # take them): with banks on several GPUs, or staged, the band goes bank by bank
+    if op in _lib.STAT_OPS and (force_copy or {int(w) for w in ws} != {root}):
+        raw = chunked = False
     if chunked:
         chunked = _band_chunked(ws, fs, geo, idxs, fqavby, op, tavby, band, root, force_copy, tm,
                                 peer_store)

@@ -9,7 +9,7 @@ See INTEGRATION.md for the two-line patch to src/gbtworkerfunctions.jl.
 =#
 module BLDPHip
 
-using Statistics: mean
+using Statistics: mean, median, var, std
 
 export gpu_init, gpu_finalize, gpu_pin, gpu_unpin, gpu_fqav, gpu_reduce, gpu_kurtosis, gpu_band,
        gpu_comm_id, gpu_comm_init, gpu_comm_destroy, gpu_band_gather
@@ -32,6 +32,11 @@ dtypecode(::Type{T}) where {T<:GPUElt} = Cint(findfirst(==(T), ELTYPES) - 1)
 # else keeps the reference's host fqav.
 opcode(f) = f === sum ? Cint(0) : f === mean ? Cint(1) : f === maximum ? Cint(2) :
             f === minimum ? Cint(3) : nothing
+# Statistics' var (corrected), std and median have kernels for Float32 data
+# (BLDP_OP_VAR / _STD / _MEDIAN, no time integration); arrays of any other
+# element type return nothing here, so the reference's host fqav runs.
+opcode(f, A) = opcode(f) !== nothing ? opcode(f) : !(A isa Array{Float32,3}) ? nothing :
+               f === var ? Cint(4) : f === std ? Cint(5) : f === median ? Cint(6) : nothing
 
 function lasterror()
     buf = Vector{UInt8}(undef, 1024)
@@ -98,7 +103,7 @@ end
 spectra, computed on GPU `dev` (bldp_reduce_host_f32)."""
 function gpu_reduce(A::Array{Float32,3}, fqavby::Integer, tavby::Integer=1;
                     f=sum, idxs::Tuple=(:, :, :), dev::Integer=0)
-    op = opcode(f)
+    op = opcode(f, A)
     op === nothing && throw(ArgumentError("no GPU kernel for $f"))
     win = window(idxs, size(A))
     shp = zeros(Int64, 3)
@@ -142,10 +147,11 @@ end
 
 Drop-in for `fqav(A, n; f)` (src/gbtworkerfunctions.jl:16-20): same
 pass-through for `n <= 1`, same DimensionMismatch, GPU for sum/mean/maximum/
-minimum, the reference's host code for any other `f`."""
+minimum (and, for Float32 arrays with `tavby <= 1`, var/std/median), the
+reference's host code for any other `f`."""
 function gpu_fqav(A, n::Integer; f=sum, tavby::Integer=1, dev::Integer=0)
     (n <= 1 && tavby <= 1) && return A
-    if A isa Array{<:GPUElt,3} && opcode(f) !== nothing
+    if A isa Array{<:GPUElt,3} && opcode(f, A) !== nothing
         return gpu_reduce(A, n, tavby; f, dev)
     end
     tavby <= 1 || throw(ArgumentError("tavby needs a 3-D array and sum/mean/max/min"))

@@ -12,7 +12,13 @@ Same names, argument meanings and error behaviour as the reference:
 * ``getinventory`` / headers — :35-159 (host metadata, see .readers).
 
 ``fqavfunc`` is one of ``"sum" | "mean" | "max" | "min"`` (or the Python
-builtins ``sum``/``max``/``min``, ``numpy.sum``/``mean``/``max``/``min``).
+builtins ``sum``/``max``/``min``, ``numpy.sum``/``mean``/``max``/``min``), or
+one of the strings ``"var" | "std" | "median"``: Julia's ``Statistics`` (the
+corrected variance, its root, and the median with ``middle(a, b) = a/2 + b/2``
+of an even block) on the GPU for Float32 data, without time integration
+(``tavby > 1`` is a TypeError); data of other element types get the same
+rules on the host in Float64, as Julia's result type is.  Only the strings
+select them: ``numpy.std`` is the population form, not Julia's.
 Any other callable is applied on the host exactly like the reference's
 generic ``f(reshape(A, ...); dims=1)`` path (README.md:192-195) — that is the
 reference behaviour for functions the GPU does not implement, not a fallback
@@ -101,6 +107,36 @@ def _host_generic(A: np.ndarray, n: int, f) -> np.ndarray:
     return np.asfortranarray(np.asarray(f(R, axis=0)))
 
 
+def _host_stat(a: np.ndarray, n: int, op: str, win=None) -> np.ndarray:
+    """Julia's var / std / median of every n channels in Float64, for the
+    element types the GPU ops do not take (integers, Float64): the corrected
+    two-pass variance about the mean, its root, and the median ordered by
+    isless (-0.0 < 0.0), the middle element of an odd block, a/2 + b/2 of an
+    even one, NaN when the block holds a NaN."""
+    a = np.asarray(a)
+    if win is not None:
+        a = a[np.ix_(*[win[3 * k] + win[3 * k + 2] * np.arange(win[3 * k + 1])
+                       for k in range(3)])]
+    n = max(int(n), 1)
+    if a.shape[0] % n:
+        raise _lib.DimensionMismatch(_lib.BLDP_EDIM,
+                                     f"DimensionMismatch: fqavby={n} does not divide {a.shape[0]}")
+    R = np.asfortranarray(a, dtype=np.float64).reshape((n, a.shape[0] // n) + a.shape[1:],
+                                                       order="F")
+    with np.errstate(invalid="ignore", divide="ignore"):
+        if op == "var":
+            r = np.var(R, axis=0, ddof=1)
+        elif op == "std":
+            r = np.std(R, axis=0, ddof=1)
+        else:
+            bits = R.view(np.int64)
+            key = np.where(bits < 0, bits ^ np.int64(0x7FFFFFFFFFFFFFFF), bits)  # isless order
+            S = np.take_along_axis(R, np.argsort(key, axis=0, kind="stable"), axis=0)
+            r = S[n // 2] if n % 2 else S[n // 2 - 1] / 2 + S[n // 2] / 2
+            r = np.where(np.isnan(R).any(axis=0), np.nan, r)
+    return np.asfortranarray(r)
+
+
 def fqav(A, n: int, f="sum"):
     """Reduce every ``n`` elements of the first dimension of ``A`` with ``f``
     (src/gbtworkerfunctions.jl:16-20).  ``n <= 1`` returns ``A`` itself (:17).
@@ -113,7 +149,7 @@ def fqav(A, n: int, f="sum"):
     op = _opname(f)
     if _is_tensor(A):
         if op is None:
-            raise TypeError("only sum/mean/max/min run on device tensors")
+            raise TypeError("only sum/mean/max/min/var/std/median run on device tensors")
         return engine.reduce(A, n, 1, op)
     A = np.asarray(A)
     if op is None:
@@ -129,12 +165,16 @@ def _reduce_host(a, fqavby, tavby, op, win, device):
     """A host array through the GPU with fqav's Julia result type: Float32
     stays Float32; integer and Float64 arrays take the typed kernels (sum
     widened to (U)Int64, mean Float64, max / min the input type,
-    src/gbtworkerfunctions.jl:19).  Nothing is converted on the way."""
+    src/gbtworkerfunctions.jl:19).  Nothing is converted on the way.
+    var / std / median of those arrays are Float64 from the host (_host_stat)."""
+    engine._check_stat(op, tavby)
     if a.dtype == np.float32:
         return engine.reduce_host(np.asfortranarray(a), fqavby, tavby, op, win, device=device)
     if engine._dtype_code(a.dtype) is None:
         raise TypeError(f"fqav: element type {a.dtype} is not supported (Float32, Float64, "
                         f"8- to 64-bit integers)")
+    if op in _lib.STAT_OPS:
+        return _host_stat(a, fqavby, op, win)
     return engine.reduce_host_typed(a, fqavby, tavby, op, win, device=device)
 
 
@@ -295,7 +335,7 @@ def getdata_device(fname, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum", 
     band product (GBT.getband); None when the data are not Float32."""
     op = _opname(fqavfunc)
     if op is None:
-        raise TypeError("the device path takes fqavfunc in sum/mean/max/min")
+        raise TypeError("the device path takes fqavfunc in sum/mean/max/min/var/std/median")
     got = window_on_device(fname, idxs, device)
     if got is None:
         return None

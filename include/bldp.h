@@ -85,7 +85,8 @@ extern "C" {
  * 5: bldp_reduce_prepare / bldp_kurtosis_prepare (any element type) launched
  *    by bldp_reduce_launch; bldp_band_reduce_multi_f32 flag
  *    BLDP_BAND_PEER_STORE (direct xGMI stores are opt-in); plan option
- *    "typed_kurt" */
+ *    "typed_kurt"; (additive, same version) bldp_op gains BLDP_OP_VAR,
+ *    BLDP_OP_STD, BLDP_OP_MEDIAN for the Float32 reduce entry points */
 #define BLDP_ABI_VERSION 5
 
 #if defined(BLDP_BUILD)
@@ -94,8 +95,16 @@ extern "C" {
 #define BLDP_API
 #endif
 
-/* fqavfunc values named by README.md:192-195 */
-enum bldp_op { BLDP_OP_SUM = 0, BLDP_OP_MEAN = 1, BLDP_OP_MAX = 2, BLDP_OP_MIN = 3 };
+/* fqavfunc values named by README.md:192-195, and its "etc.": Statistics'
+ * var (corrected), std and median over the fqavby channels of a block.  Those
+ * three take Float32 data and no time integration (tavby <= 1, else
+ * BLDP_EINVAL); Float32 in, Float32 out.  median orders by isless
+ * (-0.0 < 0.0), returns the middle element of an odd block and
+ * middle(a, b) = a/2 + b/2 of an even one, and NaN for a block holding a NaN. */
+enum bldp_op {
+  BLDP_OP_SUM = 0, BLDP_OP_MEAN = 1, BLDP_OP_MAX = 2, BLDP_OP_MIN = 3,
+  BLDP_OP_VAR = 4, BLDP_OP_STD = 5, BLDP_OP_MEDIAN = 6
+};
 
 /* error codes */
 #define BLDP_OK 0
@@ -138,7 +147,10 @@ BLDP_API int bldp_reduce_shape(int64_t nchan, int64_t nif, int64_t ntime, const 
 
 /* Introspection (tests/bench): the launch plan bldp_reduce_f32 would use for
  * these pointers.  info = {path (0 vector, 1 narrow, 2 scalar, 3 tile,
- * 4 interleaved, 5 row, 6 narrow_mis, 7 lane), lanes per group, waves (row
+ * 4 interleaved, 5 row, 6 narrow_mis, 7 lane; var / std: 8 moments; median:
+ * 9 bitonic sort of blocks <= 64, 10 radix select with the keys in registers,
+ * 11 radix select re-reading the block), lanes per group (8-11: 256 = one
+ * workgroup per block), waves (row
  * path: workgroup slices) splitting T, float4 per lane per row, time chunks,
  * workgroups, workspace bytes, vector output stores}.  Launches nothing. */
 BLDP_API int bldp_reduce_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
