@@ -92,6 +92,11 @@ SIGNATURES = {
     "bldp_kurtosis_plan_f32": ([P, I64, I64, I64, P, P], I),
     "bldp_kurtosis_host_f32": ([I, P, I64, I64, I64, P, P], I),
     "bldp_band_kurtosis_f32": ([I, P, I64, I64, I64, P, P, P], I),
+    "bldp_kurtosis_blocks_shape": ([I64, I64, I64, P, I64, P], I),
+    "bldp_kurtosis_blocks_plan_f32": ([P, I64, I64, I64, P, I64, P], I),
+    "bldp_kurtosis_blocks_f32": ([P, I64, I64, I64, P, I64, P, I64, I64, P], I),
+    "bldp_band_kurtosis_blocks_f32": ([I, P, I64, I64, I64, P, I64, P, P], I),
+    "bldp_kurtosis_blocks_host_f32": ([I, P, I64, I64, I64, P, I64, P], I),
     "bldp_fqav_range": ([D, D, I64, I64, P, P, P], I),
     "bldp_synth_f32": ([P, I64, I64, I64, I64, U64, I, P], I),
     "bldp_reduce_out_dtype": ([I, I], I),

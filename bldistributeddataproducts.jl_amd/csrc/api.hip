@@ -880,6 +880,176 @@ int bldp_band_kurtosis_f32(int nbank, const float *const *in, int64_t nchan, int
   return kurt_run(k, out, nullptr, stream);
 }
 
+// ---- kurtosis over blocks of spectra (tblock) ------------------------------
+// The rule tavby follows: tblock must divide the selected spectra.
+static int kblk_count(int64_t nt, int64_t tblock, int64_t *nb) {
+  if (tblock < 1) return fail(BLDP_EINVAL, "tblock=%lld must be >= 1", (long long)tblock);
+  if (nt % tblock != 0)
+    return fail(BLDP_EDIM, "DimensionMismatch: tblock=%lld does not divide ntime=%lld",
+                (long long)tblock, (long long)nt);
+  *nb = nt / tblock;
+  return BLDP_OK;
+}
+
+// The window of block b: the same channels and IFs, spectra [b*M, (b+1)*M) of
+// the selected ones.
+static void kblk_window(int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win, int64_t M,
+                        int64_t b, int64_t bw[9]) {
+  const int64_t full[9] = {0, nchan, 1, 0, nif, 1, 0, ntime, 1};
+  for (int q = 0; q < 9; ++q) bw[q] = win ? win[q] : full[q];
+  bw[6] += b * M * bw[8];
+  bw[7] = M;
+}
+
+// Plan of a blocked kurtosis: *whole is the whole window's KurtArgs (checks,
+// float4 columns), *blk the first block's (the block-by-block form's path and
+// workspace; every block has the same shape).
+struct KblkPlan {
+  KurtArgs whole, blk;
+  int64_t nb;
+  bool fused;
+  int path;
+  size_t tmp_off, ws_bytes;  // block-by-block: a block's dense results after its workspace
+};
+static int kblk_plan(int nbank, const float *const *in, int64_t nchan, int64_t nif, int64_t ntime,
+                     const int64_t *win, int64_t tblock, KblkPlan *p) {
+  int rc = kurt_setup(nbank, in, nchan, nif, ntime, win, &p->whole);
+  if (rc) return rc;
+  rc = kblk_count(p->whole.nt, tblock, &p->nb);
+  if (rc) return rc;
+  p->fused = kurt_blocks_fused(p->whole, tblock);
+  p->tmp_off = p->ws_bytes = 0;
+  if (p->fused) {
+    p->path = tblock <= 32 ? 0 : 2;  // regs : leaf (KURT_PATHS)
+    return BLDP_OK;
+  }
+  int64_t bw[9];
+  kblk_window(nchan, nif, ntime, win, tblock, 0, bw);
+  if (p->nb == 0) bw[6] = 0, bw[7] = 0;  // (no block: the empty window's plan)
+  rc = kurt_setup(nbank, in, nchan, nif, ntime, bw, &p->blk);
+  if (rc) return rc;
+  p->path = kurtosis_path(p->blk);
+  p->tmp_off = (kurtosis_ws_bytes(p->blk) + 255) & ~(size_t)255;
+  p->ws_bytes = p->tmp_off + (size_t)(p->blk.nrow * p->blk.nc) * sizeof(double);
+  return BLDP_OK;
+}
+
+static int kblk_run(int nbank, const float *const *in, int64_t nchan, int64_t nif, int64_t ntime,
+                    const int64_t *win, int64_t tblock, double *out, int64_t out_bank,
+                    int64_t out_ld_i, int64_t out_ld_b, void *stream) {
+  KblkPlan p;
+  int rc = kblk_plan(nbank, in, nchan, nif, ntime, win, tblock, &p);
+  if (rc) return rc;
+  const KurtArgs &w = p.whole;
+  if (w.nc * w.ni * p.nb == 0) return BLDP_OK;
+  for (int b = 0; b < nbank; ++b)
+    if (!w.in[b]) return fail(BLDP_EINVAL, "tblock kurtosis: null input pointer (bank %d)", b);
+  if (!out) return fail(BLDP_EINVAL, "tblock kurtosis: null output pointer");
+  if (out_ld_i < w.nc || out_ld_b < (w.ni - 1) * out_ld_i + w.nc)
+    return fail(BLDP_EINVAL,
+                "tblock kurtosis: out strides (%lld, %lld) overlap for a (%lld, %lld, %lld) result",
+                (long long)out_ld_i, (long long)out_ld_b, (long long)w.nc, (long long)w.ni,
+                (long long)p.nb);
+  hipStream_t s = (hipStream_t)stream;
+  if (p.fused) {
+    KurtBlkArgs k{};
+    for (int b = 0; b < nbank; ++b) k.in[b] = w.in[b];
+    k.nbank = nbank;
+    k.in_off = w.in_off;
+    k.in_ld_i = w.in_ld_i;
+    k.in_ld_t = w.in_ld_t;
+    k.nc = w.nc;
+    k.ni = w.ni;
+    k.M = tblock;
+    k.nb = p.nb;
+    k.out_bank = out_bank;
+    k.out_ld_i = out_ld_i;
+    k.out_ld_b = out_ld_b;
+    k.out = out;
+    plan_kurt_blocks(k, num_cus_current());
+    if (kurt_blocks_grid(k) > INT32_MAX)
+      return fail(BLDP_EINVAL, "tblock=%lld kurtosis: %lld blocks are too many for one launch",
+                  (long long)tblock, (long long)p.nb);
+    hipError_t e = launch_kurt_blocks(k, s);
+    if (e != hipSuccess)
+      return fail(BLDP_EHIP, "tblock kurtosis launch: %s", hipGetErrorString(e));
+    return BLDP_OK;
+  }
+  // block by block through the whole-window paths: one scratch lease, every
+  // launch on the caller's stream (which orders the reuse of the scratch)
+  ScratchLease lease;
+  rc = scratch_lease(s, p.ws_bytes, &lease);
+  if (rc) return rc;
+  char *ws = static_cast<char *>(lease.ptr);
+  double *tmp = reinterpret_cast<double *>(ws + p.tmp_off);
+  const bool direct = nbank == 1 && out_ld_i == w.nc;  // a block's results are dense in out
+  for (int64_t b = 0; b < p.nb; ++b) {
+    int64_t bw[9];
+    kblk_window(nchan, nif, ntime, win, tblock, b, bw);
+    KurtArgs k;
+    rc = kurt_setup(nbank, in, nchan, nif, ntime, bw, &k);
+    if (rc) return rc;
+    if (kurtosis_ws_bytes(k) > p.tmp_off)  // (a plan option changed under the call)
+      return fail(BLDP_EINVAL, "tblock kurtosis: the plan changed during the call");
+    rc = kurt_run(k, direct ? out + b * out_ld_b : tmp, ws, stream);
+    if (rc) return rc;
+    if (!direct) {
+      hipError_t e = launch_kurt_scatter(tmp, nbank, w.ni, w.nc, out + b * out_ld_b, out_bank,
+                                         out_ld_i, s);
+      if (e != hipSuccess)
+        return fail(BLDP_EHIP, "tblock kurtosis launch: %s", hipGetErrorString(e));
+    }
+  }
+  return BLDP_OK;
+}
+
+int bldp_kurtosis_blocks_shape(int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win,
+                               int64_t tblock, int64_t dims[3]) {
+  if (!dims) return fail(BLDP_EINVAL, "null dims");
+  Geo g;
+  int rc = resolve_window(nchan, nif, ntime, win, &g);
+  if (rc) return rc;
+  int64_t nb;
+  rc = kblk_count(g.nt, tblock, &nb);
+  if (rc) return rc;
+  dims[0] = g.nc;
+  dims[1] = g.ni;
+  dims[2] = nb;
+  return BLDP_OK;
+}
+
+int bldp_kurtosis_blocks_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                                  const int64_t *win, int64_t tblock, int64_t info[4]) {
+  if (!info) return fail(BLDP_EINVAL, "null info");
+  KblkPlan p;
+  const float *ins[1] = {in};
+  int rc = kblk_plan(1, ins, nchan, nif, ntime, win, tblock, &p);
+  if (rc) return rc;
+  info[0] = p.path;
+  info[1] = p.fused ? 1 : 0;
+  info[2] = p.nb;
+  info[3] = (int64_t)p.ws_bytes;
+  return BLDP_OK;
+}
+
+int bldp_kurtosis_blocks_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                             const int64_t *win, int64_t tblock, double *out, int64_t out_ld_i,
+                             int64_t out_ld_b, void *stream) {
+  const float *ins[1] = {in};
+  return kblk_run(1, ins, nchan, nif, ntime, win, tblock, out, 0, out_ld_i, out_ld_b, stream);
+}
+
+int bldp_band_kurtosis_blocks_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                                  int64_t ntime, const int64_t *win, int64_t tblock, double *out,
+                                  void *stream) {
+  if (!in) return fail(BLDP_EINVAL, "tblock kurtosis: null input pointer array");
+  int64_t d[3];
+  int rc = bldp_kurtosis_blocks_shape(nchan, nif, ntime, win, tblock, d);
+  if (rc) return rc;
+  return kblk_run(nbank, in, nchan, nif, ntime, win, tblock, out, d[0] * d[1] * d[2], d[0],
+                  d[0] * d[1], stream);
+}
+
 int bldp_reduce_out_dtype(int dtype, int op) {
   const int d = typed_out_dtype(dtype, op);
   if (d < 0) return fail(BLDP_EINVAL, "unknown element type %d or op %d", dtype, op);

@@ -196,6 +196,28 @@ hipError_t launch_kurtosis(KurtArgs &k, char *ws, hipStream_t s);
 int kurtosis_path(const KurtArgs &k);
 int64_t kurtosis_max_grid(const KurtArgs &k);  // largest grid of the plan
 
+// Kurtosis over blocks of M spectra, the one-launch form (kurtosis.hip):
+// float4-column windows (unit channel step), M <= 1024.  Block b holds the
+// window's spectra [b*M, (b+1)*M); output (c, i, b) of bank k at
+// out[k*out_bank + c + i*out_ld_i + b*out_ld_b].
+struct KurtBlkArgs {
+  const float *in[BLDP_MAX_BANKS];  // banks with identical geometry
+  int32_t nbank;
+  int32_t leafw;  // channels per lane of the streamed form (M > 32)
+  int64_t in_off, in_ld_i, in_ld_t;
+  int64_t nc, ni, M, nb;
+  int64_t out_bank, out_ld_i, out_ld_b;
+  double *out;
+};
+// `whole`: the KurtArgs of the whole window (its float4 columns are every block's)
+bool kurt_blocks_fused(const KurtArgs &whole, int64_t M);
+void plan_kurt_blocks(KurtBlkArgs &k, int num_cus);
+int64_t kurt_blocks_grid(const KurtBlkArgs &k);
+hipError_t launch_kurt_blocks(const KurtBlkArgs &k, hipStream_t s);
+// block-by-block form: dense [nbank][ni][nc] results of one block into the product
+hipError_t launch_kurt_scatter(const double *src, int64_t nbank, int64_t ni, int64_t nc,
+                               double *out, int64_t out_bank, int64_t out_ld_i, hipStream_t s);
+
 // Window of a chunked dataset: chunk dims (ct, ci, cc) in C order, a chunk
 // bounding box starting at (bt0, bi0, bc0) with (gt, gi, gc) chunks, and the
 // window {c0, nc, cs, i0, ni, is, t0, nt, ts} in dataset coordinates.

@@ -19,6 +19,10 @@ extern "C" int bldp_reduce_shape(int64_t, int64_t, int64_t, const int64_t *, int
                                  int64_t *);
 extern "C" int bldp_kurtosis_f32(const float *, int64_t, int64_t, int64_t, const int64_t *,
                                  double *, void *, void *);
+extern "C" int bldp_kurtosis_blocks_shape(int64_t, int64_t, int64_t, const int64_t *, int64_t,
+                                          int64_t *);
+extern "C" int bldp_kurtosis_blocks_f32(const float *, int64_t, int64_t, int64_t, const int64_t *,
+                                        int64_t, double *, int64_t, int64_t, void *);
 extern "C" int bldp_reduce_strided_f32(const float *, int64_t, int64_t, int64_t,
                                        const int64_t *, int64_t, int64_t, int, float *, int64_t,
                                        int64_t, void *);
@@ -185,6 +189,34 @@ extern "C" int bldp_kurtosis_host_f32(int dev, const float *in, int64_t nchan, i
     r = bldp_kurtosis_f32(dbuf, h.span, ni, nt, dwin, dout, nullptr, sg->st[0]);
     if (r) return r;
     HCHK(hipMemcpyAsync(out, dout, (size_t)(nc * ni) * sizeof(double), hipMemcpyDeviceToHost,
+                        sg->st[0]));
+    return BLDP_OK;
+  });
+}
+
+// The same staging for the kurtosis over blocks of tblock spectra: the window's
+// rows go to the device once, the (nc, ni, nb) product comes back.
+extern "C" int bldp_kurtosis_blocks_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                             int64_t ntime, const int64_t *win, int64_t tblock,
+                                             double *out) {
+  int64_t sh[3];
+  int rc = bldp_kurtosis_blocks_shape(nchan, nif, ntime, win, tblock, sh);
+  if (rc) return rc;
+  const int64_t nc = sh[0], ni = sh[1], nb = sh[2], nt = nb * tblock;
+  if (nc * ni * nb == 0) return BLDP_OK;
+  if (!out || !in) return bldp::set_error(BLDP_EINVAL, "tblock kurtosis: null pointer");
+  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
+  return with_stager(dev, [&](bldp::Stager *sg) -> int {
+    float *dbuf;
+    double *dout;
+    int r = bldp::stager_buffer(sg, 0, (size_t)(h.span * ni * nt) * 4, (void **)&dbuf);
+    if (!r) r = bldp::stager_buffer(sg, 2, (size_t)(nc * ni * nb) * sizeof(double), (void **)&dout);
+    if (!r) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
+    if (r) return r;
+    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
+    r = bldp_kurtosis_blocks_f32(dbuf, h.span, ni, nt, dwin, tblock, dout, nc, nc * ni, sg->st[0]);
+    if (r) return r;
+    HCHK(hipMemcpyAsync(out, dout, (size_t)(nc * ni * nb) * sizeof(double), hipMemcpyDeviceToHost,
                         sg->st[0]));
     return BLDP_OK;
   });

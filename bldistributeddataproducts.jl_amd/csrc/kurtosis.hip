@@ -46,6 +46,12 @@
 //               16-wave workgroup; the recipe itself for nt <= 1024.
 //   unaligned   k_kurt_leafsum + the same tree (sum only) -> m, then the
 //               recipe in a second pass (k_kurt_pass, k_kurt_fold).
+//
+// Blocks of spectra (tblock = M, one result per block; the end of this file):
+//   M <= 32     k_kurtb_regs  : k_kurt_regs' body per (block, float4 column).
+//   33..1024    k_kurtb_stream: one wave per (block, 256 channels), the leaf
+//               method finished in place by kurt_ratio (a block is one leaf).
+//   otherwise   block by block through the paths above (api.hip).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -1306,6 +1312,237 @@ int64_t kurtosis_max_grid(const KurtArgs &k) {
       return std::max(cdivk(k.nc, kB) * k.nrow * k.nslot,
                       cdivk(cdivk(k.nc, 64), 4 / k.ts) * k.nrow * k.nchunk);
   }
+}
+
+// ---------------------------------------------------------------------------
+// Kurtosis over blocks of spectra (getkurtosis(...; tblock = M)): block b of
+// the window holds its spectra [b*M, (b+1)*M) and out[c, i, b] is what the
+// whole-window kurtosis of that block alone gives.  Float4-column windows with
+// M <= 1024 (one leaf of Julia's tree, so the mean is the sequential Float32
+// sum from the block's first spectrum) take one launch over (bank, IF, block,
+// channel tile); everything else goes block by block through launch_kurtosis
+// (api.hip).  Output element (c, i, b) of bank k at
+// out[k*out_bank + c + i*out_ld_i + b*out_ld_b].
+namespace {
+
+// 16-byte stores where the address allows them, else one value at a time
+template <int W>
+__device__ __forceinline__ void store_kurt(double *o, const double (&r)[W]) {
+  if constexpr (W == 4) {
+    if ((reinterpret_cast<uintptr_t>(o) & 15) == 0) {
+      __builtin_nontemporal_store(d2v{r[0], r[1]}, reinterpret_cast<d2v *>(o));
+      __builtin_nontemporal_store(d2v{r[2], r[3]}, reinterpret_cast<d2v *>(o) + 1);
+      return;
+    }
+  }
+#pragma unroll
+  for (int w = 0; w < W; ++w) o[w] = r[w];
+}
+
+// M <= NTMAX (<= 32): k_kurt_regs' body per (block, float4 column), the
+// recipe in the recipe's order, bit-identical to it.  The lanes of a (bank,
+// IF) row run over (block, column) pairs, column fastest, so narrow products
+// (the 0001 product: 128 columns) still fill their workgroups; when the
+// columns of a block are whole waves (nc % 256 == 0) a wave's 256 results are
+// contiguous and go through LDS to 1 KiB stores as in k_kurt_regs.
+template <int NTMAX, bool EXACT>
+__global__ __launch_bounds__(kB) void k_kurtb_regs(const KurtBlkArgs k) {
+  const int64_t ncols = k.nc / 4;
+  const int64_t per_row = k.nb * ncols;  // (block, column) pairs of a row
+  const int64_t wgs = (per_row + kB - 1) / kB;
+  const int64_t g = blockIdx.x;
+  const int64_t row = g / wgs, u = (g - row * wgs) * kB + threadIdx.x;
+  if (u >= per_row) return;
+  const int64_t b = u / ncols, col = u - b * ncols;
+  const int bank = (int)(row / k.ni);
+  const int64_t i = row - (int64_t)bank * k.ni;
+  const int nt = EXACT ? NTMAX : (int)k.M;
+  const int64_t ld = k.in_ld_t;
+  const float *p = k.in[bank] + k.in_off + i * k.in_ld_i + b * k.M * ld + 4 * col;
+  float4 v[NTMAX];
+#pragma unroll
+  for (int t = 0; t < NTMAX; ++t)
+    if (EXACT || t < nt) v[t] = ldnt(p + t * ld);
+  // Base.sum: sequential Float32 from the block's first spectrum
+  f2v sa = {v[0].x, v[0].y}, sb = {v[0].z, v[0].w};
+#pragma unroll
+  for (int t = 1; t < NTMAX; ++t)
+    if (EXACT || t < nt) {
+      sa += f2v{v[t].x, v[t].y};
+      sb += f2v{v[t].z, v[t].w};
+    }
+  const float m[4] = {sa.x / (float)nt, sa.y / (float)nt, sb.x / (float)nt, sb.y / (float)nt};
+  double c2[4] = {0, 0, 0, 0}, c4[4] = {0, 0, 0, 0};
+#pragma unroll
+  for (int t = 0; t < NTMAX; ++t)
+    if (EXACT || t < nt) {
+      const float x[4] = {v[t].x, v[t].y, v[t].z, v[t].w};
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        const float z = x[w] - m[w];  // StatsBase: z, z2 in Float32; Float64 moments
+        const float z2 = z * z;
+        c2[w] += (double)z2;
+        c4[w] += (double)(z2 * z2);
+      }
+    }
+  double r[4];
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const double cm2 = c2[w] / (double)nt, cm4 = c4[w] / (double)nt;
+    r[w] = (cm4 / (cm2 * cm2)) - 3.0;
+  }
+  double *o = k.out + bank * k.out_bank + i * k.out_ld_i + b * k.out_ld_b + 4 * col;
+  const int lane = threadIdx.x & 63;
+  // (ncols % 64 == 0: a wave lies in one block, per_row is whole waves, and
+  // o - 4*lane is the first of the wave's 256 outputs)
+  if (ncols % 64 == 0 && (reinterpret_cast<uintptr_t>(o - 4 * lane) & 15) == 0) {
+    __shared__ d2v st[4][128];
+    const int wave = threadIdx.x >> 6;
+    st[wave][2 * lane] = d2v{r[0], r[1]};
+    st[wave][2 * lane + 1] = d2v{r[2], r[3]};
+    __builtin_amdgcn_wave_barrier();
+    const d2v a0 = st[wave][lane], a1 = st[wave][64 + lane];
+    d2v *ow = reinterpret_cast<d2v *>(o - 4 * lane);
+    __builtin_nontemporal_store(a0, ow + lane);
+    __builtin_nontemporal_store(a1, ow + 64 + lane);
+  } else {
+    store_kurt<4>(o, r);
+  }
+}
+
+// 32 < M <= 1024: one wave per (block, 64 columns of W channels, bank x IF
+// row) streams the block once, as k_kurt_leaf streams a leaf (B spectra per
+// batch in flight): the sequential Float32 sum from the block's first
+// spectrum (-> Julia's m), max, min and the Float64 power sums about that
+// spectrum, moved to the block's own mean and finished by kurt_ratio.  No
+// tree, no workspace, no second pass; class "leaf" (exact z^2, z^4).
+template <int W, int B>
+__global__ __launch_bounds__(kB) void k_kurtb_stream(const KurtBlkArgs k) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nseg = (k.nc / W + 63) / 64;
+  const int64_t u = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t seg = u % nseg, q = u / nseg;
+  const int64_t b = q % k.nb, row = q / k.nb;
+  const int64_t col = seg * 64 + lane;
+  if (row >= (int64_t)k.nbank * k.ni || col >= k.nc / W) return;
+  const int bank = (int)(row / k.ni);
+  const int64_t i = row - (int64_t)bank * k.ni;
+  const int64_t ld = k.in_ld_t, len = k.M;
+  const float *p = k.in[bank] + k.in_off + i * k.in_ld_i + b * len * ld + W * col;
+  LeafAcc<W> A;
+  {
+    float x0[W];
+    ldw<W>(p, x0);
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+      A.s[w] = A.hi[w] = A.lo[w] = x0[w];  // the sum starts from the first element
+      A.c[w] = (double)x0[w];
+      A.a1[w] = A.a2[w] = A.a3[w] = A.a4[w] = 0.0;
+    }
+  }
+  p += ld;
+  const int64_t rem = len - 1, nbt = rem / B;
+  float cur[B][W];
+  if (nbt > 0) {
+#pragma unroll
+    for (int j = 0; j < B; ++j) ldw<W>(p + j * ld, cur[j]);
+  }
+  for (int64_t bt = 0; bt < nbt; ++bt) {
+    p += B * ld;
+#pragma unroll
+    for (int j = 0; j < B; ++j) leaf_step<W>(A, cur[j]);
+    if (bt + 1 < nbt) {
+#pragma unroll
+      for (int j = 0; j < B; ++j) ldw<W>(p + j * ld, cur[j]);
+    }
+  }
+  const int tail = (int)(rem - nbt * B);
+  if (tail > 0) {
+#pragma unroll
+    for (int j = 0; j < B; ++j)
+      if (j < tail) ldw<W>(p + j * ld, cur[j]);
+#pragma unroll
+    for (int j = 0; j < B; ++j)
+      if (j < tail) leaf_step<W>(A, cur[j]);
+  }
+  // power sums about the first spectrum -> central moments about the block's
+  // own mean (leaf_store's step) -> the recipe's ratio about its Float32 m
+  const double cnt = (double)len;
+  double r[W];
+#pragma unroll
+  for (int w = 0; w < W; ++w) {
+    const double dl = A.a1[w] / cnt, dl2 = dl * dl;
+    const double ma = A.c[w] + dl;
+    const double m2 = A.a2[w] - A.a1[w] * dl;
+    const double m3 = A.a3[w] - 3.0 * dl * A.a2[w] + 2.0 * cnt * dl2 * dl;
+    const double m4 = A.a4[w] - 4.0 * dl * A.a3[w] + 6.0 * dl2 * A.a2[w] - 3.0 * cnt * dl2 * dl2;
+    r[w] = kurt_ratio(len, A.s[w], ma, m2, m3, m4, A.hi[w], A.lo[w]);
+  }
+  store_kurt<W>(k.out + bank * k.out_bank + i * k.out_ld_i + b * k.out_ld_b + W * col, r);
+}
+
+// Block-by-block form: one block's dense [nbank][ni][nc] results into the
+// caller's strided product.
+__global__ __launch_bounds__(kB) void k_kurtb_scatter(const double *src, int64_t nc, int64_t ni,
+                                                      int64_t n, double *out, int64_t out_bank,
+                                                      int64_t out_ld_i) {
+  for (int64_t e = (int64_t)blockIdx.x * kB + threadIdx.x; e < n; e += (int64_t)gridDim.x * kB) {
+    const int64_t c = e % nc, row = e / nc;
+    const int64_t bank = row / ni, i = row - bank * ni;
+    out[bank * out_bank + i * out_ld_i + c] = src[e];
+  }
+}
+
+}  // namespace
+
+// Float4-column windows of blocks of one leaf run in one launch.
+bool kurt_blocks_fused(const KurtArgs &whole, int64_t M) {
+  return whole.vec && M >= 1 && M <= 1024;
+}
+
+// Channels per lane of the streamed form: as plan_kurtosis' "kurt_leaf_narrow",
+// plans with fewer than that many waves per CU at kLeafW channels per lane take
+// one channel per lane (4x the waves) and kLeafNB spectra per batch.
+void plan_kurt_blocks(KurtBlkArgs &k, int num_cus) {
+  k.leafw = kLeafW;
+  const int64_t narrow = opt(OPT_KURT_LEAF_NARROW);
+  const int64_t rows = (int64_t)k.nbank * k.ni;
+  if (narrow > 0 && rows * k.nb * cdivk(k.nc / kLeafW, 64) < num_cus * narrow) k.leafw = 1;
+}
+
+int64_t kurt_blocks_grid(const KurtBlkArgs &k) {
+  const int64_t rows = (int64_t)k.nbank * k.ni;
+  if (k.M <= 32) return cdivk(k.nb * (k.nc / 4), kB) * rows;
+  return cdivk(rows * k.nb * cdivk(k.nc / k.leafw, 64), 4);
+}
+
+hipError_t launch_kurt_blocks(const KurtBlkArgs &k, hipStream_t s) {
+  const dim3 g((unsigned)kurt_blocks_grid(k)), block(kB);
+  if (k.M <= 32) {
+    const bool exact = opt(OPT_KURT_EXACT) != 0;
+    if (exact && k.M == 16)
+      hipLaunchKernelGGL((k_kurtb_regs<16, true>), g, block, 0, s, k);
+    else if (exact && k.M == 32)
+      hipLaunchKernelGGL((k_kurtb_regs<32, true>), g, block, 0, s, k);
+    else if (k.M <= 16)
+      hipLaunchKernelGGL((k_kurtb_regs<16, false>), g, block, 0, s, k);
+    else
+      hipLaunchKernelGGL((k_kurtb_regs<32, false>), g, block, 0, s, k);
+  } else if (k.leafw == 1) {
+    hipLaunchKernelGGL((k_kurtb_stream<1, kLeafNB>), g, block, 0, s, k);
+  } else {
+    hipLaunchKernelGGL((k_kurtb_stream<kLeafW, kLeafB>), g, block, 0, s, k);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_kurt_scatter(const double *src, int64_t nbank, int64_t ni, int64_t nc,
+                               double *out, int64_t out_bank, int64_t out_ld_i, hipStream_t s) {
+  const int64_t n = nbank * ni * nc;
+  const unsigned g = (unsigned)std::min<int64_t>(cdivk(n, kB), 16384);
+  hipLaunchKernelGGL(k_kurtb_scatter, dim3(g), dim3(kB), 0, s, src, nc, ni, n, out, out_bank,
+                     out_ld_i);
+  return hipGetLastError();
 }
 
 }  // namespace bldp

@@ -23,7 +23,7 @@ __all__ = [
     "fb_empty", "fb_from_numpy", "fb_to_numpy", "reduce", "band_reduce", "PreparedBandReduce",
     "band_reduce_multi",
     "stitch",
-    "despike", "kurtosis", "band_kurtosis", "synth", "plan", "reduce_host", "kurtosis_host",
+    "despike", "kurtosis", "kurtosis_blocks_plan", "band_kurtosis", "synth", "plan", "reduce_host", "kurtosis_host",
     "init", "finalize", "pinned",
 ]
 
@@ -580,13 +580,55 @@ def despike(x, nfpc, stream=None):
     return x
 
 
-def kurtosis(x, win=None, stream=None):
-    """Excess kurtosis over time per (channel, IF): (nc, ni) float64 tensor."""
+def _check_tblock(tblock, nt) -> int:
+    """Blocks of ``tblock`` selected spectra: the count nt / tblock, with the
+    library's own errors (bldp_kurtosis_blocks_shape) raised before any launch."""
+    if isinstance(tblock, bool) or int(tblock) != tblock:
+        raise TypeError(f"tblock must be an integer, not {tblock!r}")
+    M = int(tblock)
+    if M < 1:
+        raise _lib.ArgumentError(_lib.BLDP_EINVAL, f"tblock={M} must be >= 1")
+    if nt % M:
+        raise _lib.DimensionMismatch(
+            _lib.BLDP_EDIM, f"DimensionMismatch: tblock={M} does not divide ntime={nt}")
+    return nt // M
+
+
+def _block_win(win, shape, M, b):
+    """The window of block b: spectra [b*M, (b+1)*M) of the selected ones."""
+    w = _full_win(win, shape)
+    w[6] += b * M * w[8]
+    w[7] = M
+    return w
+
+
+def kurtosis(x, win=None, tblock=None, stream=None):
+    """Excess kurtosis over time per (channel, IF): (nc, ni) float64 tensor.
+
+    ``tblock=M``: the kurtosis of every block of M selected spectra, a
+    Julia-order (nc, ni, nt/M) float64 tensor (bldp_kurtosis_blocks_f32: one
+    call; M must divide nt).  Element types other than Float32 go block by
+    block through the typed kurtosis."""
     torch = _torch()
     L = _lib.lib()
     shape = tuple(x.shape)
     _check_bounds(win, shape)
-    nc, ni, _ = window_shape(win, shape)
+    nc, ni, nt = window_shape(win, shape)
+    if tblock is not None:
+        nb = _check_tblock(tblock, nt)
+        M = int(tblock)
+        out = torch.empty((nb, ni, nc), dtype=torch.float64, device=x.device).permute(2, 1, 0)
+        if x.dtype != torch.float32:
+            for b in range(nb):
+                out[:, :, b] = kurtosis(x, _block_win(win, shape, M, b), stream=stream)
+            return out
+        ptr, nchan, nif, ntime = _abi_dims(x)
+        keep, wp = _lib.win_arg(_full_win(win, shape))
+        rc = L.bldp_kurtosis_blocks_f32(ptr, nchan, nif, ntime, wp, M,
+                                        out.data_ptr() if out.numel() else None, nc, nc * ni,
+                                        _lib.stream_ptr(stream))
+        _lib.check(rc, "bldp_kurtosis_blocks_f32")
+        return out
     out = torch.empty((ni, nc), dtype=torch.float64, device=x.device).t()
     ptr, nchan, nif, ntime = _abi_dims(x, allow_typed=True)
     keep, wp = _lib.win_arg(_full_win(win, shape))
@@ -615,9 +657,28 @@ def kurtosis_plan(x, win=None) -> dict:
             "workspace_bytes": info[3]}
 
 
-def band_kurtosis(banks, win=None, stream=None):
+def kurtosis_blocks_plan(x, tblock, win=None) -> dict:
+    """Plan of ``kurtosis(x, win, tblock)``: the path of the blocks ("regs",
+    "mid", "leaf", "twopass": the class of the results), fused (1 = the
+    one-launch kernel, 0 = block by block through the whole-window paths),
+    the block count and the workspace bytes."""
+    L = _lib.lib()
+    shape = tuple(x.shape)
+    _check_bounds(win, shape)
+    _check_tblock(tblock, window_shape(win, shape)[2])
+    ptr, nchan, nif, ntime = _abi_dims(x)
+    info = (ctypes.c_int64 * 4)()
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    _lib.check(L.bldp_kurtosis_blocks_plan_f32(ptr, nchan, nif, ntime, wp, int(tblock), info),
+               "bldp_kurtosis_blocks_plan_f32")
+    return {"path": _lib.KURT_PATHS[info[0]], "fused": int(info[1]), "blocks": int(info[2]),
+            "workspace_bytes": int(info[3])}
+
+
+def band_kurtosis(banks, win=None, tblock=None, stream=None):
     """Kurtosis of every bank of a band on one GPU in one set of launches;
-    returns a list of (nc, ni) float64 tensors (views of one buffer)."""
+    returns a list of (nc, ni) float64 tensors (views of one buffer), or with
+    ``tblock`` of (nc, ni, nt/tblock) ones (bldp_band_kurtosis_blocks_f32)."""
     torch = _torch()
     L = _lib.lib()
     banks = list(banks)
@@ -629,10 +690,19 @@ def band_kurtosis(banks, win=None, stream=None):
         if tuple(b.shape) != shape or _abi_dims(b)[1:] != geo:
             raise ValueError("all banks of a band must have the same shape and layout")
     _check_bounds(win, shape)
-    nc, ni, _ = window_shape(win, shape)
-    buf = torch.empty((len(banks), ni, nc), dtype=torch.float64, device=banks[0].device)
+    nc, ni, nt = window_shape(win, shape)
     ptrs = (ctypes.c_void_p * len(banks))(*[b.data_ptr() for b in banks])
     keep, wp = _lib.win_arg(_full_win(win, shape))
+    if tblock is not None:
+        nb = _check_tblock(tblock, nt)
+        buf = torch.empty((len(banks), nb, ni, nc), dtype=torch.float64, device=banks[0].device)
+        rc = L.bldp_band_kurtosis_blocks_f32(len(banks), ctypes.cast(ptrs, ctypes.c_void_p), *geo,
+                                             wp, int(tblock),
+                                             buf.data_ptr() if buf.numel() else None,
+                                             _lib.stream_ptr(stream))
+        _lib.check(rc, "bldp_band_kurtosis_blocks_f32")
+        return [buf[k].permute(2, 1, 0) for k in range(len(banks))]
+    buf = torch.empty((len(banks), ni, nc), dtype=torch.float64, device=banks[0].device)
     rc = L.bldp_band_kurtosis_f32(len(banks), ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp,
                                   buf.data_ptr() if buf.numel() else None,
                                   _lib.stream_ptr(stream))
@@ -675,14 +745,25 @@ def reduce_host(a: np.ndarray, fqavby=1, tavby=1, op="sum", win=None, device=0) 
     return out
 
 
-def kurtosis_host(a: np.ndarray, win=None, device=0) -> np.ndarray:
-    """Host array in, (nc, ni) float64 host array out (bldp_kurtosis_host_f32)."""
+def kurtosis_host(a: np.ndarray, win=None, device=0, tblock=None) -> np.ndarray:
+    """Host array in, (nc, ni) float64 host array out (bldp_kurtosis_host_f32);
+    with ``tblock`` the (nc, ni, nt/tblock) kurtosis of every block of tblock
+    selected spectra (bldp_kurtosis_blocks_host_f32)."""
     L = _lib.lib()
     a = np.asarray(a)
     if a.dtype != np.float32 or not a.flags.f_contiguous or a.ndim != 3:
         raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
     _check_bounds(win, a.shape)
-    nc, ni, _ = window_shape(win, a.shape)
+    nc, ni, nt = window_shape(win, a.shape)
+    if tblock is not None:
+        nb = _check_tblock(tblock, nt)
+        out = np.empty((nc, ni, nb), dtype=np.float64, order="F")
+        keep, wp = _lib.win_arg(_full_win(win, a.shape))
+        rc = L.bldp_kurtosis_blocks_host_f32(int(device), a.ctypes.data if a.size else None,
+                                             a.shape[0], a.shape[1], a.shape[2], wp, int(tblock),
+                                             out.ctypes.data if out.size else None)
+        _lib.check(rc, "bldp_kurtosis_blocks_host_f32")
+        return out
     out = np.empty((nc, ni), dtype=np.float64, order="F")
     keep, wp = _lib.win_arg(_full_win(win, a.shape))
     rc = L.bldp_kurtosis_host_f32(int(device), a.ctypes.data if a.size else None, a.shape[0],
@@ -714,10 +795,11 @@ def reduce_host_typed(a: np.ndarray, fqavby=1, tavby=1, op="sum", win=None, devi
     return out
 
 
-def kurtosis_host_typed(a: np.ndarray, win=None, device=0) -> np.ndarray:
+def kurtosis_host_typed(a: np.ndarray, win=None, device=0, tblock=None) -> np.ndarray:
     """Host array of any supported element type in, (nc, ni) float64 out
     (bldp_kurtosis_host; StatsBase's recipe in Float64 for non-Float32 rows,
-    8- and 16-bit integer rows from exact integer power sums)."""
+    8- and 16-bit integer rows from exact integer power sums).  With ``tblock``:
+    one such call per block of tblock selected spectra, (nc, ni, nt/tblock)."""
     L = _lib.lib()
     a = np.asarray(a)
     code = _dtype_code(a.dtype)
@@ -725,7 +807,14 @@ def kurtosis_host_typed(a: np.ndarray, win=None, device=0) -> np.ndarray:
         raise TypeError(f"unsupported host filterbank {a.dtype} {a.shape}")
     a = np.asfortranarray(a)
     _check_bounds(win, a.shape)
-    nc, ni, _ = window_shape(win, a.shape)
+    nc, ni, nt = window_shape(win, a.shape)
+    if tblock is not None:
+        nb = _check_tblock(tblock, nt)
+        out = np.empty((nc, ni, nb), dtype=np.float64, order="F")
+        for b in range(nb):
+            out[:, :, b] = kurtosis_host_typed(a, _block_win(win, a.shape, int(tblock), b),
+                                               device=device)
+        return out
     out = np.empty((nc, ni), dtype=np.float64, order="F")
     keep, wp = _lib.win_arg(_full_win(win, a.shape))
     rc = L.bldp_kurtosis_host(int(device), code, a.ctypes.data if a.size else None, a.shape[0],

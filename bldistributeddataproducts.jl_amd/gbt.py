@@ -82,9 +82,11 @@ def getdata(workers, fnames, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum
                    lambda w, f: W.getdata(f, idxs, fqavby, fqavfunc, tavby, device=int(w)))
 
 
-def getkurtosis(workers, fnames, idxs=(COLON, COLON, COLON)):
-    """src/gbt.jl:81-88."""
-    return _fanout(workers, fnames, lambda w, f: W.getkurtosis(f, idxs, device=int(w)))
+def getkurtosis(workers, fnames, idxs=(COLON, COLON, COLON), tblock=None):
+    """src/gbt.jl:81-88; ``tblock`` as in WorkerFunctions.getkurtosis (the
+    kurtosis of every block of tblock selected spectra, (nc, ni, nt/tblock))."""
+    return _fanout(workers, fnames,
+                   lambda w, f: W.getkurtosis(f, idxs, device=int(w), tblock=tblock))
 
 
 def _chan_window(idxs, nchans):

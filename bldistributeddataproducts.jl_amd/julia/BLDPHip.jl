@@ -160,14 +160,29 @@ function gpu_fqav(A, n::Integer; f=sum, tavby::Integer=1, dev::Integer=0)
 end
 
 """
-    gpu_kurtosis(A::Array{Float32,3}; idxs=(:,:,:), dev=0) -> Matrix{Float64}
+    gpu_kurtosis(A::Array{Float32,3}; idxs=(:,:,:), dev=0, tblock=nothing)
 
 getkurtosis' per-(channel, IF) excess kurtosis over time
 (src/gbtworkerfunctions.jl:197-202), computed on GPU `dev`
 (bldp_kurtosis_host_f32: window staged on the device, StatsBase recipe,
-Float64 result)."""
-function gpu_kurtosis(A::Array{Float32,3}; idxs::Tuple=(:, :, :), dev::Integer=0)
+Float64 result): a `Matrix{Float64}`.  With `tblock = M` the selected spectra
+are cut into blocks of M and the result is the `Array{Float64,3}` (nc, ni,
+nt / M) of every block's kurtosis (bldp_kurtosis_blocks_host_f32, one call);
+M must divide the selected spectra (DimensionMismatch)."""
+function gpu_kurtosis(A::Array{Float32,3}; idxs::Tuple=(:, :, :), dev::Integer=0,
+                      tblock::Union{Nothing,Integer}=nothing)
     win = window(idxs, size(A))
+    if tblock !== nothing
+        shp = zeros(Int64, 3)
+        GC.@preserve win check(ccall((:bldp_kurtosis_blocks_shape, libbldp), Cint,
+            (Int64, Int64, Int64, Ptr{Int64}, Int64, Ptr{Int64}),
+            size(A, 1), size(A, 2), size(A, 3), win, tblock, shp))
+        out = Array{Float64,3}(undef, shp...)
+        GC.@preserve A win out check(ccall((:bldp_kurtosis_blocks_host_f32, libbldp), Cint,
+            (Cint, Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Int64, Ptr{Float64}),
+            dev, A, size(A, 1), size(A, 2), size(A, 3), win, tblock, out))
+        return out
+    end
     shp = zeros(Int64, 3)
     GC.@preserve win check(ccall((:bldp_reduce_shape, libbldp), Cint,
         (Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Ptr{Int64}),
@@ -180,12 +195,34 @@ function gpu_kurtosis(A::Array{Float32,3}; idxs::Tuple=(:, :, :), dev::Integer=0
 end
 
 """
-    gpu_kurtosis(A::Array{T,3}; idxs=(:,:,:), dev=0) for T other than Float32
+    gpu_kurtosis(A::Array{T,3}; idxs=(:,:,:), dev=0, tblock=nothing) for T other than Float32
 
 StatsBase.kurtosis of integer or Float64 rows (Float64 throughout: Base.sum's
-pairwise mean, sequential moments), on GPU `dev` (bldp_kurtosis_host)."""
-function gpu_kurtosis(A::Array{T,3}; idxs::Tuple=(:, :, :), dev::Integer=0) where {T<:GPUElt}
+pairwise mean, sequential moments), on GPU `dev` (bldp_kurtosis_host).  With
+`tblock = M`: one such call per block of M selected spectra, stacked along the
+third axis."""
+function gpu_kurtosis(A::Array{T,3}; idxs::Tuple=(:, :, :), dev::Integer=0,
+                      tblock::Union{Nothing,Integer}=nothing) where {T<:GPUElt}
     win = window(idxs, size(A))
+    if tblock !== nothing
+        shp = zeros(Int64, 3)
+        GC.@preserve win check(ccall((:bldp_kurtosis_blocks_shape, libbldp), Cint,
+            (Int64, Int64, Int64, Ptr{Int64}, Int64, Ptr{Int64}),
+            size(A, 1), size(A, 2), size(A, 3), win, tblock, shp))
+        out = Array{Float64,3}(undef, shp...)
+        # (window(...) of (:,:,:) is a null pointer: spell the whole array out)
+        bwin = win isa Ptr ? Int64[0, size(A, 1), 1, 0, size(A, 2), 1, 0, size(A, 3), 1] : copy(win)
+        t0 = bwin[7]
+        bwin[8] = tblock
+        for b in 1:shp[3]
+            bwin[7] = t0 + (b - 1) * tblock * bwin[9]
+            o = view(out, :, :, b)
+            GC.@preserve A bwin out check(ccall((:bldp_kurtosis_host, libbldp), Cint,
+                (Cint, Cint, Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Int64}, Ptr{Float64}),
+                dev, dtypecode(T), A, size(A, 1), size(A, 2), size(A, 3), bwin, pointer(o)))
+        end
+        return out
+    end
     shp = zeros(Int64, 3)
     GC.@preserve win check(ccall((:bldp_reduce_shape, libbldp), Cint,
         (Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Ptr{Int64}),

@@ -360,12 +360,14 @@ def getdata(fname, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum", tavby=1
     return getfbdata(fname, idxs, fqavby, fqavfunc, tavby, device)
 
 
-def getkurtosis(fname, idxs=(COLON, COLON, COLON), device=0):
+def getkurtosis(fname, idxs=(COLON, COLON, COLON), device=0, tblock=None):
     """Excess kurtosis of every (channel, IF) row over time, Float64 (nc, ni)
-    (src/gbtworkerfunctions.jl:197-202)."""
+    (src/gbtworkerfunctions.jl:197-202).  With ``tblock=M`` the selected
+    spectra are cut into blocks of M and the result is the (nc, ni, nt/M)
+    kurtosis of every block (M must divide nt: DimensionMismatch)."""
     idxs = sanitizeidxs(idxs)
     if _is_tensor(fname):
-        return engine.kurtosis(fname, to_window(idxs, fname.shape))
+        return engine.kurtosis(fname, to_window(idxs, fname.shape), tblock=tblock)
     if isinstance(fname, (str, bytes)) or hasattr(fname, "__fspath__"):
         from . import fbh5
 
@@ -379,7 +381,7 @@ def getkurtosis(fname, idxs=(COLON, COLON, COLON), device=0):
                                                   raw_chunks=not fbh5.needs_bslz4(fname),
                                                   dense=False)
             with torch.cuda.device(x.device):
-                return engine.fb_to_numpy(engine.kurtosis(x, rwin))
+                return engine.fb_to_numpy(engine.kurtosis(x, rwin, tblock=tblock))
         raw = fbh5.raw_layout(fname) if h5 else readers.fil_raw_layout(fname)
         got = _raw_to_device(fname, raw, idxs, device) if raw is not None else None
         if got is not None:  # window streamed to the GPU, kurtosis there
@@ -387,7 +389,7 @@ def getkurtosis(fname, idxs=(COLON, COLON, COLON), device=0):
 
             x, rwin = got
             with torch.cuda.device(x.device):
-                return engine.fb_to_numpy(engine.kurtosis(x, rwin))
+                return engine.fb_to_numpy(engine.kurtosis(x, rwin, tblock=tblock))
         if h5:
             a, idxs = readers.fbh5_read(fname, idxs), (COLON, COLON, COLON)
         else:
@@ -399,8 +401,8 @@ def getkurtosis(fname, idxs=(COLON, COLON, COLON), device=0):
     if a.dtype != np.float32:  # StatsBase in Float64 for integer / Float64 rows (:200)
         if engine._dtype_code(a.dtype) is None:
             raise TypeError(f"getkurtosis: element type {a.dtype} is not supported")
-        return engine.kurtosis_host_typed(a, win, device=device)
-    return engine.kurtosis_host(np.asfortranarray(a), win, device=device)
+        return engine.kurtosis_host_typed(a, win, device=device, tblock=tblock)
+    return engine.kurtosis_host(np.asfortranarray(a), win, device=device, tblock=tblock)
 
 
 getinventory = readers.getinventory

@@ -325,6 +325,46 @@ BLDP_API int bldp_band_kurtosis_f32(int nbank, const float *const *in, int64_t n
 BLDP_API int bldp_kurtosis_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
                                     int64_t ntime, const int64_t *win, double *out);
 
+/* Kurtosis over blocks of spectra (getkurtosis(...; tblock)): the window's
+ * selected spectra are cut into nb = nt / tblock blocks, block b holding
+ * spectra [b*tblock, (b+1)*tblock), and element (c, i, b) of the (nc, ni, nb)
+ * float64 result is what bldp_kurtosis_f32 gives for block b alone (the same
+ * recipe, Base.sum's Float32 mean of the block).  tblock < 1 is BLDP_EINVAL,
+ * a tblock that does not divide nt BLDP_EDIM (the rule of tavby).  Additive in
+ * ABI 5.
+ *
+ * Float4-column windows (unit channel step, channel count a multiple of 4)
+ * with tblock <= 1024 run in one launch with no workspace: tblock <= 32
+ * bit-identical to the recipe, longer blocks with the moments exact in
+ * Float64 (the "leaf" class).  Every other shape runs block by block through
+ * the paths of bldp_kurtosis_f32 inside the call, on `stream`, with library
+ * scratch leased once.  Asynchronous.
+ *
+ * bldp_kurtosis_blocks_shape: dims = {nc, ni, nb}; every argument check.
+ * bldp_kurtosis_blocks_plan_f32: info = {path of the blocks (as
+ * bldp_kurtosis_plan_f32), 1 = the one-launch form / 0 = block by block, nb,
+ * workspace bytes}; launches nothing and needs no GPU.
+ * bldp_kurtosis_blocks_f32: element (c, i, b) at out[c + i*out_ld_i +
+ * b*out_ld_b] (elements; dense = (nc, nc*ni)).
+ * bldp_band_kurtosis_blocks_f32: in[] is a HOST array of device pointers; out
+ * is dense [nbank][nb][ni][nc], one set of launches for the band.
+ * bldp_kurtosis_blocks_host_f32: host in, host (nc, ni, nb) out; the window's
+ * rows are staged on device `dev`.  Synchronous. */
+BLDP_API int bldp_kurtosis_blocks_shape(int64_t nchan, int64_t nif, int64_t ntime,
+                                        const int64_t *win, int64_t tblock, int64_t dims[3]);
+BLDP_API int bldp_kurtosis_blocks_plan_f32(const float *in, int64_t nchan, int64_t nif,
+                                           int64_t ntime, const int64_t *win, int64_t tblock,
+                                           int64_t info[4]);
+BLDP_API int bldp_kurtosis_blocks_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                                      const int64_t *win, int64_t tblock, double *out,
+                                      int64_t out_ld_i, int64_t out_ld_b, void *stream);
+BLDP_API int bldp_band_kurtosis_blocks_f32(int nbank, const float *const *in, int64_t nchan,
+                                           int64_t nif, int64_t ntime, const int64_t *win,
+                                           int64_t tblock, double *out, void *stream);
+BLDP_API int bldp_kurtosis_blocks_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                           int64_t ntime, const int64_t *win, int64_t tblock,
+                                           double *out);
+
 /* Element types other than Float32 (what Blio maps SIGPROC nbits 8 / 16 to, and
  * what HDF5.jl returns for an integer or Float64 dataset: the reference's
  * readers hand any of them to fqav / kurtosis, src/gbtworkerfunctions.jl:173,
