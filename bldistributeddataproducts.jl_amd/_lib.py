@@ -22,6 +22,11 @@ PATHS = {0: "vector", 1: "narrow", 2: "scalar", 3: "tile", 4: "interleaved", 5: 
          6: "narrow_mis", 7: "lane", 8: "moments", 9: "median_sort", 10: "median_select",
          11: "median_stream"}
 KURT_PATHS = {0: "regs", 1: "mid", 2: "leaf", 3: "twopass"}
+# tavfunc var / std / median (csrc/tstats.hip): blocks of <= 32 spectra in
+# registers, longer ones split over the time slices of a workgroup, and var /
+# std of blocks too few to fill the GPU also over workgroups (time chunks)
+TSTAT_PATHS = {0: "regs_moments", 1: "regs_median", 2: "split_moments", 3: "split_median",
+               4: "chunk_moments"}
 
 BLDP_OK, BLDP_EINVAL, BLDP_EDIM, BLDP_EHIP, BLDP_ENOMEM, BLDP_EBOUNDS = 0, -1, -2, -3, -5, -6
 BLDP_ECOMM, BLDP_EIO = -7, -8
@@ -97,6 +102,11 @@ SIGNATURES = {
     "bldp_kurtosis_blocks_f32": ([P, I64, I64, I64, P, I64, P, I64, I64, P], I),
     "bldp_band_kurtosis_blocks_f32": ([I, P, I64, I64, I64, P, I64, P, P], I),
     "bldp_kurtosis_blocks_host_f32": ([I, P, I64, I64, I64, P, I64, P], I),
+    "bldp_tstat_shape": ([I64, I64, I64, P, I64, P], I),
+    "bldp_tstat_plan_f32": ([P, I64, I64, I64, P, I64, I, P, P], I),
+    "bldp_tstat_f32": ([P, I64, I64, I64, P, I64, I, P, I64, I64, P], I),
+    "bldp_band_tstat_f32": ([I, P, I64, I64, I64, P, I64, I, P, P], I),
+    "bldp_tstat_host_f32": ([I, P, I64, I64, I64, P, I64, I, P], I),
     "bldp_fqav_range": ([D, D, I64, I64, P, P, P], I),
     "bldp_synth_f32": ([P, I64, I64, I64, I64, U64, I, P], I),
     "bldp_reduce_out_dtype": ([I, I], I),

@@ -1050,6 +1050,147 @@ int bldp_band_kurtosis_blocks_f32(int nbank, const float *const *in, int64_t nch
                   d[0] * d[1], stream);
 }
 
+// ---- tavfunc: median / var / std over blocks of spectra ---------------------
+// Checks, window and plan of a tstat (every entry point): *copy when tavby <= 1
+// (fqav's n <= 1 rule: the window itself, whatever the op).
+static int tstat_prepare(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                         int64_t ntime, const int64_t *win, int64_t tavby, int op, float *out,
+                         int64_t out_bank, int64_t out_ld_i, int64_t out_ld_b, bool query,
+                         TStatArgs *ap, TStatPlan *pp, bool *copy, bool *empty) {
+  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
+    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
+  if (!stat_op(op))
+    return fail(BLDP_EINVAL,
+                "tstat: op %d is not 4=var 5=std 6=median (sum/mean/max/min over time: "
+                "bldp_reduce_* with tavby)",
+                op);
+  Geo g;
+  int rc = resolve_window(nchan, nif, ntime, win, &g);
+  if (rc) return rc;
+  int64_t F, T;
+  rc = resolve_factors(g, 1, tavby, &F, &T);
+  if (rc) return rc;
+  *copy = T <= 1;
+  TStatArgs &a = *ap;
+  a = TStatArgs{};
+  a.nbank = nbank;
+  a.nc = g.nc;
+  a.ni = g.ni;
+  a.T = T;
+  a.nb = g.nt / T;
+  a.in_off = g.off;
+  a.in_cs = g.cs;
+  a.in_ld_i = g.ld_i;
+  a.in_ld_t = g.ld_t;
+  a.out = out;
+  a.out_bank = out_bank;
+  a.out_ld_i = out_ld_i;
+  a.out_ld_b = out_ld_b;
+  *empty = a.nc == 0 || a.ni == 0 || a.nb == 0;
+  if (!in) return fail(BLDP_EINVAL, "tstat: null input pointer array");
+  bool words = true;
+  for (int b = 0; b < nbank; ++b) {
+    a.in[b] = in[b];
+    words = words && aligned4(in[b]);
+  }
+  *pp = TStatPlan{};
+  if (!*copy) {
+    rc = plan_tstat(a, op, words, num_cus_current(), xcd_log2_current(), pp);
+    if (rc) return rc;
+  }
+  if (!query && !*empty) {
+    for (int b = 0; b < nbank; ++b)
+      if (!in[b]) return fail(BLDP_EINVAL, "tstat: null input pointer (bank %d)", b);
+    if (!out) return fail(BLDP_EINVAL, "tstat: null output pointer");
+    if (out_ld_i < a.nc || out_ld_b < (a.ni - 1) * out_ld_i + a.nc ||
+        (nbank > 1 && out_bank < a.nc))
+      return fail(BLDP_EINVAL,
+                  "tstat: out strides (%lld, %lld) overlap for a (%lld, %lld, %lld) result",
+                  (long long)out_ld_i, (long long)out_ld_b, (long long)a.nc, (long long)a.ni,
+                  (long long)a.nb);
+  }
+  return BLDP_OK;
+}
+
+static int tstat_run(int nbank, const float *const *in, int64_t nchan, int64_t nif, int64_t ntime,
+                     const int64_t *win, int64_t tavby, int op, float *out, int64_t out_bank,
+                     int64_t out_ld_i, int64_t out_ld_b, void *stream) {
+  TStatArgs a;
+  TStatPlan p;
+  bool copy = false, empty = false;
+  int rc = tstat_prepare(nbank, in, nchan, nif, ntime, win, tavby, op, out, out_bank, out_ld_i,
+                         out_ld_b, false, &a, &p, &copy, &empty);
+  if (rc || empty) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (copy)  // the window itself: the reduce's F = T = 1 copy
+    return reduce_impl(nbank, in, nchan, nif, ntime, win, 1, 1, BLDP_OP_SUM, out, out_bank,
+                       out_ld_i, out_ld_b, false, s, nullptr);
+  ScratchLease lease;  // held until the launches are queued
+  if (p.ws_bytes) {
+    rc = scratch_lease(s, p.ws_bytes, &lease);
+    if (rc) return rc;
+    a.ws = (double *)lease.ptr;
+  }
+  hipError_t e = launch_tstat(a, p, op, s);
+  if (e != hipSuccess) return fail(BLDP_EHIP, "tstat launch: %s", hipGetErrorString(e));
+  return BLDP_OK;
+}
+
+int bldp_tstat_shape(int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win, int64_t tavby,
+                     int64_t dims[3]) {
+  return bldp_reduce_shape(nchan, nif, ntime, win, 1, tavby, dims);
+}
+
+int bldp_tstat_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                        const int64_t *win, int64_t tavby, int op, const float *out,
+                        int64_t info[8]) {
+  if (!info) return fail(BLDP_EINVAL, "null info");
+  TStatArgs a;
+  TStatPlan p;
+  bool copy = false, empty = false;
+  const float *ins[1] = {in};
+  int rc = tstat_prepare(1, ins, nchan, nif, ntime, win, tavby, op, (float *)out, 0, 0, 0, true,
+                         &a, &p, &copy, &empty);
+  if (rc) return rc;
+  if (copy) {  // the plan of the copy (bldp_reduce_plan_f32 of F = T = 1), path -1
+    rc = bldp_reduce_plan_f32(in, nchan, nif, ntime, win, 1, 1, BLDP_OP_SUM, out, info);
+    if (rc) return rc;
+    const int64_t grid = info[5], ws = info[6];
+    info[0] = -1, info[1] = 1, info[2] = 1, info[3] = 1, info[4] = grid, info[5] = ws;
+    info[6] = a.nb, info[7] = 0;
+    return BLDP_OK;
+  }
+  info[0] = p.path;
+  info[1] = p.cpl;
+  info[2] = p.tsplit;
+  info[3] = p.passes;
+  info[4] = p.grid;
+  info[5] = (int64_t)p.ws_bytes;
+  info[6] = a.nb;
+  info[7] = p.tsplit > 1 ? ((int64_t)1 << a.lx_log2) : 0;
+  return BLDP_OK;
+}
+
+int bldp_tstat_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win,
+                   int64_t tavby, int op, float *out, int64_t out_ld_i, int64_t out_ld_b,
+                   void *stream) {
+  const float *ins[1] = {in};
+  return tstat_run(1, ins, nchan, nif, ntime, win, tavby, op, out, 0, out_ld_i, out_ld_b, stream);
+}
+
+int bldp_band_tstat_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                        int64_t ntime, const int64_t *win, int64_t tavby, int op, float *out,
+                        void *stream) {
+  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
+    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
+  int64_t d[3];
+  int rc = bldp_tstat_shape(nchan, nif, ntime, win, tavby, d);
+  if (rc) return rc;
+  // the vcat of the banks: bank k's channels at k*nc of every (IF, block) row
+  return tstat_run(nbank, in, nchan, nif, ntime, win, tavby, op, out, d[0], nbank * d[0],
+                   nbank * d[0] * d[1], stream);
+}
+
 int bldp_reduce_out_dtype(int dtype, int op) {
   const int d = typed_out_dtype(dtype, op);
   if (d < 0) return fail(BLDP_EINVAL, "unknown element type %d or op %d", dtype, op);

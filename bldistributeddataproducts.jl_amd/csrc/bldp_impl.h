@@ -155,6 +155,44 @@ inline bool stat_op(int op) { return op >= BLDP_OP_VAR && op <= BLDP_OP_MEDIAN; 
 int plan_stats(RedArgs &a, int op, bool words, int xcd_lg, Plan *p);
 hipError_t launch_stats(const RedArgs &a, const Plan &p, int op, hipStream_t s);
 
+// median / var / std of every block of T selected spectra of every (channel,
+// IF) column (tstats.hip): tavfunc, fqav's rule on the time axis.  Window
+// element (c, i, t) of bank k at in[k][in_off + c*in_cs + i*in_ld_i +
+// t*in_ld_t], output (c, i, b) at out[k*out_bank + c + i*out_ld_i + b*out_ld_b].
+struct TStatArgs {
+  const float *in[BLDP_MAX_BANKS];  // banks with identical geometry
+  float *out;
+  int32_t nbank;
+  int32_t vec;      // float4 columns (4 channels per lane), else one
+  int32_t lx_log2;  // split form: log2 of a workgroup's lanes along the channels
+  int32_t xcd_lg;   // log2 XCDs of the per-XCD tile order, 0 = off
+  int64_t in_off, in_cs, in_ld_i, in_ld_t;
+  int64_t nc, ni, T, nb;
+  int64_t ncg;      // column groups: nc / (4 or 1)
+  int64_t ctiles;   // split form: channel tiles of 2^lx_log2 column groups
+  int64_t out_bank, out_ld_i, out_ld_b;
+  // chunked moments: a block's spectra in nchunk chunks of tchunk, one workgroup
+  // each; ws holds the partials, Float64 [2][nchunk][nbank][nb][ni][nc]
+  int32_t nchunk;
+  int64_t tchunk;
+  double *ws;
+};
+enum TStatPath { TSTAT_REGS_MOMENTS = 0, TSTAT_REGS_MEDIAN = 1, TSTAT_SPLIT_MOMENTS = 2,
+                 TSTAT_SPLIT_MEDIAN = 3, TSTAT_CHUNK_MOMENTS = 4 };
+struct TStatPlan {
+  int path;
+  int cpl;          // channels per lane
+  int tsplit;       // time slices of a workgroup splitting a block (1: register form)
+  int passes;       // reads of the block
+  int64_t grid;     // workgroups of 256 threads (per bank)
+  size_t ws_bytes;  // workspace (the chunked moments' partials, else 0)
+};
+// Fills the launch geometry of an args struct whose shape / stride fields are
+// set (`words`: every bank pointer is dword-aligned); BLDP_OK or, with the
+// message recorded, BLDP_EINVAL for a launch too large for one grid.
+int plan_tstat(TStatArgs &a, int op, bool words, int num_cus, int xcd_lg, TStatPlan *p);
+hipError_t launch_tstat(const TStatArgs &a, const TStatPlan &p, int op, hipStream_t s);
+
 hipError_t launch_stitch(int nbank, const float *g, int64_t nc, int64_t nrows, float *out,
                          hipStream_t s);
 hipError_t launch_despike(float *d, int64_t nchan, int64_t nrows, int64_t nfpc, int64_t nspike,

@@ -222,6 +222,39 @@ extern "C" int bldp_kurtosis_blocks_host_f32(int dev, const float *in, int64_t n
   });
 }
 
+// The same staging for tavfunc's var / std / median over blocks of tavby
+// spectra: the window's rows go to the device once (in window order: a
+// reversed time range is staged reversed), the (nc, ni, nb) product comes back.
+extern "C" int bldp_tstat_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                   int64_t ntime, const int64_t *win, int64_t tavby, int op,
+                                   float *out) {
+  int64_t sh[3];
+  int rc = bldp_tstat_shape(nchan, nif, ntime, win, tavby, sh);
+  if (rc) return rc;
+  // (the op check, before any staging)
+  int64_t info[8];
+  rc = bldp_tstat_plan_f32(nullptr, nchan, nif, ntime, win, tavby, op, nullptr, info);
+  if (rc) return rc;
+  const int64_t T = tavby <= 1 ? 1 : tavby;
+  const int64_t nc = sh[0], ni = sh[1], nb = sh[2], nt = nb * T;
+  if (nc * ni * nb == 0) return BLDP_OK;
+  if (!out || !in) return bldp::set_error(BLDP_EINVAL, "tstat: null pointer");
+  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
+  return with_stager(dev, [&](bldp::Stager *sg) -> int {
+    float *dbuf, *dout;
+    int r = bldp::stager_buffer(sg, 0, (size_t)(h.span * ni * nt) * 4, (void **)&dbuf);
+    if (!r) r = bldp::stager_buffer(sg, 2, (size_t)(nc * ni * nb) * sizeof(float), (void **)&dout);
+    if (!r) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
+    if (r) return r;
+    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
+    r = bldp_tstat_f32(dbuf, h.span, ni, nt, dwin, tavby, op, dout, nc, nc * ni, sg->st[0]);
+    if (r) return r;
+    HCHK(hipMemcpyAsync(out, dout, (size_t)(nc * ni * nb) * sizeof(float), hipMemcpyDeviceToHost,
+                        sg->st[0]));
+    return BLDP_OK;
+  });
+}
+
 // ---------------------------------------------------------------------------
 // Host forms of the typed entry points (include/bldp.h), staged like the
 // Float32 forms above: only the window's rows (its channel span of every

@@ -1,0 +1,634 @@
+// tstats.hip — tavfunc median, var and std of Float32 windows (gfx950).
+//
+// Julia's Statistics applied along time, fqav's rule on axis 3: one result per
+// block of T selected spectra (b T .. b T + T - 1) of every (channel, IF)
+// column, R[c, i, b] = f(A[c, i, bT+1 : (b+1)T]).  The rules are those of
+// stats.hip (the channel-axis forms): the corrected variance about the mean,
+// its root, the median ordered by isless with middle(a, b) = a/2 + b/2 of an
+// even block and NaN for a block holding a NaN.
+//
+// The window geometry is the reduce's (any channel offset, step and direction,
+// IF and time steps).  A column's T values lie in_ld_t apart, so consecutive
+// lanes own consecutive channels and every load is a row segment: float4 per
+// lane (4 columns) on unit-step windows whose channel count is a multiple of
+// 4, at any dword alignment (f4u), one dword per lane otherwise.
+//
+//   T <= 32    register form (k_tstat_regs): a lane holds its columns' T values
+//              in registers, templated on the next power of two and fully
+//              unrolled (a register array indexed at run time would go to
+//              scratch).  var / std: mean = K + sum(x - K) / T with K the
+//              block's first element, then the squared deviations (the recipe
+//              of stats.hip k_mom_lanes: a constant block gives exactly 0.0).
+//              median: the order-preserving uint32 keys, padded with the
+//              maximal key, through a bitonic compare-exchange network in
+//              registers; the two ranks are picked by an unrolled chain.
+//   T > 32     split form: a workgroup takes a tile of 2^lx_log2 lanes of
+//              channels and one block; its 256 >> lx_log2 time slices stride
+//              the block's spectra and meet through LDS.
+//              k_tstat_mom_split: two passes (sum(x - K), then the squared
+//              deviations about the mean; the second read hits L2 / MALL where
+//              the tile's block fits), Float64 accumulators.  Blocks too few
+//              to fill the GPU are cut into time chunks, one workgroup each:
+//              k_tstat_mom_chunk leaves the chunks' partials in a workspace
+//              (sum(x - K), then the squared deviations about the mean of the
+//              partials added in chunk order), k_tstat_mom_finish adds them.
+//              k_tstat_med_split: an MSB-first radix select of rank (T-1)/2,
+//              8 bits a pass, one 256-bin LDS histogram per column (<= 32
+//              columns a workgroup), the block re-read every pass.  The last
+//              pass also tells how many keys equal the selected one; rank T/2
+//              of an even block is that key again, or else the smallest key
+//              above it, found by a fifth pass.
+#include <hip/hip_ext.h>
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "bldp_impl.h"
+
+namespace bldp {
+namespace {
+
+constexpr int kBlock = 256;  // 4 waves of 64
+// a float4 on any dword boundary (kernels.hip f4u)
+typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
+
+constexpr int64_t kRegMaxT = 32;  // k_tstat_regs
+constexpr int kMedCols = 32;      // k_tstat_med_split: columns (histograms) per workgroup
+constexpr int kScanLanes = kBlock / kMedCols;  // lanes scanning one column's histogram
+constexpr int kScanBins = 256 / kScanLanes;    // bins each of them sums
+constexpr int64_t kChunkMin = 4096;            // chunked moments: spectra a chunk, at least
+
+// the CPL values of consecutive channels at p (CPL = 4: unit channel step)
+template <int CPL>
+__device__ __forceinline__ void ldcols(const float *p, float (&x)[CPL]) {
+  if constexpr (CPL == 4) {
+    const f4u v = *reinterpret_cast<const f4u *>(p);
+    x[0] = v.x, x[1] = v.y, x[2] = v.z, x[3] = v.w;
+  } else {
+    x[0] = *p;
+  }
+}
+
+// q = x / d, r = x % d for x >= 0 and a wave-uniform d > 0 (stats.hip divmod)
+__device__ __forceinline__ void divmod(int64_t x, int64_t d, int64_t &q, int64_t &r) {
+  if ((d & (d - 1)) == 0) {
+    q = x >> __builtin_ctzll((unsigned long long)d);
+    r = x & (d - 1);
+  } else if ((((uint64_t)x | (uint64_t)d) >> 32) == 0) {
+    const uint32_t q32 = (uint32_t)x / (uint32_t)d;
+    q = q32;
+    r = (uint32_t)x - q32 * (uint32_t)d;
+  } else {
+    q = x / d;
+    r = x - q * d;
+  }
+}
+
+// isless order of Float32 as unsigned order (NaN aside), as stats.hip
+__device__ __forceinline__ uint32_t f2key(float x) {
+  const uint32_t u = __float_as_uint(x);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float key2f(uint32_t k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+// Statistics.middle(a, b) = a/2 + b/2, each half rounded before the sum.  The
+// products must not be contracted into a fused multiply-add: fma(a, 0.5, b/2)
+// of a = -1e-45, b = 0 keeps the exact -2^-150 and rounds to -0.0 where
+// -0.0 + 0.0 is +0.0 (hipcc contracts by default, __fmul_rn or not).
+__device__ __forceinline__ float middle(float x, float y) {
+#pragma clang fp contract(off)
+  const float hx = x * 0.5f, hy = y * 0.5f;
+  return hx + hy;
+}
+__device__ __forceinline__ float median_of(uint32_t k0, uint32_t k1, bool odd, bool nan) {
+  if (nan) return __uint_as_float(0x7fc00000u);
+  return odd ? key2f(k0) : middle(key2f(k0), key2f(k1));
+}
+constexpr uint32_t kPadKey = 0xffffffffu;  // above every non-NaN key
+
+// ---------------------------------------------------------------------------
+// T <= TP <= 32: the block in registers
+
+template <int TP, int CPL, bool MED>
+__global__ __launch_bounds__(kBlock) void k_tstat_regs(const TStatArgs a, const int op) {
+  const int64_t tile = xcd_order(blockIdx.x, gridDim.x, a.xcd_lg);
+  const int64_t item = tile * kBlock + threadIdx.x;
+  if (item >= a.ncg * a.ni * a.nb) return;  // (no shuffle or barrier below)
+  int64_t cg, r, i, b;
+  divmod(item, a.ncg, r, cg);
+  divmod(r, a.ni, b, i);
+  const float *p = a.in[blockIdx.y] + a.in_off + cg * CPL * a.in_cs + i * a.in_ld_i +
+                   b * a.T * a.in_ld_t;
+  float *o = a.out + blockIdx.y * a.out_bank + cg * CPL + i * a.out_ld_i + b * a.out_ld_b;
+  const int T = (int)a.T;
+  float v[TP][CPL];
+#pragma unroll
+  for (int t = 0; t < TP; ++t)
+    if (t < T) ldcols<CPL>(p + t * a.in_ld_t, v[t]);
+  if constexpr (!MED) {
+    const float n = (float)T;
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+      const float K = v[0][c];
+      float s = 0.0f;  // of x - K
+#pragma unroll
+      for (int t = 0; t < TP; ++t)
+        if (t < T) s += v[t][c] - K;
+      const float mean = K + s / n;
+      float q = 0.0f;
+#pragma unroll
+      for (int t = 0; t < TP; ++t)
+        if (t < T) {
+          const float d = v[t][c] - mean;
+          q += d * d;
+        }
+      const float var = q / (n - 1.0f);
+      o[c] = op == BLDP_OP_STD ? sqrtf(var) : var;
+    }
+  } else {
+    uint32_t k[TP][CPL];
+    bool nan[CPL];
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) nan[c] = false;
+#pragma unroll
+    for (int t = 0; t < TP; ++t)
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) {
+        if (t < T) {
+          nan[c] = nan[c] || v[t][c] != v[t][c];
+          k[t][c] = f2key(v[t][c]);
+        } else {
+          k[t][c] = kPadKey;
+        }
+      }
+    // bitonic network over the time index: runs of kk keys, ascending where
+    // (e & kk) == 0; every index is a compile-time constant
+#pragma unroll
+    for (int kk = 2; kk <= TP; kk *= 2) {
+#pragma unroll
+      for (int j = kk / 2; j >= 1; j /= 2) {
+#pragma unroll
+        for (int e = 0; e < TP; ++e) {
+          if ((e & j) == 0) {
+            const bool up = kk == TP || (e & kk) == 0;
+#pragma unroll
+            for (int c = 0; c < CPL; ++c) {
+              const uint32_t lo = min(k[e][c], k[e | j][c]), hi = max(k[e][c], k[e | j][c]);
+              k[e][c] = up ? lo : hi;
+              k[e | j][c] = up ? hi : lo;
+            }
+          }
+        }
+      }
+    }
+    // ranks (T-1)/2 and T/2 (the same for odd T); the padding sorts above them
+    const int q0 = (T - 1) / 2, q1 = T / 2;
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+      uint32_t k0 = 0, k1 = 0;
+#pragma unroll
+      for (int e = 0; e < TP; ++e) {
+        k0 = e == q0 ? k[e][c] : k0;
+        k1 = e == q1 ? k[e][c] : k1;
+      }
+      o[c] = median_of(k0, k1, T & 1, nan[c]);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// T > 32: the time slices of a workgroup split the block
+
+// The tile of workgroup x: channel tile ct of (IF i, block b); thread tid is
+// lane tx of the tile's lx lanes (column group cg) in time slice ty.
+struct SplitGeo {
+  int lx, tx, ty, ny;
+  int64_t cg, i, b;
+  bool ok;  // the column group exists
+};
+__device__ __forceinline__ SplitGeo split_geo(const TStatArgs &a) {
+  SplitGeo g;
+  g.lx = 1 << a.lx_log2;
+  g.tx = threadIdx.x & (g.lx - 1);
+  g.ty = threadIdx.x >> a.lx_log2;
+  g.ny = kBlock >> a.lx_log2;
+  int64_t ct, r;
+  divmod(blockIdx.x, a.ctiles, r, ct);
+  divmod(r, a.ni, g.b, g.i);
+  g.cg = ct * g.lx + g.tx;
+  g.ok = g.cg < a.ncg;
+  return g;
+}
+
+template <int CPL>
+__global__ __launch_bounds__(kBlock) void k_tstat_mom_split(const TStatArgs a, const int op) {
+  __shared__ double sh[kBlock][CPL];
+  const SplitGeo g = split_geo(a);
+  const int64_t T = a.T;
+  const float *p = a.in[blockIdx.y] + a.in_off + (g.ok ? g.cg : 0) * CPL * a.in_cs +
+                   g.i * a.in_ld_i + g.b * T * a.in_ld_t;
+  // sum over the time slices of this lane's columns, the same value (the same
+  // order of additions) in every slice
+  auto meet = [&](double (&x)[CPL]) {
+    __syncthreads();  // (sh is free again)
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) sh[threadIdx.x][c] = x[c];
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) x[c] = 0.0;
+    for (int y = 0; y < g.ny; ++y)
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) x[c] += sh[y * g.lx + g.tx][c];
+  };
+  float K[CPL];  // the block's first element
+#pragma unroll
+  for (int c = 0; c < CPL; ++c) K[c] = 0.0f;
+  if (g.ok) ldcols<CPL>(p, K);
+  double s[CPL];  // of x - K
+#pragma unroll
+  for (int c = 0; c < CPL; ++c) s[c] = 0.0;
+  if (g.ok) {
+#pragma unroll 4
+    for (int64_t t = g.ty; t < T; t += g.ny) {
+      float x[CPL];
+      ldcols<CPL>(p + t * a.in_ld_t, x);
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) s[c] += (double)x[c] - (double)K[c];
+    }
+  }
+  meet(s);
+  double mean[CPL], q[CPL];
+#pragma unroll
+  for (int c = 0; c < CPL; ++c) mean[c] = (double)K[c] + s[c] / (double)T, q[c] = 0.0;
+  if (g.ok) {
+#pragma unroll 4
+    for (int64_t t = g.ty; t < T; t += g.ny) {
+      float x[CPL];
+      ldcols<CPL>(p + t * a.in_ld_t, x);
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) {
+        const double d = (double)x[c] - mean[c];
+        q[c] += d * d;
+      }
+    }
+  }
+  meet(q);
+  if (g.ok && g.ty == 0) {
+    float *o = a.out + blockIdx.y * a.out_bank + g.cg * CPL + g.i * a.out_ld_i + g.b * a.out_ld_b;
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+      // std is the root of the Float32 variance (Julia's sqrt(var(x))): Inf
+      // where the variance overflows Float32
+      const float var = (float)(q[c] / (double)(T - 1));
+      o[c] = op == BLDP_OP_STD ? sqrtf(var) : var;
+    }
+  }
+}
+
+// var / std of blocks too few to fill the GPU: a block's spectra in nchunk
+// chunks of tchunk, one workgroup (tile of channels x time slices, as above)
+// each.  PHASE 0 leaves every chunk's sum(x - K) in ws, PHASE 1 adds them (in
+// chunk order, the same in every workgroup) for the mean and leaves the
+// chunk's squared deviations, k_tstat_mom_finish adds those.  Workgroup x is
+// tile ct of chunk ch of (IF i, block b); ws is Float64
+// [2][nchunk][nbank][nb][ni][nc].
+template <int CPL, int PHASE>
+__global__ __launch_bounds__(kBlock) void k_tstat_mom_chunk(const TStatArgs a) {
+  __shared__ double sh[kBlock][CPL];
+  const int lx = 1 << a.lx_log2, tx = threadIdx.x & (lx - 1), ty = threadIdx.x >> a.lx_log2;
+  const int ny = kBlock >> a.lx_log2;
+  int64_t ct, r, ch, r2, i, b;
+  divmod(blockIdx.x, a.ctiles, r, ct);
+  divmod(r, a.nchunk, r2, ch);
+  divmod(r2, a.ni, b, i);
+  const int64_t cg = ct * lx + tx;
+  const bool ok = cg < a.ncg;
+  const int64_t T = a.T;
+  const float *p = a.in[blockIdx.y] + a.in_off + (ok ? cg : 0) * CPL * a.in_cs + i * a.in_ld_i +
+                   b * T * a.in_ld_t;
+  const int64_t ncols = (int64_t)a.nbank * a.nb * a.ni * a.nc;  // one plane of ws
+  const int64_t col = ((blockIdx.y * a.nb + b) * a.ni + i) * a.nc + (ok ? cg : 0) * CPL;
+  float K[CPL];  // the block's first element
+#pragma unroll
+  for (int c = 0; c < CPL; ++c) K[c] = 0.0f;
+  if (ok) ldcols<CPL>(p, K);
+  double ref[CPL];  // what the deviations are taken from: K, then the mean
+#pragma unroll
+  for (int c = 0; c < CPL; ++c) ref[c] = (double)K[c];
+  if (PHASE == 1 && ok) {
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+      double s = 0.0;
+      for (int g = 0; g < a.nchunk; ++g) s += a.ws[g * ncols + col + c];
+      ref[c] += s / (double)T;
+    }
+  }
+  double acc[CPL];
+#pragma unroll
+  for (int c = 0; c < CPL; ++c) acc[c] = 0.0;
+  const int64_t t1 = (ch + 1) * a.tchunk < T ? (ch + 1) * a.tchunk : T;
+  if (ok) {
+#pragma unroll 4
+    for (int64_t t = ch * a.tchunk + ty; t < t1; t += ny) {
+      float x[CPL];
+      ldcols<CPL>(p + t * a.in_ld_t, x);
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) {
+        const double d = (double)x[c] - ref[c];
+        acc[c] += PHASE == 0 ? d : d * d;
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < CPL; ++c) sh[threadIdx.x][c] = acc[c];
+  __syncthreads();
+  if (ok && ty == 0) {
+    double *w = a.ws + (PHASE * (int64_t)a.nchunk + ch) * ncols + col;
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+      double s = 0.0;
+      for (int y = 0; y < ny; ++y) s += sh[y * lx + tx][c];
+      w[c] = s;
+    }
+  }
+}
+
+// one thread per output of bank blockIdx.y: the chunks' squared deviations, in order
+__global__ __launch_bounds__(kBlock) void k_tstat_mom_finish(const TStatArgs a, const int op) {
+  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t per_bank = a.nb * a.ni * a.nc;
+  if (e >= per_bank) return;
+  const int64_t ncols = (int64_t)a.nbank * per_bank;
+  const double *w = a.ws + (int64_t)a.nchunk * ncols + blockIdx.y * per_bank + e;
+  double q = 0.0;
+  for (int g = 0; g < a.nchunk; ++g) q += w[g * ncols];
+  int64_t c, r, i, b;
+  divmod(e, a.nc, r, c);
+  divmod(r, a.ni, b, i);
+  const float var = (float)(q / (double)(a.T - 1));  // (std: the root of the Float32 variance)
+  a.out[blockIdx.y * a.out_bank + c + i * a.out_ld_i + b * a.out_ld_b] =
+      op == BLDP_OP_STD ? sqrtf(var) : var;
+}
+
+template <int CPL>
+__global__ __launch_bounds__(kBlock) void k_tstat_med_split(const TStatArgs a) {
+  __shared__ uint32_t hist[kMedCols][256];
+  __shared__ uint32_t rank[2][kMedCols];  // of the wanted key among the prefix's keys, by pass parity
+  __shared__ uint32_t seld[kMedCols];     // the digit selected by the pass
+  __shared__ uint32_t selc[kMedCols];     // how many of the prefix's keys have it
+  __shared__ uint32_t mingt[kMedCols];    // smallest key above the selected one
+  __shared__ int nanflag[kMedCols];
+  const SplitGeo g = split_geo(a);
+  const int tid = threadIdx.x;
+  const int64_t T = a.T;
+  const float *p = a.in[blockIdx.y] + a.in_off + (g.ok ? g.cg : 0) * CPL * a.in_cs +
+                   g.i * a.in_ld_i + g.b * T * a.in_ld_t;
+  const int lc0 = g.tx * CPL;  // this lane's first column of the workgroup's (lx * CPL <= kMedCols)
+  if (tid < kMedCols) {
+    rank[0][tid] = (uint32_t)((T - 1) / 2);
+    seld[tid] = 0;
+    selc[tid] = 0;
+    mingt[tid] = kPadKey;
+    nanflag[tid] = 0;
+  }
+  uint32_t pre[CPL];  // key bits fixed so far
+#pragma unroll
+  for (int c = 0; c < CPL; ++c) pre[c] = 0;
+  for (int pass = 0; pass < 4; ++pass) {
+    const int shift = 24 - 8 * pass;
+    const uint32_t mask = ~(0xffffffffu >> (8 * pass));  // the bits fixed so far
+    for (int k = tid; k < kMedCols * 256; k += kBlock) (&hist[0][0])[k] = 0;
+    __syncthreads();
+    if (g.ok) {
+      // a run of equal digits is counted once (spectra share their exponent byte)
+      uint32_t rd[CPL], rn[CPL];
+      bool nan[CPL];
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) rd[c] = 0, rn[c] = 0, nan[c] = false;
+#pragma unroll 4
+      for (int64_t t = g.ty; t < T; t += g.ny) {
+        float x[CPL];
+        ldcols<CPL>(p + t * a.in_ld_t, x);
+#pragma unroll
+        for (int c = 0; c < CPL; ++c) {
+          nan[c] = nan[c] || x[c] != x[c];
+          const uint32_t key = f2key(x[c]);
+          if ((key & mask) == pre[c]) {
+            const uint32_t d = (key >> shift) & 255u;
+            if (d == rd[c]) {
+              ++rn[c];
+            } else {
+              if (rn[c]) atomicAdd(&hist[lc0 + c][rd[c]], rn[c]);
+              rd[c] = d;
+              rn[c] = 1;
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) {
+        if (rn[c]) atomicAdd(&hist[lc0 + c][rd[c]], rn[c]);
+        if (pass == 0 && nan[c]) nanflag[lc0 + c] = 1;
+      }
+    }
+    __syncthreads();
+    // the bin holding the rank: kScanLanes lanes a column sum kScanBins bins
+    // each, a prefix over them, and the lane whose bins hold it walks them
+    {
+      const int col = tid / kScanLanes, part = tid % kScanLanes;
+      const uint32_t r = rank[pass & 1][col];
+      uint32_t mine = 0;
+      for (int j = 0; j < kScanBins; ++j) mine += hist[col][part * kScanBins + j];
+      uint32_t incl = mine;
+#pragma unroll
+      for (int w = 1; w < kScanLanes; w *= 2) {
+        const uint32_t u = __shfl_up(incl, w, kScanLanes);
+        if (part >= w) incl += u;
+      }
+      uint32_t acc = incl - mine;
+      const bool here = mine && acc <= r && r < incl;
+      for (int j = 0; j < kScanBins; ++j) {
+        const uint32_t n = hist[col][part * kScanBins + j];
+        if (here && acc <= r && r < acc + n) {
+          seld[col] = (uint32_t)(part * kScanBins + j);
+          selc[col] = n;
+          rank[(pass + 1) & 1][col] = r - acc;
+        }
+        acc += n;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) pre[c] |= seld[lc0 + c] << shift;
+  }
+  // pre = the key of rank (T-1)/2; selc of them are equal, and it is number
+  // rank[0] among those (four passes: parity 0 again)
+  const bool odd = (T & 1) != 0;
+  if (!odd) {
+    if (g.ok) {
+      uint32_t mn[CPL];
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) mn[c] = kPadKey;
+#pragma unroll 4
+      for (int64_t t = g.ty; t < T; t += g.ny) {
+        float x[CPL];
+        ldcols<CPL>(p + t * a.in_ld_t, x);
+#pragma unroll
+        for (int c = 0; c < CPL; ++c) {
+          const uint32_t key = f2key(x[c]);
+          if (key > pre[c]) mn[c] = min(mn[c], key);
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) atomicMin(&mingt[lc0 + c], mn[c]);
+    }
+    __syncthreads();
+  }
+  if (g.ok && g.ty == 0) {
+    float *o = a.out + blockIdx.y * a.out_bank + g.cg * CPL + g.i * a.out_ld_i + g.b * a.out_ld_b;
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+      const int lc = lc0 + c;
+      const uint32_t k1 = rank[0][lc] + 1 < selc[lc] ? pre[c] : mingt[lc];
+      o[c] = median_of(pre[c], k1, odd, nanflag[lc] != 0);
+    }
+  }
+}
+
+int pow2_ceil_log2(int64_t n, int cap) {
+  int l = 0;
+  while (l < cap && ((int64_t)1 << l) < n) ++l;
+  return l;
+}
+
+}  // namespace
+
+int plan_tstat(TStatArgs &a, int op, bool words, int num_cus, int xcd_lg, TStatPlan *pp) {
+  TStatPlan p{};
+  const int64_t T = a.T;
+  const bool med = op == BLDP_OP_MEDIAN;
+  a.vec = (words && a.in_cs == 1 && a.nc % 4 == 0) ? 1 : 0;  // float4 columns
+  const int cpl = a.vec ? 4 : 1;
+  a.ncg = a.nc / cpl;
+  a.lx_log2 = 0;
+  a.ctiles = 1;
+  a.xcd_lg = 0;
+  a.nchunk = 1;
+  a.tchunk = T;
+  p.cpl = cpl;
+  p.ws_bytes = 0;
+  if (med && T >= ((int64_t)1 << 31))
+    return set_error(BLDP_EINVAL, "median: tavby=%lld is beyond 2^31 - 1", (long long)T);
+  int64_t grid;
+  if (T <= kRegMaxT) {
+    p.path = med ? TSTAT_REGS_MEDIAN : TSTAT_REGS_MOMENTS;
+    p.tsplit = 1;
+    p.passes = 1;
+    const int64_t items = a.ncg * a.ni * a.nb;
+    grid = (items + kBlock - 1) / kBlock;
+    // the per-XCD tile order where neighbouring workgroups read neighbouring
+    // memory, as plan_stats
+    a.xcd_lg = xcd_lg;
+  } else {
+    // lanes along the channels: as many as there are column groups, the
+    // median's at most kMedCols columns; the moments' tile is narrowed (down
+    // to 64-byte row segments) until the workgroups fill the GPU
+    int lg = pow2_ceil_log2(a.ncg, 6);
+    if (med) {
+      lg = std::min(lg, cpl == 4 ? 3 : 5);
+    } else {
+      const int lg_min = std::min(lg, cpl == 4 ? 2 : 4);
+      auto groups = [&](int l) {
+        return ((a.ncg + ((int64_t)1 << l) - 1) >> l) * a.ni * a.nb * a.nbank;
+      };
+      // too few even then: the blocks are cut into time chunks, one
+      // workgroup each (4 a CU), the tile as wide as the channels allow
+      const int64_t want = 4 * (int64_t)num_cus;
+      const int64_t g0 = std::max<int64_t>(groups(lg), 1);
+      const int64_t nch = std::min<int64_t>((want + g0 - 1) / g0, T / kChunkMin);
+      if (groups(lg_min) < 2 * (int64_t)num_cus && nch >= 2) {
+        a.tchunk = (T + nch - 1) / nch;
+        a.nchunk = (int32_t)((T + a.tchunk - 1) / a.tchunk);
+      } else {
+        while (lg > lg_min && groups(lg) < 2 * (int64_t)num_cus) --lg;
+      }
+    }
+    a.lx_log2 = lg;
+    a.ctiles = (a.ncg + ((int64_t)1 << lg) - 1) >> lg;
+    p.path = med ? TSTAT_SPLIT_MEDIAN : a.nchunk > 1 ? TSTAT_CHUNK_MOMENTS : TSTAT_SPLIT_MOMENTS;
+    p.tsplit = kBlock >> lg;
+    p.passes = med ? (T % 2 ? 4 : 5) : 2;
+    grid = a.ctiles * a.nchunk * a.ni * a.nb;
+    if (a.nchunk > 1)
+      p.ws_bytes = (size_t)2 * a.nchunk * a.nbank * a.nb * a.ni * a.nc * sizeof(double);
+  }
+  if (grid > INT32_MAX)
+    return set_error(BLDP_EINVAL,
+                     "tavfunc median/var/std: %lld blocks of %lld spectra are too many for one "
+                     "launch",
+                     (long long)a.nb, (long long)T);
+  p.grid = grid;
+  *pp = p;
+  return BLDP_OK;
+}
+
+namespace {
+// One dispatch; it carries the timing events of bldp_reduce_launch_timed when set.
+template <typename... Args>
+hipError_t launch1(void (*kn)(Args...), dim3 grid, hipStream_t s, Args... args) {
+  hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+  take_launch_events(&ev_start, &ev_stop);
+  if (ev_stop)
+    hipExtLaunchKernelGGL(kn, grid, dim3(kBlock), 0, s, ev_start, ev_stop, 0, args...);
+  else
+    hipLaunchKernelGGL(kn, grid, dim3(kBlock), 0, s, args...);
+  return hipGetLastError();
+}
+
+template <int TP>
+hipError_t launch_regs(const TStatArgs &a, bool med, dim3 grid, int op, hipStream_t s) {
+  if (a.vec)
+    return launch1(med ? k_tstat_regs<TP, 4, true> : k_tstat_regs<TP, 4, false>, grid, s, a, op);
+  return launch1(med ? k_tstat_regs<TP, 1, true> : k_tstat_regs<TP, 1, false>, grid, s, a, op);
+}
+}  // namespace
+
+hipError_t launch_tstat(const TStatArgs &a, const TStatPlan &p, int op, hipStream_t s) {
+  if (p.grid <= 0) return hipSuccess;
+  const dim3 grid((unsigned)p.grid, (unsigned)a.nbank);
+  switch (p.path) {
+    case TSTAT_REGS_MOMENTS:
+    case TSTAT_REGS_MEDIAN: {
+      const bool med = p.path == TSTAT_REGS_MEDIAN;
+      if (a.T <= 2) return launch_regs<2>(a, med, grid, op, s);
+      if (a.T <= 4) return launch_regs<4>(a, med, grid, op, s);
+      if (a.T <= 8) return launch_regs<8>(a, med, grid, op, s);
+      if (a.T <= 16) return launch_regs<16>(a, med, grid, op, s);
+      if (a.T <= 32) return launch_regs<32>(a, med, grid, op, s);
+      break;
+    }
+    case TSTAT_SPLIT_MOMENTS:
+      return launch1(a.vec ? k_tstat_mom_split<4> : k_tstat_mom_split<1>, grid, s, a, op);
+    case TSTAT_SPLIT_MEDIAN:
+      return launch1(a.vec ? k_tstat_med_split<4> : k_tstat_med_split<1>, grid, s, a);
+    case TSTAT_CHUNK_MOMENTS: {
+      if (!a.ws) return hipErrorInvalidValue;
+      const hipStream_t st = s;
+      void (*sums)(TStatArgs) = a.vec ? k_tstat_mom_chunk<4, 0> : k_tstat_mom_chunk<1, 0>;
+      void (*devs)(TStatArgs) = a.vec ? k_tstat_mom_chunk<4, 1> : k_tstat_mom_chunk<1, 1>;
+      hipLaunchKernelGGL(sums, grid, dim3(kBlock), 0, st, a);
+      hipLaunchKernelGGL(devs, grid, dim3(kBlock), 0, st, a);
+      const int64_t per_bank = a.nb * a.ni * a.nc;
+      hipLaunchKernelGGL(k_tstat_mom_finish, dim3((unsigned)((per_bank + kBlock - 1) / kBlock),
+                                                  (unsigned)a.nbank),
+                         dim3(kBlock), 0, st, a, op);
+      return hipGetLastError();
+    }
+  }
+  return hipErrorInvalidValue;
+}
+
+}  // namespace bldp

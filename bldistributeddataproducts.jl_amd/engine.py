@@ -24,6 +24,7 @@ __all__ = [
     "band_reduce_multi",
     "stitch",
     "despike", "kurtosis", "kurtosis_blocks_plan", "band_kurtosis", "synth", "plan", "reduce_host", "kurtosis_host",
+    "tstat", "tstat_plan", "band_tstat", "tstat_host",
     "init", "finalize", "pinned",
 ]
 
@@ -545,6 +546,117 @@ def band_reduce_multi(banks, fqavby=1, tavby=1, op="sum", win=None, root=0, out=
                                       (_lib.BLDP_BAND_STAGED if staged else 0)
                                       | (_lib.BLDP_BAND_PEER_STORE if peer_store else 0))
     _lib.check(rc, "bldp_band_reduce_multi_f32")
+    return out
+
+
+def _tstat_op(op) -> int:
+    if op not in _lib.STAT_OPS:
+        raise _lib.ArgumentError(
+            _lib.BLDP_EINVAL, f"tstat takes var/std/median, not {op!r} (sum/mean/max/min over "
+                              f"time: reduce with tavby)")
+    return _lib.OPS[op]
+
+
+def _tstat_out(out, dims, device):
+    """A caller's ``out`` of a tstat, checked before any launch: a Float32
+    (nc, ni, nb) tensor on ``device`` with the channels fastest and rows that
+    do not overlap; returns (pointer, out_ld_i, out_ld_b)."""
+    torch = _torch()
+    nc, ni, nb = dims
+    if not isinstance(out, torch.Tensor):
+        raise TypeError("out must be a device tensor")
+    if out.dtype != torch.float32:
+        raise TypeError(f"out must be Float32, not {out.dtype}")
+    if tuple(out.shape) != (nc, ni, nb):
+        raise ValueError(f"out is {tuple(out.shape)}, expected {(nc, ni, nb)}")
+    if out.device != torch.device(device):
+        raise ValueError(f"out is on {out.device}, the data on {device}")
+    s0, s1, s2 = out.stride()
+    ld_i = s1 if ni > 1 else nc
+    ld_b = s2 if nb > 1 else max(ni - 1, 0) * ld_i + nc
+    if (nc > 1 and s0 != 1) or ld_i < nc or ld_b < (ni - 1) * ld_i + nc:
+        raise ValueError(f"out strides {out.stride()} are not a Julia-order (channel-fastest) "
+                         f"layout of {(nc, ni, nb)}")
+    return (out.data_ptr() if out.numel() else None), ld_i, ld_b
+
+
+def tstat(x, tavby, op, win=None, out=None, stream=None):
+    """var / std / median of every block of ``tavby`` selected spectra of every
+    (channel, IF) column, on the GPU (bldp_tstat_f32): fqav's rule on the time
+    axis with Julia's Statistics.  x: a Float32 device filterbank tensor;
+    returns a Julia-order (nc, ni, nt/tavby) Float32 device tensor (``out``
+    when given: e.g. a bank's slot of a stitched product).  tavby <= 1 copies
+    the window."""
+    L = _lib.lib()
+    code = _tstat_op(op)
+    shape = tuple(x.shape)
+    _check_bounds(win, shape)
+    dims = out_shape(shape, win, 1, tavby)
+    ptr, nchan, nif, ntime = _abi_dims(x)
+    if out is None:
+        out = fb_empty(*dims, device=x.device)
+    optr, ld_i, ld_b = _tstat_out(out, dims, x.device)
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    rc = L.bldp_tstat_f32(ptr, nchan, nif, ntime, wp, int(tavby), code, optr, ld_i, ld_b,
+                          _lib.stream_ptr(stream))
+    _lib.check(rc, "bldp_tstat_f32")
+    return out
+
+
+def tstat_plan(x, tavby, op, win=None) -> dict:
+    """Launch plan of ``tstat(x, tavby, op, win)`` (bldp_tstat_plan_f32): the
+    path (_lib.TSTAT_PATHS, "copy" for tavby <= 1), channels per lane, the time
+    slices of a workgroup splitting a block (1: the register form), passes over
+    the block, workgroups, workspace bytes, blocks and the lanes along the
+    channels of a split workgroup."""
+    L = _lib.lib()
+    code = _tstat_op(op)
+    shape = tuple(x.shape)
+    _check_bounds(win, shape)
+    ptr, nchan, nif, ntime = _abi_dims(x)
+    info = (ctypes.c_int64 * 8)()
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    _lib.check(L.bldp_tstat_plan_f32(ptr, nchan, nif, ntime, wp, int(tavby), code, None, info),
+               "bldp_tstat_plan_f32")
+    keys = ["path", "channels_per_lane", "time_split_lanes", "passes", "workgroups",
+            "workspace_bytes", "blocks", "channel_lanes"]
+    d = dict(zip(keys, [int(v) for v in info]))
+    d["path"] = _lib.TSTAT_PATHS.get(d["path"], "copy")
+    return d
+
+
+def band_tstat(banks, tavby, op, win=None, out=None, stream=None):
+    """``tstat`` of every bank of a band resident on ONE GPU, stitched in bank
+    order (the vcat of the per-bank results) in one launch
+    (bldp_band_tstat_f32): a dense (nbank*nc, ni, nt/tavby) Float32 tensor."""
+    L = _lib.lib()
+    code = _tstat_op(op)
+    banks, geo, out, ptrs, (keep, wp) = _band_args(banks, 1, tavby, win, out)
+    if out.device != banks[0].device:
+        raise ValueError(f"out is on {out.device}, the banks on {banks[0].device}")
+    rc = L.bldp_band_tstat_f32(len(banks), ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp,
+                               int(tavby), code, out.data_ptr() if out.numel() else None,
+                               _lib.stream_ptr(stream))
+    _lib.check(rc, "bldp_band_tstat_f32")
+    return out
+
+
+def tstat_host(a: np.ndarray, tavby, op, win=None, device=0) -> np.ndarray:
+    """Host Fortran-ordered Float32 array in, (nc, ni, nt/tavby) Float32 host
+    array out (bldp_tstat_host_f32: the window's rows staged on ``device``)."""
+    L = _lib.lib()
+    code = _tstat_op(op)
+    a = np.asarray(a)
+    if a.dtype != np.float32 or not a.flags.f_contiguous or a.ndim != 3:
+        raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
+    _check_bounds(win, a.shape)
+    dims = out_shape(a.shape, win, 1, tavby)
+    out = np.empty(dims, dtype=np.float32, order="F")
+    keep, wp = _lib.win_arg(_full_win(win, a.shape))
+    rc = L.bldp_tstat_host_f32(int(device), a.ctypes.data if a.size else None, a.shape[0],
+                               a.shape[1], a.shape[2], wp, int(tavby), code,
+                               out.ctypes.data if out.size else None)
+    _lib.check(rc, "bldp_tstat_host_f32")
     return out
 
 

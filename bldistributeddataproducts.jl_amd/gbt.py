@@ -75,11 +75,14 @@ def getheaders(workers, fnames):
     return _fanout(workers, fnames, lambda w, f: readers.getheader(f))
 
 
-def getdata(workers, fnames, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum", tavby=1):
+def getdata(workers, fnames, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum", tavby=1,
+            tavfunc=None):
     """src/gbt.jl:69-79 (+ tavby): an array of per-bank (nchan/fqavby, nif,
-    ntime/tavby) Float32 arrays, the same size as workers/fnames."""
+    ntime/tavby) Float32 arrays, the same size as workers/fnames.  ``tavfunc``
+    as in WorkerFunctions.getdata (the time integration's own function)."""
     return _fanout(workers, fnames,
-                   lambda w, f: W.getdata(f, idxs, fqavby, fqavfunc, tavby, device=int(w)))
+                   lambda w, f: W.getdata(f, idxs, fqavby, fqavfunc, tavby, device=int(w),
+                                          tavfunc=tavfunc))
 
 
 def getkurtosis(workers, fnames, idxs=(COLON, COLON, COLON), tblock=None):
@@ -283,7 +286,7 @@ def _band_chunked(ws, fs, geo, idxs, fqavby, op, tavby, band, root, force_copy, 
 
 
 def _band_on_device(ws, fs, idxs, fqavby, op, tavby, nfpc, timings=None, staged=None,
-                    peer_store=None):
+                    peer_store=None, tavfunc=None):
     """One band stitched on the GPU (src/gbt.jl:103): every
     bank is read and reduced on its worker's GPU straight into its vcat slot
     of the band product on the first worker's GPU, the DC-spike patch runs on
@@ -334,6 +337,10 @@ def _band_on_device(ws, fs, idxs, fqavby, op, tavby, nfpc, timings=None, staged=
     # take them): with banks on several GPUs, or staged, the band goes bank by bank
     if op in _lib.STAT_OPS and (force_copy or {int(w) for w in ws} != {root}):
         raw = chunked = False
+    # tavfunc (two stages, the window staying on its GPU in between): bank by
+    # bank, each bank's last stage writing its slot (copied there from another GPU)
+    if tavfunc is not None:
+        raw = chunked = False
     if chunked:
         chunked = _band_chunked(ws, fs, geo, idxs, fqavby, op, tavby, band, root, force_copy, tm,
                                 peer_store)
@@ -359,8 +366,9 @@ def _band_on_device(ws, fs, idxs, fqavby, op, tavby, nfpc, timings=None, staged=
             dev = int(ws[b])
             with torch.cuda.device(dev), torch.cuda.stream(cur[dev]):
                 if direct[dev]:
-                    return W.getdata_device(fs[b], idxs, fqavby, op, tavby, device=dev, out=slot)
-                r = W.getdata_device(fs[b], idxs, fqavby, op, tavby, device=dev)
+                    return W.getdata_device(fs[b], idxs, fqavby, op, tavby, device=dev, out=slot,
+                                            tavfunc=tavfunc)
+                r = W.getdata_device(fs[b], idxs, fqavby, op, tavby, device=dev, tavfunc=tavfunc)
                 if r is not None:  # (torch orders a cross-device copy on both devices' streams)
                     slot.copy_(r, non_blocking=True)
                 return r
@@ -406,7 +414,8 @@ def _despike_host(d: np.ndarray, nfpc: int) -> np.ndarray:
 
 
 def getband(workers, fnames, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum", tavby=1,
-            despike_nfpc=None, freqs=False, stitch="device", staged=None, peer_store=None):
+            despike_nfpc=None, freqs=False, stitch="device", staged=None, peer_store=None,
+            tavfunc=None):
     """The stitched band product: reduce(vcat, getdata(...)) in the given
     bank order (src/gbt.jl:103).  ``workers``/``fnames`` are one band's banks
     (1-D), or a (nbank, nband) matrix like loadscan's ``ds``, whose columns are
@@ -427,7 +436,9 @@ def getband(workers, fnames, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum
     the environment's BLDP_BAND_FORCE_COPY, else off).  ``peer_store=True``
     lets a bank's GPU other than the root store its slot over xGMI straight
     from the reduce kernel (default: the environment's BLDP_BAND_PEER_STORE,
-    else off: such banks are reduced on their GPU and copied into the slot)."""
+    else off: such banks are reduced on their GPU and copied into the slot).
+    ``tavfunc`` as in WorkerFunctions.getdata: each bank's last stage writes
+    its slot of the stitched product."""
     w = np.asarray(workers, dtype=object)
     f = np.asarray(fnames, dtype=object)
     if w.ndim not in (1, 2):
@@ -438,15 +449,17 @@ def getband(workers, fnames, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum
     wcol = [list(w)] if w.ndim == 1 else [list(w[:, j]) for j in range(w.shape[1])]
     fcol = [list(f)] if f.ndim == 1 else [list(f[:, j]) for j in range(f.shape[1])]
     op = W._opname(fqavfunc)
+    if tavfunc is not None:
+        W._tav_ops(fqavby, fqavfunc, tavfunc)  # the errors, before any read
     bands = [None] * len(wcol)
     if stitch == "device" and op is not None:
         for j, (ws, fs) in enumerate(zip(wcol, fcol)):
             bands[j] = _band_on_device(ws, fs, idxs, fqavby, op, tavby, despike_nfpc,
-                                       staged=staged, peer_store=peer_store)
+                                       staged=staged, peer_store=peer_store, tavfunc=tavfunc)
     for j, (ws, fs) in enumerate(zip(wcol, fcol)):
         if bands[j] is not None:
             continue
-        parts = list(getdata(ws, fs, idxs, fqavby, fqavfunc, tavby))
+        parts = list(getdata(ws, fs, idxs, fqavby, fqavfunc, tavby, tavfunc))
         nfpc = despike_nfpc
         if nfpc is True:
             nfpc = parts[0].shape[0] // 64  # size(ds[1], 1) ÷ 64

@@ -12,7 +12,7 @@ module BLDPHip
 using Statistics: mean, median, var, std
 
 export gpu_init, gpu_finalize, gpu_pin, gpu_unpin, gpu_fqav, gpu_reduce, gpu_kurtosis, gpu_band,
-       gpu_comm_id, gpu_comm_init, gpu_comm_destroy, gpu_band_gather
+       gpu_tstat, gpu_comm_id, gpu_comm_init, gpu_comm_destroy, gpu_band_gather
 
 const libbldp = get(ENV, "BLDP_LIB", joinpath(@__DIR__, "..", "libbldp_hip.so"))
 
@@ -232,6 +232,95 @@ function gpu_kurtosis(A::Array{T,3}; idxs::Tuple=(:, :, :), dev::Integer=0,
         (Cint, Cint, Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Int64}, Ptr{Float64}),
         dev, dtypecode(T), A, size(A, 1), size(A, 2), size(A, 3), win, out))
     out
+end
+
+# tavfunc values with a time-axis kernel of their own (csrc/tstats.hip)
+statcode(f) = f === var ? Cint(4) : f === std ? Cint(5) : f === median ? Cint(6) : nothing
+
+"""
+    gpu_tstat(A::Array{Float32,3}, tavby; f=median, idxs=(:,:,:), dev=0) -> Array{Float32,3}
+
+`f` (Statistics' `var`, `std` or `median`) of every block of `tavby` selected
+spectra of every (channel, IF) column, fqav's rule on axis 3:
+`R[c, i, b] = f(A[idxs...][c, i, (b-1)*tavby+1 : b*tavby])`, computed on GPU `dev`
+(bldp_tstat_host_f32: the window staged on the device).  `tavby` must divide
+the selected spectra (DimensionMismatch); `tavby <= 1` returns the window."""
+function gpu_tstat(A::Array{Float32,3}, tavby::Integer; f=median, idxs::Tuple=(:, :, :),
+                   dev::Integer=0)
+    op = statcode(f)
+    op === nothing && throw(ArgumentError("gpu_tstat takes var, std or median, not $f"))
+    win = window(idxs, size(A))
+    shp = zeros(Int64, 3)
+    GC.@preserve win check(ccall((:bldp_tstat_shape, libbldp), Cint,
+        (Int64, Int64, Int64, Ptr{Int64}, Int64, Ptr{Int64}),
+        size(A, 1), size(A, 2), size(A, 3), win, tavby, shp))
+    out = Array{Float32,3}(undef, shp...)
+    GC.@preserve A win out check(ccall((:bldp_tstat_host_f32, libbldp), Cint,
+        (Cint, Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Int64, Cint, Ptr{Float32}),
+        dev, A, size(A, 1), size(A, 2), size(A, 3), win, tavby, op, out))
+    out
+end
+
+"""
+    gpu_tstat(in::Ptr{Float32}, dims, tavby, out::Ptr{Float32}; f=median, win=C_NULL,
+              out_ld=nothing, stream=C_NULL)
+
+The same on DEVICE memory (bldp_tstat_f32; asynchronous on `stream`): `in` a
+(nchan, nif, ntime) = `dims` device array, `win` the 9-element window or
+C_NULL, element (c, i, b) written at `out[c + i*out_ld[1] + b*out_ld[2]]`
+(0-based; dense by default), e.g. a bank's slot of a stitched product."""
+function gpu_tstat(in::Ptr{Float32}, dims::NTuple{3,Integer}, tavby::Integer, out::Ptr{Float32};
+                   f=median, win=Ptr{Int64}(C_NULL), out_ld=nothing, stream::Ptr{Cvoid}=C_NULL)
+    op = statcode(f)
+    op === nothing && throw(ArgumentError("gpu_tstat takes var, std or median, not $f"))
+    shp = zeros(Int64, 3)
+    GC.@preserve win check(ccall((:bldp_tstat_shape, libbldp), Cint,
+        (Int64, Int64, Int64, Ptr{Int64}, Int64, Ptr{Int64}),
+        dims[1], dims[2], dims[3], win, tavby, shp))
+    ld = out_ld === nothing ? (shp[1], shp[1] * shp[2]) : out_ld
+    GC.@preserve win check(ccall((:bldp_tstat_f32, libbldp), Cint,
+        (Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Int64, Cint, Ptr{Float32}, Int64, Int64,
+         Ptr{Cvoid}),
+        in, dims[1], dims[2], dims[3], win, tavby, op, out, ld[1], ld[2], stream))
+    (shp[1], shp[2], shp[3])
+end
+
+"""
+    getdata(A::Array; idxs=(:,:,:), fqavby=1, fqavfunc=sum, tavby=1, tavfunc=nothing, dev=0)
+
+WorkerFunctions.getdata's reduction (src/gbtworkerfunctions.jl:191-195) of an
+array the worker has read, on GPU `dev`.  `tavfunc === nothing`: `fqavfunc`
+reduces the fqavby x tavby block (gpu_fqav).  `tavfunc` given: the time
+integration takes its own function,
+`tav(fqav(A[idxs...], fqavby; f=fqavfunc), tavby; f=tavfunc)`; either stage is
+skipped when its factor is <= 1.  var / std / median of Float32 data run in
+gpu_tstat, sum / mean / maximum / minimum in gpu_reduce, anything else (other
+element types, other functions) in Julia on the host."""
+function getdata(A::Array{T,3}; idxs::Tuple=(:, :, :), fqavby::Integer=1, fqavfunc=sum,
+                 tavby::Integer=1, tavfunc=nothing, dev::Integer=0) where {T}
+    W = all(i -> i isa Colon, idxs) ? A : A[map(i -> i isa Integer ? (i:i) : i, idxs)...]
+    tavfunc === nothing && return gpu_fqav(W, fqavby; f=fqavfunc, tavby, dev)
+    B = gpu_fqav(W, fqavby; f=fqavfunc, dev)
+    tavby <= 1 && return B
+    size(B, 3) % tavby == 0 ||
+        throw(DimensionMismatch("tavby=$tavby does not divide ntime=$(size(B, 3))"))
+    if B isa Array{Float32,3} && statcode(tavfunc) !== nothing
+        return gpu_tstat(B, tavby; f=tavfunc, dev)
+    elseif B isa Array{<:GPUElt,3} && opcode(tavfunc) !== nothing
+        return gpu_reduce(B, 1, tavby; f=tavfunc, dev)
+    end
+    R = reshape(B, size(B, 1), size(B, 2), tavby, :)
+    dropdims(tavfunc(R, dims=3), dims=3)
+end
+
+"""
+    getband(parts; idxs=(:,:,:), fqavby=1, fqavfunc=sum, tavby=1, tavfunc=nothing, dev=0)
+
+`reduce(vcat, ...)` of `getdata` of every bank's array, in bank order
+(src/gbt.jl:103)."""
+function getband(parts::AbstractVector; idxs::Tuple=(:, :, :), fqavby::Integer=1, fqavfunc=sum,
+                 tavby::Integer=1, tavfunc=nothing, dev::Integer=0)
+    reduce(vcat, [getdata(A; idxs, fqavby, fqavfunc, tavby, tavfunc, dev) for A in parts])
 end
 
 """

@@ -6,7 +6,8 @@ Same names, argument meanings and error behaviour as the reference:
 * ``fqav(A, n, f="sum")``  — :16-20 (array) and :27-33 (range);
 * ``sanitizeidxs``          — :167-169 (re-exported from .idxs);
 * ``getdata(fname, idxs, fqavby=1, fqavfunc="sum")`` — :191-195, plus the
-  additive ``tavby`` time integration;
+  additive ``tavby`` time integration and its own function ``tavfunc``
+  (var / std / median over blocks of spectra included, csrc/tstats.hip);
 * ``getfbdata`` / ``getfbh5data`` — :171-177 / :179-189;
 * ``getkurtosis``            — :197-202;
 * ``getinventory`` / headers — :35-159 (host metadata, see .readers).
@@ -107,8 +108,9 @@ def _host_generic(A: np.ndarray, n: int, f) -> np.ndarray:
     return np.asfortranarray(np.asarray(f(R, axis=0)))
 
 
-def _host_stat(a: np.ndarray, n: int, op: str, win=None) -> np.ndarray:
-    """Julia's var / std / median of every n channels in Float64, for the
+def _host_stat(a: np.ndarray, n: int, op: str, win=None, axis: int = 0) -> np.ndarray:
+    """Julia's var / std / median of every n channels (``axis=0``, fqavfunc) or
+    every n spectra (``axis=2``, tavfunc) in Float64, for the
     element types the GPU ops do not take (integers, Float64): the corrected
     two-pass variance about the mean, its root, and the median ordered by
     isless (-0.0 < 0.0), the middle element of an odd block, a/2 + b/2 of an
@@ -118,11 +120,13 @@ def _host_stat(a: np.ndarray, n: int, op: str, win=None) -> np.ndarray:
         a = a[np.ix_(*[win[3 * k] + win[3 * k + 2] * np.arange(win[3 * k + 1])
                        for k in range(3)])]
     n = max(int(n), 1)
-    if a.shape[0] % n:
-        raise _lib.DimensionMismatch(_lib.BLDP_EDIM,
-                                     f"DimensionMismatch: fqavby={n} does not divide {a.shape[0]}")
-    R = np.asfortranarray(a, dtype=np.float64).reshape((n, a.shape[0] // n) + a.shape[1:],
-                                                       order="F")
+    if a.shape[axis] % n:
+        raise _lib.DimensionMismatch(
+            _lib.BLDP_EDIM, f"DimensionMismatch: {'fqavby' if axis == 0 else 'tavby'}={n} does "
+                            f"not divide {a.shape[axis]}")
+    # the reduced axis first: blocks of n along it, whatever axis it was
+    m = np.moveaxis(np.asarray(a, dtype=np.float64), axis, 0)
+    R = np.asfortranarray(m).reshape((n, m.shape[0] // n) + m.shape[1:], order="F")
     with np.errstate(invalid="ignore", divide="ignore"):
         if op == "var":
             r = np.var(R, axis=0, ddof=1)
@@ -134,7 +138,7 @@ def _host_stat(a: np.ndarray, n: int, op: str, win=None) -> np.ndarray:
             S = np.take_along_axis(R, np.argsort(key, axis=0, kind="stable"), axis=0)
             r = S[n // 2] if n % 2 else S[n // 2 - 1] / 2 + S[n // 2] / 2
             r = np.where(np.isnan(R).any(axis=0), np.nan, r)
-    return np.asfortranarray(r)
+    return np.asfortranarray(np.moveaxis(r, 0, axis))
 
 
 def fqav(A, n: int, f="sum"):
@@ -178,7 +182,9 @@ def _reduce_host(a, fqavby, tavby, op, win, device):
     return engine.reduce_host_typed(a, fqavby, tavby, op, win, device=device)
 
 
-def _reduce_array(x, idxs, fqavby, fqavfunc, tavby, device):
+def _reduce_array(x, idxs, fqavby, fqavfunc, tavby, device, tavfunc=None):
+    if tavfunc is not None:
+        return _tav_array(x, idxs, fqavby, fqavfunc, tavby, tavfunc, device)
     idxs = sanitizeidxs(idxs)
     win = to_window(idxs, x.shape)
     op = _opname(fqavfunc)
@@ -203,6 +209,100 @@ def _reduce_array(x, idxs, fqavby, fqavfunc, tavby, device):
         ax = [win[3 * k] + win[3 * k + 2] * np.arange(win[3 * k + 1]) for k in range(3)]
         return np.asfortranarray(a[np.ix_(*ax)])
     return _reduce_host(a, fqavby, tavby, op, win, device)
+
+
+def _tav_ops(fqavby, fqavfunc, tavfunc):
+    """The two ops of getdata(...; tavfunc): R = tav(fqav(A, fqavby; f=fqavfunc),
+    tavby; f=tavfunc), tav being fqav's rule on axis 3."""
+    op2 = _opname(tavfunc) if isinstance(tavfunc, str) or callable(tavfunc) else None
+    if op2 is None:
+        raise TypeError(f"tavfunc {tavfunc!r} is not one of {sorted(_lib.OPS)}")
+    op1 = _opname(fqavfunc)
+    if op1 is None and fqavby > 1:
+        raise TypeError("tavfunc needs fqavfunc in sum/mean/max/min/var/std/median")
+    return op1 or "sum", op2
+
+
+def _tav_device(x, win, fqavby, op1, tavby, op2, out=None):
+    """Both stages on a device tensor, the window staying on the GPU: stage 1
+    is the reduce with tavby = 1 (skipped for fqavby <= 1, its result a
+    temporary device tensor), stage 2 the reduce with fqavby = 1 for
+    sum / mean / max / min and engine.tstat for var / std / median (skipped
+    for tavby <= 1: fqav's n <= 1 rule)."""
+    if tavby <= 1:
+        return engine.reduce(x, fqavby, 1, op1 if fqavby > 1 else "sum", win, out=out)
+    if fqavby > 1:
+        x, win = engine.reduce(x, fqavby, 1, op1, win), None
+    if op2 in _lib.STAT_OPS:
+        return engine.tstat(x, tavby, op2, win, out=out)
+    return engine.reduce(x, 1, tavby, op2, win, out=out)
+
+
+def _tav_host(a, win, fqavby, op1, tavby, op2, device):
+    """Both stages for a host array of an element type the GPU statistics do
+    not take: var / std / median on the host in Float64 (_host_stat, Julia's
+    result type), sum / mean / max / min through the typed GPU reduce."""
+    if engine._dtype_code(a.dtype) is None:
+        raise TypeError(f"element type {a.dtype} is not supported")
+    engine._check_bounds(win, a.shape)
+    engine.out_shape(a.shape, win, fqavby, tavby)  # DimensionMismatch before any work
+    if fqavby > 1:
+        a = _reduce_host(a, fqavby, 1, op1, win, device)
+    elif win is not None:
+        a = np.asfortranarray(a[np.ix_(*[win[3 * k] + win[3 * k + 2] * np.arange(win[3 * k + 1])
+                                         for k in range(3)])])
+    if tavby <= 1:
+        return a
+    if op2 in _lib.STAT_OPS:
+        return _host_stat(a, tavby, op2, axis=2)
+    return _reduce_host(np.asfortranarray(a), 1, tavby, op2, None, device)
+
+
+def _tav_array(x, idxs, fqavby, fqavfunc, tavby, tavfunc, device):
+    """getdata(...; tavfunc) of an in-memory filterbank (host array: result on
+    the host; device tensor: result on the device)."""
+    op1, op2 = _tav_ops(fqavby, fqavfunc, tavfunc)
+    idxs = sanitizeidxs(idxs)
+    if _is_tensor(x):
+        return _tav_device(x, to_window(idxs, x.shape), fqavby, op1, tavby, op2)
+    a = np.asarray(x)
+    if a.ndim != 3:
+        raise ValueError("filterbank arrays are 3-D (nchan, nif, ntime)")
+    win = to_window(idxs, a.shape)
+    if a.dtype != np.float32:
+        return _tav_host(a, win, fqavby, op1, tavby, op2, device)
+    engine._check_bounds(win, a.shape)
+    dims = engine.out_shape(a.shape, win, fqavby, tavby)
+    if 0 in dims:
+        return np.empty(dims, dtype=np.float32, order="F")
+    import torch
+
+    xd = engine.fb_from_numpy(a, device=f"cuda:{int(device)}")
+    with torch.cuda.device(xd.device):
+        return engine.fb_to_numpy(_tav_device(xd, win, fqavby, op1, tavby, op2))
+
+
+def _tav_file(fname, idxs, fqavby, fqavfunc, tavby, tavfunc, device):
+    """getdata(...; tavfunc) of a file: the window is read onto the GPU the way
+    getdata reads it (window_on_device: raw preads, chunks decoded on the GPU,
+    else libhdf5 / mmap and one copy) and stays there between the two stages."""
+    op1, op2 = _tav_ops(fqavby, fqavfunc, tavfunc)
+    got = window_on_device(fname, idxs, device)
+    if got is not None:
+        import torch
+
+        x, rwin = got
+        with torch.cuda.device(x.device):
+            return engine.fb_to_numpy(_tav_device(x, rwin, fqavby, op1, tavby, op2))
+    # not Float32, or an empty window: the host-array path
+    if readers.ishdf5(fname):
+        return _tav_array(readers.fbh5_read(fname, idxs), (COLON, COLON, COLON), fqavby, fqavfunc,
+                          tavby, tavfunc, device)
+    _, data = readers.fil_mmap(fname)
+    try:
+        return _tav_array(data, idxs, fqavby, fqavfunc, tavby, tavfunc, device)
+    finally:
+        del data
 
 
 def _raw_to_device(fname, raw, idxs, device):
@@ -232,12 +332,15 @@ def _reduce_raw_file(fname, raw, idxs, fqavby, op, tavby, device):
 
 
 def getfbdata(fbname, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum", tavby=1,
-              device=0):
+              device=0, tavfunc=None):
     """SIGPROC filterbank: mmap, window, reduce (src/gbtworkerfunctions.jl:171-177).
     32-bit data with a GPU reduction: only the window's rows / channel spans
-    are read (parallel preads into pinned memory, streamed to the GPU)."""
+    are read (parallel preads into pinned memory, streamed to the GPU).
+    ``tavfunc``: as getdata."""
     assert len(idxs) == 3, "idxs must have exactly three indices"  # :172
     idxs = sanitizeidxs(idxs)
+    if tavfunc is not None:
+        return _tav_file(fbname, idxs, fqavby, fqavfunc, tavby, tavfunc, device)
     op = _opname(fqavfunc)
     if op is not None:
         raw = readers.fil_raw_layout(fbname)
@@ -253,11 +356,13 @@ def getfbdata(fbname, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum", tavb
 
 
 def getfbh5data(fbh5name, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum", tavby=1,
-                device=0):
+                device=0, tavfunc=None):
     """FBH5: read the window (whole dataset for (:,:,:)), then reduce
-    (src/gbtworkerfunctions.jl:179-189)."""
+    (src/gbtworkerfunctions.jl:179-189).  ``tavfunc``: as getdata."""
     assert len(idxs) == 3, "idxs must have exactly three indices"  # :180
     idxs = sanitizeidxs(idxs)
+    if tavfunc is not None:
+        return _tav_file(fbh5name, idxs, fqavby, fqavfunc, tavby, tavfunc, device)
     op = _opname(fqavfunc)
     from . import fbh5
 
@@ -329,10 +434,20 @@ def window_on_device(fname, idxs, device=0):
 
 
 def getdata_device(fname, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum", tavby=1,
-                   device=0, out=None):
+                   device=0, out=None, tavfunc=None):
     """getdata with the result left on GPU ``device`` (a Julia-order Float32
     tensor), written into ``out`` when given — e.g. a bank's slot of a stitched
-    band product (GBT.getband); None when the data are not Float32."""
+    band product (GBT.getband); None when the data are not Float32.  With
+    ``tavfunc`` (as getdata) the last stage writes ``out``."""
+    if tavfunc is not None:
+        op1, op2 = _tav_ops(fqavby, fqavfunc, tavfunc)
+        got = window_on_device(fname, idxs, device)
+        if got is None:
+            return None
+        import torch
+
+        with torch.cuda.device(got[0].device):
+            return _tav_device(got[0], got[1], fqavby, op1, tavby, op2, out=out)
     op = _opname(fqavfunc)
     if op is None:
         raise TypeError("the device path takes fqavfunc in sum/mean/max/min/var/std/median")
@@ -346,18 +461,28 @@ def getdata_device(fname, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum", 
         return engine.reduce(x, fqavby, tavby, op, rwin, out=out)
 
 
-def getdata(fname, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum", tavby=1, device=0):
+def getdata(fname, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum", tavby=1, device=0,
+            tavfunc=None):
     """WorkerFunctions.getdata (src/gbtworkerfunctions.jl:191-195).
 
     ``fname`` may also be an in-memory filterbank: a Fortran-ordered
     (nchan, nif, ntime) float32 array (result on the host) or a Julia-order
-    device tensor (result stays on the device)."""
+    device tensor (result stays on the device).
+
+    ``tavfunc=None`` (default): ``fqavfunc`` reduces the fqavby x tavby block,
+    as ever.  ``tavfunc`` given (a name of ``fqavfunc``'s, var / std / median
+    included): the time integration takes its own function, fqav's rule on
+    axis 3: ``R = tav(fqav(A, fqavby; f=fqavfunc), tavby; f=tavfunc)`` with
+    ``R[c, i, b] = tavfunc(B[c, i, b*tavby : (b+1)*tavby])``.  Either stage is
+    skipped when its factor is <= 1; tavby must divide the selected spectra
+    (DimensionMismatch).  Float32 data stay on the GPU between the stages;
+    var / std / median of other element types are Float64 from the host."""
     if not isinstance(fname, (str, bytes)) and not hasattr(fname, "__fspath__"):
-        return _reduce_array(fname, idxs, fqavby, fqavfunc, tavby, device)
+        return _reduce_array(fname, idxs, fqavby, fqavfunc, tavby, device, tavfunc)
     idxs = sanitizeidxs(idxs)  # :192
     if readers.ishdf5(fname):  # :193
-        return getfbh5data(fname, idxs, fqavby, fqavfunc, tavby, device)
-    return getfbdata(fname, idxs, fqavby, fqavfunc, tavby, device)
+        return getfbh5data(fname, idxs, fqavby, fqavfunc, tavby, device, tavfunc)
+    return getfbdata(fname, idxs, fqavby, fqavfunc, tavby, device, tavfunc)
 
 
 def getkurtosis(fname, idxs=(COLON, COLON, COLON), device=0, tblock=None):

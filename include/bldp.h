@@ -365,6 +365,59 @@ BLDP_API int bldp_kurtosis_blocks_host_f32(int dev, const float *in, int64_t nch
                                            int64_t ntime, const int64_t *win, int64_t tblock,
                                            double *out);
 
+/* Statistics over blocks of spectra (getdata(...; tavby, tavfunc)): fqav's rule
+ * on the time axis with Julia's Statistics as the function.  The window's
+ * selected spectra are cut into nb = nt / tavby blocks, block b holding spectra
+ * [b*tavby, (b+1)*tavby), and element (c, i, b) of the (nc, ni, nb) Float32
+ * result is op of that block of column (c, i): BLDP_OP_VAR (the corrected
+ * variance about the mean), BLDP_OP_STD (its root) or BLDP_OP_MEDIAN (ordered
+ * by isless, the middle element of an odd block, a/2 + b/2 in Float32 of an
+ * even one, NaN when the block holds a NaN).  A constant block gives exactly
+ * +0.0 for var / std.  Any other op is BLDP_EINVAL (sum / mean / max / min over
+ * time are bldp_reduce_* with tavby); a tavby that does not divide nt is
+ * BLDP_EDIM, a window outside the array BLDP_EBOUNDS.  tavby <= 1 copies the
+ * window (fqav's n <= 1 rule, as bldp_reduce_f32 with fqavby = tavby = 1).
+ * Additive in ABI 5.
+ *
+ * Blocks of <= 32 spectra are held in registers, one lane per column (four
+ * columns with float4 loads: unit channel step, nc a multiple of 4); longer
+ * blocks are split over the time slices of a workgroup that meet through LDS,
+ * var / std in two passes with Float64 accumulators, the median by an 8-bit
+ * radix select that re-reads the block every pass.  One launch, no workspace;
+ * var / std of blocks too few to fill the GPU are also cut into time chunks
+ * across workgroups (three launches, Float64 partials in library scratch leased
+ * for the call, added in a fixed order).
+ *
+ * bldp_tstat_shape: dims = {nc, ni, nb}; pure host, every argument check but
+ * the op's.
+ * bldp_tstat_plan_f32: info = {path (0 regs_moments, 1 regs_median,
+ * 2 split_moments, 3 split_median, 4 chunk_moments; -1 the copy of tavby <= 1), channels per
+ * lane, time slices of a workgroup splitting a block, passes over the block,
+ * workgroups per bank, workspace bytes, nb, lanes along the channels of a split
+ * workgroup}; launches nothing and needs no GPU (pointers may be null).
+ * bldp_tstat_f32: device pointers, asynchronous on `stream`; element (c, i, b)
+ * at out[c + i*out_ld_i + b*out_ld_b] (elements; dense = (nc, nc*ni)), so a
+ * bank can write its slot of a stitched product.
+ * bldp_band_tstat_f32: in[] is a HOST array of device pointers of banks with
+ * one geometry; out is the vcat of the banks, dense (nbank*nc, ni, nb); one
+ * launch for the band.
+ * bldp_tstat_host_f32: host in, host dense (nc, ni, nb) out; the window's rows
+ * are staged on device `dev`.  Synchronous. */
+BLDP_API int bldp_tstat_shape(int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win,
+                              int64_t tavby, int64_t dims[3]);
+BLDP_API int bldp_tstat_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                                 const int64_t *win, int64_t tavby, int op, const float *out,
+                                 int64_t info[8]);
+BLDP_API int bldp_tstat_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                            const int64_t *win, int64_t tavby, int op, float *out,
+                            int64_t out_ld_i, int64_t out_ld_b, void *stream);
+BLDP_API int bldp_band_tstat_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                                 int64_t ntime, const int64_t *win, int64_t tavby, int op,
+                                 float *out, void *stream);
+BLDP_API int bldp_tstat_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                 int64_t ntime, const int64_t *win, int64_t tavby, int op,
+                                 float *out);
+
 /* Element types other than Float32 (what Blio maps SIGPROC nbits 8 / 16 to, and
  * what HDF5.jl returns for an integer or Float64 dataset: the reference's
  * readers hand any of them to fqav / kurtosis, src/gbtworkerfunctions.jl:173,
