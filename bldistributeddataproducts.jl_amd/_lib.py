@@ -27,6 +27,13 @@ KURT_PATHS = {0: "regs", 1: "mid", 2: "leaf", 3: "twopass"}
 # std of blocks too few to fill the GPU also over workgroups (time chunks)
 TSTAT_PATHS = {0: "regs_moments", 1: "regs_median", 2: "split_moments", 3: "split_median",
                4: "chunk_moments"}
+# fqavfunc argmax / argmin (csrc/argext.hip; enum bldp_argop): the winner's
+# offset k + F*tt in its F x T block, Julia's rule (first occurrence, NaN first
+# of all).  Not reduce ops: the output is an index, so they stay out of OPS.
+ARG_OPS = {"argmax": 0, "argmin": 1}
+# blocks of F <= 1024 over the lanes of a wave streaming the T rows, the same
+# with the rows split over the time slices of a workgroup, F > 1024 a workgroup
+ARGEXT_PATHS = {0: "lanes", 1: "lanes_tsplit", 2: "block"}
 
 BLDP_OK, BLDP_EINVAL, BLDP_EDIM, BLDP_EHIP, BLDP_ENOMEM, BLDP_EBOUNDS = 0, -1, -2, -3, -5, -6
 BLDP_ECOMM, BLDP_EIO = -7, -8
@@ -107,6 +114,10 @@ SIGNATURES = {
     "bldp_tstat_f32": ([P, I64, I64, I64, P, I64, I, P, I64, I64, P], I),
     "bldp_band_tstat_f32": ([I, P, I64, I64, I64, P, I64, I, P, P], I),
     "bldp_tstat_host_f32": ([I, P, I64, I64, I64, P, I64, I, P], I),
+    "bldp_argext_plan_f32": ([P, I64, I64, I64, P, I64, I64, I, P, P], I),
+    "bldp_argext_f32": ([P, I64, I64, I64, P, I64, I64, I, P, P, I64, I64, P], I),
+    "bldp_band_argext_f32": ([I, P, I64, I64, I64, P, I64, I64, I, P, P, P], I),
+    "bldp_argext_host_f32": ([I, P, I64, I64, I64, P, I64, I64, I, P, P], I),
     "bldp_fqav_range": ([D, D, I64, I64, P, P, P], I),
     "bldp_synth_f32": ([P, I64, I64, I64, I64, U64, I, P], I),
     "bldp_reduce_out_dtype": ([I, I], I),

@@ -1191,6 +1191,147 @@ int bldp_band_tstat_f32(int nbank, const float *const *in, int64_t nchan, int64_
                    nbank * d[0] * d[1], stream);
 }
 
+// ---- fqavfunc argmax / argmin: the winner's offset in every F x T block ------
+// Checks, window and plan of an argext (every entry point).  The outputs'
+// element (c', i, t') of bank b sits at [b*out_bank + c' + i*out_ld_i + t'*out_ld_t].
+static int argext_prepare(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                          int64_t ntime, const int64_t *win, int64_t fqavby, int64_t tavby,
+                          int argop, uint32_t *idx, float *val, int64_t out_bank,
+                          int64_t out_ld_i, int64_t out_ld_t, bool query, ArgArgs *ap, Plan *pp,
+                          bool *empty) {
+  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
+    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
+  if (argop != BLDP_ARG_MAX && argop != BLDP_ARG_MIN)
+    return fail(BLDP_EINVAL, "argext: unknown argop %d (0=argmax 1=argmin)", argop);
+  Geo g;
+  int rc = resolve_window(nchan, nif, ntime, win, &g);
+  if (rc) return rc;
+  int64_t F, T;
+  rc = resolve_factors(g, fqavby, tavby, &F, &T);
+  if (rc) return rc;
+  // offsets are 31-bit (F <= nc and T <= nt: the product cannot overflow int64
+  // for arrays that exist, and is checked by division anyway)
+  if (F > INT32_MAX / T)
+    return fail(BLDP_EINVAL, "argext: blocks of fqavby x tavby = %lld x %lld elements are beyond "
+                "2^31 - 1", (long long)F, (long long)T);
+  ArgArgs &aa = *ap;
+  aa = ArgArgs{};
+  RedArgs &a = aa.r;
+  a.nco = g.nc / F;
+  a.ni = g.ni;
+  a.nto = g.nt / T;
+  a.F = F;
+  a.T = T;
+  a.nbank = nbank;
+  a.out_bank = out_bank;
+  a.out_ld_i = out_ld_i;
+  a.out_ld_t = out_ld_t;
+  a.in_off = g.off;
+  a.in_cs = g.cs;
+  a.in_ld_i = g.ld_i;
+  a.in_ld_t = g.ld_t;
+  a.out = val;
+  aa.idx = idx;
+  aa.inv = argop == BLDP_ARG_MIN ? 0xffffffffu : 0u;
+  *empty = a.nco == 0 || a.ni == 0 || a.nto == 0;
+  if (!in) return fail(BLDP_EINVAL, "argext: null input pointer array");
+  bool words = true;
+  for (int b = 0; b < nbank; ++b) {
+    a.in[b] = in[b];
+    words = words && aligned4(in[b]);
+  }
+  rc = plan_argext(aa, words && g.cs == 1, num_cus_current(), xcd_log2_current(), pp);
+  if (rc) return rc;
+  if (query || *empty) return BLDP_OK;
+  for (int b = 0; b < nbank; ++b)
+    if (!in[b]) return fail(BLDP_EINVAL, "argext: null input pointer (bank %d)", b);
+  if (!idx) return fail(BLDP_EINVAL, "argext: null idx pointer");
+  if (out_ld_i < a.nco || out_ld_t < (a.ni - 1) * out_ld_i + a.nco ||
+      (nbank > 1 && out_bank < a.nco))
+    return fail(BLDP_EINVAL,
+                "argext: out strides (%lld, %lld) overlap for a (%lld, %lld, %lld) result",
+                (long long)out_ld_i, (long long)out_ld_t, (long long)a.nco, (long long)a.ni,
+                (long long)a.nto);
+  // the outputs may not overlap the window's elements, nor each other
+  int64_t lo = g.off, hi = g.off;  // lowest and highest element offset of the window
+  const int64_t span[3] = {(g.nc - 1) * g.cs, (g.ni - 1) * g.ld_i, (g.nt - 1) * g.ld_t};
+  for (int ax = 0; ax < 3; ++ax) (span[ax] < 0 ? lo : hi) += span[ax];
+  const int64_t last = (nbank - 1) * out_bank + (a.nco - 1) + (a.ni - 1) * out_ld_i +
+                       (a.nto - 1) * out_ld_t;  // of an output
+  auto overlap = [](const void *p, int64_t pn, const void *q, int64_t qn) {
+    const uintptr_t a0 = (uintptr_t)p, b0 = (uintptr_t)q;
+    return a0 < b0 + (uintptr_t)qn && b0 < a0 + (uintptr_t)pn;
+  };
+  const int64_t obytes = 4 * (last + 1);
+  for (int b = 0; b < nbank; ++b) {
+    const float *w0 = in[b] + lo;
+    const int64_t wbytes = 4 * (hi - lo + 1);
+    if (overlap(idx, obytes, w0, wbytes) || (val && overlap(val, obytes, w0, wbytes)))
+      return fail(BLDP_EINVAL, "argext: idx / val overlap the input window (bank %d)", b);
+  }
+  if (val && overlap(idx, obytes, val, obytes))
+    return fail(BLDP_EINVAL, "argext: idx and val overlap");
+  return BLDP_OK;
+}
+
+static int argext_run(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                      int64_t ntime, const int64_t *win, int64_t fqavby, int64_t tavby, int argop,
+                      uint32_t *idx, float *val, int64_t out_bank, int64_t out_ld_i,
+                      int64_t out_ld_t, void *stream) {
+  ArgArgs a;
+  Plan p;
+  bool empty = false;
+  int rc = argext_prepare(nbank, in, nchan, nif, ntime, win, fqavby, tavby, argop, idx, val,
+                          out_bank, out_ld_i, out_ld_t, false, &a, &p, &empty);
+  if (rc || empty) return rc;
+  hipError_t e = launch_argext(a, p, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(BLDP_EHIP, "argext launch: %s", hipGetErrorString(e));
+  return BLDP_OK;
+}
+
+int bldp_argext_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                         const int64_t *win, int64_t fqavby, int64_t tavby, int argop,
+                         const uint32_t *idx, int64_t info[8]) {
+  if (!info) return fail(BLDP_EINVAL, "null info");
+  ArgArgs a;
+  Plan p;
+  bool empty = false;
+  const float *ins[1] = {in};
+  int rc = argext_prepare(1, ins, nchan, nif, ntime, win, fqavby, tavby, argop, (uint32_t *)idx,
+                          nullptr, 0, 0, 0, true, &a, &p, &empty);
+  if (rc) return rc;
+  info[0] = p.path;
+  info[1] = p.lpg;
+  info[2] = a.r.ts;
+  info[3] = a.r.k4;
+  info[4] = p.grid;
+  info[5] = (int64_t)p.ws_bytes;
+  info[6] = p.nout;
+  info[7] = a.r.k4 != 0;
+  return BLDP_OK;
+}
+
+int bldp_argext_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                    const int64_t *win, int64_t fqavby, int64_t tavby, int argop, uint32_t *idx,
+                    float *val, int64_t out_ld_i, int64_t out_ld_t, void *stream) {
+  const float *ins[1] = {in};
+  return argext_run(1, ins, nchan, nif, ntime, win, fqavby, tavby, argop, idx, val, 0, out_ld_i,
+                    out_ld_t, stream);
+}
+
+int bldp_band_argext_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                         int64_t ntime, const int64_t *win, int64_t fqavby, int64_t tavby,
+                         int argop, uint32_t *idx, float *val, void *stream) {
+  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
+    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
+  int64_t d[3];
+  int rc = bldp_reduce_shape(nchan, nif, ntime, win, fqavby, tavby, d);
+  if (rc) return rc;
+  // the vcat of the banks: bank k's channels at k*nco of every (IF, time) row
+  return argext_run(nbank, in, nchan, nif, ntime, win, fqavby, tavby, argop, idx, val, d[0],
+                    nbank * d[0], nbank * d[0] * d[1], stream);
+}
+
 int bldp_reduce_out_dtype(int dtype, int op) {
   const int d = typed_out_dtype(dtype, op);
   if (d < 0) return fail(BLDP_EINVAL, "unknown element type %d or op %d", dtype, op);

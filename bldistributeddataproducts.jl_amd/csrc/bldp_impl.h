@@ -155,6 +155,21 @@ inline bool stat_op(int op) { return op >= BLDP_OP_VAR && op <= BLDP_OP_MEDIAN; 
 int plan_stats(RedArgs &a, int op, bool words, int xcd_lg, Plan *p);
 hipError_t launch_stats(const RedArgs &a, const Plan &p, int op, hipStream_t s);
 
+// argmax / argmin of every F x T block (argext.hip): the offset k + F * tt of the
+// winner in its block (column-major, channel fastest), first occurrence, NaN
+// first of all; optionally the winner's bits.  r is the reduce's geometry
+// (r.out: the value output or null; r.ts / r.tsub_log2: the time slices of a
+// workgroup that split a block's rows; r.k4: float4 loads per lane per row, 0 =
+// one dword per element).  plan_argext fills the launch geometry like plan_stats.
+struct ArgArgs {
+  RedArgs r;
+  uint32_t *idx;  // output (c', i, t') of bank b at idx[b*out_bank + c' + i*out_ld_i + t'*out_ld_t]
+  uint32_t inv;   // 0 = argmax, 0xffffffff = argmin (the key is inverted)
+};
+enum ArgExtPath { ARGEXT_LANES = 0, ARGEXT_LANES_TSPLIT = 1, ARGEXT_BLOCK = 2 };
+int plan_argext(ArgArgs &a, bool words, int num_cus, int xcd_lg, Plan *p);
+hipError_t launch_argext(const ArgArgs &a, const Plan &p, hipStream_t s);
+
 // median / var / std of every block of T selected spectra of every (channel,
 // IF) column (tstats.hip): tavfunc, fqav's rule on the time axis.  Window
 // element (c, i, t) of bank k at in[k][in_off + c*in_cs + i*in_ld_i +

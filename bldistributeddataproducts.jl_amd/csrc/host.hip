@@ -255,6 +255,47 @@ extern "C" int bldp_tstat_host_f32(int dev, const float *in, int64_t nchan, int6
   });
 }
 
+// The same staging for fqavfunc argmax / argmin: the window's rows go to the
+// device once (in window order), the (nco, ni, nto) offsets, and the winners'
+// bits when val is given, come back.
+extern "C" int bldp_argext_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                    int64_t ntime, const int64_t *win, int64_t fqavby,
+                                    int64_t tavby, int argop, uint32_t *idx, float *val) {
+  // (every argument check, before any staging)
+  int64_t info[8];
+  int rc = bldp_argext_plan_f32(nullptr, nchan, nif, ntime, win, fqavby, tavby, argop, nullptr,
+                                info);
+  if (rc) return rc;
+  int64_t sh[3];
+  rc = bldp_reduce_shape(nchan, nif, ntime, win, fqavby, tavby, sh);
+  if (rc) return rc;
+  const int64_t nco = sh[0], ni = sh[1], nto = sh[2], nout = nco * ni * nto;
+  if (nout == 0) return BLDP_OK;
+  if (!in || !idx) return bldp::set_error(BLDP_EINVAL, "argext: null pointer");
+  const int64_t F = fqavby <= 1 ? 1 : fqavby, T = tavby <= 1 ? 1 : tavby;
+  const int64_t nc = nco * F, nt = nto * T;
+  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
+  return with_stager(dev, [&](bldp::Stager *sg) -> int {
+    float *dbuf, *dval = nullptr;
+    uint32_t *didx;
+    int r = bldp::stager_buffer(sg, 0, (size_t)(h.span * ni * nt) * 4, (void **)&dbuf);
+    if (!r) r = bldp::stager_buffer(sg, 2, (size_t)nout * sizeof(uint32_t), (void **)&didx);
+    if (!r && val) r = bldp::stager_buffer(sg, 3, (size_t)nout * sizeof(float), (void **)&dval);
+    if (!r) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
+    if (r) return r;
+    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
+    r = bldp_argext_f32(dbuf, h.span, ni, nt, dwin, fqavby, tavby, argop, didx, dval, nco,
+                        nco * ni, sg->st[0]);
+    if (r) return r;
+    HCHK(hipMemcpyAsync(idx, didx, (size_t)nout * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                        sg->st[0]));
+    if (val)
+      HCHK(hipMemcpyAsync(val, dval, (size_t)nout * sizeof(float), hipMemcpyDeviceToHost,
+                          sg->st[0]));
+    return BLDP_OK;
+  });
+}
+
 // ---------------------------------------------------------------------------
 // Host forms of the typed entry points (include/bldp.h), staged like the
 // Float32 forms above: only the window's rows (its channel span of every

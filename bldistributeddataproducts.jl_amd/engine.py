@@ -25,6 +25,7 @@ __all__ = [
     "stitch",
     "despike", "kurtosis", "kurtosis_blocks_plan", "band_kurtosis", "synth", "plan", "reduce_host", "kurtosis_host",
     "tstat", "tstat_plan", "band_tstat", "tstat_host",
+    "argext", "argext_plan", "band_argext", "argext_host",
     "init", "finalize", "pinned",
 ]
 
@@ -658,6 +659,160 @@ def tstat_host(a: np.ndarray, tavby, op, win=None, device=0) -> np.ndarray:
                                out.ctypes.data if out.size else None)
     _lib.check(rc, "bldp_tstat_host_f32")
     return out
+
+
+def _argext_op(op) -> int:
+    if op not in _lib.ARG_OPS:
+        raise _lib.ArgumentError(_lib.BLDP_EINVAL,
+                                 f"argext takes {sorted(_lib.ARG_OPS)}, not {op!r}")
+    return _lib.ARG_OPS[op]
+
+
+def _argext_out(out, dims, device, values):
+    """The outputs of an argext, checked before any launch: ``out`` is None
+    (new dense tensors), the int32 index tensor, or with ``values`` the pair
+    (idx, val) with val Float32; each a (nco, ni, nto) tensor on ``device``
+    with the channels fastest and rows that do not overlap, both of one layout
+    (the ABI takes one pair of strides).  Returns (idx, val or None, idx
+    pointer, val pointer, out_ld_i, out_ld_t)."""
+    torch = _torch()
+    nco, ni, nto = dims
+    if out is None:
+        idx = fb_empty(*dims, device=device, dtype=torch.int32)
+        val = fb_empty(*dims, device=device) if values else None
+    elif values:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise TypeError("out must be the pair (idx, val) when values=True")
+        idx, val = out
+    else:
+        idx, val = out, None
+    lds = []
+    for t, dt, name in ((idx, torch.int32, "idx"), (val, torch.float32, "val")):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a device tensor")
+        if t.dtype != dt:
+            raise TypeError(f"{name} must be {dt}, not {t.dtype}")
+        if tuple(t.shape) != (nco, ni, nto):
+            raise ValueError(f"{name} is {tuple(t.shape)}, expected {(nco, ni, nto)}")
+        if t.device != torch.device(device):
+            raise ValueError(f"{name} is on {t.device}, the data on {device}")
+        s0, s1, s2 = t.stride()
+        ld_i = s1 if ni > 1 else nco
+        ld_t = s2 if nto > 1 else max(ni - 1, 0) * ld_i + nco
+        if (nco > 1 and s0 != 1) or ld_i < nco or ld_t < (ni - 1) * ld_i + nco:
+            raise ValueError(f"{name} strides {t.stride()} are not a Julia-order "
+                             f"(channel-fastest) layout of {(nco, ni, nto)}")
+        lds.append((ld_i, ld_t))
+    if len(lds) == 2 and lds[0] != lds[1]:
+        raise ValueError(f"idx and val must share one layout, not strides {idx.stride()} and "
+                         f"{val.stride()}")
+    n = nco * ni * nto
+    return (idx, val, idx.data_ptr() if n else None,
+            val.data_ptr() if (n and val is not None) else None, lds[0][0], lds[0][1])
+
+
+def argext(x, fqavby, tavby, op, win=None, values=False, out=None, stream=None):
+    """"argmax" / "argmin" of every fqavby x tavby block of the window, on the
+    GPU (bldp_argext_f32): where in its block the extreme lies, as the 0-based
+    offset ``k + fqavby * tt`` (k along the block's channels, tt along its
+    spectra: Julia's column-major order), Julia's rule: the first of the
+    isless-greatest (least) elements, and the first NaN when the block holds
+    one.  x: a Float32 device filterbank tensor; returns a Julia-order
+    (nc/F, ni, nt/T) int32 device tensor, or with ``values`` the pair
+    (idx, val), val holding the winners' bits (Float32).  ``out``: the idx
+    tensor (the pair with ``values``) to write, e.g. a bank's slot of a
+    stitched product."""
+    L = _lib.lib()
+    code = _argext_op(op)
+    shape = tuple(x.shape)
+    _check_bounds(win, shape)
+    dims = out_shape(shape, win, fqavby, tavby)
+    ptr, nchan, nif, ntime = _abi_dims(x)
+    idx, val, iptr, vptr, ld_i, ld_t = _argext_out(out, dims, x.device, values)
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    rc = L.bldp_argext_f32(ptr, nchan, nif, ntime, wp, int(fqavby), int(tavby), code, iptr, vptr,
+                           ld_i, ld_t, _lib.stream_ptr(stream))
+    _lib.check(rc, "bldp_argext_f32")
+    return (idx, val) if values else idx
+
+
+def argext_plan(x, fqavby, tavby, op, win=None) -> dict:
+    """Launch plan of ``argext(x, fqavby, tavby, op, win)``
+    (bldp_argext_plan_f32): the path (_lib.ARGEXT_PATHS), the lanes sharing a
+    block (256: a workgroup), the time slices of a workgroup splitting a
+    block's rows, float4 loads per lane per row, workgroups, workspace bytes,
+    outputs and whether the loads are float4."""
+    L = _lib.lib()
+    code = _argext_op(op)
+    shape = tuple(x.shape)
+    _check_bounds(win, shape)
+    ptr, nchan, nif, ntime = _abi_dims(x)
+    info = (ctypes.c_int64 * 8)()
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    _lib.check(L.bldp_argext_plan_f32(ptr, nchan, nif, ntime, wp, int(fqavby), int(tavby), code,
+                                      None, info), "bldp_argext_plan_f32")
+    keys = ["path", "lanes_per_block", "time_slices", "float4_per_lane", "workgroups",
+            "workspace_bytes", "outputs", "vector_loads"]
+    d = dict(zip(keys, [int(v) for v in info]))
+    d["path"] = _lib.ARGEXT_PATHS[d["path"]]
+    return d
+
+
+def band_argext(banks, fqavby, tavby, op, win=None, values=False, stream=None):
+    """``argext`` of every bank of a band resident on ONE GPU in one launch
+    (bldp_band_argext_f32): dense (nbank*nco, ni, nto) tensors, the vcat of the
+    per-bank results (offsets are relative to each block, so stitching is
+    concatenation)."""
+    L = _lib.lib()
+    code = _argext_op(op)
+    torch = _torch()
+    banks = list(banks)
+    if not banks:
+        raise ValueError("no banks")
+    shape = tuple(banks[0].shape)
+    geo = _abi_dims(banks[0])[1:]
+    for b in banks:
+        if tuple(b.shape) != shape or _abi_dims(b)[1:] != geo or b.device != banks[0].device:
+            raise ValueError("all banks of a band must have the same shape, layout and device")
+    _check_bounds(win, shape)
+    nco, ni, nto = out_shape(shape, win, fqavby, tavby)
+    nb = len(banks)
+    idx = fb_empty(nb * nco, ni, nto, device=banks[0].device, dtype=torch.int32)
+    val = fb_empty(nb * nco, ni, nto, device=banks[0].device) if values else None
+    ptrs = (ctypes.c_void_p * nb)(*[b.data_ptr() for b in banks])
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    n = idx.numel()
+    rc = L.bldp_band_argext_f32(nb, ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp, int(fqavby),
+                                int(tavby), code, idx.data_ptr() if n else None,
+                                val.data_ptr() if (n and values) else None,
+                                _lib.stream_ptr(stream))
+    _lib.check(rc, "bldp_band_argext_f32")
+    return (idx, val) if values else idx
+
+
+def argext_host(a: np.ndarray, fqavby, tavby, op, win=None, values=False, device=0):
+    """Host Fortran-ordered Float32 array in, (nco, ni, nto) int32 host array of
+    offsets out, with ``values`` the pair (idx, val)
+    (bldp_argext_host_f32: the window's rows staged on ``device``)."""
+    L = _lib.lib()
+    code = _argext_op(op)
+    a = np.asarray(a)
+    if a.dtype != np.float32 or not a.flags.f_contiguous or a.ndim != 3:
+        raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
+    _check_bounds(win, a.shape)
+    dims = out_shape(a.shape, win, fqavby, tavby)
+    idx = np.empty(dims, dtype=np.uint32, order="F")
+    val = np.empty(dims, dtype=np.float32, order="F") if values else None
+    keep, wp = _lib.win_arg(_full_win(win, a.shape))
+    rc = L.bldp_argext_host_f32(int(device), a.ctypes.data if a.size else None, a.shape[0],
+                                a.shape[1], a.shape[2], wp, int(fqavby), int(tavby), code,
+                                idx.ctypes.data if idx.size else None,
+                                val.ctypes.data if (values and val.size) else None)
+    _lib.check(rc, "bldp_argext_host_f32")
+    idx = idx.view(np.int32)  # offsets are < 2^31
+    return (idx, val) if values else idx
 
 
 def stitch(gathered, nbank, out=None, stream=None):

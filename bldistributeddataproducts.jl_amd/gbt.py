@@ -79,7 +79,8 @@ def getdata(workers, fnames, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum
             tavfunc=None):
     """src/gbt.jl:69-79 (+ tavby): an array of per-bank (nchan/fqavby, nif,
     ntime/tavby) Float32 arrays, the same size as workers/fnames.  ``tavfunc``
-    as in WorkerFunctions.getdata (the time integration's own function)."""
+    as in WorkerFunctions.getdata (the time integration's own function).
+    ``fqavfunc="argmax" | "argmin"``: per-bank int32 arrays of block offsets."""
     return _fanout(workers, fnames,
                    lambda w, f: W.getdata(f, idxs, fqavby, fqavfunc, tavby, device=int(w),
                                           tavfunc=tavfunc))
@@ -438,7 +439,10 @@ def getband(workers, fnames, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum
     from the reduce kernel (default: the environment's BLDP_BAND_PEER_STORE,
     else off: such banks are reduced on their GPU and copied into the slot).
     ``tavfunc`` as in WorkerFunctions.getdata: each bank's last stage writes
-    its slot of the stitched product."""
+    its slot of the stitched product.  ``fqavfunc="argmax" | "argmin"`` returns
+    the vcat of the banks' int32 offset arrays (offsets are relative to each
+    block, so stitching is concatenation; stitched on the host); an index
+    product has no DC spike to patch (``despike_nfpc``: TypeError)."""
     w = np.asarray(workers, dtype=object)
     f = np.asarray(fnames, dtype=object)
     if w.ndim not in (1, 2):
@@ -448,7 +452,10 @@ def getband(workers, fnames, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum
         raise ValueError("stitch must be 'device' or 'host'")
     wcol = [list(w)] if w.ndim == 1 else [list(w[:, j]) for j in range(w.shape[1])]
     fcol = [list(f)] if f.ndim == 1 else [list(f[:, j]) for j in range(f.shape[1])]
-    op = W._opname(fqavfunc)
+    aop = W._check_argop(fqavfunc, tavfunc)
+    if aop is not None and despike_nfpc:
+        raise TypeError(f"fqavfunc {aop!r} gives block offsets: despike_nfpc does not apply")
+    op = None if aop is not None else W._opname(fqavfunc)  # (offsets: the host stitch below)
     if tavfunc is not None:
         W._tav_ops(fqavby, fqavfunc, tavfunc)  # the errors, before any read
     bands = [None] * len(wcol)

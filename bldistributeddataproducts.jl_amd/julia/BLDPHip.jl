@@ -12,7 +12,7 @@ module BLDPHip
 using Statistics: mean, median, var, std
 
 export gpu_init, gpu_finalize, gpu_pin, gpu_unpin, gpu_fqav, gpu_reduce, gpu_kurtosis, gpu_band,
-       gpu_tstat, gpu_comm_id, gpu_comm_init, gpu_comm_destroy, gpu_band_gather
+       gpu_tstat, gpu_argext, gpu_comm_id, gpu_comm_init, gpu_comm_destroy, gpu_band_gather
 
 const libbldp = get(ENV, "BLDP_LIB", joinpath(@__DIR__, "..", "libbldp_hip.so"))
 
@@ -285,6 +285,39 @@ function gpu_tstat(in::Ptr{Float32}, dims::NTuple{3,Integer}, tavby::Integer, ou
     (shp[1], shp[2], shp[3])
 end
 
+# fqavfunc values whose result is a position (csrc/argext.hip, enum bldp_argop)
+argcode(f) = f === argmax ? Cint(0) : f === argmin ? Cint(1) : nothing
+
+"""
+    gpu_argext(A::Array{Float32,3}, fqavby, tavby=1; f=argmax, idxs=(:,:,:), dev=0, values=false)
+
+Where in each `fqavby` x `tavby` block of `A[idxs...]` the extreme lies, computed
+on GPU `dev` (bldp_argext_host_f32): an `Array{Int32,3}` of 1-based offsets
+`k + fqavby * (tt - 1)` into the block in column-major order, i.e. the linear
+index of `argmax(reshape(block, fqavby, tavby))`: the first of the
+isless-greatest (`f=argmin`: least) elements, and the first NaN when the block
+holds one.  `values=true` returns `(vals, offs)` as `findmax` orders them,
+`vals` being the elements at the offsets."""
+function gpu_argext(A::Array{Float32,3}, fqavby::Integer, tavby::Integer=1;
+                    f=argmax, idxs::Tuple=(:, :, :), dev::Integer=0, values::Bool=false)
+    op = argcode(f)
+    op === nothing && throw(ArgumentError("gpu_argext takes argmax or argmin, not $f"))
+    win = window(idxs, size(A))
+    shp = zeros(Int64, 3)
+    GC.@preserve win check(ccall((:bldp_reduce_shape, libbldp), Cint,
+        (Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Ptr{Int64}),
+        size(A, 1), size(A, 2), size(A, 3), win, fqavby, tavby, shp))
+    idx = Array{UInt32,3}(undef, shp...)
+    val = values ? Array{Float32,3}(undef, shp...) : nothing
+    vp = values ? pointer(val) : Ptr{Float32}(C_NULL)
+    GC.@preserve A win idx val check(ccall((:bldp_argext_host_f32, libbldp), Cint,
+        (Cint, Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Cint, Ptr{UInt32},
+         Ptr{Float32}),
+        dev, A, size(A, 1), size(A, 2), size(A, 3), win, fqavby, tavby, op, idx, vp))
+    offs = Int32.(idx) .+ Int32(1)   # 0-based offsets < 2^31 -> Julia's 1-based
+    values ? (val, offs) : offs
+end
+
 """
     getdata(A::Array; idxs=(:,:,:), fqavby=1, fqavfunc=sum, tavby=1, tavfunc=nothing, dev=0)
 
@@ -295,10 +328,19 @@ integration takes its own function,
 `tav(fqav(A[idxs...], fqavby; f=fqavfunc), tavby; f=tavfunc)`; either stage is
 skipped when its factor is <= 1.  var / std / median of Float32 data run in
 gpu_tstat, sum / mean / maximum / minimum in gpu_reduce, anything else (other
-element types, other functions) in Julia on the host."""
+element types, other functions) in Julia on the host.  `fqavfunc === argmax` /
+`argmin` of Float32 data with `tavby <= 1` run in gpu_argext and return the
+`CartesianIndex(k, c', i, t)` array the reference's fqav returns."""
 function getdata(A::Array{T,3}; idxs::Tuple=(:, :, :), fqavby::Integer=1, fqavfunc=sum,
                  tavby::Integer=1, tavfunc=nothing, dev::Integer=0) where {T}
     W = all(i -> i isa Colon, idxs) ? A : A[map(i -> i isa Integer ? (i:i) : i, idxs)...]
+    if argcode(fqavfunc) !== nothing && W isa Array{Float32,3} && tavby <= 1 && fqavby > 1
+        # fqav(W, fqavby; f=argmax) is argmax(reshape(W, fqavby, :, ni, nt); dims=1)
+        # with dims=1 dropped: the CartesianIndex (k, c', i, t) of each block's winner
+        tavfunc === nothing || throw(ArgumentError("argmax / argmin take no tavfunc"))
+        offs = gpu_argext(W, fqavby; f=fqavfunc, dev)
+        return [CartesianIndex(Int(offs[I]), I[1], I[2], I[3]) for I in CartesianIndices(offs)]
+    end
     tavfunc === nothing && return gpu_fqav(W, fqavby; f=fqavfunc, tavby, dev)
     B = gpu_fqav(W, fqavby; f=fqavfunc, dev)
     tavby <= 1 && return B

@@ -20,6 +20,14 @@ of an even block) on the GPU for Float32 data, without time integration
 (``tavby > 1`` is a TypeError); data of other element types get the same
 rules on the host in Float64, as Julia's result type is.  Only the strings
 select them: ``numpy.std`` is the population form, not Julia's.
+The strings ``"argmax" | "argmin"`` give where in each fqavby x tavby block the
+extreme lies (Julia's ``argmax`` / ``argmin`` with ``dims``, the position half
+of ``findmax``): an int32 array of 0-based offsets ``k + fqavby * tt`` into the
+block in Julia's column-major order, the first of the isless-greatest (least)
+elements and the first NaN when the block holds one; Float32 data on the GPU
+(csrc/argext.hip), other element types by the same rule on the host.
+``findmax`` / ``findmin`` return the values and the offsets from one pass.
+``numpy.argmax`` is NumPy's rule and stays a host callable.
 Any other callable is applied on the host exactly like the reference's
 generic ``f(reshape(A, ...); dims=1)`` path (README.md:192-195) — that is the
 reference behaviour for functions the GPU does not implement, not a fallback
@@ -36,7 +44,7 @@ from .idxs import COLON, JRange, sanitizeidxs, to_window  # noqa: F401  (re-expo
 
 __all__ = [
     "fqav", "FRange", "sanitizeidxs", "getdata", "getfbdata", "getfbh5data", "getkurtosis",
-    "getinventory", "getfbheader", "getfbh5header", "getheader",
+    "getinventory", "getfbheader", "getfbh5header", "getheader", "findmax", "findmin",
 ]
 
 
@@ -68,6 +76,16 @@ def _opname(f) -> str | None:
     names = {sum: "sum", max: "max", min: "min", np.sum: "sum", np.mean: "mean",
              np.max: "max", np.min: "min", np.amax: "max", np.amin: "min"}
     return names.get(f)
+
+
+def _argop(f) -> str | None:
+    """"argmax" / "argmin" for those strings (Julia's rule, csrc/argext.hip),
+    else None: numpy.argmax and friends stay host callables with NumPy's rule."""
+    return f if isinstance(f, str) and f in _lib.ARG_OPS else None
+
+
+def _is_path(x) -> bool:
+    return isinstance(x, (str, bytes)) or hasattr(x, "__fspath__")
 
 
 def _is_tensor(x) -> bool:
@@ -141,6 +159,111 @@ def _host_stat(a: np.ndarray, n: int, op: str, win=None, axis: int = 0) -> np.nd
     return np.asfortranarray(np.moveaxis(r, 0, axis))
 
 
+def _host_argext(a: np.ndarray, fqavby, tavby, op: str, win=None, values=False):
+    """Julia's argmax / argmin of every fqavby x tavby block for the element
+    types the GPU op does not take (integers, Float64): the int32 offset
+    ``k + fqavby * tt`` of the winner in its block (column-major), the first of
+    the isless-greatest (least) elements (-0.0 < 0.0), and the first NaN when
+    the block holds one; with ``values`` also the winning elements."""
+    a = np.asarray(a)
+    if win is not None:
+        a = a[np.ix_(*[win[3 * k] + win[3 * k + 2] * np.arange(win[3 * k + 1])
+                       for k in range(3)])]
+    F, T = max(int(fqavby), 1), max(int(tavby), 1)
+    nc, ni, nt = a.shape
+    if nc % F:
+        raise _lib.DimensionMismatch(_lib.BLDP_EDIM,
+                                     f"DimensionMismatch: fqavby={F} does not divide nchan={nc}")
+    if nt % T:
+        raise _lib.DimensionMismatch(_lib.BLDP_EDIM,
+                                     f"DimensionMismatch: tavby={T} does not divide ntime={nt}")
+    if F * T > 2 ** 31 - 1:
+        raise _lib.ArgumentError(_lib.BLDP_EINVAL, f"blocks of {F} x {T} are beyond 2^31 - 1")
+    # (F*T, nco, ni, nto): a block along axis 0 in Julia's order, channel fastest
+    R = np.asfortranarray(a).reshape((F, nc // F, ni, T, nt // T), order="F")
+    B = np.asfortranarray(np.moveaxis(R, 3, 1)).reshape((F * T, nc // F, ni, nt // T), order="F")
+    if B.dtype.kind == "f":
+        ut = {4: np.uint32, 8: np.uint64}[B.dtype.itemsize]
+        top = ut(1) << ut(8 * B.dtype.itemsize - 1)
+        u = B.view(ut)
+        key = np.where(u & top != 0, ~u, u | top)  # isless order as unsigned order
+        if op == "argmin":
+            key = ~key
+        key = np.where(np.isnan(B), ut(np.iinfo(ut).max), key)  # any NaN wins
+        idx = np.argmax(key, axis=0)  # (first occurrence)
+    else:
+        idx = np.argmax(B, axis=0) if op == "argmax" else np.argmin(B, axis=0)
+    val = np.take_along_axis(B, idx[None], axis=0)[0] if values else None
+    idx = np.asfortranarray(idx.astype(np.int32))
+    return (idx, np.asfortranarray(val)) if values else idx
+
+
+def _argext_array(x, idxs, fqavby, tavby, aop, device, values=False):
+    """argmax / argmin of an in-memory filterbank: a device tensor stays on the
+    device, a Float32 host array goes through the GPU, other element types get
+    the same rule on the host."""
+    idxs = sanitizeidxs(idxs)
+    if _is_tensor(x):
+        return engine.argext(x, fqavby, tavby, aop, to_window(idxs, x.shape), values=values)
+    a = np.asarray(x)
+    if a.ndim != 3:
+        raise ValueError("filterbank arrays are 3-D (nchan, nif, ntime)")
+    win = to_window(idxs, a.shape)
+    if a.dtype == np.float32:
+        return engine.argext_host(np.asfortranarray(a), fqavby, tavby, aop, win, values=values,
+                                  device=device)
+    if engine._dtype_code(a.dtype) is None:
+        raise TypeError(f"element type {a.dtype} is not supported")
+    engine._check_bounds(win, a.shape)
+    return _host_argext(a, fqavby, tavby, aop, win, values=values)
+
+
+def _argext_file(fname, idxs, fqavby, tavby, aop, device, values=False):
+    """argmax / argmin of a file's window: read onto the GPU the way getdata
+    reads it (window_on_device) and reduced there; only the offsets (and the
+    values) come back."""
+    got = window_on_device(fname, idxs, device)
+    if got is not None:
+        import torch
+
+        x, rwin = got
+        with torch.cuda.device(x.device):
+            r = engine.argext(x, fqavby, tavby, aop, rwin, values=values)
+            return tuple(engine.fb_to_numpy(t) for t in r) if values else engine.fb_to_numpy(r)
+    # not Float32, or an empty window: the host-array path
+    if readers.ishdf5(fname):
+        return _argext_array(readers.fbh5_read(fname, idxs), (COLON, COLON, COLON), fqavby, tavby,
+                             aop, device, values)
+    _, data = readers.fil_mmap(fname)
+    try:
+        return _argext_array(data, idxs, fqavby, tavby, aop, device, values)
+    finally:
+        del data
+
+
+def _findext(src, idxs, fqavby, tavby, device, aop):
+    assert len(idxs) == 3, "idxs must have exactly three indices"
+    if _is_path(src):
+        idx, val = _argext_file(src, sanitizeidxs(idxs), fqavby, tavby, aop, device, values=True)
+    else:
+        idx, val = _argext_array(src, idxs, fqavby, tavby, aop, device, values=True)
+    return val, idx
+
+
+def findmax(x_or_fname, idxs=(COLON, COLON, COLON), fqavby=1, tavby=1, device=0):
+    """Julia's ``findmax`` over every fqavby x tavby block of the window, in
+    one pass: ``(values, idx)`` with ``idx`` as ``fqavfunc="argmax"`` gives it
+    (int32, 0-based ``k + fqavby * tt``) and ``values`` the elements there (a
+    NaN where the block holds one).  A file or host array gives host arrays, a
+    device tensor device tensors."""
+    return _findext(x_or_fname, idxs, fqavby, tavby, device, "argmax")
+
+
+def findmin(x_or_fname, idxs=(COLON, COLON, COLON), fqavby=1, tavby=1, device=0):
+    """``findmax``'s counterpart for the isless-least element (``"argmin"``)."""
+    return _findext(x_or_fname, idxs, fqavby, tavby, device, "argmin")
+
+
 def fqav(A, n: int, f="sum"):
     """Reduce every ``n`` elements of the first dimension of ``A`` with ``f``
     (src/gbtworkerfunctions.jl:16-20).  ``n <= 1`` returns ``A`` itself (:17).
@@ -150,6 +273,16 @@ def fqav(A, n: int, f="sum"):
         return fqav_range(A, n)
     if n <= 1:
         return A
+    aop = _argop(f)
+    if aop is not None:  # where in each block of n the extreme lies (int32 offsets)
+        if _is_tensor(A):
+            return engine.argext(A, n, 1, aop)
+        A = np.asarray(A)
+        if A.ndim > 3:
+            raise ValueError("fqav arrays are at most 3-D (nchan, nif, ntime)")
+        a3 = A.reshape(A.shape + (1,) * (3 - A.ndim), order="F")
+        out = _argext_array(a3, (COLON, COLON, COLON), n, 1, aop, 0)
+        return out.reshape((out.shape[0],) + A.shape[1:], order="F")
     op = _opname(f)
     if _is_tensor(A):
         if op is None:
@@ -182,7 +315,21 @@ def _reduce_host(a, fqavby, tavby, op, win, device):
     return engine.reduce_host_typed(a, fqavby, tavby, op, win, device=device)
 
 
+def _check_argop(fqavfunc, tavfunc):
+    """fqavfunc's arg op, or None; an arg op's result is an index, which no
+    tavfunc can integrate (TypeError, as Julia's MethodError)."""
+    aop = _argop(fqavfunc)
+    if aop is not None and tavfunc is not None:
+        raise TypeError(f"fqavfunc {aop!r} gives block offsets: it takes tavby, not a tavfunc")
+    return aop
+
+
 def _reduce_array(x, idxs, fqavby, fqavfunc, tavby, device, tavfunc=None):
+    aop = _check_argop(fqavfunc, tavfunc)
+    if aop is not None:
+        if fqavby <= 1 and tavby <= 1:  # fqav(A, n <= 1) returns A whatever f is (:17)
+            return _reduce_array(x, idxs, 1, "sum", 1, device)
+        return _argext_array(x, idxs, fqavby, tavby, aop, device)
     if tavfunc is not None:
         return _tav_array(x, idxs, fqavby, fqavfunc, tavby, tavfunc, device)
     idxs = sanitizeidxs(idxs)
@@ -339,6 +486,12 @@ def getfbdata(fbname, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum", tavb
     ``tavfunc``: as getdata."""
     assert len(idxs) == 3, "idxs must have exactly three indices"  # :172
     idxs = sanitizeidxs(idxs)
+    aop = _check_argop(fqavfunc, tavfunc)
+    if aop is not None:
+        if fqavby <= 1 and tavby <= 1:  # fqav(A, n <= 1) returns A whatever f is (:17)
+            fqavfunc = "sum"
+        else:
+            return _argext_file(fbname, idxs, fqavby, tavby, aop, device)
     if tavfunc is not None:
         return _tav_file(fbname, idxs, fqavby, fqavfunc, tavby, tavfunc, device)
     op = _opname(fqavfunc)
@@ -361,6 +514,12 @@ def getfbh5data(fbh5name, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum", 
     (src/gbtworkerfunctions.jl:179-189).  ``tavfunc``: as getdata."""
     assert len(idxs) == 3, "idxs must have exactly three indices"  # :180
     idxs = sanitizeidxs(idxs)
+    aop = _check_argop(fqavfunc, tavfunc)
+    if aop is not None:
+        if fqavby <= 1 and tavby <= 1:  # fqav(A, n <= 1) returns A whatever f is (:17)
+            fqavfunc = "sum"
+        else:
+            return _argext_file(fbh5name, idxs, fqavby, tavby, aop, device)
     if tavfunc is not None:
         return _tav_file(fbh5name, idxs, fqavby, fqavfunc, tavby, tavfunc, device)
     op = _opname(fqavfunc)
@@ -439,6 +598,9 @@ def getdata_device(fname, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum", 
     tensor), written into ``out`` when given — e.g. a bank's slot of a stitched
     band product (GBT.getband); None when the data are not Float32.  With
     ``tavfunc`` (as getdata) the last stage writes ``out``."""
+    if _check_argop(fqavfunc, tavfunc) is not None:
+        raise TypeError("the device path writes Float32 products: argmax / argmin go through "
+                        "getdata or engine.argext")
     if tavfunc is not None:
         op1, op2 = _tav_ops(fqavby, fqavfunc, tavfunc)
         got = window_on_device(fname, idxs, device)
@@ -476,7 +638,11 @@ def getdata(fname, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum", tavby=1
     ``R[c, i, b] = tavfunc(B[c, i, b*tavby : (b+1)*tavby])``.  Either stage is
     skipped when its factor is <= 1; tavby must divide the selected spectra
     (DimensionMismatch).  Float32 data stay on the GPU between the stages;
-    var / std / median of other element types are Float64 from the host."""
+    var / std / median of other element types are Float64 from the host.
+
+    ``fqavfunc="argmax" | "argmin"``: an int32 array of each block's winner's
+    0-based offset ``k + fqavby * tt`` (module docstring); no ``tavfunc``."""
+    _check_argop(fqavfunc, tavfunc)  # (the TypeError before any file is touched)
     if not isinstance(fname, (str, bytes)) and not hasattr(fname, "__fspath__"):
         return _reduce_array(fname, idxs, fqavby, fqavfunc, tavby, device, tavfunc)
     idxs = sanitizeidxs(idxs)  # :192

@@ -86,7 +86,8 @@ extern "C" {
  *    by bldp_reduce_launch; bldp_band_reduce_multi_f32 flag
  *    BLDP_BAND_PEER_STORE (direct xGMI stores are opt-in); plan option
  *    "typed_kurt"; (additive, same version) bldp_op gains BLDP_OP_VAR,
- *    BLDP_OP_STD, BLDP_OP_MEDIAN for the Float32 reduce entry points */
+ *    BLDP_OP_STD, BLDP_OP_MEDIAN for the Float32 reduce entry points; the
+ *    bldp_kurtosis_blocks_*, bldp_tstat_* and bldp_argext_* entry points */
 #define BLDP_ABI_VERSION 5
 
 #if defined(BLDP_BUILD)
@@ -417,6 +418,63 @@ BLDP_API int bldp_band_tstat_f32(int nbank, const float *const *in, int64_t ncha
 BLDP_API int bldp_tstat_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
                                  int64_t ntime, const int64_t *win, int64_t tavby, int op,
                                  float *out);
+
+/* fqavfunc argmax / argmin (fqav(A, n; f=argmax), the position half of Julia's
+ * findmax / findmin): where in each block of the reduce the extreme lies.  For
+ * output element (c', i, t') the block is the F x T selected elements
+ * bldp_reduce_f32 takes (F = fqavby channels by T = tavby spectra, after the
+ * window's offsets, steps and direction), numbered off = k + F * tt, 0-based,
+ * k along the selected channels and tt along the selected spectra: column-major,
+ * the order of reshape(A, (F, :, ni, T, :)).
+ *   BLDP_ARG_MAX  a block holding a NaN gives the smallest off of a NaN (any
+ *                 sign or payload); otherwise the smallest off among the
+ *                 elements greatest under isless (-0.0 < 0.0, +Inf highest).
+ *   BLDP_ARG_MIN  NaN wins the same way; otherwise the smallest off among the
+ *                 isless-least elements (of (0.0, -0.0) the -0.0).
+ * idx receives off (< 2^31, so the buffer may be read as int32); val, when not
+ * NULL, the bit pattern of the winning element, copied (a NaN result carries the
+ * first NaN's payload).  The result does not depend on how the launch divides a
+ * block.  fqavby <= 1 and tavby <= 1 (blocks of one element) give index 0 and
+ * the window itself.  Divisibility, window and bounds rules are those of
+ * bldp_reduce_f32 (BLDP_EDIM, BLDP_EBOUNDS; the output shape is
+ * bldp_reduce_shape's); F * T > 2^31 - 1, an argop other than the two, a null
+ * in / idx for a non-empty result, and idx / val overlapping the input or each
+ * other are BLDP_EINVAL.  An empty result launches nothing.  Float32 input;
+ * additive in ABI 5.
+ *
+ * Blocks of F <= 1024 are shared by the 1 .. 64 lanes of a wave that stream the
+ * T rows (path 0, "lanes"); with long T and too few outputs to fill the GPU the
+ * rows are split over the time slices of a workgroup that meet through LDS
+ * (path 1, "lanes_tsplit"); F > 1024 takes one workgroup per block (path 2,
+ * "block").  One launch, no workspace; chunks of T across workgroups are not
+ * built.
+ *
+ * bldp_argext_plan_f32: info = {path, lanes per block (256 = a workgroup), time
+ * slices, float4 loads per lane per row (0: one dword per element), workgroups
+ * per bank, workspace bytes (0), outputs per bank, vector loads 1 / 0}; launches
+ * nothing and needs no GPU (pointers may be null).
+ * bldp_argext_f32: device pointers, asynchronous on `stream`; element
+ * (c', i, t') of both outputs at [c' + out_ld_i * i + out_ld_t * t'].
+ * bldp_band_argext_f32: in[] is a HOST array of device pointers of banks with
+ * one geometry; idx / val are dense (nbank*nco, ni, nto), the vcat of the banks
+ * (offsets are relative to each block, so stitching is concatenation); one launch.
+ * bldp_argext_host_f32: host in, host dense (nco, ni, nto) out; the window's
+ * rows are staged on device `dev`.  Synchronous. */
+enum bldp_argop { BLDP_ARG_MAX = 0, BLDP_ARG_MIN = 1 };
+BLDP_API int bldp_argext_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                                  const int64_t *win, int64_t fqavby, int64_t tavby, int argop,
+                                  const uint32_t *idx, int64_t info[8]);
+BLDP_API int bldp_argext_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                             const int64_t *win, int64_t fqavby, int64_t tavby, int argop,
+                             uint32_t *idx, float *val, int64_t out_ld_i, int64_t out_ld_t,
+                             void *stream);
+BLDP_API int bldp_band_argext_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                                  int64_t ntime, const int64_t *win, int64_t fqavby,
+                                  int64_t tavby, int argop, uint32_t *idx, float *val,
+                                  void *stream);
+BLDP_API int bldp_argext_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                  int64_t ntime, const int64_t *win, int64_t fqavby,
+                                  int64_t tavby, int argop, uint32_t *idx, float *val);
 
 /* Element types other than Float32 (what Blio maps SIGPROC nbits 8 / 16 to, and
  * what HDF5.jl returns for an integer or Float64 dataset: the reference's
