@@ -109,6 +109,10 @@ SIGNATURES = {
     "bldp_kurtosis_blocks_f32": ([P, I64, I64, I64, P, I64, P, I64, I64, P], I),
     "bldp_band_kurtosis_blocks_f32": ([I, P, I64, I64, I64, P, I64, P, P], I),
     "bldp_kurtosis_blocks_host_f32": ([I, P, I64, I64, I64, P, I64, P], I),
+    "bldp_skewness_plan_f32": ([P, I64, I64, I64, P, I64, P], I),
+    "bldp_skewness_f32": ([P, I64, I64, I64, P, I64, P, I64, I64, P], I),
+    "bldp_band_skewness_f32": ([I, P, I64, I64, I64, P, I64, P, P], I),
+    "bldp_skewness_host_f32": ([I, P, I64, I64, I64, P, I64, P], I),
     "bldp_tstat_shape": ([I64, I64, I64, P, I64, P], I),
     "bldp_tstat_plan_f32": ([P, I64, I64, I64, P, I64, I, P, P], I),
     "bldp_tstat_f32": ([P, I64, I64, I64, P, I64, I, P, I64, I64, P], I),

@@ -786,14 +786,16 @@ int bldp_despike_f32(float *data, int64_t nchan, int64_t nif, int64_t ntime, int
   return BLDP_OK;
 }
 
+// `order`: the moment of the plan, 4 = kurtosis, 3 = skewness (bldp_skewness_*)
 static int kurt_setup(int nbank, const float *const *in, int64_t nchan, int64_t nif,
-                      int64_t ntime, const int64_t *win, KurtArgs *k) {
+                      int64_t ntime, const int64_t *win, KurtArgs *k, int order = 4) {
   if (nbank < 1 || nbank > BLDP_MAX_BANKS)
     return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
   Geo g;
   int rc = resolve_window(nchan, nif, ntime, win, &g);
   if (rc) return rc;
   *k = KurtArgs{};
+  k->order = order;
   k->nbank = nbank;
   bool aligned = true, words = true;
   for (int b = 0; b < nbank; ++b) {
@@ -912,8 +914,8 @@ struct KblkPlan {
   size_t tmp_off, ws_bytes;  // block-by-block: a block's dense results after its workspace
 };
 static int kblk_plan(int nbank, const float *const *in, int64_t nchan, int64_t nif, int64_t ntime,
-                     const int64_t *win, int64_t tblock, KblkPlan *p) {
-  int rc = kurt_setup(nbank, in, nchan, nif, ntime, win, &p->whole);
+                     const int64_t *win, int64_t tblock, KblkPlan *p, int order = 4) {
+  int rc = kurt_setup(nbank, in, nchan, nif, ntime, win, &p->whole, order);
   if (rc) return rc;
   rc = kblk_count(p->whole.nt, tblock, &p->nb);
   if (rc) return rc;
@@ -926,7 +928,7 @@ static int kblk_plan(int nbank, const float *const *in, int64_t nchan, int64_t n
   int64_t bw[9];
   kblk_window(nchan, nif, ntime, win, tblock, 0, bw);
   if (p->nb == 0) bw[6] = 0, bw[7] = 0;  // (no block: the empty window's plan)
-  rc = kurt_setup(nbank, in, nchan, nif, ntime, bw, &p->blk);
+  rc = kurt_setup(nbank, in, nchan, nif, ntime, bw, &p->blk, order);
   if (rc) return rc;
   p->path = kurtosis_path(p->blk);
   p->tmp_off = (kurtosis_ws_bytes(p->blk) + 255) & ~(size_t)255;
@@ -936,18 +938,19 @@ static int kblk_plan(int nbank, const float *const *in, int64_t nchan, int64_t n
 
 static int kblk_run(int nbank, const float *const *in, int64_t nchan, int64_t nif, int64_t ntime,
                     const int64_t *win, int64_t tblock, double *out, int64_t out_bank,
-                    int64_t out_ld_i, int64_t out_ld_b, void *stream) {
+                    int64_t out_ld_i, int64_t out_ld_b, void *stream, int order = 4) {
+  const char *what = order == 3 ? "skewness" : "tblock kurtosis";
   KblkPlan p;
-  int rc = kblk_plan(nbank, in, nchan, nif, ntime, win, tblock, &p);
+  int rc = kblk_plan(nbank, in, nchan, nif, ntime, win, tblock, &p, order);
   if (rc) return rc;
   const KurtArgs &w = p.whole;
   if (w.nc * w.ni * p.nb == 0) return BLDP_OK;
   for (int b = 0; b < nbank; ++b)
-    if (!w.in[b]) return fail(BLDP_EINVAL, "tblock kurtosis: null input pointer (bank %d)", b);
-  if (!out) return fail(BLDP_EINVAL, "tblock kurtosis: null output pointer");
+    if (!w.in[b]) return fail(BLDP_EINVAL, "%s: null input pointer (bank %d)", what, b);
+  if (!out) return fail(BLDP_EINVAL, "%s: null output pointer", what);
   if (out_ld_i < w.nc || out_ld_b < (w.ni - 1) * out_ld_i + w.nc)
     return fail(BLDP_EINVAL,
-                "tblock kurtosis: out strides (%lld, %lld) overlap for a (%lld, %lld, %lld) result",
+                "%s: out strides (%lld, %lld) overlap for a (%lld, %lld, %lld) result", what,
                 (long long)out_ld_i, (long long)out_ld_b, (long long)w.nc, (long long)w.ni,
                 (long long)p.nb);
   hipStream_t s = (hipStream_t)stream;
@@ -966,13 +969,14 @@ static int kblk_run(int nbank, const float *const *in, int64_t nchan, int64_t ni
     k.out_ld_i = out_ld_i;
     k.out_ld_b = out_ld_b;
     k.out = out;
+    k.order = order;
     plan_kurt_blocks(k, num_cus_current());
     if (kurt_blocks_grid(k) > INT32_MAX)
       return fail(BLDP_EINVAL, "tblock=%lld kurtosis: %lld blocks are too many for one launch",
                   (long long)tblock, (long long)p.nb);
     hipError_t e = launch_kurt_blocks(k, s);
     if (e != hipSuccess)
-      return fail(BLDP_EHIP, "tblock kurtosis launch: %s", hipGetErrorString(e));
+      return fail(BLDP_EHIP, "%s launch: %s", what, hipGetErrorString(e));
     return BLDP_OK;
   }
   // block by block through the whole-window paths: one scratch lease, every
@@ -987,17 +991,17 @@ static int kblk_run(int nbank, const float *const *in, int64_t nchan, int64_t ni
     int64_t bw[9];
     kblk_window(nchan, nif, ntime, win, tblock, b, bw);
     KurtArgs k;
-    rc = kurt_setup(nbank, in, nchan, nif, ntime, bw, &k);
+    rc = kurt_setup(nbank, in, nchan, nif, ntime, bw, &k, order);
     if (rc) return rc;
     if (kurtosis_ws_bytes(k) > p.tmp_off)  // (a plan option changed under the call)
-      return fail(BLDP_EINVAL, "tblock kurtosis: the plan changed during the call");
+      return fail(BLDP_EINVAL, "%s: the plan changed during the call", what);
     rc = kurt_run(k, direct ? out + b * out_ld_b : tmp, ws, stream);
     if (rc) return rc;
     if (!direct) {
       hipError_t e = launch_kurt_scatter(tmp, nbank, w.ni, w.nc, out + b * out_ld_b, out_bank,
                                          out_ld_i, s);
       if (e != hipSuccess)
-        return fail(BLDP_EHIP, "tblock kurtosis launch: %s", hipGetErrorString(e));
+        return fail(BLDP_EHIP, "%s launch: %s", what, hipGetErrorString(e));
     }
   }
   return BLDP_OK;
@@ -1048,6 +1052,100 @@ int bldp_band_kurtosis_blocks_f32(int nbank, const float *const *in, int64_t nch
   if (rc) return rc;
   return kblk_run(nbank, in, nchan, nif, ntime, win, tblock, out, d[0] * d[1] * d[2], d[0],
                   d[0] * d[1], stream);
+}
+
+// ---- skewness (getskewness): the recipe one order down ----------------------
+// One family for the whole window (tblock = 0: the whole-window planner, nb =
+// 1) and for blocks of tblock spectra (the block planner); the kernels, paths
+// and workspace are the kurtosis' with KurtArgs.order = 3.
+static int skew_check(int64_t tblock) {
+  if (tblock < 0) return fail(BLDP_EINVAL, "skewness: tblock=%lld must be >= 0", (long long)tblock);
+  return BLDP_OK;
+}
+
+// Whole window: element (c, i) at out[bank*out_bank + c + i*out_ld_i].
+static int skew_whole(int nbank, const float *const *in, int64_t nchan, int64_t nif, int64_t ntime,
+                      const int64_t *win, double *out, int64_t out_bank, int64_t out_ld_i,
+                      void *stream) {
+  KurtArgs k;
+  int rc = kurt_setup(nbank, in, nchan, nif, ntime, win, &k, 3);
+  if (rc) return rc;
+  if (k.nc * k.nrow == 0) return BLDP_OK;
+  for (int b = 0; b < nbank; ++b)
+    if (!k.in[b] && k.nt > 0) return fail(BLDP_EINVAL, "skewness: null input pointer (bank %d)", b);
+  if (!out) return fail(BLDP_EINVAL, "skewness: null output pointer");
+  if (out_ld_i < k.nc || (nbank > 1 && out_bank < (k.ni - 1) * out_ld_i + k.nc))
+    return fail(BLDP_EINVAL, "skewness: out strides (%lld, %lld) overlap for a (%lld, %lld) result",
+                (long long)out_ld_i, (long long)out_bank, (long long)k.nc, (long long)k.ni);
+  if (out_ld_i == k.nc && (nbank == 1 || out_bank == k.nc * k.ni))
+    return kurt_run(k, out, nullptr, stream);  // dense: the kernels write the product
+  hipStream_t s = (hipStream_t)stream;
+  const size_t tmp_off = (kurtosis_ws_bytes(k) + 255) & ~(size_t)255;
+  ScratchLease lease;  // held until the launches are queued
+  rc = scratch_lease(s, tmp_off + (size_t)(k.nrow * k.nc) * sizeof(double), &lease);
+  if (rc) return rc;
+  char *ws = static_cast<char *>(lease.ptr);
+  double *tmp = reinterpret_cast<double *>(ws + tmp_off);
+  rc = kurt_run(k, tmp, ws, stream);
+  if (rc) return rc;
+  hipError_t e = launch_kurt_scatter(tmp, nbank, k.ni, k.nc, out, out_bank, out_ld_i, s);
+  if (e != hipSuccess) return fail(BLDP_EHIP, "skewness launch: %s", hipGetErrorString(e));
+  return BLDP_OK;
+}
+
+int bldp_skewness_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                           const int64_t *win, int64_t tblock, int64_t info[4]) {
+  if (!info) return fail(BLDP_EINVAL, "null info");
+  int rc = skew_check(tblock);
+  if (rc) return rc;
+  const float *ins[1] = {in};
+  if (tblock == 0) {
+    KurtArgs k;
+    rc = kurt_setup(1, ins, nchan, nif, ntime, win, &k, 3);
+    if (rc) return rc;
+    info[0] = kurtosis_path(k);
+    info[1] = 1;  // one set of launches for the window
+    info[2] = 1;
+    info[3] = (int64_t)kurtosis_ws_bytes(k);
+    return BLDP_OK;
+  }
+  KblkPlan p;
+  rc = kblk_plan(1, ins, nchan, nif, ntime, win, tblock, &p, 3);
+  if (rc) return rc;
+  info[0] = p.path;
+  info[1] = p.fused ? 1 : 0;
+  info[2] = p.nb;
+  info[3] = (int64_t)p.ws_bytes;
+  return BLDP_OK;
+}
+
+int bldp_skewness_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                      const int64_t *win, int64_t tblock, double *out, int64_t out_ld_i,
+                      int64_t out_ld_b, void *stream) {
+  int rc = skew_check(tblock);
+  if (rc) return rc;
+  const float *ins[1] = {in};
+  if (tblock == 0) return skew_whole(1, ins, nchan, nif, ntime, win, out, 0, out_ld_i, stream);
+  return kblk_run(1, ins, nchan, nif, ntime, win, tblock, out, 0, out_ld_i, out_ld_b, stream, 3);
+}
+
+int bldp_band_skewness_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                           int64_t ntime, const int64_t *win, int64_t tblock, double *out,
+                           void *stream) {
+  int rc = skew_check(tblock);
+  if (rc) return rc;
+  if (!in) return fail(BLDP_EINVAL, "skewness: null input pointer array");
+  if (tblock == 0) {
+    Geo g;
+    rc = resolve_window(nchan, nif, ntime, win, &g);
+    if (rc) return rc;
+    return skew_whole(nbank, in, nchan, nif, ntime, win, out, g.nc * g.ni, g.nc, stream);
+  }
+  int64_t d[3];
+  rc = bldp_kurtosis_blocks_shape(nchan, nif, ntime, win, tblock, d);
+  if (rc) return rc;
+  return kblk_run(nbank, in, nchan, nif, ntime, win, tblock, out, d[0] * d[1] * d[2], d[0],
+                  d[0] * d[1], stream, 3);
 }
 
 // ---- tavfunc: median / var / std over blocks of spectra ---------------------

@@ -240,6 +240,7 @@ struct KurtArgs {
   double *pm;
   float *pf;
   double *out;      // [nbank][ni][nc]
+  int32_t order;    // the moment: 4 = kurtosis, 3 = skewness (set before plan_kurtosis)
 };
 void plan_kurtosis(KurtArgs &k, int num_cus);
 size_t kurtosis_ws_bytes(const KurtArgs &k);
@@ -261,6 +262,7 @@ struct KurtBlkArgs {
   int64_t nc, ni, M, nb;
   int64_t out_bank, out_ld_i, out_ld_b;
   double *out;
+  int32_t order;  // 4 = kurtosis, 3 = skewness
 };
 // `whole`: the KurtArgs of the whole window (its float4 columns are every block's)
 bool kurt_blocks_fused(const KurtArgs &whole, int64_t M);

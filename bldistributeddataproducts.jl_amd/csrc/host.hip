@@ -222,6 +222,38 @@ extern "C" int bldp_kurtosis_blocks_host_f32(int dev, const float *in, int64_t n
   });
 }
 
+// The same staging for the skewness: tblock = 0 the whole window ((nc, ni) out),
+// tblock >= 1 every block of tblock spectra ((nc, ni, nb) out).
+extern "C" int bldp_skewness_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                      int64_t ntime, const int64_t *win, int64_t tblock,
+                                      double *out) {
+  int64_t sh[3], info[4];
+  // (every argument check, before any staging)
+  int rc = bldp_skewness_plan_f32(nullptr, nchan, nif, ntime, win, tblock, info);
+  if (rc) return rc;
+  rc = bldp_reduce_shape(nchan, nif, ntime, win, 1, 1, sh);
+  if (rc) return rc;
+  const int64_t nc = sh[0], ni = sh[1], nt = sh[2], nb = info[2];
+  if (nc * ni * nb == 0) return BLDP_OK;
+  if (!out || (!in && nt > 0)) return bldp::set_error(BLDP_EINVAL, "skewness: null pointer");
+  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
+  return with_stager(dev, [&](bldp::Stager *sg) -> int {
+    float *dbuf;
+    double *dout;
+    int r = bldp::stager_buffer(sg, 0, (size_t)std::max<int64_t>(1, h.span * ni * nt) * 4,
+                                (void **)&dbuf);
+    if (!r) r = bldp::stager_buffer(sg, 2, (size_t)(nc * ni * nb) * sizeof(double), (void **)&dout);
+    if (!r && nt > 0) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
+    if (r) return r;
+    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
+    r = bldp_skewness_f32(dbuf, h.span, ni, nt, dwin, tblock, dout, nc, nc * ni, sg->st[0]);
+    if (r) return r;
+    HCHK(hipMemcpyAsync(out, dout, (size_t)(nc * ni * nb) * sizeof(double), hipMemcpyDeviceToHost,
+                        sg->st[0]));
+    return BLDP_OK;
+  });
+}
+
 // The same staging for tavfunc's var / std / median over blocks of tavby
 // spectra: the window's rows go to the device once (in window order: a
 // reversed time range is staged reversed), the (nc, ni, nb) product comes back.

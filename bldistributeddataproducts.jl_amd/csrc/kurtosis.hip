@@ -52,6 +52,15 @@
 //   33..1024    k_kurtb_stream: one wave per (block, 256 channels), the leaf
 //               method finished in place by kurt_ratio (a block is one leaf).
 //   otherwise   block by block through the paths above (api.hip).
+//
+// getskewness (StatsBase.skewness mapped over the same rows) is the same
+// recipe one order down, on the same paths with the same Float32 m:
+//   cm3 += z2 * z              Float32 product, Float64 accumulator
+//   (cm3 / n) / sqrt((cm2 / n) * (cm2 / n) * (cm2 / n))
+// The order (KurtArgs.order, 4 or 3) is a template parameter of every kernel
+// that forms the top moment; the leaf partials and the tree carry M3 and M4
+// for both and skew_ratio finishes the streamed paths.  k_kurt_tile has no
+// order-3 form: skewness plans as if kurt_leaf_tile = 0.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -164,6 +173,61 @@ __device__ __forceinline__ double kurt_ratio(int64_t nt, float S, double ma, dou
   return (cm4 / (cm2 * cm2)) - 3.0;
 }
 
+// The moment order ORD of a launch is a template parameter of the kernels: 4 =
+// StatsBase.kurtosis (above), 3 = StatsBase.skewness, the same recipe with
+//   cm3 += z2 * z            Float32 product, Float64 accumulator
+//   (cm3 / n) / sqrt((cm2 / n) * (cm2 / n) * (cm2 / n))
+// top_term is the recipe's Float32 product (rounded on its own: nothing may
+// contract across it), mom_ratio its last line from cm2 = sum / n and cmk =
+// sum / n (Float64 sqrt and division are correctly rounded).
+template <int ORD>
+__device__ __forceinline__ float top_term(float z2, float z) {
+#pragma clang fp contract(off)
+  if constexpr (ORD == 4)
+    return z2 * z2;
+  else
+    return z2 * z;
+}
+template <int ORD>
+__device__ __forceinline__ double mom_ratio(double cm2, double cmk) {
+  if constexpr (ORD == 4)
+    return (cmk / (cm2 * cm2)) - 3.0;
+  else
+    return cmk / sqrt(cm2 * cm2 * cm2);
+}
+
+// skewness from central moments about the exact mean `ma`, as kurt_ratio: the
+// moments move to the recipe's Float32 m (z = (x - ma) + eps), and the Float32
+// cube's overflow and underflow come from the row's max and min.
+// fl(fl(z^2) * z) is monotone in z, so the most positive cube is hi's and the
+// most negative lo's: an infinite cube of each sign adds up to NaN, of one
+// sign to that infinity, and cm3 is 0 when both cubes are (every one between
+// them is).  cm2 follows kurt_ratio's rule.
+__device__ __forceinline__ double skew_ratio(int64_t nt, float S, double ma, double a2,
+                                             double a3, float hi, float lo) {
+  const float m = S / (float)nt;  // mean(v): Float32 sum / length
+  const double n = (double)nt, eps = ma - (double)m, e2 = eps * eps;
+  double cm2 = (a2 + n * e2) / n;
+  double cm3 = (a3 + 3.0 * eps * a2 + n * e2 * eps) / n;
+  const float zh = hi - m, zl = lo - m;
+  const float h2 = zh * zh, l2 = zl * zl;
+  const float h3 = top_term<3>(h2, zh), l3 = top_term<3>(l2, zl);
+  if (isinf(h2) || isinf(l2))
+    cm2 = INFINITY;
+  else if (h2 == 0.0f && l2 == 0.0f)
+    cm2 = 0.0;
+  const bool pinf = h3 == INFINITY || l3 == INFINITY, ninf = h3 == -INFINITY || l3 == -INFINITY;
+  if (pinf && ninf)
+    cm3 = NAN;
+  else if (pinf)
+    cm3 = INFINITY;
+  else if (ninf)
+    cm3 = -INFINITY;
+  else if (h3 == 0.0f && l3 == 0.0f)
+    cm3 = 0.0;
+  return mom_ratio<3>(cm2, cm3);
+}
+
 // ---------------------------------------------------------------------------
 // nt <= NTMAX (<= 32): each lane keeps its float4 column of every spectrum in
 // registers and runs the recipe in the recipe's own order, so the result is
@@ -173,7 +237,7 @@ __device__ __forceinline__ double kurt_ratio(int64_t nt, float S, double ma, dou
 // wave's 256 Float64 results go through LDS so every nt store instruction
 // writes 1 KiB contiguous (+2.5% on the 0000 band against each lane's 32 B as
 // two nt 16-byte stores).
-template <int NTMAX, bool EXACT>
+template <int NTMAX, bool EXACT, int ORD>
 __global__ __launch_bounds__(kB) void k_kurt_regs(const KurtArgs k) {
   const int64_t ncols = k.nc / 4;
   const int64_t ctiles = (ncols + kB - 1) / kB;
@@ -208,14 +272,14 @@ __global__ __launch_bounds__(kB) void k_kurt_regs(const KurtArgs k) {
         const float z = x[w] - m[w];  // StatsBase: z, z2 in Float32; Float64 moments
         const float z2 = z * z;
         c2[w] += (double)z2;
-        c4[w] += (double)(z2 * z2);
+        c4[w] += (double)top_term<ORD>(z2, z);
       }
     }
   double r[4];
 #pragma unroll
   for (int w = 0; w < 4; ++w) {
     const double cm2 = c2[w] / (double)nt, cm4 = c4[w] / (double)nt;
-    r[w] = (cm4 / (cm2 * cm2)) - 3.0;
+    r[w] = mom_ratio<ORD>(cm2, cm4);
   }
   d2v *o = reinterpret_cast<d2v *>(k.out + ib * k.nc + 4 * col);
   if (ncols % 64 == 0 &&
@@ -250,7 +314,7 @@ __global__ __launch_bounds__(kB) void k_kurt_regs(const KurtArgs k) {
 // running sum handed on through LDS), every lane doing its own channel.  Then
 // z, z2 and the Float64 sums run over the registers and the 4 partial sums are
 // added through LDS in wave order.
-template <int NR>
+template <int NR, int ORD>
 __global__ __launch_bounds__(kB) void k_kurt_mid(const KurtArgs k) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t ctiles = (k.nc + 63) / 64;
@@ -289,7 +353,7 @@ __global__ __launch_bounds__(kB) void k_kurt_mid(const KurtArgs k) {
       const float z = v[r] - m;  // StatsBase: z, z2 in Float32; Float64 moments
       const float z2 = z * z;
       c2 += (double)z2;
-      c4 += (double)(z2 * z2);
+      c4 += (double)top_term<ORD>(z2, z);
     }
   __shared__ double part[4][2][64];
   part[wave][0][lane] = c2;
@@ -303,7 +367,7 @@ __global__ __launch_bounds__(kB) void k_kurt_mid(const KurtArgs k) {
       a4 += part[q][1][lane];
     }
     const double cm2 = a2 / (double)nt, cm4 = a4 / (double)nt;
-    k.out[ib * k.nc + c] = (cm4 / (cm2 * cm2)) - 3.0;
+    k.out[ib * k.nc + c] = mom_ratio<ORD>(cm2, cm4);
   }
 }
 
@@ -322,7 +386,16 @@ __global__ __launch_bounds__(kB) void k_kurt_mid(const KurtArgs k) {
 // 1.34 / 1.22 / 1.04x; nt >= 100 and one file no gain).  kMidNW waves per
 // workgroup otherwise (4 and 16 measured and lost).
 constexpr int kMidNW = 8;
-template <int NR, int NW>
+// top_term for both channels of a lane
+template <int ORD>
+__device__ __forceinline__ f2v top2(f2v q, f2v z) {
+#pragma clang fp contract(off)
+  if constexpr (ORD == 4)
+    return q * q;
+  else
+    return q * z;
+}
+template <int NR, int NW, int ORD>
 __global__ __launch_bounds__(64 * NW) void k_kurt_mid2(const KurtArgs k) {
   constexpr int TW = 128;  // channels per tile
   // wave and the per-wave spectrum counts are uniform over a wave: scalar
@@ -369,7 +442,7 @@ __global__ __launch_bounds__(64 * NW) void k_kurt_mid2(const KurtArgs k) {
       // (v_pk_add_f32 / v_pk_mul_f32), Float64 moments
       const f2v z = v[r] - mv;
       const f2v q = z * z;
-      const f2v q2 = q * q;
+      const f2v q2 = top2<ORD>(q, z);
       a2 += (double)q.x;
       a4 += (double)q2.x;
       b2 += (double)q.y;
@@ -391,8 +464,8 @@ __global__ __launch_bounds__(64 * NW) void k_kurt_mid2(const KurtArgs k) {
       y4 += part[q][3][lane];
     }
     const double n = (double)nt;
-    const double k0 = ((x4 / n) / ((x2 / n) * (x2 / n))) - 3.0;
-    const double k1 = ((y4 / n) / ((y2 / n) * (y2 / n))) - 3.0;
+    const double k0 = mom_ratio<ORD>(x2 / n, x4 / n);
+    const double k1 = mom_ratio<ORD>(y2 / n, y4 / n);
     double *o = k.out + ib * k.nc + c;
     if ((reinterpret_cast<uintptr_t>(o) & 15) == 0) {
       *reinterpret_cast<d2v *>(o) = d2v{k0, k1};
@@ -863,14 +936,15 @@ __global__ __launch_bounds__(kB) void k_kurt_tree(const KurtArgs k, const TreeIO
 
 // Last level, one thread per output (Q = all remaining nodes): MOM -> the
 // excess kurtosis, else the Float32 mean for the two-pass path.
-template <int Q, bool FIRST, bool MOM>
+template <int Q, bool FIRST, bool MOM, int ORD>
 __global__ __launch_bounds__(kB) void k_kurt_final_t(const KurtArgs k, const TreeIO io) {
   const int64_t n = k.nrow * k.nc;
   for (int64_t e = (int64_t)blockIdx.x * kB + threadIdx.x; e < n;
        e += (int64_t)gridDim.x * kB) {
     const Node a = fold_nodes<Q, FIRST, MOM>(k, io, n, e, 0);
     if (MOM)
-      k.out[e] = kurt_ratio(k.nt, a.S, a.m, a.a2, a.a3, a.a4, a.hi, a.lo);
+      k.out[e] = ORD == 4 ? kurt_ratio(k.nt, a.S, a.m, a.a2, a.a3, a.a4, a.hi, a.lo)
+                          : skew_ratio(k.nt, a.S, a.m, a.a2, a.a3, a.hi, a.lo);
     else
       k.mean[e] = a.S / (float)k.nt;
   }
@@ -880,7 +954,7 @@ __global__ __launch_bounds__(kB) void k_kurt_final_t(const KurtArgs k, const Tre
 // butterfly over consecutive lanes is exactly the perfect tree of the sums
 // (Float32 addition commutes); the moments merge the lower lane's first, so
 // both lanes of a pair agree.
-template <bool FIRST, bool MOM>
+template <bool FIRST, bool MOM, int ORD>
 __global__ __launch_bounds__(kB) void k_kurt_final_w(const KurtArgs k, const TreeIO io) {
   const int lane = threadIdx.x & 63;
   const int64_t n = k.nrow * k.nc;
@@ -912,7 +986,8 @@ __global__ __launch_bounds__(kB) void k_kurt_final_w(const KurtArgs k, const Tre
     }
     if (lane == 0) {
       if (MOM)
-        k.out[e] = kurt_ratio(k.nt, a.S, a.m, a.a2, a.a3, a.a4, a.hi, a.lo);
+        k.out[e] = ORD == 4 ? kurt_ratio(k.nt, a.S, a.m, a.a2, a.a3, a.a4, a.hi, a.lo)
+                            : skew_ratio(k.nt, a.S, a.m, a.a2, a.a3, a.hi, a.lo);
       else
         k.mean[e] = a.S / (float)k.nt;
     }
@@ -926,6 +1001,7 @@ __global__ __launch_bounds__(kB) void k_kurt_final_w(const KurtArgs k, const Tre
 // LDS in wave order.  With one time chunk the ratio is written here;
 // otherwise chunks are folded in a fixed order by k_kurt_fold.
 // At most 4 resident waves per SIMD.
+template <int ORD>
 __global__ __launch_bounds__(kB) __attribute__((amdgpu_waves_per_eu(1, 4)))
 void k_kurt_pass(const KurtArgs k) {
   constexpr int B = 8;  // spectra in flight per lane
@@ -960,7 +1036,7 @@ void k_kurt_pass(const KurtArgs k) {
         const float z = v[u] - m;
         const float z2 = z * z;
         a2 += (double)z2;
-        a4 += (double)(z2 * z2);
+        a4 += (double)top_term<ORD>(z2, z);
       }
     }
   }
@@ -979,7 +1055,7 @@ void k_kurt_pass(const KurtArgs k) {
     const int64_t n = k.nrow * k.nc;
     if (k.nchunk == 1) {
       const double cm2 = a2 / (double)k.nt, cm4 = a4 / (double)k.nt;
-      k.out[e] = (cm4 / (cm2 * cm2)) - 3.0;
+      k.out[e] = mom_ratio<ORD>(cm2, cm4);
     } else {
       k.ws_mom[(chunk * 2) * n + e] = a2;
       k.ws_mom[(chunk * 2 + 1) * n + e] = a4;
@@ -988,6 +1064,7 @@ void k_kurt_pass(const KurtArgs k) {
 }
 
 // Fold the time-chunk partials of every output, chunks in order.
+template <int ORD>
 __global__ __launch_bounds__(kB) void k_kurt_fold(const KurtArgs k) {
   const int64_t n = k.nrow * k.nc;
   for (int64_t e = (int64_t)blockIdx.x * kB + threadIdx.x; e < n;
@@ -998,7 +1075,7 @@ __global__ __launch_bounds__(kB) void k_kurt_fold(const KurtArgs k) {
       c += k.ws_mom[(ch * 2 + 1) * n + e];
     }
     const double cm2 = a / (double)k.nt, cm4 = c / (double)k.nt;
-    k.out[e] = (cm4 / (cm2 * cm2)) - 3.0;
+    k.out[e] = mom_ratio<ORD>(cm2, cm4);
   }
 }
 
@@ -1072,24 +1149,24 @@ hipError_t launch_tree_pass(const KurtArgs &k, const TreeIO &io, int q, bool fir
   return hipGetLastError();
 }
 
-template <bool MOM>
+template <bool MOM, int ORD>
 hipError_t launch_final(const KurtArgs &k, const TreeIO &io, bool first, hipStream_t s) {
   const int64_t n = k.nrow * k.nc;
   const dim3 b(kB);
   if (io.L >= 3) {
     const dim3 g((unsigned)std::min<int64_t>(cdivk(n, 4), 1 << 20));
     if (first)
-      hipLaunchKernelGGL((k_kurt_final_w<true, MOM>), g, b, 0, s, k, io);
+      hipLaunchKernelGGL((k_kurt_final_w<true, MOM, ORD>), g, b, 0, s, k, io);
     else
-      hipLaunchKernelGGL((k_kurt_final_w<false, MOM>), g, b, 0, s, k, io);
+      hipLaunchKernelGGL((k_kurt_final_w<false, MOM, ORD>), g, b, 0, s, k, io);
     return hipGetLastError();
   }
   const dim3 g((unsigned)std::min<int64_t>(cdivk(n, kB), 1 << 20));
 #define BLDP_FINAL(Q)                                                         \
   if (first)                                                                  \
-    hipLaunchKernelGGL((k_kurt_final_t<Q, true, MOM>), g, b, 0, s, k, io);    \
+    hipLaunchKernelGGL((k_kurt_final_t<Q, true, MOM, ORD>), g, b, 0, s, k, io);  \
   else                                                                        \
-    hipLaunchKernelGGL((k_kurt_final_t<Q, false, MOM>), g, b, 0, s, k, io);
+    hipLaunchKernelGGL((k_kurt_final_t<Q, false, MOM, ORD>), g, b, 0, s, k, io);
   switch (io.L) {
     case 0: BLDP_FINAL(1) break;
     case 1: BLDP_FINAL(2) break;
@@ -1128,7 +1205,10 @@ hipError_t launch_tree(const KurtArgs &k, char *ws, const KLayout &L, hipStream_
     io.L -= q;
     first = false;
   }
-  return launch_final<MOM>(k, io, first, s);
+  if constexpr (MOM) {
+    if (k.order == 3) return launch_final<true, 3>(k, io, first, s);
+  }
+  return launch_final<MOM, 4>(k, io, first, s);
 }
 
 }  // namespace
@@ -1159,7 +1239,8 @@ void plan_kurtosis(KurtArgs &k, int num_cus) {
   if (narrow > 0 && kLeafW > 1 && k.nrow * k.nslot * cdivk(k.nc / kLeafW, 64) < num_cus * narrow)
     k.leafw = 1;
   k.leaftile = 0;  // lane groups per channel of k_kurt_tile; 0 = streamed leaves
-  if (opt(OPT_KURT_LEAF_TILE) == 1 && k.leafw == 1) {
+  // (skewness plans as if kurt_leaf_tile = 0: k_kurt_tile has no order-3 form)
+  if (opt(OPT_KURT_LEAF_TILE) == 1 && k.leafw == 1 && k.order != 3) {
     const int64_t units = k.nrow * (k.nt <= 1024 ? 1 : k.nslot);  // leaves x rows
     if (units * cdivk(k.nc, 32) <= num_cus)
       k.leaftile = 2;
@@ -1184,6 +1265,15 @@ int kurtosis_path(const KurtArgs &k) { return path_of(k); }
 
 size_t kurtosis_ws_bytes(const KurtArgs &k) { return layout(k).total; }
 
+// Launch NAME<..., ORD> for the plan's moment order (4 kurtosis, 3 skewness).
+#define BLDP_KLAUNCH(grid, blk, shm, NAME, ...)                                \
+  do {                                                                        \
+    if (k.order == 3)                                                         \
+      hipLaunchKernelGGL((NAME<__VA_ARGS__, 3>), grid, blk, shm, s, k);       \
+    else                                                                      \
+      hipLaunchKernelGGL((NAME<__VA_ARGS__, 4>), grid, blk, shm, s, k);       \
+  } while (0)
+
 hipError_t launch_kurtosis(KurtArgs &k, char *ws, hipStream_t s) {
   const int64_t n = k.nrow * k.nc;
   if (n == 0) return hipSuccess;
@@ -1200,26 +1290,26 @@ hipError_t launch_kurtosis(KurtArgs &k, char *ws, hipStream_t s) {
     const bool exact = opt(OPT_KURT_EXACT) != 0;
     const unsigned shm = k.nt >= kKurtRegsCapLo && k.nt <= kKurtRegsCapHi ? kKurtRegsShm : 0;
     if (exact && k.nt == 16)
-      hipLaunchKernelGGL((k_kurt_regs<16, true>), g1, block, shm, s, k);
+      BLDP_KLAUNCH(g1, block, shm, k_kurt_regs, 16, true);
     else if (exact && k.nt == 32)
-      hipLaunchKernelGGL((k_kurt_regs<32, true>), g1, block, shm, s, k);
+      BLDP_KLAUNCH(g1, block, shm, k_kurt_regs, 32, true);
     else if (k.nt <= 16)
-      hipLaunchKernelGGL((k_kurt_regs<16, false>), g1, block, shm, s, k);
+      BLDP_KLAUNCH(g1, block, shm, k_kurt_regs, 16, false);
     else
-      hipLaunchKernelGGL((k_kurt_regs<32, false>), g1, block, shm, s, k);
+      BLDP_KLAUNCH(g1, block, shm, k_kurt_regs, 32, false);
     return hipGetLastError();
   }
   if (p == KP_MID && opt(OPT_KURT_MID_CPL) == 2 && k.vec && cdivk(k.nt, 8) <= 48) {
     constexpr int NW = kMidNW;
     const dim3 g1((unsigned)(cdivk(k.nc, 128) * k.nrow)), b2(64 * NW);
     if (opt(OPT_KURT_MID_SMALL) && k.nt <= 64) {  // (33..64 here) 4 waves of <= 16 spectra
-      hipLaunchKernelGGL((k_kurt_mid2<16, 4>), g1, dim3(256), 0, s, k);
+      BLDP_KLAUNCH(g1, dim3(256), 0, k_kurt_mid2, 16, 4);
       return hipGetLastError();
     }
     // registers sized to a wave's spectra, 8 at a time (occupancy: 113 VGPRs
     // at 48 spectra = 4 waves/SIMD, 80 at 32 = 6, 48 at 16 = 8)
     switch (cdivk(cdivk(k.nt, NW), 8)) {
-#define BLDP_MID2(NR) hipLaunchKernelGGL((k_kurt_mid2<NR, NW>), g1, b2, kKurtMidShm, s, k); break;
+#define BLDP_MID2(NR) BLDP_KLAUNCH(g1, b2, kKurtMidShm, k_kurt_mid2, NR, NW); break;
       case 1: BLDP_MID2(8)
       case 2: BLDP_MID2(16)
       case 3: BLDP_MID2(24)
@@ -1234,14 +1324,14 @@ hipError_t launch_kurtosis(KurtArgs &k, char *ws, hipStream_t s) {
   if (p == KP_MID) {  // registers sized to the quarter window, 16 spectra at a time
     const dim3 g1((unsigned)(cdivk(k.nc, 64) * k.nrow));
     switch (cdivk(cdivk(k.nt, 4), 16)) {
-      case 1: hipLaunchKernelGGL(k_kurt_mid<16>, g1, block, 0, s, k); break;
-      case 2: hipLaunchKernelGGL(k_kurt_mid<32>, g1, block, 0, s, k); break;
-      case 3: hipLaunchKernelGGL(k_kurt_mid<48>, g1, block, 0, s, k); break;
-      case 4: hipLaunchKernelGGL(k_kurt_mid<64>, g1, block, 0, s, k); break;
-      case 5: hipLaunchKernelGGL(k_kurt_mid<80>, g1, block, 0, s, k); break;
-      case 6: hipLaunchKernelGGL(k_kurt_mid<96>, g1, block, 0, s, k); break;
-      case 7: hipLaunchKernelGGL(k_kurt_mid<112>, g1, block, 0, s, k); break;
-      default: hipLaunchKernelGGL(k_kurt_mid<128>, g1, block, 0, s, k); break;
+      case 1: BLDP_KLAUNCH(g1, block, 0, k_kurt_mid, 16); break;
+      case 2: BLDP_KLAUNCH(g1, block, 0, k_kurt_mid, 32); break;
+      case 3: BLDP_KLAUNCH(g1, block, 0, k_kurt_mid, 48); break;
+      case 4: BLDP_KLAUNCH(g1, block, 0, k_kurt_mid, 64); break;
+      case 5: BLDP_KLAUNCH(g1, block, 0, k_kurt_mid, 80); break;
+      case 6: BLDP_KLAUNCH(g1, block, 0, k_kurt_mid, 96); break;
+      case 7: BLDP_KLAUNCH(g1, block, 0, k_kurt_mid, 112); break;
+      default: BLDP_KLAUNCH(g1, block, 0, k_kurt_mid, 128); break;
     }
     return hipGetLastError();
   }
@@ -1290,10 +1380,16 @@ hipError_t launch_kurtosis(KurtArgs &k, char *ws, hipStream_t s) {
     if (e != hipSuccess) return e;
   }
   const dim3 grid((unsigned)(cdivk(cdivk(k.nc, 64), 4 / k.ts) * k.nrow * k.nchunk));
-  hipLaunchKernelGGL(k_kurt_pass, grid, block, 0, s, k);
+  if (k.order == 3)
+    hipLaunchKernelGGL(k_kurt_pass<3>, grid, block, 0, s, k);
+  else
+    hipLaunchKernelGGL(k_kurt_pass<4>, grid, block, 0, s, k);
   if (k.nchunk > 1) {
     const unsigned fg = (unsigned)std::min<int64_t>(cdivk(n, kB), 16384);
-    hipLaunchKernelGGL(k_kurt_fold, dim3(fg), block, 0, s, k);
+    if (k.order == 3)
+      hipLaunchKernelGGL(k_kurt_fold<3>, dim3(fg), block, 0, s, k);
+    else
+      hipLaunchKernelGGL(k_kurt_fold<4>, dim3(fg), block, 0, s, k);
   }
   return hipGetLastError();
 }
@@ -1345,7 +1441,7 @@ __device__ __forceinline__ void store_kurt(double *o, const double (&r)[W]) {
 // (the 0001 product: 128 columns) still fill their workgroups; when the
 // columns of a block are whole waves (nc % 256 == 0) a wave's 256 results are
 // contiguous and go through LDS to 1 KiB stores as in k_kurt_regs.
-template <int NTMAX, bool EXACT>
+template <int NTMAX, bool EXACT, int ORD>
 __global__ __launch_bounds__(kB) void k_kurtb_regs(const KurtBlkArgs k) {
   const int64_t ncols = k.nc / 4;
   const int64_t per_row = k.nb * ncols;  // (block, column) pairs of a row
@@ -1382,14 +1478,14 @@ __global__ __launch_bounds__(kB) void k_kurtb_regs(const KurtBlkArgs k) {
         const float z = x[w] - m[w];  // StatsBase: z, z2 in Float32; Float64 moments
         const float z2 = z * z;
         c2[w] += (double)z2;
-        c4[w] += (double)(z2 * z2);
+        c4[w] += (double)top_term<ORD>(z2, z);
       }
     }
   double r[4];
 #pragma unroll
   for (int w = 0; w < 4; ++w) {
     const double cm2 = c2[w] / (double)nt, cm4 = c4[w] / (double)nt;
-    r[w] = (cm4 / (cm2 * cm2)) - 3.0;
+    r[w] = mom_ratio<ORD>(cm2, cm4);
   }
   double *o = k.out + bank * k.out_bank + i * k.out_ld_i + b * k.out_ld_b + 4 * col;
   const int lane = threadIdx.x & 63;
@@ -1416,7 +1512,7 @@ __global__ __launch_bounds__(kB) void k_kurtb_regs(const KurtBlkArgs k) {
 // spectrum (-> Julia's m), max, min and the Float64 power sums about that
 // spectrum, moved to the block's own mean and finished by kurt_ratio.  No
 // tree, no workspace, no second pass; class "leaf" (exact z^2, z^4).
-template <int W, int B>
+template <int W, int B, int ORD>
 __global__ __launch_bounds__(kB) void k_kurtb_stream(const KurtBlkArgs k) {
   const int lane = threadIdx.x & 63;
   const int64_t nseg = (k.nc / W + 63) / 64;
@@ -1476,7 +1572,8 @@ __global__ __launch_bounds__(kB) void k_kurtb_stream(const KurtBlkArgs k) {
     const double m2 = A.a2[w] - A.a1[w] * dl;
     const double m3 = A.a3[w] - 3.0 * dl * A.a2[w] + 2.0 * cnt * dl2 * dl;
     const double m4 = A.a4[w] - 4.0 * dl * A.a3[w] + 6.0 * dl2 * A.a2[w] - 3.0 * cnt * dl2 * dl2;
-    r[w] = kurt_ratio(len, A.s[w], ma, m2, m3, m4, A.hi[w], A.lo[w]);
+    r[w] = ORD == 4 ? kurt_ratio(len, A.s[w], ma, m2, m3, m4, A.hi[w], A.lo[w])
+                    : skew_ratio(len, A.s[w], ma, m2, m3, A.hi[w], A.lo[w]);
   }
   store_kurt<W>(k.out + bank * k.out_bank + i * k.out_ld_i + b * k.out_ld_b + W * col, r);
 }
@@ -1521,20 +1618,21 @@ hipError_t launch_kurt_blocks(const KurtBlkArgs &k, hipStream_t s) {
   if (k.M <= 32) {
     const bool exact = opt(OPT_KURT_EXACT) != 0;
     if (exact && k.M == 16)
-      hipLaunchKernelGGL((k_kurtb_regs<16, true>), g, block, 0, s, k);
+      BLDP_KLAUNCH(g, block, 0, k_kurtb_regs, 16, true);
     else if (exact && k.M == 32)
-      hipLaunchKernelGGL((k_kurtb_regs<32, true>), g, block, 0, s, k);
+      BLDP_KLAUNCH(g, block, 0, k_kurtb_regs, 32, true);
     else if (k.M <= 16)
-      hipLaunchKernelGGL((k_kurtb_regs<16, false>), g, block, 0, s, k);
+      BLDP_KLAUNCH(g, block, 0, k_kurtb_regs, 16, false);
     else
-      hipLaunchKernelGGL((k_kurtb_regs<32, false>), g, block, 0, s, k);
+      BLDP_KLAUNCH(g, block, 0, k_kurtb_regs, 32, false);
   } else if (k.leafw == 1) {
-    hipLaunchKernelGGL((k_kurtb_stream<1, kLeafNB>), g, block, 0, s, k);
+    BLDP_KLAUNCH(g, block, 0, k_kurtb_stream, 1, kLeafNB);
   } else {
-    hipLaunchKernelGGL((k_kurtb_stream<kLeafW, kLeafB>), g, block, 0, s, k);
+    BLDP_KLAUNCH(g, block, 0, k_kurtb_stream, kLeafW, kLeafB);
   }
   return hipGetLastError();
 }
+#undef BLDP_KLAUNCH
 
 hipError_t launch_kurt_scatter(const double *src, int64_t nbank, int64_t ni, int64_t nc,
                                double *out, int64_t out_bank, int64_t out_ld_i, hipStream_t s) {

@@ -25,6 +25,7 @@ __all__ = [
     "stitch",
     "despike", "kurtosis", "kurtosis_blocks_plan", "band_kurtosis", "synth", "plan", "reduce_host", "kurtosis_host",
     "tstat", "tstat_plan", "band_tstat", "tstat_host",
+    "skewness", "skewness_plan", "band_skewness", "skewness_host",
     "argext", "argext_plan", "band_argext", "argext_host",
     "init", "finalize", "pinned",
 ]
@@ -975,6 +976,115 @@ def band_kurtosis(banks, win=None, tblock=None, stream=None):
                                   _lib.stream_ptr(stream))
     _lib.check(rc, "bldp_band_kurtosis_f32")
     return [buf[k].t() for k in range(len(banks))]
+
+
+def _skew_tblock(tblock, nt) -> int:
+    """The ABI's tblock of a skewness call: 0 = the whole window (``None``),
+    else the checked block length (the errors of ``_check_tblock``)."""
+    if tblock is None:
+        return 0
+    _check_tblock(tblock, nt)
+    return int(tblock)
+
+
+def _need_f32(what, dtype):
+    raise TypeError(f"{what}: element type {dtype} is not supported; skewness takes Float32 "
+                    "(float32) data only")
+
+
+def skewness(x, win=None, tblock=None, stream=None):
+    """Skewness over time per (channel, IF), StatsBase.skewness with Julia's
+    Float32 mean (bldp_skewness_f32): an (nc, ni) float64 tensor, or with
+    ``tblock=M`` the Julia-order (nc, ni, nt/M) skewness of every block of M
+    selected spectra (M must divide nt).  Float32 tensors only."""
+    torch = _torch()
+    L = _lib.lib()
+    if x.dtype != torch.float32:
+        _need_f32("skewness", x.dtype)
+    shape = tuple(x.shape)
+    _check_bounds(win, shape)
+    nc, ni, nt = window_shape(win, shape)
+    M = _skew_tblock(tblock, nt)
+    nb = nt // M if M else 1
+    out = torch.empty((nb, ni, nc), dtype=torch.float64, device=x.device).permute(2, 1, 0)
+    ptr, nchan, nif, ntime = _abi_dims(x)
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    rc = L.bldp_skewness_f32(ptr, nchan, nif, ntime, wp, M, out.data_ptr() if out.numel() else None,
+                             nc, nc * ni, _lib.stream_ptr(stream))
+    _lib.check(rc, "bldp_skewness_f32")
+    return out if M else out[:, :, 0]
+
+
+def skewness_plan(x, win=None, tblock=None) -> dict:
+    """Plan of ``skewness(x, win, tblock)``: the path ("regs", "mid", "leaf",
+    "twopass": the class of the results), fused (1 = one set of launches, 0 =
+    block by block), the block count and the workspace bytes."""
+    L = _lib.lib()
+    shape = tuple(x.shape)
+    _check_bounds(win, shape)
+    M = _skew_tblock(tblock, window_shape(win, shape)[2])
+    ptr, nchan, nif, ntime = _abi_dims(x)
+    info = (ctypes.c_int64 * 4)()
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    _lib.check(L.bldp_skewness_plan_f32(ptr, nchan, nif, ntime, wp, M, info),
+               "bldp_skewness_plan_f32")
+    return {"path": _lib.KURT_PATHS[info[0]], "fused": int(info[1]), "blocks": int(info[2]),
+            "workspace_bytes": int(info[3])}
+
+
+def band_skewness(banks, win=None, tblock=None, stream=None):
+    """Skewness of every bank of a band on one GPU in one set of launches
+    (bldp_band_skewness_f32): a list of (nc, ni) float64 tensors (views of one
+    buffer), or with ``tblock`` of (nc, ni, nt/tblock) ones."""
+    torch = _torch()
+    L = _lib.lib()
+    banks = list(banks)
+    if not banks:
+        raise ValueError("no banks")
+    for b in banks:
+        if b.dtype != torch.float32:
+            _need_f32("band_skewness", b.dtype)
+    shape = tuple(banks[0].shape)
+    _check_bounds(win, shape)
+    nc, ni, nt = window_shape(win, shape)
+    M = _skew_tblock(tblock, nt)
+    nb = nt // M if M else 1
+    geo = _abi_dims(banks[0])[1:]
+    for b in banks[1:]:
+        if tuple(b.shape) != shape or _abi_dims(b)[1:] != geo:
+            raise ValueError("all banks of a band must have the same shape and layout")
+    ptrs = (ctypes.c_void_p * len(banks))(*[b.data_ptr() for b in banks])
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    buf = torch.empty((len(banks), nb, ni, nc), dtype=torch.float64, device=banks[0].device)
+    rc = L.bldp_band_skewness_f32(len(banks), ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp, M,
+                                  buf.data_ptr() if buf.numel() else None,
+                                  _lib.stream_ptr(stream))
+    _lib.check(rc, "bldp_band_skewness_f32")
+    if M:
+        return [buf[k].permute(2, 1, 0) for k in range(len(banks))]
+    return [buf[k, 0].t() for k in range(len(banks))]
+
+
+def skewness_host(a: np.ndarray, win=None, device=0, tblock=None) -> np.ndarray:
+    """Host array in, (nc, ni) float64 host array out (bldp_skewness_host_f32);
+    with ``tblock`` the (nc, ni, nt/tblock) skewness of every block of tblock
+    selected spectra.  Float32 arrays only."""
+    L = _lib.lib()
+    a = np.asarray(a)
+    if a.dtype != np.float32:
+        _need_f32("skewness_host", a.dtype)
+    if not a.flags.f_contiguous or a.ndim != 3:
+        raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
+    _check_bounds(win, a.shape)
+    nc, ni, nt = window_shape(win, a.shape)
+    M = _skew_tblock(tblock, nt)
+    out = np.empty((nc, ni, nt // M) if M else (nc, ni), dtype=np.float64, order="F")
+    keep, wp = _lib.win_arg(_full_win(win, a.shape))
+    rc = L.bldp_skewness_host_f32(int(device), a.ctypes.data if a.size else None, a.shape[0],
+                                  a.shape[1], a.shape[2], wp, M,
+                                  out.ctypes.data if out.size else None)
+    _lib.check(rc, "bldp_skewness_host_f32")
+    return out
 
 
 def synth(nchan, nif, ntime, nfpc=1024, seed=0, kind=0, device=None, stream=None, out=None):

@@ -18,7 +18,7 @@ from . import _lib, readers, worker as W
 from .idxs import COLON
 
 __all__ = ["datahosts", "setupworkers", "getinventories", "getheaders", "getdata",
-           "getkurtosis", "getband", "bandaxis", "fqav"]
+           "getkurtosis", "getskewness", "getband", "bandaxis", "fqav"]
 
 fqav = W.fqav  # `using .WorkerFunctions` re-exports fqav (src/gbt.jl:6)
 
@@ -91,6 +91,14 @@ def getkurtosis(workers, fnames, idxs=(COLON, COLON, COLON), tblock=None):
     kurtosis of every block of tblock selected spectra, (nc, ni, nt/tblock))."""
     return _fanout(workers, fnames,
                    lambda w, f: W.getkurtosis(f, idxs, device=int(w), tblock=tblock))
+
+
+def getskewness(workers, fnames, idxs=(COLON, COLON, COLON), tblock=None):
+    """getkurtosis' fan-out (src/gbt.jl:81-88) with StatsBase.skewness as the
+    mapped function: per-bank (nc, ni) Float64 arrays, or (nc, ni, nt/tblock)
+    with ``tblock`` (WorkerFunctions.getskewness)."""
+    return _fanout(workers, fnames,
+                   lambda w, f: W.getskewness(f, idxs, device=int(w), tblock=tblock))
 
 
 def _chan_window(idxs, nchans):

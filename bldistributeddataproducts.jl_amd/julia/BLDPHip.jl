@@ -12,7 +12,7 @@ module BLDPHip
 using Statistics: mean, median, var, std
 
 export gpu_init, gpu_finalize, gpu_pin, gpu_unpin, gpu_fqav, gpu_reduce, gpu_kurtosis, gpu_band,
-       gpu_tstat, gpu_argext, gpu_comm_id, gpu_comm_init, gpu_comm_destroy, gpu_band_gather
+       gpu_tstat, gpu_argext, gpu_skewness, gpu_comm_id, gpu_comm_init, gpu_comm_destroy, gpu_band_gather
 
 const libbldp = get(ENV, "BLDP_LIB", joinpath(@__DIR__, "..", "libbldp_hip.so"))
 
@@ -191,6 +191,35 @@ function gpu_kurtosis(A::Array{Float32,3}; idxs::Tuple=(:, :, :), dev::Integer=0
     GC.@preserve A win out check(ccall((:bldp_kurtosis_host_f32, libbldp), Cint,
         (Cint, Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Ptr{Float64}),
         dev, A, size(A, 1), size(A, 2), size(A, 3), win, out))
+    out
+end
+
+"""
+    gpu_skewness(A::Array{Float32,3}; idxs=(:,:,:), dev=0, tblock=0)
+
+`map(skewness, eachrow(reshape(data, :, size(data, 3))))` in place of
+getkurtosis' line (src/gbtworkerfunctions.jl:200): StatsBase.skewness of every
+(channel, IF) row over time with Base.sum's Float32 mean, on GPU `dev`
+(bldp_skewness_host_f32).  `tblock = 0`: the whole window, a `Matrix{Float64}`;
+`tblock = M`: the `Array{Float64,3}` (nc, ni, nt / M) of every block of M
+selected spectra (M must divide them: DimensionMismatch).  Float32 only."""
+function gpu_skewness(A::Array{Float32,3}; idxs::Tuple=(:, :, :), dev::Integer=0,
+                      tblock::Integer=0)
+    win = window(idxs, size(A))
+    shp = zeros(Int64, 3)
+    if tblock > 0
+        GC.@preserve win check(ccall((:bldp_kurtosis_blocks_shape, libbldp), Cint,
+            (Int64, Int64, Int64, Ptr{Int64}, Int64, Ptr{Int64}),
+            size(A, 1), size(A, 2), size(A, 3), win, tblock, shp))
+    else
+        GC.@preserve win check(ccall((:bldp_reduce_shape, libbldp), Cint,
+            (Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Ptr{Int64}),
+            size(A, 1), size(A, 2), size(A, 3), win, 1, 1, shp))
+    end
+    out = tblock > 0 ? Array{Float64,3}(undef, shp...) : Matrix{Float64}(undef, shp[1], shp[2])
+    GC.@preserve A win out check(ccall((:bldp_skewness_host_f32, libbldp), Cint,
+        (Cint, Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Int64, Ptr{Float64}),
+        dev, A, size(A, 1), size(A, 2), size(A, 3), win, tblock, out))
     out
 end
 

@@ -43,7 +43,7 @@ from . import _lib, engine, readers
 from .idxs import COLON, JRange, sanitizeidxs, to_window  # noqa: F401  (re-exports)
 
 __all__ = [
-    "fqav", "FRange", "sanitizeidxs", "getdata", "getfbdata", "getfbh5data", "getkurtosis",
+    "fqav", "FRange", "sanitizeidxs", "getdata", "getfbdata", "getfbh5data", "getkurtosis", "getskewness",
     "getinventory", "getfbheader", "getfbh5header", "getheader", "findmax", "findmin",
 ]
 
@@ -694,6 +694,40 @@ def getkurtosis(fname, idxs=(COLON, COLON, COLON), device=0, tblock=None):
             raise TypeError(f"getkurtosis: element type {a.dtype} is not supported")
         return engine.kurtosis_host_typed(a, win, device=device, tblock=tblock)
     return engine.kurtosis_host(np.asfortranarray(a), win, device=device, tblock=tblock)
+
+
+def getskewness(fname, idxs=(COLON, COLON, COLON), device=0, tblock=None):
+    """Skewness of every (channel, IF) row over time, Float64 (nc, ni): what
+    ``map(skewness, eachrow(...))`` in place of src/gbtworkerfunctions.jl:200
+    gives (StatsBase.skewness with Julia's Float32 mean).  With ``tblock=M``
+    the (nc, ni, nt/M) skewness of every block of M selected spectra (M must
+    divide nt: DimensionMismatch).  Files reach the GPU as getdata reads them
+    (window_on_device).  Float32 data only: any other element type (host
+    array, device tensor, 8/16-bit SIGPROC file) is a TypeError."""
+    idxs = sanitizeidxs(idxs)
+    if _is_tensor(fname):
+        return engine.skewness(fname, to_window(idxs, fname.shape), tblock=tblock)
+    if isinstance(fname, (str, bytes)) or hasattr(fname, "__fspath__"):
+        got = window_on_device(fname, idxs, device)
+        if got is not None:
+            import torch
+
+            x, rwin = got
+            with torch.cuda.device(x.device):
+                return engine.fb_to_numpy(engine.skewness(x, rwin, tblock=tblock))
+        # not Float32, or an empty window: the host array tells which
+        if readers.ishdf5(fname):
+            a, idxs = readers.fbh5_read(fname, idxs), (COLON, COLON, COLON)
+        else:
+            _, a = readers.fil_mmap(fname)
+    else:
+        a = fname
+    a = np.asarray(a)
+    if a.dtype != np.float32:
+        raise TypeError(f"getskewness: element type {a.dtype} is not supported; skewness takes "
+                        "Float32 (float32) data only")
+    return engine.skewness_host(np.asfortranarray(a), to_window(idxs, a.shape), device=device,
+                                tblock=tblock)
 
 
 getinventory = readers.getinventory

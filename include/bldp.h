@@ -87,7 +87,8 @@ extern "C" {
  *    BLDP_BAND_PEER_STORE (direct xGMI stores are opt-in); plan option
  *    "typed_kurt"; (additive, same version) bldp_op gains BLDP_OP_VAR,
  *    BLDP_OP_STD, BLDP_OP_MEDIAN for the Float32 reduce entry points; the
- *    bldp_kurtosis_blocks_*, bldp_tstat_* and bldp_argext_* entry points */
+ *    bldp_kurtosis_blocks_*, bldp_tstat_*, bldp_argext_* and bldp_skewness_*
+ *    entry points */
 #define BLDP_ABI_VERSION 5
 
 #if defined(BLDP_BUILD)
@@ -365,6 +366,46 @@ BLDP_API int bldp_band_kurtosis_blocks_f32(int nbank, const float *const *in, in
 BLDP_API int bldp_kurtosis_blocks_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
                                            int64_t ntime, const int64_t *win, int64_t tblock,
                                            double *out);
+
+/* Skewness over time of every (channel, if) row of the window (getskewness:
+ * StatsBase.skewness where getkurtosis maps StatsBase.kurtosis), Float64:
+ *   m = mean(v) (Float32, Base.sum's pairwise sum / n, the kurtosis' m)
+ *   z = v[i] - m, z2 = z * z (Float32); cm2 += z2; cm3 += z2 * z (a Float32
+ *   product; Float64 sums); (cm3 / n) / sqrt((cm2/n) * (cm2/n) * (cm2/n))
+ * n = 1 and constant rows give NaN.  One family covers the whole window and
+ * blocks of spectra: tblock = 0 is the whole window (nb = 1, the planner of
+ * bldp_kurtosis_f32), tblock >= 1 cuts the selected spectra into nb = nt /
+ * tblock blocks as bldp_kurtosis_blocks_f32 does (its planner, its one-launch
+ * forms, block by block otherwise) and element (c, i, b) is the rule applied
+ * to block b alone.  tblock < 0 is BLDP_EINVAL, a tblock that does not divide
+ * nt BLDP_EDIM, a window outside the array BLDP_EBOUNDS, a null in / out for
+ * a non-empty result BLDP_EINVAL.  The result has the shape
+ * bldp_kurtosis_blocks_shape gives (nb = 1 for tblock = 0).  Paths and
+ * classes are the kurtosis': <= 32 spectra bit-identical to the rule, the
+ * register tile and the two-pass path the rule's terms in another order, the
+ * streamed leaves exact z^2 and z^3 in Float64.  Scratch is leased from the
+ * library; bldp_kurtosis_workspace_size bounds it.  Additive in ABI 5.
+ *
+ * bldp_skewness_plan_f32: info = {path (as bldp_kurtosis_plan_f32), 1 = one
+ * launch set / 0 = block by block, nb, workspace bytes}; launches nothing and
+ * needs no GPU.
+ * bldp_skewness_f32: element (c, i, b) at out[c + i*out_ld_i + b*out_ld_b]
+ * (elements; out_ld_b is not read for tblock = 0).  Asynchronous.
+ * bldp_band_skewness_f32: in[] is a HOST array of device pointers; out is
+ * dense [nbank][nb][ni][nc], one set of launches for the band.
+ * bldp_skewness_host_f32: host in, host (nc, ni, nb) out; the window's rows
+ * are staged on device `dev`.  Synchronous. */
+BLDP_API int bldp_skewness_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                                    const int64_t *win, int64_t tblock, int64_t info[4]);
+BLDP_API int bldp_skewness_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                               const int64_t *win, int64_t tblock, double *out, int64_t out_ld_i,
+                               int64_t out_ld_b, void *stream);
+BLDP_API int bldp_band_skewness_f32(int nbank, const float *const *in, int64_t nchan,
+                                    int64_t nif, int64_t ntime, const int64_t *win,
+                                    int64_t tblock, double *out, void *stream);
+BLDP_API int bldp_skewness_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                    int64_t ntime, const int64_t *win, int64_t tblock,
+                                    double *out);
 
 /* Statistics over blocks of spectra (getdata(...; tavby, tavfunc)): fqav's rule
  * on the time axis with Julia's Statistics as the function.  The window's
