@@ -113,6 +113,10 @@ SIGNATURES = {
     "bldp_skewness_f32": ([P, I64, I64, I64, P, I64, P, I64, I64, P], I),
     "bldp_band_skewness_f32": ([I, P, I64, I64, I64, P, I64, P, P], I),
     "bldp_skewness_host_f32": ([I, P, I64, I64, I64, P, I64, P], I),
+    "bldp_moments_plan_f32": ([P, I64, I64, I64, P, I64, P], I),
+    "bldp_moments_f32": ([P, I64, I64, I64, P, I64, P, P, P, P, I64, I64, P], I),
+    "bldp_band_moments_f32": ([I, P, I64, I64, I64, P, I64, P, P, P, P, P], I),
+    "bldp_moments_host_f32": ([I, P, I64, I64, I64, P, I64, P, P, P, P], I),
     "bldp_tstat_shape": ([I64, I64, I64, P, I64, P], I),
     "bldp_tstat_plan_f32": ([P, I64, I64, I64, P, I64, I, P, P], I),
     "bldp_tstat_f32": ([P, I64, I64, I64, P, I64, I, P, I64, I64, P], I),

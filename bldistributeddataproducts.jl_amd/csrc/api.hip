@@ -786,7 +786,12 @@ int bldp_despike_f32(float *data, int64_t nchan, int64_t nif, int64_t ntime, int
   return BLDP_OK;
 }
 
-// `order`: the moment of the plan, 4 = kurtosis, 3 = skewness (bldp_skewness_*)
+// `order`: the moment of the plan, 4 = kurtosis, 3 = skewness (bldp_skewness_*),
+// kOrdAll = every plane of KurtArgs.mo (bldp_moments_*)
+static const char *kurt_what(int order, const char *k4) {
+  return order == 3 ? "skewness" : order == kOrdAll ? "moments" : k4;
+}
+static bool any_plane(double *const *mo) { return mo && (mo[0] || mo[1] || mo[2] || mo[3]); }
 static int kurt_setup(int nbank, const float *const *in, int64_t nchan, int64_t nif,
                       int64_t ntime, const int64_t *win, KurtArgs *k, int order = 4) {
   if (nbank < 1 || nbank > BLDP_MAX_BANKS)
@@ -817,13 +822,15 @@ static int kurt_setup(int nbank, const float *const *in, int64_t nchan, int64_t 
   return BLDP_OK;
 }
 
+// (order kOrdAll: the caller has set k.mo, `out` is not read)
 static int kurt_run(KurtArgs &k, double *out, void *workspace, void *stream) {
   if (k.nc * k.nrow == 0) return BLDP_OK;
   if (kurtosis_max_grid(k) > INT32_MAX)
     return fail(BLDP_EINVAL, "kurtosis window too large for one launch");
   for (int b = 0; b < k.nbank; ++b)
     if (!k.in[b] && k.nt > 0) return fail(BLDP_EINVAL, "null input pointer (bank %d)", b);
-  if (!out) return fail(BLDP_EINVAL, "null output pointer");
+  if (k.order == kOrdAll ? !any_plane(k.mo) : !out)
+    return fail(BLDP_EINVAL, "null output pointer");
   k.out = out;
   hipStream_t s = (hipStream_t)stream;
   void *ws = workspace;
@@ -932,14 +939,18 @@ static int kblk_plan(int nbank, const float *const *in, int64_t nchan, int64_t n
   if (rc) return rc;
   p->path = kurtosis_path(p->blk);
   p->tmp_off = (kurtosis_ws_bytes(p->blk) + 255) & ~(size_t)255;
-  p->ws_bytes = p->tmp_off + (size_t)(p->blk.nrow * p->blk.nc) * sizeof(double);
+  // (order kOrdAll stages up to four planes of a block)
+  p->ws_bytes = p->tmp_off +
+                (order == kOrdAll ? 4 : 1) * (size_t)(p->blk.nrow * p->blk.nc) * sizeof(double);
   return BLDP_OK;
 }
 
 static int kblk_run(int nbank, const float *const *in, int64_t nchan, int64_t nif, int64_t ntime,
                     const int64_t *win, int64_t tblock, double *out, int64_t out_bank,
-                    int64_t out_ld_i, int64_t out_ld_b, void *stream, int order = 4) {
-  const char *what = order == 3 ? "skewness" : "tblock kurtosis";
+                    int64_t out_ld_i, int64_t out_ld_b, void *stream, int order = 4,
+                    double *const *mo = nullptr) {
+  // (order kOrdAll: the planes `mo`, each laid out as `out`, which is not read)
+  const char *what = kurt_what(order, "tblock kurtosis");
   KblkPlan p;
   int rc = kblk_plan(nbank, in, nchan, nif, ntime, win, tblock, &p, order);
   if (rc) return rc;
@@ -947,7 +958,8 @@ static int kblk_run(int nbank, const float *const *in, int64_t nchan, int64_t ni
   if (w.nc * w.ni * p.nb == 0) return BLDP_OK;
   for (int b = 0; b < nbank; ++b)
     if (!w.in[b]) return fail(BLDP_EINVAL, "%s: null input pointer (bank %d)", what, b);
-  if (!out) return fail(BLDP_EINVAL, "%s: null output pointer", what);
+  if (order == kOrdAll ? !any_plane(mo) : !out)
+    return fail(BLDP_EINVAL, "%s: null output pointer", what);
   if (out_ld_i < w.nc || out_ld_b < (w.ni - 1) * out_ld_i + w.nc)
     return fail(BLDP_EINVAL,
                 "%s: out strides (%lld, %lld) overlap for a (%lld, %lld, %lld) result", what,
@@ -970,6 +982,7 @@ static int kblk_run(int nbank, const float *const *in, int64_t nchan, int64_t ni
     k.out_ld_b = out_ld_b;
     k.out = out;
     k.order = order;
+    for (int q = 0; q < 4; ++q) k.mo[q] = order == kOrdAll ? mo[q] : nullptr;
     plan_kurt_blocks(k, num_cus_current());
     if (kurt_blocks_grid(k) > INT32_MAX)
       return fail(BLDP_EINVAL, "tblock=%lld kurtosis: %lld blocks are too many for one launch",
@@ -995,11 +1008,20 @@ static int kblk_run(int nbank, const float *const *in, int64_t nchan, int64_t ni
     if (rc) return rc;
     if (kurtosis_ws_bytes(k) > p.tmp_off)  // (a plan option changed under the call)
       return fail(BLDP_EINVAL, "%s: the plan changed during the call", what);
-    rc = kurt_run(k, direct ? out + b * out_ld_b : tmp, ws, stream);
+    const int64_t n = k.nrow * k.nc;
+    if (order == kOrdAll) {
+      for (int q = 0; q < 4; ++q)
+        k.mo[q] = !mo[q] ? nullptr : direct ? mo[q] + b * out_ld_b : tmp + q * n;
+      rc = kurt_run(k, nullptr, ws, stream);
+    } else {
+      rc = kurt_run(k, direct ? out + b * out_ld_b : tmp, ws, stream);
+    }
     if (rc) return rc;
-    if (!direct) {
-      hipError_t e = launch_kurt_scatter(tmp, nbank, w.ni, w.nc, out + b * out_ld_b, out_bank,
-                                         out_ld_i, s);
+    for (int q = 0; !direct && q < (order == kOrdAll ? 4 : 1); ++q) {
+      double *dst = order == kOrdAll ? mo[q] : out;
+      if (!dst) continue;
+      hipError_t e = launch_kurt_scatter(tmp + q * n, nbank, w.ni, w.nc, dst + b * out_ld_b,
+                                         out_bank, out_ld_i, s);
       if (e != hipSuccess)
         return fail(BLDP_EHIP, "%s launch: %s", what, hipGetErrorString(e));
     }
@@ -1064,32 +1086,44 @@ static int skew_check(int64_t tblock) {
 }
 
 // Whole window: element (c, i) at out[bank*out_bank + c + i*out_ld_i].
+// (order kOrdAll: the planes `mo`, each laid out as `out`, which is not read)
 static int skew_whole(int nbank, const float *const *in, int64_t nchan, int64_t nif, int64_t ntime,
                       const int64_t *win, double *out, int64_t out_bank, int64_t out_ld_i,
-                      void *stream) {
+                      void *stream, int order = 3, double *const *mo = nullptr) {
+  const char *what = kurt_what(order, "kurtosis");
+  const bool all = order == kOrdAll;
   KurtArgs k;
-  int rc = kurt_setup(nbank, in, nchan, nif, ntime, win, &k, 3);
+  int rc = kurt_setup(nbank, in, nchan, nif, ntime, win, &k, order);
   if (rc) return rc;
   if (k.nc * k.nrow == 0) return BLDP_OK;
   for (int b = 0; b < nbank; ++b)
-    if (!k.in[b] && k.nt > 0) return fail(BLDP_EINVAL, "skewness: null input pointer (bank %d)", b);
-  if (!out) return fail(BLDP_EINVAL, "skewness: null output pointer");
+    if (!k.in[b] && k.nt > 0) return fail(BLDP_EINVAL, "%s: null input pointer (bank %d)", what, b);
+  if (all ? !any_plane(mo) : !out) return fail(BLDP_EINVAL, "%s: null output pointer", what);
   if (out_ld_i < k.nc || (nbank > 1 && out_bank < (k.ni - 1) * out_ld_i + k.nc))
-    return fail(BLDP_EINVAL, "skewness: out strides (%lld, %lld) overlap for a (%lld, %lld) result",
+    return fail(BLDP_EINVAL, "%s: out strides (%lld, %lld) overlap for a (%lld, %lld) result", what,
                 (long long)out_ld_i, (long long)out_bank, (long long)k.nc, (long long)k.ni);
-  if (out_ld_i == k.nc && (nbank == 1 || out_bank == k.nc * k.ni))
-    return kurt_run(k, out, nullptr, stream);  // dense: the kernels write the product
+  const int64_t n = k.nrow * k.nc;
+  if (out_ld_i == k.nc && (nbank == 1 || out_bank == k.nc * k.ni)) {
+    // dense: the kernels write the product
+    for (int q = 0; all && q < 4; ++q) k.mo[q] = mo[q];
+    return kurt_run(k, out, nullptr, stream);
+  }
   hipStream_t s = (hipStream_t)stream;
   const size_t tmp_off = (kurtosis_ws_bytes(k) + 255) & ~(size_t)255;
   ScratchLease lease;  // held until the launches are queued
-  rc = scratch_lease(s, tmp_off + (size_t)(k.nrow * k.nc) * sizeof(double), &lease);
+  rc = scratch_lease(s, tmp_off + (all ? 4 : 1) * (size_t)n * sizeof(double), &lease);
   if (rc) return rc;
   char *ws = static_cast<char *>(lease.ptr);
   double *tmp = reinterpret_cast<double *>(ws + tmp_off);
+  for (int q = 0; all && q < 4; ++q) k.mo[q] = mo[q] ? tmp + q * n : nullptr;
   rc = kurt_run(k, tmp, ws, stream);
   if (rc) return rc;
-  hipError_t e = launch_kurt_scatter(tmp, nbank, k.ni, k.nc, out, out_bank, out_ld_i, s);
-  if (e != hipSuccess) return fail(BLDP_EHIP, "skewness launch: %s", hipGetErrorString(e));
+  for (int q = 0; q < (all ? 4 : 1); ++q) {
+    double *dst = all ? mo[q] : out;
+    if (!dst) continue;
+    hipError_t e = launch_kurt_scatter(tmp + q * n, nbank, k.ni, k.nc, dst, out_bank, out_ld_i, s);
+    if (e != hipSuccess) return fail(BLDP_EHIP, "%s launch: %s", what, hipGetErrorString(e));
+  }
   return BLDP_OK;
 }
 
@@ -1146,6 +1180,115 @@ int bldp_band_skewness_f32(int nbank, const float *const *in, int64_t nchan, int
   if (rc) return rc;
   return kblk_run(nbank, in, nchan, nif, ntime, win, tblock, out, d[0] * d[1] * d[2], d[0],
                   d[0] * d[1], stream, 3);
+}
+
+// ---- moments (getmoments): mean, var, skewness and kurtosis from one read -----
+// The skewness family with KurtArgs.order = kOrdAll and four planes that share
+// their strides; a null plane is skipped.  The planes may not overlap each
+// other or the input array.
+static bool spans_overlap(const void *a, size_t na, const void *b, size_t nb) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return na > 0 && nb > 0 && x < y + nb && y < x + na;
+}
+
+// Checks of a moments call whose result is not empty: `span` elements from
+// each plane's pointer hold its result, `in_elems` floats each bank's array.
+static int mom_check(int nbank, const float *const *in, int64_t in_elems, double *const mo[4],
+                     int64_t span) {
+  if (!any_plane(mo)) return fail(BLDP_EINVAL, "moments: every output plane is null");
+  const size_t pb = (size_t)span * sizeof(double), ib = (size_t)in_elems * sizeof(float);
+  for (int q = 0; q < 4; ++q) {
+    if (!mo[q]) continue;
+    for (int r = q + 1; r < 4; ++r)
+      if (mo[r] && spans_overlap(mo[q], pb, mo[r], pb))
+        return fail(BLDP_EINVAL, "moments: output planes %d and %d overlap", q, r);
+    for (int b = 0; b < nbank; ++b)
+      if (in[b] && spans_overlap(mo[q], pb, in[b], ib))
+        return fail(BLDP_EINVAL, "moments: output plane %d overlaps the input (bank %d)", q, b);
+  }
+  return BLDP_OK;
+}
+
+int bldp_moments_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                          const int64_t *win, int64_t tblock, int64_t info[4]) {
+  if (!info) return fail(BLDP_EINVAL, "null info");
+  if (tblock < 0) return fail(BLDP_EINVAL, "moments: tblock=%lld must be >= 0", (long long)tblock);
+  const float *ins[1] = {in};
+  if (tblock == 0) {
+    KurtArgs k;
+    int rc = kurt_setup(1, ins, nchan, nif, ntime, win, &k, kOrdAll);
+    if (rc) return rc;
+    info[0] = kurtosis_path(k);
+    info[1] = 1;  // one set of launches for the window
+    info[2] = 1;
+    info[3] = (int64_t)kurtosis_ws_bytes(k);
+    return BLDP_OK;
+  }
+  KblkPlan p;
+  int rc = kblk_plan(1, ins, nchan, nif, ntime, win, tblock, &p, kOrdAll);
+  if (rc) return rc;
+  info[0] = p.path;
+  info[1] = p.fused ? 1 : 0;
+  info[2] = p.nb;
+  info[3] = (int64_t)p.ws_bytes;
+  return BLDP_OK;
+}
+
+// Every entry point: the argument checks in the skewness' order, then the run.
+// Element (c, i, b) of bank k at plane[k*out_bank + c + i*out_ld_i + b*out_ld_b].
+static int mom_run(int nbank, const float *const *in, int64_t nchan, int64_t nif, int64_t ntime,
+                   const int64_t *win, int64_t tblock, double *const mo[4], bool dense,
+                   int64_t out_ld_i, int64_t out_ld_b, void *stream) {
+  if (tblock < 0) return fail(BLDP_EINVAL, "moments: tblock=%lld must be >= 0", (long long)tblock);
+  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
+    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
+  Geo g;
+  int rc = resolve_window(nchan, nif, ntime, win, &g);
+  if (rc) return rc;
+  int64_t nb = 1;
+  if (tblock > 0) {
+    rc = kblk_count(g.nt, tblock, &nb);
+    if (rc) return rc;
+  }
+  if (g.nc * g.ni * nb == 0) return BLDP_OK;
+  int64_t out_bank = 0;
+  if (dense) {  // [nbank][nb][ni][nc]
+    out_ld_i = g.nc;
+    out_ld_b = g.nc * g.ni;
+    out_bank = g.nc * g.ni * nb;
+  }
+  for (int b = 0; b < nbank; ++b)
+    if (!in[b] && g.nt > 0) return fail(BLDP_EINVAL, "moments: null input pointer (bank %d)", b);
+  if (out_ld_i < g.nc || (tblock > 0 && out_ld_b < (g.ni - 1) * out_ld_i + g.nc))
+    return fail(BLDP_EINVAL, "moments: out strides (%lld, %lld) overlap for a (%lld, %lld, %lld) "
+                "result", (long long)out_ld_i, (long long)out_ld_b, (long long)g.nc,
+                (long long)g.ni, (long long)nb);
+  const int64_t span = (nbank - 1) * out_bank + (tblock > 0 ? (nb - 1) * out_ld_b : 0) +
+                       (g.ni - 1) * out_ld_i + g.nc;
+  rc = mom_check(nbank, in, nchan * nif * ntime, mo, span);
+  if (rc) return rc;
+  if (tblock == 0)
+    return skew_whole(nbank, in, nchan, nif, ntime, win, nullptr, out_bank, out_ld_i, stream,
+                      kOrdAll, mo);
+  return kblk_run(nbank, in, nchan, nif, ntime, win, tblock, nullptr, out_bank, out_ld_i,
+                  out_ld_b, stream, kOrdAll, mo);
+}
+
+int bldp_moments_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                     const int64_t *win, int64_t tblock, double *mean, double *var, double *skew,
+                     double *kurt, int64_t out_ld_i, int64_t out_ld_b, void *stream) {
+  const float *ins[1] = {in};
+  double *const mo[4] = {mean, var, skew, kurt};
+  return mom_run(1, ins, nchan, nif, ntime, win, tblock, mo, false, out_ld_i, out_ld_b, stream);
+}
+
+int bldp_band_moments_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                          int64_t ntime, const int64_t *win, int64_t tblock, double *mean,
+                          double *var, double *skew, double *kurt, void *stream) {
+  if (tblock < 0) return fail(BLDP_EINVAL, "moments: tblock=%lld must be >= 0", (long long)tblock);
+  if (!in) return fail(BLDP_EINVAL, "moments: null input pointer array");
+  double *const mo[4] = {mean, var, skew, kurt};
+  return mom_run(nbank, in, nchan, nif, ntime, win, tblock, mo, true, 0, 0, stream);
 }
 
 // ---- tavfunc: median / var / std over blocks of spectra ---------------------

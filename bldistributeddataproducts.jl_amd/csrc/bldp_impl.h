@@ -234,14 +234,22 @@ struct KurtArgs {
   int32_t nchunk;
   int32_t ts;       // waves of a workgroup splitting the spectra of a tile (1, 2, 4)
   float *mean;      // [nbank*ni][nc]  Float32 mean (two-pass path)
-  double *ws_mom;   // [nchunk][2][nbank*ni][nc]
+  double *ws_mom;   // [nchunk][2][nbank*ni][nc] (order kOrdAll: [nchunk][3])
   // leaf / tree-node partials: pm [4][nodes][n] Float64 (mean, M2, M3, M4
   // about the node's own mean), pf [3][nodes][n] Float32 (pairwise sum, max, min)
   double *pm;
   float *pf;
   double *out;      // [nbank][ni][nc]
-  int32_t order;    // the moment: 4 = kurtosis, 3 = skewness (set before plan_kurtosis)
+  int32_t order;    // the moment: 4 = kurtosis, 3 = skewness, kOrdAll = every plane
+                    // of `mo` (set before plan_kurtosis)
+  // order kOrdAll (getmoments): the planes mean, var = cm2/n, skewness and
+  // kurtosis, each [nbank][ni][nc]; a null plane is neither formed nor stored
+  double *mo[4];
 };
+// The third moment order: one pass keeps cm2, cm3 and cm4 and writes KurtArgs.mo
+// (KurtBlkArgs.mo) instead of `out`.
+constexpr int kOrdAll = 0;
+enum { MO_MEAN = 0, MO_VAR = 1, MO_SKEW = 2, MO_KURT = 3 };
 void plan_kurtosis(KurtArgs &k, int num_cus);
 size_t kurtosis_ws_bytes(const KurtArgs &k);
 hipError_t launch_kurtosis(KurtArgs &k, char *ws, hipStream_t s);
@@ -262,7 +270,8 @@ struct KurtBlkArgs {
   int64_t nc, ni, M, nb;
   int64_t out_bank, out_ld_i, out_ld_b;
   double *out;
-  int32_t order;  // 4 = kurtosis, 3 = skewness
+  int32_t order;  // 4 = kurtosis, 3 = skewness, kOrdAll = the planes of `mo`
+  double *mo[4];  // order kOrdAll: mean, var, skewness, kurtosis, each laid out as `out`
 };
 // `whole`: the KurtArgs of the whole window (its float4 columns are every block's)
 bool kurt_blocks_fused(const KurtArgs &whole, int64_t M);

@@ -254,6 +254,52 @@ extern "C" int bldp_skewness_host_f32(int dev, const float *in, int64_t nchan, i
   });
 }
 
+// The same staging for the moments: up to four (nc, ni, nb) planes come back, a
+// null plane is neither computed nor copied.
+extern "C" int bldp_moments_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                     int64_t ntime, const int64_t *win, int64_t tblock,
+                                     double *mean, double *var, double *skew, double *kurt) {
+  int64_t sh[3], info[4];
+  // (every argument check, before any staging)
+  int rc = bldp_moments_plan_f32(nullptr, nchan, nif, ntime, win, tblock, info);
+  if (rc) return rc;
+  rc = bldp_reduce_shape(nchan, nif, ntime, win, 1, 1, sh);
+  if (rc) return rc;
+  const int64_t nc = sh[0], ni = sh[1], nt = sh[2], nb = info[2];
+  const int64_t n = nc * ni * nb;
+  if (n == 0) return BLDP_OK;
+  double *const out[4] = {mean, var, skew, kurt};
+  int np = 0;
+  for (int q = 0; q < 4; ++q) np += out[q] != nullptr;
+  if (np == 0) return bldp::set_error(BLDP_EINVAL, "moments: every output plane is null");
+  if (!in && nt > 0) return bldp::set_error(BLDP_EINVAL, "moments: null pointer");
+  for (int q = 0; q < 4; ++q)  // (host planes: the same rule as the device entry's)
+    for (int r = q + 1; r < 4; ++r)
+      if (out[q] && out[r] && out[q] < out[r] + n && out[r] < out[q] + n)
+        return bldp::set_error(BLDP_EINVAL, "moments: output planes overlap");
+  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
+  return with_stager(dev, [&](bldp::Stager *sg) -> int {
+    float *dbuf;
+    double *dout;
+    int r = bldp::stager_buffer(sg, 0, (size_t)std::max<int64_t>(1, h.span * ni * nt) * 4,
+                                (void **)&dbuf);
+    if (!r) r = bldp::stager_buffer(sg, 2, (size_t)(np * n) * sizeof(double), (void **)&dout);
+    if (!r && nt > 0) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
+    if (r) return r;
+    double *d[4];
+    for (int q = 0, j = 0; q < 4; ++q) d[q] = out[q] ? dout + (j++) * n : nullptr;
+    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
+    r = bldp_moments_f32(dbuf, h.span, ni, nt, dwin, tblock, d[0], d[1], d[2], d[3], nc, nc * ni,
+                         sg->st[0]);
+    if (r) return r;
+    for (int q = 0; q < 4; ++q)
+      if (out[q])
+        HCHK(hipMemcpyAsync(out[q], d[q], (size_t)n * sizeof(double), hipMemcpyDeviceToHost,
+                            sg->st[0]));
+    return BLDP_OK;
+  });
+}
+
 // The same staging for tavfunc's var / std / median over blocks of tavby
 // spectra: the window's rows go to the device once (in window order: a
 // reversed time range is staged reversed), the (nc, ni, nb) product comes back.

@@ -61,6 +61,14 @@
 // that forms the top moment; the leaf partials and the tree carry M3 and M4
 // for both and skew_ratio finishes the streamed paths.  k_kurt_tile has no
 // order-3 form: skewness plans as if kurt_leaf_tile = 0.
+//
+// getmoments is the third order, kOrdAll: one pass keeps cm2, cm3 and cm4 (the
+// two top terms as above, added in the same fixed order) and writes up to four
+// planes, KurtArgs.mo: mean = Float64(m), var = cm2 / n (uncorrected: what
+// both ratios divide by), skewness and kurtosis.  A null plane is neither
+// formed nor stored.  The streamed paths take all four from one set of merged
+// moments (skew_ratio hands out the cm2 it forms under its overflow rule); the
+// two-pass path keeps three partial sums per chunk; it plans as skewness does.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -204,7 +212,8 @@ __device__ __forceinline__ double mom_ratio(double cm2, double cmk) {
 // sign to that infinity, and cm3 is 0 when both cubes are (every one between
 // them is).  cm2 follows kurt_ratio's rule.
 __device__ __forceinline__ double skew_ratio(int64_t nt, float S, double ma, double a2,
-                                             double a3, float hi, float lo) {
+                                             double a3, float hi, float lo,
+                                             double *cm2_out = nullptr, float *m_out = nullptr) {
   const float m = S / (float)nt;  // mean(v): Float32 sum / length
   const double n = (double)nt, eps = ma - (double)m, e2 = eps * eps;
   double cm2 = (a2 + n * e2) / n;
@@ -225,7 +234,49 @@ __device__ __forceinline__ double skew_ratio(int64_t nt, float S, double ma, dou
     cm3 = -INFINITY;
   else if (h3 == 0.0f && l3 == 0.0f)
     cm3 = 0.0;
+  if (cm2_out) *cm2_out = cm2;  // (getmoments: the variance and the mean of the same call)
+  if (m_out) *m_out = m;
   return mom_ratio<3>(cm2, cm3);
+}
+
+// Order kOrdAll (getmoments): one pass keeps the three sums and every plane of
+// `mo` that is not null takes its value; var is the cm2 / n both ratios share
+// (the uncorrected variance), mean the Float32 m widened.
+//   mom_plane : plane q of a recipe path, from m and the sums' cmk = sum / n
+//   put_all   : element e of every requested plane (dense planes)
+//   put_moved : the same on the streamed paths, from the merged moments
+__device__ __forceinline__ double mom_plane(int q, float m, double cm2, double cm3, double cm4) {
+  switch (q) {
+    case MO_MEAN: return (double)m;
+    case MO_VAR: return cm2;
+    case MO_SKEW: return mom_ratio<3>(cm2, cm3);
+    default: return mom_ratio<4>(cm2, cm4);
+  }
+}
+__device__ __forceinline__ void put_all(double *const (&mo)[4], int64_t e, float m, double n,
+                                        double s2, double s3, double s4) {
+  const double cm2 = s2 / n, cm3 = s3 / n, cm4 = s4 / n;
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    if (mo[q]) mo[q][e] = mom_plane(q, m, cm2, cm3, cm4);
+}
+// The variance plane of a streamed row from the cm2 skew_ratio hands out: its
+// rule makes cm2 Inf whenever an extreme's square is, also where the recipe
+// adds a NaN (m itself infinite: an infinite value of m's sign gives z = Inf -
+// Inf).  Both ratios are NaN either way (Inf / Inf); the variance is not.
+__device__ __forceinline__ double var_plane(double cm2, float m, float hi, float lo) {
+  return isnan(hi - m) || isnan(lo - m) ? (double)NAN : cm2;
+}
+__device__ __forceinline__ void put_moved(double *const (&mo)[4], int64_t e, int64_t nt, float S,
+                                          double ma, double a2, double a3, double a4, float hi,
+                                          float lo) {
+  float m;
+  double var;
+  const double sk = skew_ratio(nt, S, ma, a2, a3, hi, lo, &var, &m);
+  if (mo[MO_MEAN]) mo[MO_MEAN][e] = (double)m;
+  if (mo[MO_VAR]) mo[MO_VAR][e] = var_plane(var, m, hi, lo);
+  if (mo[MO_SKEW]) mo[MO_SKEW][e] = sk;
+  if (mo[MO_KURT]) mo[MO_KURT][e] = kurt_ratio(nt, S, ma, a2, a3, a4, hi, lo);
 }
 
 // ---------------------------------------------------------------------------
@@ -236,7 +287,34 @@ __device__ __forceinline__ double skew_ratio(int64_t nt, float S, double ma, dou
 // (plan option "kurt_exact": 1 = use the exact-count instantiation).  The
 // wave's 256 Float64 results go through LDS so every nt store instruction
 // writes 1 KiB contiguous (+2.5% on the 0000 band against each lane's 32 B as
-// two nt 16-byte stores).
+// two nt 16-byte stores).  regs_store writes one plane's four results of a
+// lane: `row` is the plane's nc results of this (bank, IF) row.
+__device__ __forceinline__ void regs_store(double *row, int64_t col, int64_t ncols,
+                                           const double (&r)[4]) {
+  d2v *o = reinterpret_cast<d2v *>(row + 4 * col);
+  if (ncols % 64 == 0 && (reinterpret_cast<uintptr_t>(row) & 15) == 0) {
+    // whole wave in range: transpose through this wave's 2 KiB of LDS so each
+    // store instruction writes 1 KiB contiguous (lane L: doubles 2L, 2L+1 of
+    // the wave's 256 outputs, then 128 + 2L, 129 + 2L)
+    __shared__ d2v st[4][128];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    st[wave][2 * lane] = d2v{r[0], r[1]};
+    st[wave][2 * lane + 1] = d2v{r[2], r[3]};
+    __builtin_amdgcn_wave_barrier();
+    const d2v a0 = st[wave][lane], a1 = st[wave][64 + lane];
+    __builtin_amdgcn_wave_barrier();  // (read before a next plane overwrites)
+    d2v *ow = reinterpret_cast<d2v *>(row + 4 * (col - lane));
+    __builtin_nontemporal_store(a0, ow + lane);
+    __builtin_nontemporal_store(a1, ow + 64 + lane);
+  } else if ((reinterpret_cast<uintptr_t>(o) & 15) == 0) {
+    __builtin_nontemporal_store(d2v{r[0], r[1]}, o);
+    __builtin_nontemporal_store(d2v{r[2], r[3]}, o + 1);
+  } else {
+    double *od = row + 4 * col;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) od[w] = r[w];
+  }
+}
 template <int NTMAX, bool EXACT, int ORD>
 __global__ __launch_bounds__(kB) void k_kurt_regs(const KurtArgs k) {
   const int64_t ncols = k.nc / 4;
@@ -263,6 +341,7 @@ __global__ __launch_bounds__(kB) void k_kurt_regs(const KurtArgs k) {
     }
   const float m[4] = {sa.x / (float)nt, sa.y / (float)nt, sb.x / (float)nt, sb.y / (float)nt};
   double c2[4] = {0, 0, 0, 0}, c4[4] = {0, 0, 0, 0};
+  double c3[ORD == kOrdAll ? 4 : 1] = {};  // (order kOrdAll keeps both top moments)
 #pragma unroll
   for (int t = 0; t < NTMAX; ++t)
     if (EXACT || t < nt) {
@@ -272,37 +351,33 @@ __global__ __launch_bounds__(kB) void k_kurt_regs(const KurtArgs k) {
         const float z = x[w] - m[w];  // StatsBase: z, z2 in Float32; Float64 moments
         const float z2 = z * z;
         c2[w] += (double)z2;
-        c4[w] += (double)top_term<ORD>(z2, z);
+        if constexpr (ORD == kOrdAll) {
+          c3[w] += (double)top_term<3>(z2, z);
+          c4[w] += (double)top_term<4>(z2, z);
+        } else {
+          c4[w] += (double)top_term<ORD>(z2, z);
+        }
       }
     }
-  double r[4];
+  if constexpr (ORD == kOrdAll) {
+    // plane after plane: 4 results live at a time, each plane with the wide store
 #pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    const double cm2 = c2[w] / (double)nt, cm4 = c4[w] / (double)nt;
-    r[w] = mom_ratio<ORD>(cm2, cm4);
-  }
-  d2v *o = reinterpret_cast<d2v *>(k.out + ib * k.nc + 4 * col);
-  if (ncols % 64 == 0 &&
-      (reinterpret_cast<uintptr_t>(k.out + ib * k.nc) & 15) == 0) {
-    // whole wave in range: transpose through this wave's 2 KiB of LDS so each
-    // store instruction writes 1 KiB contiguous (lane L: doubles 2L, 2L+1 of
-    // the wave's 256 outputs, then 128 + 2L, 129 + 2L)
-    __shared__ d2v st[4][128];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    st[wave][2 * lane] = d2v{r[0], r[1]};
-    st[wave][2 * lane + 1] = d2v{r[2], r[3]};
-    __builtin_amdgcn_wave_barrier();
-    const d2v a0 = st[wave][lane], a1 = st[wave][64 + lane];
-    d2v *ow = reinterpret_cast<d2v *>(k.out + ib * k.nc + 4 * (col - lane));
-    __builtin_nontemporal_store(a0, ow + lane);
-    __builtin_nontemporal_store(a1, ow + 64 + lane);
-  } else if ((reinterpret_cast<uintptr_t>(o) & 15) == 0) {
-    __builtin_nontemporal_store(d2v{r[0], r[1]}, o);
-    __builtin_nontemporal_store(d2v{r[2], r[3]}, o + 1);
+    for (int q = 0; q < 4; ++q)
+      if (k.mo[q]) {
+        double r[4];
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+          r[w] = mom_plane(q, m[w], c2[w] / (double)nt, c3[w] / (double)nt, c4[w] / (double)nt);
+        regs_store(k.mo[q] + ib * k.nc, col, ncols, r);
+      }
   } else {
-    double *od = k.out + ib * k.nc + 4 * col;
+    double r[4];
 #pragma unroll
-    for (int w = 0; w < 4; ++w) od[w] = r[w];
+    for (int w = 0; w < 4; ++w) {
+      const double cm2 = c2[w] / (double)nt, cm4 = c4[w] / (double)nt;
+      r[w] = mom_ratio<ORD>(cm2, cm4);
+    }
+    regs_store(k.out + ib * k.nc, col, ncols, r);
   }
 }
 
@@ -346,28 +421,36 @@ __global__ __launch_bounds__(kB) void k_kurt_mid(const KurtArgs k) {
     __syncthreads();
   }
   const float m = carry[lane] / (float)nt;
-  double c2 = 0.0, c4 = 0.0;
+  constexpr bool ALL = ORD == kOrdAll;  // both top moments: a third partial sum
+  double c2 = 0.0, c3 = 0.0, c4 = 0.0;
 #pragma unroll
   for (int r = 0; r < NR; ++r)
     if (r < cnt) {
       const float z = v[r] - m;  // StatsBase: z, z2 in Float32; Float64 moments
       const float z2 = z * z;
       c2 += (double)z2;
-      c4 += (double)top_term<ORD>(z2, z);
+      if constexpr (ALL) c3 += (double)top_term<3>(z2, z);
+      c4 += (double)top_term<ALL ? 4 : ORD>(z2, z);
     }
-  __shared__ double part[4][2][64];
+  __shared__ double part[4][ALL ? 3 : 2][64];
   part[wave][0][lane] = c2;
   part[wave][1][lane] = c4;
+  if constexpr (ALL) part[wave][2][lane] = c3;
   __syncthreads();
   if (wave == 0 && valid) {
-    double a2 = 0.0, a4 = 0.0;
+    double a2 = 0.0, a3 = 0.0, a4 = 0.0;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       a2 += part[q][0][lane];
       a4 += part[q][1][lane];
+      if constexpr (ALL) a3 += part[q][2][lane];
     }
-    const double cm2 = a2 / (double)nt, cm4 = a4 / (double)nt;
-    k.out[ib * k.nc + c] = mom_ratio<ORD>(cm2, cm4);
+    if constexpr (ALL) {
+      put_all(k.mo, ib * k.nc + c, m, (double)nt, a2, a3, a4);
+    } else {
+      const double cm2 = a2 / (double)nt, cm4 = a4 / (double)nt;
+      k.out[ib * k.nc + c] = mom_ratio<ORD>(cm2, cm4);
+    }
   }
 }
 
@@ -394,6 +477,15 @@ __device__ __forceinline__ f2v top2(f2v q, f2v z) {
     return q * q;
   else
     return q * z;
+}
+// a lane's two results: one 16-byte store where the address allows it
+__device__ __forceinline__ void store2(double *o, double k0, double k1) {
+  if ((reinterpret_cast<uintptr_t>(o) & 15) == 0) {
+    *reinterpret_cast<d2v *>(o) = d2v{k0, k1};
+  } else {
+    o[0] = k0;
+    o[1] = k1;
+  }
 }
 template <int NR, int NW, int ORD>
 __global__ __launch_bounds__(64 * NW) void k_kurt_mid2(const KurtArgs k) {
@@ -434,7 +526,8 @@ __global__ __launch_bounds__(64 * NW) void k_kurt_mid2(const KurtArgs k) {
   }
   const f2v sm = carry[lane];
   const f2v mv = {sm.x / (float)nt, sm.y / (float)nt};
-  double a2 = 0.0, a4 = 0.0, b2 = 0.0, b4 = 0.0;
+  constexpr bool ALL = ORD == kOrdAll;  // both top moments: two more partial sums
+  double a2 = 0.0, a3 = 0.0, a4 = 0.0, b2 = 0.0, b3 = 0.0, b4 = 0.0;
 #pragma unroll
   for (int r = 0; r < NR; ++r)
     if (r < cnt) {
@@ -442,20 +535,29 @@ __global__ __launch_bounds__(64 * NW) void k_kurt_mid2(const KurtArgs k) {
       // (v_pk_add_f32 / v_pk_mul_f32), Float64 moments
       const f2v z = v[r] - mv;
       const f2v q = z * z;
-      const f2v q2 = top2<ORD>(q, z);
+      const f2v q2 = top2<ALL ? 4 : ORD>(q, z);
       a2 += (double)q.x;
       a4 += (double)q2.x;
       b2 += (double)q.y;
       b4 += (double)q2.y;
+      if constexpr (ALL) {
+        const f2v q3 = top2<3>(q, z);
+        a3 += (double)q3.x;
+        b3 += (double)q3.y;
+      }
     }
-  __shared__ double part[NW][4][64];
+  __shared__ double part[NW][ALL ? 6 : 4][64];
   part[wave][0][lane] = a2;
   part[wave][1][lane] = a4;
   part[wave][2][lane] = b2;
   part[wave][3][lane] = b4;
+  if constexpr (ALL) {
+    part[wave][4][lane] = a3;
+    part[wave][5][lane] = b3;
+  }
   __syncthreads();
   if (wave == 0 && valid) {
-    double x2 = 0.0, x4 = 0.0, y2 = 0.0, y4 = 0.0;
+    double x2 = 0.0, x3 = 0.0, x4 = 0.0, y2 = 0.0, y3 = 0.0, y4 = 0.0;
 #pragma unroll
     for (int q = 0; q < NW; ++q) {
       x2 += part[q][0][lane];
@@ -463,15 +565,27 @@ __global__ __launch_bounds__(64 * NW) void k_kurt_mid2(const KurtArgs k) {
       y2 += part[q][2][lane];
       y4 += part[q][3][lane];
     }
+    if constexpr (ALL) {  // (a loop of its own: the first keeps its registers)
+#pragma unroll
+      for (int q = 0; q < NW; ++q) {
+        x3 += part[q][4][lane];
+        y3 += part[q][5][lane];
+      }
+    }
     const double n = (double)nt;
-    const double k0 = mom_ratio<ORD>(x2 / n, x4 / n);
-    const double k1 = mom_ratio<ORD>(y2 / n, y4 / n);
-    double *o = k.out + ib * k.nc + c;
-    if ((reinterpret_cast<uintptr_t>(o) & 15) == 0) {
-      *reinterpret_cast<d2v *>(o) = d2v{k0, k1};
+    if constexpr (ALL) {
+      // (unrolled: the planes' divisions and roots interleave, 106 VGPRs at
+      // every NR <= 40; rolled, 65 at NR = 8 .. 102 at NR = 40, but the 0002
+      // band's {skewness, kurtosis} call measured 1.16 of kurtosis against 1.08)
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if (k.mo[q])
+          store2(k.mo[q] + ib * k.nc + c, mom_plane(q, mv.x, x2 / n, x3 / n, x4 / n),
+                 mom_plane(q, mv.y, y2 / n, y3 / n, y4 / n));
     } else {
-      o[0] = k0;
-      o[1] = k1;
+      const double k0 = mom_ratio<ORD>(x2 / n, x4 / n);
+      const double k1 = mom_ratio<ORD>(y2 / n, y4 / n);
+      store2(k.out + ib * k.nc + c, k0, k1);
     }
   }
 }
@@ -942,7 +1056,9 @@ __global__ __launch_bounds__(kB) void k_kurt_final_t(const KurtArgs k, const Tre
   for (int64_t e = (int64_t)blockIdx.x * kB + threadIdx.x; e < n;
        e += (int64_t)gridDim.x * kB) {
     const Node a = fold_nodes<Q, FIRST, MOM>(k, io, n, e, 0);
-    if (MOM)
+    if constexpr (MOM && ORD == kOrdAll)
+      put_moved(k.mo, e, k.nt, a.S, a.m, a.a2, a.a3, a.a4, a.hi, a.lo);
+    else if (MOM)
       k.out[e] = ORD == 4 ? kurt_ratio(k.nt, a.S, a.m, a.a2, a.a3, a.a4, a.hi, a.lo)
                           : skew_ratio(k.nt, a.S, a.m, a.a2, a.a3, a.hi, a.lo);
     else
@@ -985,7 +1101,9 @@ __global__ __launch_bounds__(kB) void k_kurt_final_w(const KurtArgs k, const Tre
       }
     }
     if (lane == 0) {
-      if (MOM)
+      if constexpr (MOM && ORD == kOrdAll)
+        put_moved(k.mo, e, k.nt, a.S, a.m, a.a2, a.a3, a.a4, a.hi, a.lo);
+      else if (MOM)
         k.out[e] = ORD == 4 ? kurt_ratio(k.nt, a.S, a.m, a.a2, a.a3, a.a4, a.hi, a.lo)
                             : skew_ratio(k.nt, a.S, a.m, a.a2, a.a3, a.hi, a.lo);
       else
@@ -1019,7 +1137,9 @@ void k_kurt_pass(const KurtArgs k) {
   const bool valid = col < k.nc;
   const int64_t r0 = chunk * k.rows_per_chunk, r1 = min(k.nt, r0 + k.rows_per_chunk);
   const int64_t e = ib * k.nc + col;
-  double a2 = 0.0, a4 = 0.0;
+  constexpr bool ALL = ORD == kOrdAll;  // both top moments: NP = 3 partials per chunk
+  constexpr int NP = ALL ? 3 : 2;
+  double a2 = 0.0, a3 = 0.0, a4 = 0.0;
   if (valid) {
     const float *p = k.in[bank] + k.in_off + i * k.in_ld_i + (r0 + tsi) * k.in_ld_t + col * k.in_cs;
     const float m = k.mean[e];
@@ -1036,29 +1156,37 @@ void k_kurt_pass(const KurtArgs k) {
         const float z = v[u] - m;
         const float z2 = z * z;
         a2 += (double)z2;
-        a4 += (double)top_term<ORD>(z2, z);
+        if constexpr (ALL) a3 += (double)top_term<3>(z2, z);
+        a4 += (double)top_term<ALL ? 4 : ORD>(z2, z);
       }
     }
   }
   if (ts > 1) {
-    __shared__ double red[4][2][64];
+    __shared__ double red[4][NP][64];
     red[wave][0][lane] = a2;
     red[wave][1][lane] = a4;
+    if constexpr (ALL) red[wave][2][lane] = a3;
     __syncthreads();
     if (tsi == 0)
       for (int q = 1; q < ts; ++q) {
         a2 += red[wave + q][0][lane];
         a4 += red[wave + q][1][lane];
+        if constexpr (ALL) a3 += red[wave + q][2][lane];
       }
   }
   if (tsi == 0 && valid) {
     const int64_t n = k.nrow * k.nc;
     if (k.nchunk == 1) {
-      const double cm2 = a2 / (double)k.nt, cm4 = a4 / (double)k.nt;
-      k.out[e] = mom_ratio<ORD>(cm2, cm4);
+      if constexpr (ALL) {
+        put_all(k.mo, e, k.mean[e], (double)k.nt, a2, a3, a4);
+      } else {
+        const double cm2 = a2 / (double)k.nt, cm4 = a4 / (double)k.nt;
+        k.out[e] = mom_ratio<ORD>(cm2, cm4);
+      }
     } else {
-      k.ws_mom[(chunk * 2) * n + e] = a2;
-      k.ws_mom[(chunk * 2 + 1) * n + e] = a4;
+      k.ws_mom[(chunk * NP) * n + e] = a2;
+      k.ws_mom[(chunk * NP + 1) * n + e] = a4;
+      if constexpr (ALL) k.ws_mom[(chunk * NP + 2) * n + e] = a3;
     }
   }
 }
@@ -1069,13 +1197,20 @@ __global__ __launch_bounds__(kB) void k_kurt_fold(const KurtArgs k) {
   const int64_t n = k.nrow * k.nc;
   for (int64_t e = (int64_t)blockIdx.x * kB + threadIdx.x; e < n;
        e += (int64_t)gridDim.x * kB) {
-    double a = 0.0, c = 0.0;
+    constexpr bool ALL = ORD == kOrdAll;
+    constexpr int NP = ALL ? 3 : 2;
+    double a = 0.0, b = 0.0, c = 0.0;
     for (int ch = 0; ch < k.nchunk; ++ch) {
-      a += k.ws_mom[(ch * 2) * n + e];
-      c += k.ws_mom[(ch * 2 + 1) * n + e];
+      a += k.ws_mom[(ch * NP) * n + e];
+      c += k.ws_mom[(ch * NP + 1) * n + e];
+      if constexpr (ALL) b += k.ws_mom[(ch * NP + 2) * n + e];
     }
-    const double cm2 = a / (double)k.nt, cm4 = c / (double)k.nt;
-    k.out[e] = mom_ratio<ORD>(cm2, cm4);
+    if constexpr (ALL) {
+      put_all(k.mo, e, k.mean[e], (double)k.nt, a, b, c);
+    } else {
+      const double cm2 = a / (double)k.nt, cm4 = c / (double)k.nt;
+      k.out[e] = mom_ratio<ORD>(cm2, cm4);
+    }
   }
 }
 
@@ -1123,7 +1258,9 @@ KLayout layout(const KurtArgs &k) {
     L.a_pf = take(ns * n * sizeof(float));
     L.b_pf = take(nb * n * sizeof(float));
     L.mean = take(n * sizeof(float));
-    L.mom = k.nchunk > 1 ? take(2 * (size_t)k.nchunk * n * sizeof(double)) : off;
+    // the z pass' partial sums per chunk: cm2 and the top moment, or all three
+    const size_t np = k.order == kOrdAll ? 3 : 2;
+    L.mom = k.nchunk > 1 ? take(np * (size_t)k.nchunk * n * sizeof(double)) : off;
   }
   L.total = off;
   return L;
@@ -1207,6 +1344,7 @@ hipError_t launch_tree(const KurtArgs &k, char *ws, const KLayout &L, hipStream_
   }
   if constexpr (MOM) {
     if (k.order == 3) return launch_final<true, 3>(k, io, first, s);
+    if (k.order == kOrdAll) return launch_final<true, kOrdAll>(k, io, first, s);
   }
   return launch_final<MOM, 4>(k, io, first, s);
 }
@@ -1239,8 +1377,9 @@ void plan_kurtosis(KurtArgs &k, int num_cus) {
   if (narrow > 0 && kLeafW > 1 && k.nrow * k.nslot * cdivk(k.nc / kLeafW, 64) < num_cus * narrow)
     k.leafw = 1;
   k.leaftile = 0;  // lane groups per channel of k_kurt_tile; 0 = streamed leaves
-  // (skewness plans as if kurt_leaf_tile = 0: k_kurt_tile has no order-3 form)
-  if (opt(OPT_KURT_LEAF_TILE) == 1 && k.leafw == 1 && k.order != 3) {
+  // (skewness and moments plan as if kurt_leaf_tile = 0: k_kurt_tile has the
+  // order-4 form only)
+  if (opt(OPT_KURT_LEAF_TILE) == 1 && k.leafw == 1 && k.order == 4) {
     const int64_t units = k.nrow * (k.nt <= 1024 ? 1 : k.nslot);  // leaves x rows
     if (units * cdivk(k.nc, 32) <= num_cus)
       k.leaftile = 2;
@@ -1270,6 +1409,19 @@ size_t kurtosis_ws_bytes(const KurtArgs &k) { return layout(k).total; }
   do {                                                                        \
     if (k.order == 3)                                                         \
       hipLaunchKernelGGL((NAME<__VA_ARGS__, 3>), grid, blk, shm, s, k);       \
+    else if (k.order == kOrdAll)                                              \
+      hipLaunchKernelGGL((NAME<__VA_ARGS__, kOrdAll>), grid, blk, shm, s, k); \
+    else                                                                      \
+      hipLaunchKernelGGL((NAME<__VA_ARGS__, 4>), grid, blk, shm, s, k);       \
+  } while (0)
+// The exact-count forms of 32 spectra have no kOrdAll instantiation: with a
+// third Float64 sum per channel they need 256 VGPRs + 27 AGPRs (one wave per
+// SIMD, under the 2-workgroup cap order 4 just meets at 208); order kOrdAll
+// takes the counted form there (158 VGPRs).
+#define BLDP_KLAUNCH34(grid, blk, shm, NAME, ...)                              \
+  do {                                                                        \
+    if (k.order == 3)                                                         \
+      hipLaunchKernelGGL((NAME<__VA_ARGS__, 3>), grid, blk, shm, s, k);       \
     else                                                                      \
       hipLaunchKernelGGL((NAME<__VA_ARGS__, 4>), grid, blk, shm, s, k);       \
   } while (0)
@@ -1281,7 +1433,12 @@ hipError_t launch_kurtosis(KurtArgs &k, char *ws, hipStream_t s) {
   const int p = path_of(k);
   if (k.nt == 0) {  // mean of nothing: StatsBase gives 0/0 - 3 = NaN
     const unsigned g = (unsigned)std::min<int64_t>(cdivk(n, kB), 16384);
-    hipLaunchKernelGGL(k_fill_nan, dim3(g), block, 0, s, k.out, n);
+    if (k.order == kOrdAll) {
+      for (int q = 0; q < 4; ++q)
+        if (k.mo[q]) hipLaunchKernelGGL(k_fill_nan, dim3(g), block, 0, s, k.mo[q], n);
+    } else {
+      hipLaunchKernelGGL(k_fill_nan, dim3(g), block, 0, s, k.out, n);
+    }
     return hipGetLastError();
   }
   const int64_t ncols = k.nc / 4;
@@ -1291,8 +1448,8 @@ hipError_t launch_kurtosis(KurtArgs &k, char *ws, hipStream_t s) {
     const unsigned shm = k.nt >= kKurtRegsCapLo && k.nt <= kKurtRegsCapHi ? kKurtRegsShm : 0;
     if (exact && k.nt == 16)
       BLDP_KLAUNCH(g1, block, shm, k_kurt_regs, 16, true);
-    else if (exact && k.nt == 32)
-      BLDP_KLAUNCH(g1, block, shm, k_kurt_regs, 32, true);
+    else if (exact && k.nt == 32 && k.order != kOrdAll)
+      BLDP_KLAUNCH34(g1, block, shm, k_kurt_regs, 32, true);
     else if (k.nt <= 16)
       BLDP_KLAUNCH(g1, block, shm, k_kurt_regs, 16, false);
     else
@@ -1382,12 +1539,16 @@ hipError_t launch_kurtosis(KurtArgs &k, char *ws, hipStream_t s) {
   const dim3 grid((unsigned)(cdivk(cdivk(k.nc, 64), 4 / k.ts) * k.nrow * k.nchunk));
   if (k.order == 3)
     hipLaunchKernelGGL(k_kurt_pass<3>, grid, block, 0, s, k);
+  else if (k.order == kOrdAll)
+    hipLaunchKernelGGL(k_kurt_pass<kOrdAll>, grid, block, 0, s, k);
   else
     hipLaunchKernelGGL(k_kurt_pass<4>, grid, block, 0, s, k);
   if (k.nchunk > 1) {
     const unsigned fg = (unsigned)std::min<int64_t>(cdivk(n, kB), 16384);
     if (k.order == 3)
       hipLaunchKernelGGL(k_kurt_fold<3>, dim3(fg), block, 0, s, k);
+    else if (k.order == kOrdAll)
+      hipLaunchKernelGGL(k_kurt_fold<kOrdAll>, dim3(fg), block, 0, s, k);
     else
       hipLaunchKernelGGL(k_kurt_fold<4>, dim3(fg), block, 0, s, k);
   }
@@ -1441,6 +1602,26 @@ __device__ __forceinline__ void store_kurt(double *o, const double (&r)[W]) {
 // (the 0001 product: 128 columns) still fill their workgroups; when the
 // columns of a block are whole waves (nc % 256 == 0) a wave's 256 results are
 // contiguous and go through LDS to 1 KiB stores as in k_kurt_regs.
+// blk_store writes one plane's four results of a lane at o.
+__device__ __forceinline__ void blk_store(double *o, int64_t ncols, const double (&r)[4]) {
+  const int lane = threadIdx.x & 63;
+  // (ncols % 64 == 0: a wave lies in one block, per_row is whole waves, and
+  // o - 4*lane is the first of the wave's 256 outputs)
+  if (ncols % 64 == 0 && (reinterpret_cast<uintptr_t>(o - 4 * lane) & 15) == 0) {
+    __shared__ d2v st[4][128];
+    const int wave = threadIdx.x >> 6;
+    st[wave][2 * lane] = d2v{r[0], r[1]};
+    st[wave][2 * lane + 1] = d2v{r[2], r[3]};
+    __builtin_amdgcn_wave_barrier();
+    const d2v a0 = st[wave][lane], a1 = st[wave][64 + lane];
+    __builtin_amdgcn_wave_barrier();  // (read before a next plane overwrites)
+    d2v *ow = reinterpret_cast<d2v *>(o - 4 * lane);
+    __builtin_nontemporal_store(a0, ow + lane);
+    __builtin_nontemporal_store(a1, ow + 64 + lane);
+  } else {
+    store_kurt<4>(o, r);
+  }
+}
 template <int NTMAX, bool EXACT, int ORD>
 __global__ __launch_bounds__(kB) void k_kurtb_regs(const KurtBlkArgs k) {
   const int64_t ncols = k.nc / 4;
@@ -1469,6 +1650,7 @@ __global__ __launch_bounds__(kB) void k_kurtb_regs(const KurtBlkArgs k) {
     }
   const float m[4] = {sa.x / (float)nt, sa.y / (float)nt, sb.x / (float)nt, sb.y / (float)nt};
   double c2[4] = {0, 0, 0, 0}, c4[4] = {0, 0, 0, 0};
+  double c3[ORD == kOrdAll ? 4 : 1] = {};  // (order kOrdAll keeps both top moments)
 #pragma unroll
   for (int t = 0; t < NTMAX; ++t)
     if (EXACT || t < nt) {
@@ -1478,31 +1660,34 @@ __global__ __launch_bounds__(kB) void k_kurtb_regs(const KurtBlkArgs k) {
         const float z = x[w] - m[w];  // StatsBase: z, z2 in Float32; Float64 moments
         const float z2 = z * z;
         c2[w] += (double)z2;
-        c4[w] += (double)top_term<ORD>(z2, z);
+        if constexpr (ORD == kOrdAll) {
+          c3[w] += (double)top_term<3>(z2, z);
+          c4[w] += (double)top_term<4>(z2, z);
+        } else {
+          c4[w] += (double)top_term<ORD>(z2, z);
+        }
       }
     }
-  double r[4];
+  const int64_t oe = bank * k.out_bank + i * k.out_ld_i + b * k.out_ld_b + 4 * col;
+  if constexpr (ORD == kOrdAll) {
+    // plane after plane, as k_kurt_regs
 #pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    const double cm2 = c2[w] / (double)nt, cm4 = c4[w] / (double)nt;
-    r[w] = mom_ratio<ORD>(cm2, cm4);
-  }
-  double *o = k.out + bank * k.out_bank + i * k.out_ld_i + b * k.out_ld_b + 4 * col;
-  const int lane = threadIdx.x & 63;
-  // (ncols % 64 == 0: a wave lies in one block, per_row is whole waves, and
-  // o - 4*lane is the first of the wave's 256 outputs)
-  if (ncols % 64 == 0 && (reinterpret_cast<uintptr_t>(o - 4 * lane) & 15) == 0) {
-    __shared__ d2v st[4][128];
-    const int wave = threadIdx.x >> 6;
-    st[wave][2 * lane] = d2v{r[0], r[1]};
-    st[wave][2 * lane + 1] = d2v{r[2], r[3]};
-    __builtin_amdgcn_wave_barrier();
-    const d2v a0 = st[wave][lane], a1 = st[wave][64 + lane];
-    d2v *ow = reinterpret_cast<d2v *>(o - 4 * lane);
-    __builtin_nontemporal_store(a0, ow + lane);
-    __builtin_nontemporal_store(a1, ow + 64 + lane);
+    for (int q = 0; q < 4; ++q)
+      if (k.mo[q]) {
+        double r[4];
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+          r[w] = mom_plane(q, m[w], c2[w] / (double)nt, c3[w] / (double)nt, c4[w] / (double)nt);
+        blk_store(k.mo[q] + oe, ncols, r);
+      }
   } else {
-    store_kurt<4>(o, r);
+    double r[4];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const double cm2 = c2[w] / (double)nt, cm4 = c4[w] / (double)nt;
+      r[w] = mom_ratio<ORD>(cm2, cm4);
+    }
+    blk_store(k.out + oe, ncols, r);
   }
 }
 
@@ -1564,7 +1749,7 @@ __global__ __launch_bounds__(kB) void k_kurtb_stream(const KurtBlkArgs k) {
   // power sums about the first spectrum -> central moments about the block's
   // own mean (leaf_store's step) -> the recipe's ratio about its Float32 m
   const double cnt = (double)len;
-  double r[W];
+  double r[ORD == kOrdAll ? 4 : 1][W];  // (order kOrdAll: a row per plane)
 #pragma unroll
   for (int w = 0; w < W; ++w) {
     const double dl = A.a1[w] / cnt, dl2 = dl * dl;
@@ -1572,10 +1757,26 @@ __global__ __launch_bounds__(kB) void k_kurtb_stream(const KurtBlkArgs k) {
     const double m2 = A.a2[w] - A.a1[w] * dl;
     const double m3 = A.a3[w] - 3.0 * dl * A.a2[w] + 2.0 * cnt * dl2 * dl;
     const double m4 = A.a4[w] - 4.0 * dl * A.a3[w] + 6.0 * dl2 * A.a2[w] - 3.0 * cnt * dl2 * dl2;
-    r[w] = ORD == 4 ? kurt_ratio(len, A.s[w], ma, m2, m3, m4, A.hi[w], A.lo[w])
-                    : skew_ratio(len, A.s[w], ma, m2, m3, A.hi[w], A.lo[w]);
+    if constexpr (ORD == kOrdAll) {
+      float m;
+      r[MO_SKEW][w] = skew_ratio(len, A.s[w], ma, m2, m3, A.hi[w], A.lo[w], &r[MO_VAR][w], &m);
+      r[MO_MEAN][w] = (double)m;
+      r[MO_VAR][w] = var_plane(r[MO_VAR][w], m, A.hi[w], A.lo[w]);
+      r[MO_KURT][w] =
+          k.mo[MO_KURT] ? kurt_ratio(len, A.s[w], ma, m2, m3, m4, A.hi[w], A.lo[w]) : 0.0;
+    } else {
+      r[0][w] = ORD == 4 ? kurt_ratio(len, A.s[w], ma, m2, m3, m4, A.hi[w], A.lo[w])
+                         : skew_ratio(len, A.s[w], ma, m2, m3, A.hi[w], A.lo[w]);
+    }
   }
-  store_kurt<W>(k.out + bank * k.out_bank + i * k.out_ld_i + b * k.out_ld_b + W * col, r);
+  const int64_t oe = bank * k.out_bank + i * k.out_ld_i + b * k.out_ld_b + W * col;
+  if constexpr (ORD == kOrdAll) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (k.mo[q]) store_kurt<W>(k.mo[q] + oe, r[q]);
+  } else {
+    store_kurt<W>(k.out + oe, r[0]);
+  }
 }
 
 // Block-by-block form: one block's dense [nbank][ni][nc] results into the
@@ -1619,8 +1820,8 @@ hipError_t launch_kurt_blocks(const KurtBlkArgs &k, hipStream_t s) {
     const bool exact = opt(OPT_KURT_EXACT) != 0;
     if (exact && k.M == 16)
       BLDP_KLAUNCH(g, block, 0, k_kurtb_regs, 16, true);
-    else if (exact && k.M == 32)
-      BLDP_KLAUNCH(g, block, 0, k_kurtb_regs, 32, true);
+    else if (exact && k.M == 32 && k.order != kOrdAll)
+      BLDP_KLAUNCH34(g, block, 0, k_kurtb_regs, 32, true);
     else if (k.M <= 16)
       BLDP_KLAUNCH(g, block, 0, k_kurtb_regs, 16, false);
     else
@@ -1633,6 +1834,7 @@ hipError_t launch_kurt_blocks(const KurtBlkArgs &k, hipStream_t s) {
   return hipGetLastError();
 }
 #undef BLDP_KLAUNCH
+#undef BLDP_KLAUNCH34
 
 hipError_t launch_kurt_scatter(const double *src, int64_t nbank, int64_t ni, int64_t nc,
                                double *out, int64_t out_bank, int64_t out_ld_i, hipStream_t s) {

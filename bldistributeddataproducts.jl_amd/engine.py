@@ -12,6 +12,7 @@ in the HIP kernels of libbldp_hip.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 
 import numpy as np
@@ -26,6 +27,7 @@ __all__ = [
     "despike", "kurtosis", "kurtosis_blocks_plan", "band_kurtosis", "synth", "plan", "reduce_host", "kurtosis_host",
     "tstat", "tstat_plan", "band_tstat", "tstat_host",
     "skewness", "skewness_plan", "band_skewness", "skewness_host",
+    "Moments", "MOMENTS", "moments", "moments_plan", "band_moments", "moments_host",
     "argext", "argext_plan", "band_argext", "argext_host",
     "init", "finalize", "pinned",
 ]
@@ -987,8 +989,8 @@ def _skew_tblock(tblock, nt) -> int:
     return int(tblock)
 
 
-def _need_f32(what, dtype):
-    raise TypeError(f"{what}: element type {dtype} is not supported; skewness takes Float32 "
+def _need_f32(what, dtype, fn="skewness"):
+    raise TypeError(f"{what}: element type {dtype} is not supported; {fn} takes Float32 "
                     "(float32) data only")
 
 
@@ -1085,6 +1087,136 @@ def skewness_host(a: np.ndarray, win=None, device=0, tblock=None) -> np.ndarray:
                                   out.ctypes.data if out.size else None)
     _lib.check(rc, "bldp_skewness_host_f32")
     return out
+
+
+# The planes of a moments call, in the ABI's order.  ``var`` is cm2 / n, the
+# uncorrected variance both StatsBase recipes divide by (not Julia's var).
+MOMENTS = ("mean", "var", "skewness", "kurtosis")
+Moments = collections.namedtuple("Moments", MOMENTS)
+
+
+def _which_planes(which) -> tuple:
+    """The requested planes as four flags in ``MOMENTS`` order."""
+    if isinstance(which, str):
+        which = (which,)
+    which = tuple(which)
+    for w in which:
+        if w not in MOMENTS:
+            raise ValueError(f"moments: unknown plane {w!r}; which takes names from {MOMENTS}")
+    if not which:
+        raise ValueError(f"moments: which is empty; it takes names from {MOMENTS}")
+    return tuple(name in which for name in MOMENTS)
+
+
+def moments(x, win=None, tblock=None, stream=None, which=MOMENTS):
+    """Mean, variance, skewness and kurtosis over time per (channel, IF) from
+    one read of the window (bldp_moments_f32): a ``Moments`` named tuple of
+    (nc, ni) float64 tensors, or with ``tblock=M`` of Julia-order (nc, ni,
+    nt/M) ones, one value per block of M selected spectra (M must divide nt).
+    ``skewness`` and ``kurtosis`` are what ``skewness()`` and ``kurtosis()``
+    return, ``mean`` is Julia's Float32 mean widened, and ``var`` is cm2 / n,
+    the UNCORRECTED variance those two divide by (not Julia's ``var``).  A
+    plane not named in ``which`` is ``None`` and is not computed into memory.
+    Float32 tensors only."""
+    torch = _torch()
+    L = _lib.lib()
+    want = _which_planes(which)
+    if x.dtype != torch.float32:
+        _need_f32("moments", x.dtype, "moments")
+    shape = tuple(x.shape)
+    _check_bounds(win, shape)
+    nc, ni, nt = window_shape(win, shape)
+    M = _skew_tblock(tblock, nt)
+    nb = nt // M if M else 1
+    outs = [torch.empty((nb, ni, nc), dtype=torch.float64, device=x.device).permute(2, 1, 0)
+            if w else None for w in want]
+    ptr, nchan, nif, ntime = _abi_dims(x)
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    rc = L.bldp_moments_f32(ptr, nchan, nif, ntime, wp, M,
+                            *[o.data_ptr() if o is not None and o.numel() else None for o in outs],
+                            nc, nc * ni, _lib.stream_ptr(stream))
+    _lib.check(rc, "bldp_moments_f32")
+    return Moments(*[o if o is None or M else o[:, :, 0] for o in outs])
+
+
+def moments_plan(x, win=None, tblock=None) -> dict:
+    """Plan of ``moments(x, win, tblock)``: the path ("regs", "mid", "leaf",
+    "twopass": the class of the results), fused (1 = one set of launches, 0 =
+    block by block), the block count and the workspace bytes."""
+    L = _lib.lib()
+    shape = tuple(x.shape)
+    _check_bounds(win, shape)
+    M = _skew_tblock(tblock, window_shape(win, shape)[2])
+    ptr, nchan, nif, ntime = _abi_dims(x)
+    info = (ctypes.c_int64 * 4)()
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    _lib.check(L.bldp_moments_plan_f32(ptr, nchan, nif, ntime, wp, M, info),
+               "bldp_moments_plan_f32")
+    return {"path": _lib.KURT_PATHS[info[0]], "fused": int(info[1]), "blocks": int(info[2]),
+            "workspace_bytes": int(info[3])}
+
+
+def band_moments(banks, win=None, tblock=None, stream=None, which=MOMENTS):
+    """The moments of every bank of a band on one GPU in one set of launches
+    (bldp_band_moments_f32): a list of ``Moments`` (views of one buffer per
+    plane), shaped as ``moments`` shapes them."""
+    torch = _torch()
+    L = _lib.lib()
+    want = _which_planes(which)
+    banks = list(banks)
+    if not banks:
+        raise ValueError("no banks")
+    for b in banks:
+        if b.dtype != torch.float32:
+            _need_f32("band_moments", b.dtype, "moments")
+    shape = tuple(banks[0].shape)
+    _check_bounds(win, shape)
+    nc, ni, nt = window_shape(win, shape)
+    M = _skew_tblock(tblock, nt)
+    nb = nt // M if M else 1
+    geo = _abi_dims(banks[0])[1:]
+    for b in banks[1:]:
+        if tuple(b.shape) != shape or _abi_dims(b)[1:] != geo:
+            raise ValueError("all banks of a band must have the same shape and layout")
+    ptrs = (ctypes.c_void_p * len(banks))(*[b.data_ptr() for b in banks])
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    bufs = [torch.empty((len(banks), nb, ni, nc), dtype=torch.float64, device=banks[0].device)
+            if w else None for w in want]
+    rc = L.bldp_band_moments_f32(len(banks), ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp, M,
+                                 *[b.data_ptr() if b is not None and b.numel() else None
+                                   for b in bufs], _lib.stream_ptr(stream))
+    _lib.check(rc, "bldp_band_moments_f32")
+
+    def view(buf, k):
+        if buf is None:
+            return None
+        return buf[k].permute(2, 1, 0) if M else buf[k, 0].t()
+    return [Moments(*[view(buf, k) for buf in bufs]) for k in range(len(banks))]
+
+
+def moments_host(a: np.ndarray, win=None, device=0, tblock=None, which=MOMENTS):
+    """Host array in, a ``Moments`` of (nc, ni) float64 host arrays out
+    (bldp_moments_host_f32), (nc, ni, nt/tblock) with ``tblock``; the window is
+    staged on the device once.  Float32 arrays only."""
+    L = _lib.lib()
+    want = _which_planes(which)
+    a = np.asarray(a)
+    if a.dtype != np.float32:
+        _need_f32("moments_host", a.dtype, "moments")
+    if not a.flags.f_contiguous or a.ndim != 3:
+        raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
+    _check_bounds(win, a.shape)
+    nc, ni, nt = window_shape(win, a.shape)
+    M = _skew_tblock(tblock, nt)
+    outs = [np.empty((nc, ni, nt // M) if M else (nc, ni), dtype=np.float64, order="F")
+            if w else None for w in want]
+    keep, wp = _lib.win_arg(_full_win(win, a.shape))
+    rc = L.bldp_moments_host_f32(int(device), a.ctypes.data if a.size else None, a.shape[0],
+                                 a.shape[1], a.shape[2], wp, M,
+                                 *[o.ctypes.data if o is not None and o.size else None
+                                   for o in outs])
+    _lib.check(rc, "bldp_moments_host_f32")
+    return Moments(*outs)
 
 
 def synth(nchan, nif, ntime, nfpc=1024, seed=0, kind=0, device=None, stream=None, out=None):

@@ -18,7 +18,7 @@ from . import _lib, readers, worker as W
 from .idxs import COLON
 
 __all__ = ["datahosts", "setupworkers", "getinventories", "getheaders", "getdata",
-           "getkurtosis", "getskewness", "getband", "bandaxis", "fqav"]
+           "getkurtosis", "getskewness", "getmoments", "getband", "bandaxis", "fqav"]
 
 fqav = W.fqav  # `using .WorkerFunctions` re-exports fqav (src/gbt.jl:6)
 
@@ -99,6 +99,16 @@ def getskewness(workers, fnames, idxs=(COLON, COLON, COLON), tblock=None):
     with ``tblock`` (WorkerFunctions.getskewness)."""
     return _fanout(workers, fnames,
                    lambda w, f: W.getskewness(f, idxs, device=int(w), tblock=tblock))
+
+
+def getmoments(workers, fnames, idxs=(COLON, COLON, COLON), tblock=None,
+               which=("mean", "var", "skewness", "kurtosis")):
+    """getkurtosis' fan-out (src/gbt.jl:81-88) with all four moments from one
+    read of every file: per-bank ``Moments`` named tuples of (nc, ni) Float64
+    arrays, or (nc, ni, nt/tblock) with ``tblock`` (WorkerFunctions.getmoments;
+    ``var`` is the uncorrected cm2 / n)."""
+    return _fanout(workers, fnames,
+                   lambda w, f: W.getmoments(f, idxs, device=int(w), tblock=tblock, which=which))
 
 
 def _chan_window(idxs, nchans):

@@ -12,7 +12,7 @@ module BLDPHip
 using Statistics: mean, median, var, std
 
 export gpu_init, gpu_finalize, gpu_pin, gpu_unpin, gpu_fqav, gpu_reduce, gpu_kurtosis, gpu_band,
-       gpu_tstat, gpu_argext, gpu_skewness, gpu_comm_id, gpu_comm_init, gpu_comm_destroy, gpu_band_gather
+       gpu_tstat, gpu_argext, gpu_skewness, gpu_moments, gpu_comm_id, gpu_comm_init, gpu_comm_destroy, gpu_band_gather
 
 const libbldp = get(ENV, "BLDP_LIB", joinpath(@__DIR__, "..", "libbldp_hip.so"))
 
@@ -221,6 +221,39 @@ function gpu_skewness(A::Array{Float32,3}; idxs::Tuple=(:, :, :), dev::Integer=0
         (Cint, Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Int64, Ptr{Float64}),
         dev, A, size(A, 1), size(A, 2), size(A, 3), win, tblock, out))
     out
+end
+
+"""
+    gpu_moments(A::Array{Float32,3}; idxs=(:,:,:), dev=0, tblock=0)
+
+Mean, variance, skewness and kurtosis of every (channel, IF) row over time from
+one staging of the window on GPU `dev` (bldp_moments_host_f32): a NamedTuple
+`(mean, var, skewness, kurtosis)`.  `skewness` and `kurtosis` are what
+`gpu_skewness` and `gpu_kurtosis` return, `mean` is `Float64(mean(v))` of the
+Float32 row, and `var` is `cm2 / n`, the UNCORRECTED variance both StatsBase
+recipes divide by (`var(v; corrected=false)` in their arithmetic, not `var(v)`).
+`tblock = 0`: the whole window, four `Matrix{Float64}`; `tblock = M`: four
+`Array{Float64,3}` (nc, ni, nt / M), one value per block of M selected spectra
+(M must divide them: DimensionMismatch).  Float32 only."""
+function gpu_moments(A::Array{Float32,3}; idxs::Tuple=(:, :, :), dev::Integer=0,
+                     tblock::Integer=0)
+    win = window(idxs, size(A))
+    shp = zeros(Int64, 3)
+    if tblock > 0
+        GC.@preserve win check(ccall((:bldp_kurtosis_blocks_shape, libbldp), Cint,
+            (Int64, Int64, Int64, Ptr{Int64}, Int64, Ptr{Int64}),
+            size(A, 1), size(A, 2), size(A, 3), win, tblock, shp))
+    else
+        GC.@preserve win check(ccall((:bldp_reduce_shape, libbldp), Cint,
+            (Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Ptr{Int64}),
+            size(A, 1), size(A, 2), size(A, 3), win, 1, 1, shp))
+    end
+    plane() = tblock > 0 ? Array{Float64,3}(undef, shp...) : Matrix{Float64}(undef, shp[1], shp[2])
+    m, v, s, k = plane(), plane(), plane(), plane()
+    GC.@preserve A win m v s k check(ccall((:bldp_moments_host_f32, libbldp), Cint,
+        (Cint, Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        dev, A, size(A, 1), size(A, 2), size(A, 3), win, tblock, m, v, s, k))
+    (mean=m, var=v, skewness=s, kurtosis=k)
 end
 
 """

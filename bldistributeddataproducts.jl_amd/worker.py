@@ -43,7 +43,7 @@ from . import _lib, engine, readers
 from .idxs import COLON, JRange, sanitizeidxs, to_window  # noqa: F401  (re-exports)
 
 __all__ = [
-    "fqav", "FRange", "sanitizeidxs", "getdata", "getfbdata", "getfbh5data", "getkurtosis", "getskewness",
+    "fqav", "FRange", "sanitizeidxs", "getdata", "getfbdata", "getfbh5data", "getkurtosis", "getskewness", "getmoments",
     "getinventory", "getfbheader", "getfbh5header", "getheader", "findmax", "findmin",
 ]
 
@@ -728,6 +728,45 @@ def getskewness(fname, idxs=(COLON, COLON, COLON), device=0, tblock=None):
                         "Float32 (float32) data only")
     return engine.skewness_host(np.asfortranarray(a), to_window(idxs, a.shape), device=device,
                                 tblock=tblock)
+
+
+def getmoments(fname, idxs=(COLON, COLON, COLON), device=0, tblock=None, which=engine.MOMENTS):
+    """Mean, variance, skewness and kurtosis of every (channel, IF) row over
+    time from ONE read of the data: an ``engine.Moments`` named tuple of
+    Float64 (nc, ni) arrays, or (nc, ni, nt/M) with ``tblock=M`` (M must divide
+    nt: DimensionMismatch).  ``skewness`` and ``kurtosis`` are what getskewness
+    and getkurtosis give, ``mean`` is Julia's Float32 mean widened and ``var``
+    is cm2 / n, the UNCORRECTED variance those two divide by (not Julia's
+    ``var``, which divides by n - 1).  A plane not named in ``which`` is
+    ``None``.  Files reach the GPU as getdata reads them (window_on_device),
+    once.  Float32 data only: any other element type (host array, device
+    tensor, 8/16-bit SIGPROC file) is a TypeError."""
+    idxs = sanitizeidxs(idxs)
+    engine._which_planes(which)  # (the ValueError before any file is touched)
+    if _is_tensor(fname):
+        return engine.moments(fname, to_window(idxs, fname.shape), tblock=tblock, which=which)
+    if isinstance(fname, (str, bytes)) or hasattr(fname, "__fspath__"):
+        got = window_on_device(fname, idxs, device)
+        if got is not None:
+            import torch
+
+            x, rwin = got
+            with torch.cuda.device(x.device):
+                m = engine.moments(x, rwin, tblock=tblock, which=which)
+                return engine.Moments(*[None if t is None else engine.fb_to_numpy(t) for t in m])
+        # not Float32, or an empty window: the host array tells which
+        if readers.ishdf5(fname):
+            a, idxs = readers.fbh5_read(fname, idxs), (COLON, COLON, COLON)
+        else:
+            _, a = readers.fil_mmap(fname)
+    else:
+        a = fname
+    a = np.asarray(a)
+    if a.dtype != np.float32:
+        raise TypeError(f"getmoments: element type {a.dtype} is not supported; moments takes "
+                        "Float32 (float32) data only")
+    return engine.moments_host(np.asfortranarray(a), to_window(idxs, a.shape), device=device,
+                               tblock=tblock, which=which)
 
 
 getinventory = readers.getinventory

@@ -87,8 +87,8 @@ extern "C" {
  *    BLDP_BAND_PEER_STORE (direct xGMI stores are opt-in); plan option
  *    "typed_kurt"; (additive, same version) bldp_op gains BLDP_OP_VAR,
  *    BLDP_OP_STD, BLDP_OP_MEDIAN for the Float32 reduce entry points; the
- *    bldp_kurtosis_blocks_*, bldp_tstat_*, bldp_argext_* and bldp_skewness_*
- *    entry points */
+ *    bldp_kurtosis_blocks_*, bldp_tstat_*, bldp_argext_*, bldp_skewness_* and
+ *    bldp_moments_* entry points */
 #define BLDP_ABI_VERSION 5
 
 #if defined(BLDP_BUILD)
@@ -406,6 +406,54 @@ BLDP_API int bldp_band_skewness_f32(int nbank, const float *const *in, int64_t n
 BLDP_API int bldp_skewness_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
                                     int64_t ntime, const int64_t *win, int64_t tblock,
                                     double *out);
+
+/* Mean, variance, skewness and kurtosis of every (channel, if) row of the
+ * window from one read of it (getmoments): what bldp_kurtosis_f32 and
+ * bldp_skewness_f32 give, with the two numbers both already form, as up to
+ * four Float64 planes.  Over the n selected spectra of a row, or of each block
+ * of tblock spectra:
+ *   m = mean(v) (Float32, Base.sum's pairwise sum / n, the kurtosis' m)
+ *   z = v[i] - m, z2 = z * z (Float32); cm2 += z2; cm3 += z2 * z;
+ *   cm4 += z2 * z2 (Float32 products, Float64 sums, index order)
+ *   mean = Float64(m);  var = cm2 / n;
+ *   skewness = (cm3 / n) / sqrt((cm2 / n)^3);  kurtosis = (cm4 / n) / (cm2 / n)^2 - 3
+ * var is the UNCORRECTED variance cm2 / n that both StatsBase recipes divide
+ * by, not Julia's var (which divides by n - 1).  n = 0 gives NaN in every
+ * plane.  tblock, the shape, the planner, the paths and their classes are
+ * bldp_skewness_f32's; the skewness and kurtosis planes hold the bits
+ * bldp_skewness_f32 and bldp_kurtosis_f32 (bldp_kurtosis_blocks_f32) give for
+ * the same call, except that plans which take bldp_kurtosis_f32 to its
+ * register-tile leaf kernel (plan option "kurt_leaf_tile") compare with that
+ * option at 0.  The four planes share their strides; any of them may be NULL
+ * and is then neither formed in memory nor stored.  Errors: tblock < 0
+ * BLDP_EINVAL, a tblock that does not divide nt BLDP_EDIM, a window outside
+ * the array BLDP_EBOUNDS, and for a non-empty result BLDP_EINVAL for a null
+ * in, for four NULL planes, and for planes that overlap each other or the
+ * input array.  Scratch is leased from the library.  Additive in ABI 5.
+ *
+ * bldp_moments_plan_f32: info = {path, 1 = one launch set / 0 = block by
+ * block, nb, workspace bytes} as bldp_skewness_plan_f32 (the workspace differs
+ * where the two-pass path keeps a third partial sum per chunk and where the
+ * block-by-block form stages four planes); launches nothing, needs no GPU.
+ * bldp_moments_f32: element (c, i, b) at plane[c + i*out_ld_i + b*out_ld_b]
+ * (elements; out_ld_b is not read for tblock = 0).  Asynchronous.
+ * bldp_band_moments_f32: in[] is a HOST array of device pointers; each plane
+ * is dense [nbank][nb][ni][nc], one set of launches for the band.
+ * bldp_moments_host_f32: host in, host (nc, ni, nb) planes out; the window's
+ * rows are staged on device `dev` once.  Synchronous. */
+BLDP_API int bldp_moments_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                                   const int64_t *win, int64_t tblock, int64_t info[4]);
+BLDP_API int bldp_moments_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                              const int64_t *win, int64_t tblock, double *mean, double *var,
+                              double *skew, double *kurt, int64_t out_ld_i, int64_t out_ld_b,
+                              void *stream);
+BLDP_API int bldp_band_moments_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                                   int64_t ntime, const int64_t *win, int64_t tblock,
+                                   double *mean, double *var, double *skew, double *kurt,
+                                   void *stream);
+BLDP_API int bldp_moments_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                   int64_t ntime, const int64_t *win, int64_t tblock,
+                                   double *mean, double *var, double *skew, double *kurt);
 
 /* Statistics over blocks of spectra (getdata(...; tavby, tavfunc)): fqav's rule
  * on the time axis with Julia's Statistics as the function.  The window's
