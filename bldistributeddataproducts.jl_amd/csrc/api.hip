@@ -788,12 +788,9 @@ int bldp_despike_f32(float *data, int64_t nchan, int64_t nif, int64_t ntime, int
 
 // `order`: the moment of the plan, 4 = kurtosis, 3 = skewness (bldp_skewness_*),
 // kOrdAll = every plane of KurtArgs.mo (bldp_moments_*)
-static const char *kurt_what(int order, const char *k4) {
-  return order == 3 ? "skewness" : order == kOrdAll ? "moments" : k4;
-}
 static bool any_plane(double *const *mo) { return mo && (mo[0] || mo[1] || mo[2] || mo[3]); }
 static int kurt_setup(int nbank, const float *const *in, int64_t nchan, int64_t nif,
-                      int64_t ntime, const int64_t *win, KurtArgs *k, int order = 4) {
+                      int64_t ntime, const int64_t *win, KurtArgs *k, int order) {
   if (nbank < 1 || nbank > BLDP_MAX_BANKS)
     return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
   Geo g;
@@ -849,7 +846,7 @@ size_t bldp_kurtosis_workspace_size(int64_t nchan, int64_t nif, int64_t ntime,
                                     const int64_t *win) {
   KurtArgs k;
   const float *none[1] = {nullptr};
-  if (kurt_setup(1, none, nchan, nif, ntime, win, &k)) return 0;
+  if (kurt_setup(1, none, nchan, nif, ntime, win, &k, 4)) return 0;
   // enough for either plan: the path depends on the pointer's alignment
   k.vec = 1;
   const size_t a = kurtosis_ws_bytes(k);
@@ -862,7 +859,7 @@ int bldp_kurtosis_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t 
   if (!info) return fail(BLDP_EINVAL, "null info");
   KurtArgs k;
   const float *ins[1] = {in};
-  int rc = kurt_setup(1, ins, nchan, nif, ntime, win, &k);
+  int rc = kurt_setup(1, ins, nchan, nif, ntime, win, &k, 4);
   if (rc) return rc;
   info[0] = kurtosis_path(k);
   info[1] = k.K;
@@ -875,7 +872,7 @@ int bldp_kurtosis_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime
                       const int64_t *win, double *out, void *workspace, void *stream) {
   KurtArgs k;
   const float *ins[1] = {in};
-  int rc = kurt_setup(1, ins, nchan, nif, ntime, win, &k);
+  int rc = kurt_setup(1, ins, nchan, nif, ntime, win, &k, 4);
   if (rc) return rc;
   return kurt_run(k, out, workspace, stream);
 }
@@ -884,12 +881,36 @@ int bldp_band_kurtosis_f32(int nbank, const float *const *in, int64_t nchan, int
                            int64_t ntime, const int64_t *win, double *out, void *stream) {
   if (!in) return fail(BLDP_EINVAL, "null input pointer array");
   KurtArgs k;
-  int rc = kurt_setup(nbank, in, nchan, nif, ntime, win, &k);
+  int rc = kurt_setup(nbank, in, nchan, nif, ntime, win, &k, 4);
   if (rc) return rc;
   return kurt_run(k, out, nullptr, stream);
 }
 
-// ---- kurtosis over blocks of spectra (tblock) ------------------------------
+// ---- the time-moment family: kurtosis over blocks, skewness, moments ---------
+// One planner and one runner for (order, tblock); tblock = 0 is the whole
+// window (one block of every selected spectrum), tblock >= 1 every block of
+// tblock spectra.  The kernels, paths and workspace are the kurtosis' with
+// KurtArgs.order = 3 (getskewness) or kOrdAll (getmoments: four planes that
+// share their strides, a null plane is skipped).
+struct MomKind {
+  int order;         // 4, 3 or kOrdAll
+  const char *what;  // prefix of the entries' messages
+  bool whole_ok;     // tblock = 0 allowed (bldp_kurtosis_blocks_* take tblock >= 1)
+};
+static const MomKind kKurtBlocks{4, "tblock kurtosis", false};
+static const MomKind kSkewness{3, "skewness", true};
+static const MomKind kMoments{kOrdAll, "moments", true};
+
+// Where a call's results go: element (c, i, b) of bank k at plane[q][k*out_bank
+// + c + i*ld_i + b*ld_b]; orders 3 and 4 use plane[0], kOrdAll the four of
+// KurtArgs.mo.  `dense` (the band entries): [nbank][nb][ni][nc], the strides
+// follow from the window.
+struct MomOut {
+  double *plane[4];
+  bool dense;
+  int64_t ld_i, ld_b;
+};
+
 // The rule tavby follows: tblock must divide the selected spectra.
 static int kblk_count(int64_t nt, int64_t tblock, int64_t *nb) {
   if (tblock < 1) return fail(BLDP_EINVAL, "tblock=%lld must be >= 1", (long long)tblock);
@@ -897,6 +918,29 @@ static int kblk_count(int64_t nt, int64_t tblock, int64_t *nb) {
     return fail(BLDP_EDIM, "DimensionMismatch: tblock=%lld does not divide ntime=%lld",
                 (long long)tblock, (long long)nt);
   *nb = nt / tblock;
+  return BLDP_OK;
+}
+
+static int mom_tblock(const MomKind &c, int64_t tblock) {
+  if (c.whole_ok && tblock < 0)
+    return fail(BLDP_EINVAL, "%s: tblock=%lld must be >= 0", c.what, (long long)tblock);
+  return BLDP_OK;
+}
+
+// The (nc, ni, nb) of a result.
+static int mom_dims(const MomKind &c, int64_t nchan, int64_t nif, int64_t ntime,
+                    const int64_t *win, int64_t tblock, int64_t dims[3]) {
+  Geo g;
+  int rc = resolve_window(nchan, nif, ntime, win, &g);
+  if (rc) return rc;
+  int64_t nb = 1;
+  if (tblock > 0 || !c.whole_ok) {
+    rc = kblk_count(g.nt, tblock, &nb);
+    if (rc) return rc;
+  }
+  dims[0] = g.nc;
+  dims[1] = g.ni;
+  dims[2] = nb;
   return BLDP_OK;
 }
 
@@ -910,289 +954,77 @@ static void kblk_window(int64_t nchan, int64_t nif, int64_t ntime, const int64_t
   bw[7] = M;
 }
 
-// Plan of a blocked kurtosis: *whole is the whole window's KurtArgs (checks,
-// float4 columns), *blk the first block's (the block-by-block form's path and
-// workspace; every block has the same shape).
-struct KblkPlan {
+// Plan of a call: *whole is the whole window's KurtArgs (checks, float4
+// columns), *blk the first block's (the block-by-block form's path and
+// workspace; every block has the same shape; tblock = 0: the whole window).
+struct MomPlan {
   KurtArgs whole, blk;
   int64_t nb;
-  bool fused;
+  bool fused;  // the one-launch kernel over every block
   int path;
-  size_t tmp_off, ws_bytes;  // block-by-block: a block's dense results after its workspace
+  // block by block: a block's dense results after its workspace.  ws_bytes is
+  // what the plan entries report: with tblock the workspace and those results,
+  // without one the workspace alone (a dense result needs no more).
+  size_t tmp_off, ws_bytes;
 };
-static int kblk_plan(int nbank, const float *const *in, int64_t nchan, int64_t nif, int64_t ntime,
-                     const int64_t *win, int64_t tblock, KblkPlan *p, int order = 4) {
-  int rc = kurt_setup(nbank, in, nchan, nif, ntime, win, &p->whole, order);
+static int mom_plan(const MomKind &c, int nbank, const float *const *in, int64_t nchan,
+                    int64_t nif, int64_t ntime, const int64_t *win, int64_t tblock, MomPlan *p) {
+  int rc = kurt_setup(nbank, in, nchan, nif, ntime, win, &p->whole, c.order);
   if (rc) return rc;
-  rc = kblk_count(p->whole.nt, tblock, &p->nb);
-  if (rc) return rc;
-  p->fused = kurt_blocks_fused(p->whole, tblock);
+  p->nb = 1;
+  if (tblock > 0 || !c.whole_ok) {
+    rc = kblk_count(p->whole.nt, tblock, &p->nb);
+    if (rc) return rc;
+  }
+  p->fused = tblock > 0 && kurt_blocks_fused(p->whole, tblock);
   p->tmp_off = p->ws_bytes = 0;
   if (p->fused) {
     p->path = tblock <= 32 ? 0 : 2;  // regs : leaf (KURT_PATHS)
     return BLDP_OK;
   }
-  int64_t bw[9];
-  kblk_window(nchan, nif, ntime, win, tblock, 0, bw);
-  if (p->nb == 0) bw[6] = 0, bw[7] = 0;  // (no block: the empty window's plan)
-  rc = kurt_setup(nbank, in, nchan, nif, ntime, bw, &p->blk, order);
-  if (rc) return rc;
-  p->path = kurtosis_path(p->blk);
-  p->tmp_off = (kurtosis_ws_bytes(p->blk) + 255) & ~(size_t)255;
-  // (order kOrdAll stages up to four planes of a block)
-  p->ws_bytes = p->tmp_off +
-                (order == kOrdAll ? 4 : 1) * (size_t)(p->blk.nrow * p->blk.nc) * sizeof(double);
-  return BLDP_OK;
-}
-
-static int kblk_run(int nbank, const float *const *in, int64_t nchan, int64_t nif, int64_t ntime,
-                    const int64_t *win, int64_t tblock, double *out, int64_t out_bank,
-                    int64_t out_ld_i, int64_t out_ld_b, void *stream, int order = 4,
-                    double *const *mo = nullptr) {
-  // (order kOrdAll: the planes `mo`, each laid out as `out`, which is not read)
-  const char *what = kurt_what(order, "tblock kurtosis");
-  KblkPlan p;
-  int rc = kblk_plan(nbank, in, nchan, nif, ntime, win, tblock, &p, order);
-  if (rc) return rc;
-  const KurtArgs &w = p.whole;
-  if (w.nc * w.ni * p.nb == 0) return BLDP_OK;
-  for (int b = 0; b < nbank; ++b)
-    if (!w.in[b]) return fail(BLDP_EINVAL, "%s: null input pointer (bank %d)", what, b);
-  if (order == kOrdAll ? !any_plane(mo) : !out)
-    return fail(BLDP_EINVAL, "%s: null output pointer", what);
-  if (out_ld_i < w.nc || out_ld_b < (w.ni - 1) * out_ld_i + w.nc)
-    return fail(BLDP_EINVAL,
-                "%s: out strides (%lld, %lld) overlap for a (%lld, %lld, %lld) result", what,
-                (long long)out_ld_i, (long long)out_ld_b, (long long)w.nc, (long long)w.ni,
-                (long long)p.nb);
-  hipStream_t s = (hipStream_t)stream;
-  if (p.fused) {
-    KurtBlkArgs k{};
-    for (int b = 0; b < nbank; ++b) k.in[b] = w.in[b];
-    k.nbank = nbank;
-    k.in_off = w.in_off;
-    k.in_ld_i = w.in_ld_i;
-    k.in_ld_t = w.in_ld_t;
-    k.nc = w.nc;
-    k.ni = w.ni;
-    k.M = tblock;
-    k.nb = p.nb;
-    k.out_bank = out_bank;
-    k.out_ld_i = out_ld_i;
-    k.out_ld_b = out_ld_b;
-    k.out = out;
-    k.order = order;
-    for (int q = 0; q < 4; ++q) k.mo[q] = order == kOrdAll ? mo[q] : nullptr;
-    plan_kurt_blocks(k, num_cus_current());
-    if (kurt_blocks_grid(k) > INT32_MAX)
-      return fail(BLDP_EINVAL, "tblock=%lld kurtosis: %lld blocks are too many for one launch",
-                  (long long)tblock, (long long)p.nb);
-    hipError_t e = launch_kurt_blocks(k, s);
-    if (e != hipSuccess)
-      return fail(BLDP_EHIP, "%s launch: %s", what, hipGetErrorString(e));
-    return BLDP_OK;
-  }
-  // block by block through the whole-window paths: one scratch lease, every
-  // launch on the caller's stream (which orders the reuse of the scratch)
-  ScratchLease lease;
-  rc = scratch_lease(s, p.ws_bytes, &lease);
-  if (rc) return rc;
-  char *ws = static_cast<char *>(lease.ptr);
-  double *tmp = reinterpret_cast<double *>(ws + p.tmp_off);
-  const bool direct = nbank == 1 && out_ld_i == w.nc;  // a block's results are dense in out
-  for (int64_t b = 0; b < p.nb; ++b) {
+  p->blk = p->whole;
+  if (tblock > 0) {
     int64_t bw[9];
-    kblk_window(nchan, nif, ntime, win, tblock, b, bw);
-    KurtArgs k;
-    rc = kurt_setup(nbank, in, nchan, nif, ntime, bw, &k, order);
+    kblk_window(nchan, nif, ntime, win, tblock, 0, bw);
+    if (p->nb == 0) bw[6] = 0, bw[7] = 0;  // (no block: the empty window's plan)
+    rc = kurt_setup(nbank, in, nchan, nif, ntime, bw, &p->blk, c.order);
     if (rc) return rc;
-    if (kurtosis_ws_bytes(k) > p.tmp_off)  // (a plan option changed under the call)
-      return fail(BLDP_EINVAL, "%s: the plan changed during the call", what);
-    const int64_t n = k.nrow * k.nc;
-    if (order == kOrdAll) {
-      for (int q = 0; q < 4; ++q)
-        k.mo[q] = !mo[q] ? nullptr : direct ? mo[q] + b * out_ld_b : tmp + q * n;
-      rc = kurt_run(k, nullptr, ws, stream);
-    } else {
-      rc = kurt_run(k, direct ? out + b * out_ld_b : tmp, ws, stream);
-    }
-    if (rc) return rc;
-    for (int q = 0; !direct && q < (order == kOrdAll ? 4 : 1); ++q) {
-      double *dst = order == kOrdAll ? mo[q] : out;
-      if (!dst) continue;
-      hipError_t e = launch_kurt_scatter(tmp + q * n, nbank, w.ni, w.nc, dst + b * out_ld_b,
-                                         out_bank, out_ld_i, s);
-      if (e != hipSuccess)
-        return fail(BLDP_EHIP, "%s launch: %s", what, hipGetErrorString(e));
-    }
   }
+  p->path = kurtosis_path(p->blk);
+  p->ws_bytes = kurtosis_ws_bytes(p->blk);
+  p->tmp_off = (p->ws_bytes + 255) & ~(size_t)255;
+  // (order kOrdAll stages up to four planes of a block)
+  if (tblock > 0)
+    p->ws_bytes = p->tmp_off + (c.order == kOrdAll ? 4 : 1) *
+                                   (size_t)(p->blk.nrow * p->blk.nc) * sizeof(double);
   return BLDP_OK;
 }
 
-int bldp_kurtosis_blocks_shape(int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win,
-                               int64_t tblock, int64_t dims[3]) {
-  if (!dims) return fail(BLDP_EINVAL, "null dims");
-  Geo g;
-  int rc = resolve_window(nchan, nif, ntime, win, &g);
-  if (rc) return rc;
-  int64_t nb;
-  rc = kblk_count(g.nt, tblock, &nb);
-  if (rc) return rc;
-  dims[0] = g.nc;
-  dims[1] = g.ni;
-  dims[2] = nb;
-  return BLDP_OK;
-}
-
-int bldp_kurtosis_blocks_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
-                                  const int64_t *win, int64_t tblock, int64_t info[4]) {
+// The four words of bldp_kurtosis_blocks_plan_f32 / _skewness_ / _moments_.
+static int mom_plan_info(const MomKind &c, const float *in, int64_t nchan, int64_t nif,
+                         int64_t ntime, const int64_t *win, int64_t tblock, int64_t info[4]) {
   if (!info) return fail(BLDP_EINVAL, "null info");
-  KblkPlan p;
+  int rc = mom_tblock(c, tblock);
+  if (rc) return rc;
+  MomPlan p;
   const float *ins[1] = {in};
-  int rc = kblk_plan(1, ins, nchan, nif, ntime, win, tblock, &p);
+  rc = mom_plan(c, 1, ins, nchan, nif, ntime, win, tblock, &p);
   if (rc) return rc;
   info[0] = p.path;
-  info[1] = p.fused ? 1 : 0;
+  info[1] = tblock == 0 || p.fused ? 1 : 0;  // (the window: one set of launches)
   info[2] = p.nb;
   info[3] = (int64_t)p.ws_bytes;
   return BLDP_OK;
 }
 
-int bldp_kurtosis_blocks_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
-                             const int64_t *win, int64_t tblock, double *out, int64_t out_ld_i,
-                             int64_t out_ld_b, void *stream) {
-  const float *ins[1] = {in};
-  return kblk_run(1, ins, nchan, nif, ntime, win, tblock, out, 0, out_ld_i, out_ld_b, stream);
-}
-
-int bldp_band_kurtosis_blocks_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
-                                  int64_t ntime, const int64_t *win, int64_t tblock, double *out,
-                                  void *stream) {
-  if (!in) return fail(BLDP_EINVAL, "tblock kurtosis: null input pointer array");
-  int64_t d[3];
-  int rc = bldp_kurtosis_blocks_shape(nchan, nif, ntime, win, tblock, d);
-  if (rc) return rc;
-  return kblk_run(nbank, in, nchan, nif, ntime, win, tblock, out, d[0] * d[1] * d[2], d[0],
-                  d[0] * d[1], stream);
-}
-
-// ---- skewness (getskewness): the recipe one order down ----------------------
-// One family for the whole window (tblock = 0: the whole-window planner, nb =
-// 1) and for blocks of tblock spectra (the block planner); the kernels, paths
-// and workspace are the kurtosis' with KurtArgs.order = 3.
-static int skew_check(int64_t tblock) {
-  if (tblock < 0) return fail(BLDP_EINVAL, "skewness: tblock=%lld must be >= 0", (long long)tblock);
-  return BLDP_OK;
-}
-
-// Whole window: element (c, i) at out[bank*out_bank + c + i*out_ld_i].
-// (order kOrdAll: the planes `mo`, each laid out as `out`, which is not read)
-static int skew_whole(int nbank, const float *const *in, int64_t nchan, int64_t nif, int64_t ntime,
-                      const int64_t *win, double *out, int64_t out_bank, int64_t out_ld_i,
-                      void *stream, int order = 3, double *const *mo = nullptr) {
-  const char *what = kurt_what(order, "kurtosis");
-  const bool all = order == kOrdAll;
-  KurtArgs k;
-  int rc = kurt_setup(nbank, in, nchan, nif, ntime, win, &k, order);
-  if (rc) return rc;
-  if (k.nc * k.nrow == 0) return BLDP_OK;
-  for (int b = 0; b < nbank; ++b)
-    if (!k.in[b] && k.nt > 0) return fail(BLDP_EINVAL, "%s: null input pointer (bank %d)", what, b);
-  if (all ? !any_plane(mo) : !out) return fail(BLDP_EINVAL, "%s: null output pointer", what);
-  if (out_ld_i < k.nc || (nbank > 1 && out_bank < (k.ni - 1) * out_ld_i + k.nc))
-    return fail(BLDP_EINVAL, "%s: out strides (%lld, %lld) overlap for a (%lld, %lld) result", what,
-                (long long)out_ld_i, (long long)out_bank, (long long)k.nc, (long long)k.ni);
-  const int64_t n = k.nrow * k.nc;
-  if (out_ld_i == k.nc && (nbank == 1 || out_bank == k.nc * k.ni)) {
-    // dense: the kernels write the product
-    for (int q = 0; all && q < 4; ++q) k.mo[q] = mo[q];
-    return kurt_run(k, out, nullptr, stream);
-  }
-  hipStream_t s = (hipStream_t)stream;
-  const size_t tmp_off = (kurtosis_ws_bytes(k) + 255) & ~(size_t)255;
-  ScratchLease lease;  // held until the launches are queued
-  rc = scratch_lease(s, tmp_off + (all ? 4 : 1) * (size_t)n * sizeof(double), &lease);
-  if (rc) return rc;
-  char *ws = static_cast<char *>(lease.ptr);
-  double *tmp = reinterpret_cast<double *>(ws + tmp_off);
-  for (int q = 0; all && q < 4; ++q) k.mo[q] = mo[q] ? tmp + q * n : nullptr;
-  rc = kurt_run(k, tmp, ws, stream);
-  if (rc) return rc;
-  for (int q = 0; q < (all ? 4 : 1); ++q) {
-    double *dst = all ? mo[q] : out;
-    if (!dst) continue;
-    hipError_t e = launch_kurt_scatter(tmp + q * n, nbank, k.ni, k.nc, dst, out_bank, out_ld_i, s);
-    if (e != hipSuccess) return fail(BLDP_EHIP, "%s launch: %s", what, hipGetErrorString(e));
-  }
-  return BLDP_OK;
-}
-
-int bldp_skewness_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
-                           const int64_t *win, int64_t tblock, int64_t info[4]) {
-  if (!info) return fail(BLDP_EINVAL, "null info");
-  int rc = skew_check(tblock);
-  if (rc) return rc;
-  const float *ins[1] = {in};
-  if (tblock == 0) {
-    KurtArgs k;
-    rc = kurt_setup(1, ins, nchan, nif, ntime, win, &k, 3);
-    if (rc) return rc;
-    info[0] = kurtosis_path(k);
-    info[1] = 1;  // one set of launches for the window
-    info[2] = 1;
-    info[3] = (int64_t)kurtosis_ws_bytes(k);
-    return BLDP_OK;
-  }
-  KblkPlan p;
-  rc = kblk_plan(1, ins, nchan, nif, ntime, win, tblock, &p, 3);
-  if (rc) return rc;
-  info[0] = p.path;
-  info[1] = p.fused ? 1 : 0;
-  info[2] = p.nb;
-  info[3] = (int64_t)p.ws_bytes;
-  return BLDP_OK;
-}
-
-int bldp_skewness_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
-                      const int64_t *win, int64_t tblock, double *out, int64_t out_ld_i,
-                      int64_t out_ld_b, void *stream) {
-  int rc = skew_check(tblock);
-  if (rc) return rc;
-  const float *ins[1] = {in};
-  if (tblock == 0) return skew_whole(1, ins, nchan, nif, ntime, win, out, 0, out_ld_i, stream);
-  return kblk_run(1, ins, nchan, nif, ntime, win, tblock, out, 0, out_ld_i, out_ld_b, stream, 3);
-}
-
-int bldp_band_skewness_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
-                           int64_t ntime, const int64_t *win, int64_t tblock, double *out,
-                           void *stream) {
-  int rc = skew_check(tblock);
-  if (rc) return rc;
-  if (!in) return fail(BLDP_EINVAL, "skewness: null input pointer array");
-  if (tblock == 0) {
-    Geo g;
-    rc = resolve_window(nchan, nif, ntime, win, &g);
-    if (rc) return rc;
-    return skew_whole(nbank, in, nchan, nif, ntime, win, out, g.nc * g.ni, g.nc, stream);
-  }
-  int64_t d[3];
-  rc = bldp_kurtosis_blocks_shape(nchan, nif, ntime, win, tblock, d);
-  if (rc) return rc;
-  return kblk_run(nbank, in, nchan, nif, ntime, win, tblock, out, d[0] * d[1] * d[2], d[0],
-                  d[0] * d[1], stream, 3);
-}
-
-// ---- moments (getmoments): mean, var, skewness and kurtosis from one read -----
-// The skewness family with KurtArgs.order = kOrdAll and four planes that share
-// their strides; a null plane is skipped.  The planes may not overlap each
-// other or the input array.
 static bool spans_overlap(const void *a, size_t na, const void *b, size_t nb) {
   const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
   return na > 0 && nb > 0 && x < y + nb && y < x + na;
 }
 
-// Checks of a moments call whose result is not empty: `span` elements from
-// each plane's pointer hold its result, `in_elems` floats each bank's array.
+// Moments only: the planes may not overlap each other or the input array.
+// `span` elements from each plane's pointer hold its result, `in_elems` floats
+// each bank's array.
 static int mom_check(int nbank, const float *const *in, int64_t in_elems, double *const mo[4],
                      int64_t span) {
   if (!any_plane(mo)) return fail(BLDP_EINVAL, "moments: every output plane is null");
@@ -1209,86 +1041,189 @@ static int mom_check(int nbank, const float *const *in, int64_t in_elems, double
   return BLDP_OK;
 }
 
-int bldp_moments_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
-                          const int64_t *win, int64_t tblock, int64_t info[4]) {
-  if (!info) return fail(BLDP_EINVAL, "null info");
-  if (tblock < 0) return fail(BLDP_EINVAL, "moments: tblock=%lld must be >= 0", (long long)tblock);
-  const float *ins[1] = {in};
-  if (tblock == 0) {
-    KurtArgs k;
-    int rc = kurt_setup(1, ins, nchan, nif, ntime, win, &k, kOrdAll);
+// Every device entry of the family: each argument check once, then the run.
+static int mom_run(const MomKind &c, const MomOut &o, int nbank, const float *const *in,
+                   int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win, int64_t tblock,
+                   void *stream) {
+  const bool all = c.order == kOrdAll;
+  const int np = all ? 4 : 1;
+  int rc = mom_tblock(c, tblock);
+  if (rc) return rc;
+  if (!in) return fail(BLDP_EINVAL, "%s: null input pointer array", c.what);
+  if (o.dense && !all) {
+    // (the band kurtosis and skewness answer a bad window or tblock before a
+    // bad nbank, the moments after it)
+    int64_t d[3];
+    rc = mom_dims(c, nchan, nif, ntime, win, tblock, d);
     if (rc) return rc;
-    info[0] = kurtosis_path(k);
-    info[1] = 1;  // one set of launches for the window
-    info[2] = 1;
-    info[3] = (int64_t)kurtosis_ws_bytes(k);
+  }
+  MomPlan p;
+  rc = mom_plan(c, nbank, in, nchan, nif, ntime, win, tblock, &p);
+  if (rc) return rc;
+  const KurtArgs &w = p.whole;
+  if (w.nc * w.ni * p.nb == 0) return BLDP_OK;
+  for (int b = 0; b < nbank; ++b)
+    if (!w.in[b] && w.nt > 0)
+      return fail(BLDP_EINVAL, "%s: null input pointer (bank %d)", c.what, b);
+  if (!all && !o.plane[0]) return fail(BLDP_EINVAL, "%s: null output pointer", c.what);
+  const int64_t out_ld_i = o.dense ? w.nc : o.ld_i;
+  const int64_t out_ld_b = o.dense ? w.nc * w.ni : o.ld_b;
+  const int64_t out_bank = o.dense ? w.nc * w.ni * p.nb : 0;
+  if (out_ld_i < w.nc || (tblock > 0 && out_ld_b < (w.ni - 1) * out_ld_i + w.nc)) {
+    if (tblock == 0 && !all)  // (the whole-window skewness names the bank stride)
+      return fail(BLDP_EINVAL, "%s: out strides (%lld, %lld) overlap for a (%lld, %lld) result",
+                  c.what, (long long)out_ld_i, (long long)out_bank, (long long)w.nc,
+                  (long long)w.ni);
+    return fail(BLDP_EINVAL,
+                "%s: out strides (%lld, %lld) overlap for a (%lld, %lld, %lld) result", c.what,
+                (long long)out_ld_i, (long long)out_ld_b, (long long)w.nc, (long long)w.ni,
+                (long long)p.nb);
+  }
+  if (all) {
+    const int64_t span = (nbank - 1) * out_bank + (tblock > 0 ? (p.nb - 1) * out_ld_b : 0) +
+                         (w.ni - 1) * out_ld_i + w.nc;
+    rc = mom_check(nbank, in, nchan * nif * ntime, o.plane, span);
+    if (rc) return rc;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (p.fused) {
+    KurtBlkArgs k{};
+    for (int b = 0; b < nbank; ++b) k.in[b] = w.in[b];
+    k.nbank = nbank;
+    k.in_off = w.in_off;
+    k.in_ld_i = w.in_ld_i;
+    k.in_ld_t = w.in_ld_t;
+    k.nc = w.nc;
+    k.ni = w.ni;
+    k.M = tblock;
+    k.nb = p.nb;
+    k.out_bank = out_bank;
+    k.out_ld_i = out_ld_i;
+    k.out_ld_b = out_ld_b;
+    k.order = c.order;
+    if (all)
+      for (int q = 0; q < 4; ++q) k.mo[q] = o.plane[q];
+    else
+      k.out = o.plane[0];
+    plan_kurt_blocks(k, num_cus_current());
+    if (kurt_blocks_grid(k) > INT32_MAX)
+      return fail(BLDP_EINVAL, "tblock=%lld kurtosis: %lld blocks are too many for one launch",
+                  (long long)tblock, (long long)p.nb);
+    hipError_t e = launch_kurt_blocks(k, s);
+    if (e != hipSuccess)
+      return fail(BLDP_EHIP, "%s launch: %s", c.what, hipGetErrorString(e));
     return BLDP_OK;
   }
-  KblkPlan p;
-  int rc = kblk_plan(1, ins, nchan, nif, ntime, win, tblock, &p, kOrdAll);
+  // Block by block through the whole-window paths: one scratch lease, every
+  // launch on the caller's stream (which orders the reuse of the scratch).
+  // Where a block's results are dense in the planes the kernels write them;
+  // elsewhere they go to the scratch and are scattered.
+  const bool direct =
+      out_ld_i == w.nc && (nbank == 1 || (tblock == 0 && out_bank == w.nc * w.ni));
+  if (tblock == 0 && direct) {
+    // A dense whole window needs the workspace alone, and kurt_run leases it.
+    // (A lease taken here may be empty, the regs path has no workspace:
+    // kurt_run would then lease the entry this call holds.)
+    KurtArgs k = p.blk;
+    for (int q = 0; all && q < 4; ++q) k.mo[q] = o.plane[q];
+    return kurt_run(k, all ? nullptr : o.plane[0], nullptr, stream);
+  }
+  const int64_t n = p.blk.nrow * p.blk.nc;
+  ScratchLease lease;  // never empty (n > 0); held until the launches are queued
+  rc = scratch_lease(s, p.tmp_off + np * (size_t)n * sizeof(double), &lease);
   if (rc) return rc;
-  info[0] = p.path;
-  info[1] = p.fused ? 1 : 0;
-  info[2] = p.nb;
-  info[3] = (int64_t)p.ws_bytes;
+  char *ws = static_cast<char *>(lease.ptr);
+  double *tmp = reinterpret_cast<double *>(ws + p.tmp_off);
+  for (int64_t b = 0; b < p.nb; ++b) {
+    KurtArgs k = p.blk;
+    if (b > 0) {
+      int64_t bw[9];
+      kblk_window(nchan, nif, ntime, win, tblock, b, bw);
+      rc = kurt_setup(nbank, in, nchan, nif, ntime, bw, &k, c.order);
+      if (rc) return rc;
+      if (kurtosis_ws_bytes(k) > p.tmp_off)  // (a plan option changed under the call)
+        return fail(BLDP_EINVAL, "%s: the plan changed during the call", c.what);
+    }
+    double *dst[4];  // where the kernels write this block's planes
+    for (int q = 0; q < np; ++q)
+      dst[q] = !o.plane[q] ? nullptr : direct ? o.plane[q] + b * out_ld_b : tmp + q * n;
+    for (int q = 0; all && q < 4; ++q) k.mo[q] = dst[q];
+    rc = kurt_run(k, all ? nullptr : dst[0], ws, stream);
+    if (rc) return rc;
+    for (int q = 0; !direct && q < np; ++q) {
+      if (!o.plane[q]) continue;
+      hipError_t e = launch_kurt_scatter(dst[q], nbank, w.ni, w.nc, o.plane[q] + b * out_ld_b,
+                                         out_bank, out_ld_i, s);
+      if (e != hipSuccess)
+        return fail(BLDP_EHIP, "%s launch: %s", c.what, hipGetErrorString(e));
+    }
+  }
   return BLDP_OK;
 }
 
-// Every entry point: the argument checks in the skewness' order, then the run.
-// Element (c, i, b) of bank k at plane[k*out_bank + c + i*out_ld_i + b*out_ld_b].
-static int mom_run(int nbank, const float *const *in, int64_t nchan, int64_t nif, int64_t ntime,
-                   const int64_t *win, int64_t tblock, double *const mo[4], bool dense,
-                   int64_t out_ld_i, int64_t out_ld_b, void *stream) {
-  if (tblock < 0) return fail(BLDP_EINVAL, "moments: tblock=%lld must be >= 0", (long long)tblock);
-  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
-    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
-  Geo g;
-  int rc = resolve_window(nchan, nif, ntime, win, &g);
-  if (rc) return rc;
-  int64_t nb = 1;
-  if (tblock > 0) {
-    rc = kblk_count(g.nt, tblock, &nb);
-    if (rc) return rc;
-  }
-  if (g.nc * g.ni * nb == 0) return BLDP_OK;
-  int64_t out_bank = 0;
-  if (dense) {  // [nbank][nb][ni][nc]
-    out_ld_i = g.nc;
-    out_ld_b = g.nc * g.ni;
-    out_bank = g.nc * g.ni * nb;
-  }
-  for (int b = 0; b < nbank; ++b)
-    if (!in[b] && g.nt > 0) return fail(BLDP_EINVAL, "moments: null input pointer (bank %d)", b);
-  if (out_ld_i < g.nc || (tblock > 0 && out_ld_b < (g.ni - 1) * out_ld_i + g.nc))
-    return fail(BLDP_EINVAL, "moments: out strides (%lld, %lld) overlap for a (%lld, %lld, %lld) "
-                "result", (long long)out_ld_i, (long long)out_ld_b, (long long)g.nc,
-                (long long)g.ni, (long long)nb);
-  const int64_t span = (nbank - 1) * out_bank + (tblock > 0 ? (nb - 1) * out_ld_b : 0) +
-                       (g.ni - 1) * out_ld_i + g.nc;
-  rc = mom_check(nbank, in, nchan * nif * ntime, mo, span);
-  if (rc) return rc;
-  if (tblock == 0)
-    return skew_whole(nbank, in, nchan, nif, ntime, win, nullptr, out_bank, out_ld_i, stream,
-                      kOrdAll, mo);
-  return kblk_run(nbank, in, nchan, nif, ntime, win, tblock, nullptr, out_bank, out_ld_i,
-                  out_ld_b, stream, kOrdAll, mo);
+int bldp_kurtosis_blocks_shape(int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win,
+                               int64_t tblock, int64_t dims[3]) {
+  if (!dims) return fail(BLDP_EINVAL, "null dims");
+  return mom_dims(kKurtBlocks, nchan, nif, ntime, win, tblock, dims);
+}
+
+int bldp_kurtosis_blocks_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                                  const int64_t *win, int64_t tblock, int64_t info[4]) {
+  return mom_plan_info(kKurtBlocks, in, nchan, nif, ntime, win, tblock, info);
+}
+
+int bldp_skewness_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                           const int64_t *win, int64_t tblock, int64_t info[4]) {
+  return mom_plan_info(kSkewness, in, nchan, nif, ntime, win, tblock, info);
+}
+
+int bldp_moments_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                          const int64_t *win, int64_t tblock, int64_t info[4]) {
+  return mom_plan_info(kMoments, in, nchan, nif, ntime, win, tblock, info);
+}
+
+int bldp_kurtosis_blocks_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                             const int64_t *win, int64_t tblock, double *out, int64_t out_ld_i,
+                             int64_t out_ld_b, void *stream) {
+  const float *ins[1] = {in};
+  return mom_run(kKurtBlocks, {{out}, false, out_ld_i, out_ld_b}, 1, ins, nchan, nif, ntime,
+                 win, tblock, stream);
+}
+
+int bldp_band_kurtosis_blocks_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                                  int64_t ntime, const int64_t *win, int64_t tblock, double *out,
+                                  void *stream) {
+  return mom_run(kKurtBlocks, {{out}, true}, nbank, in, nchan, nif, ntime, win, tblock,
+                 stream);
+}
+
+int bldp_skewness_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                      const int64_t *win, int64_t tblock, double *out, int64_t out_ld_i,
+                      int64_t out_ld_b, void *stream) {
+  const float *ins[1] = {in};
+  return mom_run(kSkewness, {{out}, false, out_ld_i, out_ld_b}, 1, ins, nchan, nif, ntime,
+                 win, tblock, stream);
+}
+
+int bldp_band_skewness_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                           int64_t ntime, const int64_t *win, int64_t tblock, double *out,
+                           void *stream) {
+  return mom_run(kSkewness, {{out}, true}, nbank, in, nchan, nif, ntime, win, tblock, stream);
 }
 
 int bldp_moments_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
                      const int64_t *win, int64_t tblock, double *mean, double *var, double *skew,
                      double *kurt, int64_t out_ld_i, int64_t out_ld_b, void *stream) {
   const float *ins[1] = {in};
-  double *const mo[4] = {mean, var, skew, kurt};
-  return mom_run(1, ins, nchan, nif, ntime, win, tblock, mo, false, out_ld_i, out_ld_b, stream);
+  return mom_run(kMoments, {{mean, var, skew, kurt}, false, out_ld_i, out_ld_b}, 1, ins,
+                 nchan, nif, ntime, win, tblock, stream);
 }
 
 int bldp_band_moments_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
                           int64_t ntime, const int64_t *win, int64_t tblock, double *mean,
                           double *var, double *skew, double *kurt, void *stream) {
-  if (tblock < 0) return fail(BLDP_EINVAL, "moments: tblock=%lld must be >= 0", (long long)tblock);
-  if (!in) return fail(BLDP_EINVAL, "moments: null input pointer array");
-  double *const mo[4] = {mean, var, skew, kurt};
-  return mom_run(nbank, in, nchan, nif, ntime, win, tblock, mo, true, 0, 0, stream);
+  return mom_run(kMoments, {{mean, var, skew, kurt}, true}, nbank, in, nchan, nif, ntime, win,
+                 tblock, stream);
 }
 
 // ---- tavfunc: median / var / std over blocks of spectra ---------------------
@@ -1733,7 +1668,7 @@ int bldp_kurtosis_prepare(int dtype, const void *in, int64_t nchan, int64_t nif,
   if (dtype == BLDP_DT_F32) {
     h->kind = bldp_reduce_op::F32_KURT;
     const float *ins[1] = {static_cast<const float *>(in)};
-    rc = kurt_setup(1, ins, nchan, nif, ntime, win, &h->k);
+    rc = kurt_setup(1, ins, nchan, nif, ntime, win, &h->k, 4);
     h->empty = false;
   } else {
     h->kind = bldp_reduce_op::TYPED_KURT;

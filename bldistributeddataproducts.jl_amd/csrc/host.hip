@@ -166,8 +166,40 @@ extern "C" int bldp_reduce_host_f32(int dev, const float *in, int64_t nchan, int
   });
 }
 
-// Stage the window rows ([t][i][span] dense) on the device with the same copy
-// rules as bldp_reduce_host_f32, then run the two-pass kurtosis there.
+// The host entries of the time-moment family (kurtosis, kurtosis over blocks,
+// skewness, moments): stage the window's rows ([t][i][span] dense) on the
+// device once with the same copy rules as bldp_reduce_host_f32, run
+// `run(dbuf, span, dwin, planes, stream)` there and copy `n` doubles of every
+// plane back; a null plane of `out` is neither computed nor copied.
+namespace {
+template <class Run>
+int moments_staged(int dev, const float *in, int64_t nchan, int64_t nif, const int64_t *win,
+                   int64_t nc, int64_t ni, int64_t nt, int64_t n, double *const out[4], Run run) {
+  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
+  int np = 0;
+  for (int q = 0; q < 4; ++q) np += out[q] != nullptr;
+  return with_stager(dev, [&](bldp::Stager *sg) -> int {
+    float *dbuf;
+    double *dout;
+    int r = bldp::stager_buffer(sg, 0, (size_t)std::max<int64_t>(1, h.span * ni * nt) * 4,
+                                (void **)&dbuf);
+    if (!r) r = bldp::stager_buffer(sg, 2, (size_t)(np * n) * sizeof(double), (void **)&dout);
+    if (!r && nt > 0) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
+    if (r) return r;
+    double *d[4];
+    for (int q = 0, j = 0; q < 4; ++q) d[q] = out[q] ? dout + (j++) * n : nullptr;
+    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
+    r = run(dbuf, h.span, dwin, d, sg->st[0]);
+    if (r) return r;  // message already recorded
+    for (int q = 0; q < 4; ++q)
+      if (out[q])
+        HCHK(hipMemcpyAsync(out[q], d[q], (size_t)n * sizeof(double), hipMemcpyDeviceToHost,
+                            sg->st[0]));
+    return BLDP_OK;
+  });
+}
+}  // namespace
+
 extern "C" int bldp_kurtosis_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
                                       int64_t ntime, const int64_t *win, double *out) {
   int64_t sh[3];
@@ -176,26 +208,15 @@ extern "C" int bldp_kurtosis_host_f32(int dev, const float *in, int64_t nchan, i
   const int64_t nc = sh[0], ni = sh[1], nt = sh[2];
   if (nc * ni == 0) return BLDP_OK;
   if (!out || (!in && nt > 0)) return bldp::set_error(BLDP_EINVAL, "null pointer");
-  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
-  return with_stager(dev, [&](bldp::Stager *sg) -> int {
-    float *dbuf;
-    double *dout;
-    int r = bldp::stager_buffer(sg, 0, (size_t)std::max<int64_t>(1, h.span * ni * nt) * 4,
-                                (void **)&dbuf);
-    if (!r) r = bldp::stager_buffer(sg, 2, (size_t)(nc * ni) * sizeof(double), (void **)&dout);
-    if (!r && nt > 0) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
-    if (r) return r;
-    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
-    r = bldp_kurtosis_f32(dbuf, h.span, ni, nt, dwin, dout, nullptr, sg->st[0]);
-    if (r) return r;
-    HCHK(hipMemcpyAsync(out, dout, (size_t)(nc * ni) * sizeof(double), hipMemcpyDeviceToHost,
-                        sg->st[0]));
-    return BLDP_OK;
-  });
+  double *const o[4] = {out};
+  return moments_staged(dev, in, nchan, nif, win, nc, ni, nt, nc * ni, o,
+                        [&](const float *d, int64_t span, const int64_t *dwin, double *const *p,
+                            hipStream_t s) {
+                          return bldp_kurtosis_f32(d, span, ni, nt, dwin, p[0], nullptr, s);
+                        });
 }
 
-// The same staging for the kurtosis over blocks of tblock spectra: the window's
-// rows go to the device once, the (nc, ni, nb) product comes back.
+// tblock >= 1: the (nc, ni, nb) kurtosis of every block of tblock spectra.
 extern "C" int bldp_kurtosis_blocks_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
                                              int64_t ntime, const int64_t *win, int64_t tblock,
                                              double *out) {
@@ -205,25 +226,17 @@ extern "C" int bldp_kurtosis_blocks_host_f32(int dev, const float *in, int64_t n
   const int64_t nc = sh[0], ni = sh[1], nb = sh[2], nt = nb * tblock;
   if (nc * ni * nb == 0) return BLDP_OK;
   if (!out || !in) return bldp::set_error(BLDP_EINVAL, "tblock kurtosis: null pointer");
-  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
-  return with_stager(dev, [&](bldp::Stager *sg) -> int {
-    float *dbuf;
-    double *dout;
-    int r = bldp::stager_buffer(sg, 0, (size_t)(h.span * ni * nt) * 4, (void **)&dbuf);
-    if (!r) r = bldp::stager_buffer(sg, 2, (size_t)(nc * ni * nb) * sizeof(double), (void **)&dout);
-    if (!r) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
-    if (r) return r;
-    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
-    r = bldp_kurtosis_blocks_f32(dbuf, h.span, ni, nt, dwin, tblock, dout, nc, nc * ni, sg->st[0]);
-    if (r) return r;
-    HCHK(hipMemcpyAsync(out, dout, (size_t)(nc * ni * nb) * sizeof(double), hipMemcpyDeviceToHost,
-                        sg->st[0]));
-    return BLDP_OK;
-  });
+  double *const o[4] = {out};
+  return moments_staged(dev, in, nchan, nif, win, nc, ni, nt, nc * ni * nb, o,
+                        [&](const float *d, int64_t span, const int64_t *dwin, double *const *p,
+                            hipStream_t s) {
+                          return bldp_kurtosis_blocks_f32(d, span, ni, nt, dwin, tblock, p[0], nc,
+                                                          nc * ni, s);
+                        });
 }
 
-// The same staging for the skewness: tblock = 0 the whole window ((nc, ni) out),
-// tblock >= 1 every block of tblock spectra ((nc, ni, nb) out).
+// tblock = 0 the whole window ((nc, ni) out), tblock >= 1 every block of tblock
+// spectra ((nc, ni, nb) out).
 extern "C" int bldp_skewness_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
                                       int64_t ntime, const int64_t *win, int64_t tblock,
                                       double *out) {
@@ -236,26 +249,16 @@ extern "C" int bldp_skewness_host_f32(int dev, const float *in, int64_t nchan, i
   const int64_t nc = sh[0], ni = sh[1], nt = sh[2], nb = info[2];
   if (nc * ni * nb == 0) return BLDP_OK;
   if (!out || (!in && nt > 0)) return bldp::set_error(BLDP_EINVAL, "skewness: null pointer");
-  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
-  return with_stager(dev, [&](bldp::Stager *sg) -> int {
-    float *dbuf;
-    double *dout;
-    int r = bldp::stager_buffer(sg, 0, (size_t)std::max<int64_t>(1, h.span * ni * nt) * 4,
-                                (void **)&dbuf);
-    if (!r) r = bldp::stager_buffer(sg, 2, (size_t)(nc * ni * nb) * sizeof(double), (void **)&dout);
-    if (!r && nt > 0) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
-    if (r) return r;
-    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
-    r = bldp_skewness_f32(dbuf, h.span, ni, nt, dwin, tblock, dout, nc, nc * ni, sg->st[0]);
-    if (r) return r;
-    HCHK(hipMemcpyAsync(out, dout, (size_t)(nc * ni * nb) * sizeof(double), hipMemcpyDeviceToHost,
-                        sg->st[0]));
-    return BLDP_OK;
-  });
+  double *const o[4] = {out};
+  return moments_staged(dev, in, nchan, nif, win, nc, ni, nt, nc * ni * nb, o,
+                        [&](const float *d, int64_t span, const int64_t *dwin, double *const *p,
+                            hipStream_t s) {
+                          return bldp_skewness_f32(d, span, ni, nt, dwin, tblock, p[0], nc,
+                                                   nc * ni, s);
+                        });
 }
 
-// The same staging for the moments: up to four (nc, ni, nb) planes come back, a
-// null plane is neither computed nor copied.
+// Up to four (nc, ni, nb) planes come back.
 extern "C" int bldp_moments_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
                                      int64_t ntime, const int64_t *win, int64_t tblock,
                                      double *mean, double *var, double *skew, double *kurt) {
@@ -269,35 +272,19 @@ extern "C" int bldp_moments_host_f32(int dev, const float *in, int64_t nchan, in
   const int64_t n = nc * ni * nb;
   if (n == 0) return BLDP_OK;
   double *const out[4] = {mean, var, skew, kurt};
-  int np = 0;
-  for (int q = 0; q < 4; ++q) np += out[q] != nullptr;
-  if (np == 0) return bldp::set_error(BLDP_EINVAL, "moments: every output plane is null");
+  if (!mean && !var && !skew && !kurt)
+    return bldp::set_error(BLDP_EINVAL, "moments: every output plane is null");
   if (!in && nt > 0) return bldp::set_error(BLDP_EINVAL, "moments: null pointer");
   for (int q = 0; q < 4; ++q)  // (host planes: the same rule as the device entry's)
     for (int r = q + 1; r < 4; ++r)
       if (out[q] && out[r] && out[q] < out[r] + n && out[r] < out[q] + n)
         return bldp::set_error(BLDP_EINVAL, "moments: output planes overlap");
-  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
-  return with_stager(dev, [&](bldp::Stager *sg) -> int {
-    float *dbuf;
-    double *dout;
-    int r = bldp::stager_buffer(sg, 0, (size_t)std::max<int64_t>(1, h.span * ni * nt) * 4,
-                                (void **)&dbuf);
-    if (!r) r = bldp::stager_buffer(sg, 2, (size_t)(np * n) * sizeof(double), (void **)&dout);
-    if (!r && nt > 0) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
-    if (r) return r;
-    double *d[4];
-    for (int q = 0, j = 0; q < 4; ++q) d[q] = out[q] ? dout + (j++) * n : nullptr;
-    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
-    r = bldp_moments_f32(dbuf, h.span, ni, nt, dwin, tblock, d[0], d[1], d[2], d[3], nc, nc * ni,
-                         sg->st[0]);
-    if (r) return r;
-    for (int q = 0; q < 4; ++q)
-      if (out[q])
-        HCHK(hipMemcpyAsync(out[q], d[q], (size_t)n * sizeof(double), hipMemcpyDeviceToHost,
-                            sg->st[0]));
-    return BLDP_OK;
-  });
+  return moments_staged(dev, in, nchan, nif, win, nc, ni, nt, n, out,
+                        [&](const float *d, int64_t span, const int64_t *dwin, double *const *p,
+                            hipStream_t s) {
+                          return bldp_moments_f32(d, span, ni, nt, dwin, tblock, p[0], p[1], p[2],
+                                                  p[3], nc, nc * ni, s);
+                        });
 }
 
 // The same staging for tavfunc's var / std / median over blocks of tavby

@@ -872,6 +872,133 @@ def _block_win(win, shape, M, b):
     return w
 
 
+def _skew_tblock(tblock, nt) -> int:
+    """The ABI's tblock of a skewness call: 0 = the whole window (``None``),
+    else the checked block length (the errors of ``_check_tblock``)."""
+    if tblock is None:
+        return 0
+    _check_tblock(tblock, nt)
+    return int(tblock)
+
+
+def _need_f32(what, dtype, fn="skewness"):
+    raise TypeError(f"{what}: element type {dtype} is not supported; {fn} takes Float32 "
+                    "(float32) data only")
+
+
+# The time-moment family (kurtosis over blocks, skewness, moments) shares one
+# helper per kind of call.  ``fn`` names the ABI function, ``want`` flags the
+# planes to allocate (one for kurtosis and skewness, four for moments); each
+# returns the planes in ``want``'s order, ``None`` where it is false.  The
+# callers check ``which`` and the element type first, in that order.
+def _moment_call(fn, x, win, tblock, stream, want=(True,)):
+    """Device call: (nc, ni, nt/tblock) float64 tensors, (nc, ni) ones for the
+    whole window (``tblock=None``)."""
+    torch = _torch()
+    shape = tuple(x.shape)
+    _check_bounds(win, shape)
+    nc, ni, nt = window_shape(win, shape)
+    M = _skew_tblock(tblock, nt)
+    nb = nt // M if M else 1
+    outs = [torch.empty((nb, ni, nc), dtype=torch.float64, device=x.device).permute(2, 1, 0)
+            if w else None for w in want]
+    ptr, nchan, nif, ntime = _abi_dims(x)
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    rc = getattr(_lib.lib(), fn)(
+        ptr, nchan, nif, ntime, wp, M,
+        *[o.data_ptr() if o is not None and o.numel() else None for o in outs],
+        nc, nc * ni, _lib.stream_ptr(stream))
+    _lib.check(rc, fn)
+    return [o if o is None or M else o[:, :, 0] for o in outs]
+
+
+def _moment_plan(fn, x, win, tblock, check=_skew_tblock) -> dict:
+    """Plan call: the path ("regs", "mid", "leaf", "twopass"), fused, the block
+    count and the workspace bytes."""
+    shape = tuple(x.shape)
+    _check_bounds(win, shape)
+    check(tblock, window_shape(win, shape)[2])
+    ptr, nchan, nif, ntime = _abi_dims(x)
+    info = (ctypes.c_int64 * 4)()
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    _lib.check(getattr(_lib.lib(), fn)(ptr, nchan, nif, ntime, wp, int(tblock or 0), info), fn)
+    return {"path": _lib.KURT_PATHS[info[0]], "fused": int(info[1]), "blocks": int(info[2]),
+            "workspace_bytes": int(info[3])}
+
+
+def _band_geo(banks):
+    """The ABI geometry (nchan, nif, ntime) every bank of a band must share."""
+    shape = tuple(banks[0].shape)
+    geo = _abi_dims(banks[0])[1:]
+    for b in banks[1:]:
+        if tuple(b.shape) != shape or _abi_dims(b)[1:] != geo:
+            raise ValueError("all banks of a band must have the same shape and layout")
+    return geo
+
+
+def _band_moment_call(fn, banks, win, tblock, stream, want=(True,), geo=None):
+    """Band call: per bank the list of its planes, views of one buffer per
+    plane.  ``geo``: the banks' geometry where the caller has checked it."""
+    torch = _torch()
+    shape = tuple(banks[0].shape)
+    _check_bounds(win, shape)
+    nc, ni, nt = window_shape(win, shape)
+    M = _skew_tblock(tblock, nt)
+    nb = nt // M if M else 1
+    if geo is None:
+        geo = _band_geo(banks)
+    ptrs = (ctypes.c_void_p * len(banks))(*[b.data_ptr() for b in banks])
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    bufs = [torch.empty((len(banks), nb, ni, nc), dtype=torch.float64, device=banks[0].device)
+            if w else None for w in want]
+    rc = getattr(_lib.lib(), fn)(
+        len(banks), ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp, M,
+        *[b.data_ptr() if b is not None and b.numel() else None for b in bufs],
+        _lib.stream_ptr(stream))
+    _lib.check(rc, fn)
+
+    def view(buf, k):
+        if buf is None:
+            return None
+        return buf[k].permute(2, 1, 0) if M else buf[k, 0].t()
+    return [[view(buf, k) for buf in bufs] for k in range(len(banks))]
+
+
+def _f32_banks(banks, what, fn):
+    banks = list(banks)
+    if not banks:
+        raise ValueError("no banks")
+    f32 = _torch().float32
+    for b in banks:
+        if b.dtype != f32:
+            _need_f32(what, b.dtype, fn)
+    return banks
+
+
+def _moment_host(fn, a, win, device, tblock, want=(True,), what=None, takes="skewness"):
+    """Host call: Fortran-ordered (nc, ni, nt/tblock) float64 arrays, (nc, ni)
+    ones for the whole window.  ``what``: the caller's name in the TypeError of
+    an element type other than Float32 (``takes`` names the statistic)."""
+    a = np.asarray(a)
+    if what and a.dtype != np.float32:
+        _need_f32(what, a.dtype, takes)
+    if a.dtype != np.float32 or not a.flags.f_contiguous or a.ndim != 3:
+        raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
+    _check_bounds(win, a.shape)
+    nc, ni, nt = window_shape(win, a.shape)
+    M = _skew_tblock(tblock, nt)
+    outs = [np.empty((nc, ni, nt // M) if M else (nc, ni), dtype=np.float64, order="F")
+            if w else None for w in want]
+    keep, wp = _lib.win_arg(_full_win(win, a.shape))
+    # (bldp_kurtosis_host_f32, the whole-window kurtosis, takes no tblock)
+    rc = getattr(_lib.lib(), fn)(
+        int(device), a.ctypes.data if a.size else None, a.shape[0], a.shape[1], a.shape[2], wp,
+        *(() if fn == "bldp_kurtosis_host_f32" else (M,)),
+        *[o.ctypes.data if o is not None and o.size else None for o in outs])
+    _lib.check(rc, fn)
+    return outs
+
+
 def kurtosis(x, win=None, tblock=None, stream=None):
     """Excess kurtosis over time per (channel, IF): (nc, ni) float64 tensor.
 
@@ -880,24 +1007,17 @@ def kurtosis(x, win=None, tblock=None, stream=None):
     call; M must divide nt).  Element types other than Float32 go block by
     block through the typed kurtosis."""
     torch = _torch()
+    if tblock is not None and x.dtype == torch.float32:
+        return _moment_call("bldp_kurtosis_blocks_f32", x, win, tblock, stream)[0]
     L = _lib.lib()
     shape = tuple(x.shape)
     _check_bounds(win, shape)
     nc, ni, nt = window_shape(win, shape)
     if tblock is not None:
         nb = _check_tblock(tblock, nt)
-        M = int(tblock)
         out = torch.empty((nb, ni, nc), dtype=torch.float64, device=x.device).permute(2, 1, 0)
-        if x.dtype != torch.float32:
-            for b in range(nb):
-                out[:, :, b] = kurtosis(x, _block_win(win, shape, M, b), stream=stream)
-            return out
-        ptr, nchan, nif, ntime = _abi_dims(x)
-        keep, wp = _lib.win_arg(_full_win(win, shape))
-        rc = L.bldp_kurtosis_blocks_f32(ptr, nchan, nif, ntime, wp, M,
-                                        out.data_ptr() if out.numel() else None, nc, nc * ni,
-                                        _lib.stream_ptr(stream))
-        _lib.check(rc, "bldp_kurtosis_blocks_f32")
+        for b in range(nb):
+            out[:, :, b] = kurtosis(x, _block_win(win, shape, int(tblock), b), stream=stream)
         return out
     out = torch.empty((ni, nc), dtype=torch.float64, device=x.device).t()
     ptr, nchan, nif, ntime = _abi_dims(x, allow_typed=True)
@@ -932,17 +1052,7 @@ def kurtosis_blocks_plan(x, tblock, win=None) -> dict:
     "mid", "leaf", "twopass": the class of the results), fused (1 = the
     one-launch kernel, 0 = block by block through the whole-window paths),
     the block count and the workspace bytes."""
-    L = _lib.lib()
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
-    _check_tblock(tblock, window_shape(win, shape)[2])
-    ptr, nchan, nif, ntime = _abi_dims(x)
-    info = (ctypes.c_int64 * 4)()
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    _lib.check(L.bldp_kurtosis_blocks_plan_f32(ptr, nchan, nif, ntime, wp, int(tblock), info),
-               "bldp_kurtosis_blocks_plan_f32")
-    return {"path": _lib.KURT_PATHS[info[0]], "fused": int(info[1]), "blocks": int(info[2]),
-            "workspace_bytes": int(info[3])}
+    return _moment_plan("bldp_kurtosis_blocks_plan_f32", x, win, tblock, check=_check_tblock)
 
 
 def band_kurtosis(banks, win=None, tblock=None, stream=None):
@@ -955,23 +1065,14 @@ def band_kurtosis(banks, win=None, tblock=None, stream=None):
     if not banks:
         raise ValueError("no banks")
     shape = tuple(banks[0].shape)
-    geo = _abi_dims(banks[0])[1:]
-    for b in banks[1:]:
-        if tuple(b.shape) != shape or _abi_dims(b)[1:] != geo:
-            raise ValueError("all banks of a band must have the same shape and layout")
+    geo = _band_geo(banks)
     _check_bounds(win, shape)
+    if tblock is not None:
+        return [v[0] for v in _band_moment_call("bldp_band_kurtosis_blocks_f32", banks, win,
+                                                tblock, stream, geo=geo)]
     nc, ni, nt = window_shape(win, shape)
     ptrs = (ctypes.c_void_p * len(banks))(*[b.data_ptr() for b in banks])
     keep, wp = _lib.win_arg(_full_win(win, shape))
-    if tblock is not None:
-        nb = _check_tblock(tblock, nt)
-        buf = torch.empty((len(banks), nb, ni, nc), dtype=torch.float64, device=banks[0].device)
-        rc = L.bldp_band_kurtosis_blocks_f32(len(banks), ctypes.cast(ptrs, ctypes.c_void_p), *geo,
-                                             wp, int(tblock),
-                                             buf.data_ptr() if buf.numel() else None,
-                                             _lib.stream_ptr(stream))
-        _lib.check(rc, "bldp_band_kurtosis_blocks_f32")
-        return [buf[k].permute(2, 1, 0) for k in range(len(banks))]
     buf = torch.empty((len(banks), ni, nc), dtype=torch.float64, device=banks[0].device)
     rc = L.bldp_band_kurtosis_f32(len(banks), ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp,
                                   buf.data_ptr() if buf.numel() else None,
@@ -980,18 +1081,12 @@ def band_kurtosis(banks, win=None, tblock=None, stream=None):
     return [buf[k].t() for k in range(len(banks))]
 
 
-def _skew_tblock(tblock, nt) -> int:
-    """The ABI's tblock of a skewness call: 0 = the whole window (``None``),
-    else the checked block length (the errors of ``_check_tblock``)."""
-    if tblock is None:
-        return 0
-    _check_tblock(tblock, nt)
-    return int(tblock)
-
-
-def _need_f32(what, dtype, fn="skewness"):
-    raise TypeError(f"{what}: element type {dtype} is not supported; {fn} takes Float32 "
-                    "(float32) data only")
+def kurtosis_host(a: np.ndarray, win=None, device=0, tblock=None) -> np.ndarray:
+    """Host array in, (nc, ni) float64 host array out (bldp_kurtosis_host_f32);
+    with ``tblock`` the (nc, ni, nt/tblock) kurtosis of every block of tblock
+    selected spectra (bldp_kurtosis_blocks_host_f32)."""
+    fn = "bldp_kurtosis_host_f32" if tblock is None else "bldp_kurtosis_blocks_host_f32"
+    return _moment_host(fn, a, win, device, tblock)[0]
 
 
 def skewness(x, win=None, tblock=None, stream=None):
@@ -999,94 +1094,31 @@ def skewness(x, win=None, tblock=None, stream=None):
     Float32 mean (bldp_skewness_f32): an (nc, ni) float64 tensor, or with
     ``tblock=M`` the Julia-order (nc, ni, nt/M) skewness of every block of M
     selected spectra (M must divide nt).  Float32 tensors only."""
-    torch = _torch()
-    L = _lib.lib()
-    if x.dtype != torch.float32:
+    if x.dtype != _torch().float32:
         _need_f32("skewness", x.dtype)
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
-    nc, ni, nt = window_shape(win, shape)
-    M = _skew_tblock(tblock, nt)
-    nb = nt // M if M else 1
-    out = torch.empty((nb, ni, nc), dtype=torch.float64, device=x.device).permute(2, 1, 0)
-    ptr, nchan, nif, ntime = _abi_dims(x)
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    rc = L.bldp_skewness_f32(ptr, nchan, nif, ntime, wp, M, out.data_ptr() if out.numel() else None,
-                             nc, nc * ni, _lib.stream_ptr(stream))
-    _lib.check(rc, "bldp_skewness_f32")
-    return out if M else out[:, :, 0]
+    return _moment_call("bldp_skewness_f32", x, win, tblock, stream)[0]
 
 
 def skewness_plan(x, win=None, tblock=None) -> dict:
     """Plan of ``skewness(x, win, tblock)``: the path ("regs", "mid", "leaf",
     "twopass": the class of the results), fused (1 = one set of launches, 0 =
     block by block), the block count and the workspace bytes."""
-    L = _lib.lib()
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
-    M = _skew_tblock(tblock, window_shape(win, shape)[2])
-    ptr, nchan, nif, ntime = _abi_dims(x)
-    info = (ctypes.c_int64 * 4)()
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    _lib.check(L.bldp_skewness_plan_f32(ptr, nchan, nif, ntime, wp, M, info),
-               "bldp_skewness_plan_f32")
-    return {"path": _lib.KURT_PATHS[info[0]], "fused": int(info[1]), "blocks": int(info[2]),
-            "workspace_bytes": int(info[3])}
+    return _moment_plan("bldp_skewness_plan_f32", x, win, tblock)
 
 
 def band_skewness(banks, win=None, tblock=None, stream=None):
     """Skewness of every bank of a band on one GPU in one set of launches
     (bldp_band_skewness_f32): a list of (nc, ni) float64 tensors (views of one
     buffer), or with ``tblock`` of (nc, ni, nt/tblock) ones."""
-    torch = _torch()
-    L = _lib.lib()
-    banks = list(banks)
-    if not banks:
-        raise ValueError("no banks")
-    for b in banks:
-        if b.dtype != torch.float32:
-            _need_f32("band_skewness", b.dtype)
-    shape = tuple(banks[0].shape)
-    _check_bounds(win, shape)
-    nc, ni, nt = window_shape(win, shape)
-    M = _skew_tblock(tblock, nt)
-    nb = nt // M if M else 1
-    geo = _abi_dims(banks[0])[1:]
-    for b in banks[1:]:
-        if tuple(b.shape) != shape or _abi_dims(b)[1:] != geo:
-            raise ValueError("all banks of a band must have the same shape and layout")
-    ptrs = (ctypes.c_void_p * len(banks))(*[b.data_ptr() for b in banks])
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    buf = torch.empty((len(banks), nb, ni, nc), dtype=torch.float64, device=banks[0].device)
-    rc = L.bldp_band_skewness_f32(len(banks), ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp, M,
-                                  buf.data_ptr() if buf.numel() else None,
-                                  _lib.stream_ptr(stream))
-    _lib.check(rc, "bldp_band_skewness_f32")
-    if M:
-        return [buf[k].permute(2, 1, 0) for k in range(len(banks))]
-    return [buf[k, 0].t() for k in range(len(banks))]
+    banks = _f32_banks(banks, "band_skewness", "skewness")
+    return [v[0] for v in _band_moment_call("bldp_band_skewness_f32", banks, win, tblock, stream)]
 
 
 def skewness_host(a: np.ndarray, win=None, device=0, tblock=None) -> np.ndarray:
     """Host array in, (nc, ni) float64 host array out (bldp_skewness_host_f32);
     with ``tblock`` the (nc, ni, nt/tblock) skewness of every block of tblock
     selected spectra.  Float32 arrays only."""
-    L = _lib.lib()
-    a = np.asarray(a)
-    if a.dtype != np.float32:
-        _need_f32("skewness_host", a.dtype)
-    if not a.flags.f_contiguous or a.ndim != 3:
-        raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
-    _check_bounds(win, a.shape)
-    nc, ni, nt = window_shape(win, a.shape)
-    M = _skew_tblock(tblock, nt)
-    out = np.empty((nc, ni, nt // M) if M else (nc, ni), dtype=np.float64, order="F")
-    keep, wp = _lib.win_arg(_full_win(win, a.shape))
-    rc = L.bldp_skewness_host_f32(int(device), a.ctypes.data if a.size else None, a.shape[0],
-                                  a.shape[1], a.shape[2], wp, M,
-                                  out.ctypes.data if out.size else None)
-    _lib.check(rc, "bldp_skewness_host_f32")
-    return out
+    return _moment_host("bldp_skewness_host_f32", a, win, device, tblock, what="skewness_host")[0]
 
 
 # The planes of a moments call, in the ABI's order.  ``var`` is cm2 / n, the
@@ -1118,105 +1150,36 @@ def moments(x, win=None, tblock=None, stream=None, which=MOMENTS):
     the UNCORRECTED variance those two divide by (not Julia's ``var``).  A
     plane not named in ``which`` is ``None`` and is not computed into memory.
     Float32 tensors only."""
-    torch = _torch()
-    L = _lib.lib()
     want = _which_planes(which)
-    if x.dtype != torch.float32:
+    if x.dtype != _torch().float32:
         _need_f32("moments", x.dtype, "moments")
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
-    nc, ni, nt = window_shape(win, shape)
-    M = _skew_tblock(tblock, nt)
-    nb = nt // M if M else 1
-    outs = [torch.empty((nb, ni, nc), dtype=torch.float64, device=x.device).permute(2, 1, 0)
-            if w else None for w in want]
-    ptr, nchan, nif, ntime = _abi_dims(x)
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    rc = L.bldp_moments_f32(ptr, nchan, nif, ntime, wp, M,
-                            *[o.data_ptr() if o is not None and o.numel() else None for o in outs],
-                            nc, nc * ni, _lib.stream_ptr(stream))
-    _lib.check(rc, "bldp_moments_f32")
-    return Moments(*[o if o is None or M else o[:, :, 0] for o in outs])
+    return Moments(*_moment_call("bldp_moments_f32", x, win, tblock, stream, want))
 
 
 def moments_plan(x, win=None, tblock=None) -> dict:
     """Plan of ``moments(x, win, tblock)``: the path ("regs", "mid", "leaf",
     "twopass": the class of the results), fused (1 = one set of launches, 0 =
     block by block), the block count and the workspace bytes."""
-    L = _lib.lib()
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
-    M = _skew_tblock(tblock, window_shape(win, shape)[2])
-    ptr, nchan, nif, ntime = _abi_dims(x)
-    info = (ctypes.c_int64 * 4)()
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    _lib.check(L.bldp_moments_plan_f32(ptr, nchan, nif, ntime, wp, M, info),
-               "bldp_moments_plan_f32")
-    return {"path": _lib.KURT_PATHS[info[0]], "fused": int(info[1]), "blocks": int(info[2]),
-            "workspace_bytes": int(info[3])}
+    return _moment_plan("bldp_moments_plan_f32", x, win, tblock)
 
 
 def band_moments(banks, win=None, tblock=None, stream=None, which=MOMENTS):
     """The moments of every bank of a band on one GPU in one set of launches
     (bldp_band_moments_f32): a list of ``Moments`` (views of one buffer per
     plane), shaped as ``moments`` shapes them."""
-    torch = _torch()
-    L = _lib.lib()
     want = _which_planes(which)
-    banks = list(banks)
-    if not banks:
-        raise ValueError("no banks")
-    for b in banks:
-        if b.dtype != torch.float32:
-            _need_f32("band_moments", b.dtype, "moments")
-    shape = tuple(banks[0].shape)
-    _check_bounds(win, shape)
-    nc, ni, nt = window_shape(win, shape)
-    M = _skew_tblock(tblock, nt)
-    nb = nt // M if M else 1
-    geo = _abi_dims(banks[0])[1:]
-    for b in banks[1:]:
-        if tuple(b.shape) != shape or _abi_dims(b)[1:] != geo:
-            raise ValueError("all banks of a band must have the same shape and layout")
-    ptrs = (ctypes.c_void_p * len(banks))(*[b.data_ptr() for b in banks])
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    bufs = [torch.empty((len(banks), nb, ni, nc), dtype=torch.float64, device=banks[0].device)
-            if w else None for w in want]
-    rc = L.bldp_band_moments_f32(len(banks), ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp, M,
-                                 *[b.data_ptr() if b is not None and b.numel() else None
-                                   for b in bufs], _lib.stream_ptr(stream))
-    _lib.check(rc, "bldp_band_moments_f32")
-
-    def view(buf, k):
-        if buf is None:
-            return None
-        return buf[k].permute(2, 1, 0) if M else buf[k, 0].t()
-    return [Moments(*[view(buf, k) for buf in bufs]) for k in range(len(banks))]
+    banks = _f32_banks(banks, "band_moments", "moments")
+    return [Moments(*v) for v in _band_moment_call("bldp_band_moments_f32", banks, win, tblock,
+                                                    stream, want)]
 
 
 def moments_host(a: np.ndarray, win=None, device=0, tblock=None, which=MOMENTS):
     """Host array in, a ``Moments`` of (nc, ni) float64 host arrays out
     (bldp_moments_host_f32), (nc, ni, nt/tblock) with ``tblock``; the window is
     staged on the device once.  Float32 arrays only."""
-    L = _lib.lib()
     want = _which_planes(which)
-    a = np.asarray(a)
-    if a.dtype != np.float32:
-        _need_f32("moments_host", a.dtype, "moments")
-    if not a.flags.f_contiguous or a.ndim != 3:
-        raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
-    _check_bounds(win, a.shape)
-    nc, ni, nt = window_shape(win, a.shape)
-    M = _skew_tblock(tblock, nt)
-    outs = [np.empty((nc, ni, nt // M) if M else (nc, ni), dtype=np.float64, order="F")
-            if w else None for w in want]
-    keep, wp = _lib.win_arg(_full_win(win, a.shape))
-    rc = L.bldp_moments_host_f32(int(device), a.ctypes.data if a.size else None, a.shape[0],
-                                 a.shape[1], a.shape[2], wp, M,
-                                 *[o.ctypes.data if o is not None and o.size else None
-                                   for o in outs])
-    _lib.check(rc, "bldp_moments_host_f32")
-    return Moments(*outs)
+    return Moments(*_moment_host("bldp_moments_host_f32", a, win, device, tblock, want,
+                                 "moments_host", "moments"))
 
 
 def synth(nchan, nif, ntime, nfpc=1024, seed=0, kind=0, device=None, stream=None, out=None):
@@ -1251,33 +1214,6 @@ def reduce_host(a: np.ndarray, fqavby=1, tavby=1, op="sum", win=None, device=0) 
                                 shape[1], shape[2], wp, int(fqavby), int(tavby), _lib.OPS[op],
                                 out.ctypes.data if out.size else None)
     _lib.check(rc, "bldp_reduce_host_f32")
-    return out
-
-
-def kurtosis_host(a: np.ndarray, win=None, device=0, tblock=None) -> np.ndarray:
-    """Host array in, (nc, ni) float64 host array out (bldp_kurtosis_host_f32);
-    with ``tblock`` the (nc, ni, nt/tblock) kurtosis of every block of tblock
-    selected spectra (bldp_kurtosis_blocks_host_f32)."""
-    L = _lib.lib()
-    a = np.asarray(a)
-    if a.dtype != np.float32 or not a.flags.f_contiguous or a.ndim != 3:
-        raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
-    _check_bounds(win, a.shape)
-    nc, ni, nt = window_shape(win, a.shape)
-    if tblock is not None:
-        nb = _check_tblock(tblock, nt)
-        out = np.empty((nc, ni, nb), dtype=np.float64, order="F")
-        keep, wp = _lib.win_arg(_full_win(win, a.shape))
-        rc = L.bldp_kurtosis_blocks_host_f32(int(device), a.ctypes.data if a.size else None,
-                                             a.shape[0], a.shape[1], a.shape[2], wp, int(tblock),
-                                             out.ctypes.data if out.size else None)
-        _lib.check(rc, "bldp_kurtosis_blocks_host_f32")
-        return out
-    out = np.empty((nc, ni), dtype=np.float64, order="F")
-    keep, wp = _lib.win_arg(_full_win(win, a.shape))
-    rc = L.bldp_kurtosis_host_f32(int(device), a.ctypes.data if a.size else None, a.shape[0],
-                                  a.shape[1], a.shape[2], wp, out.ctypes.data if out.size else None)
-    _lib.check(rc, "bldp_kurtosis_host_f32")
     return out
 
 

@@ -696,17 +696,14 @@ def getkurtosis(fname, idxs=(COLON, COLON, COLON), device=0, tblock=None):
     return engine.kurtosis_host(np.asfortranarray(a), win, device=device, tblock=tblock)
 
 
-def getskewness(fname, idxs=(COLON, COLON, COLON), device=0, tblock=None):
-    """Skewness of every (channel, IF) row over time, Float64 (nc, ni): what
-    ``map(skewness, eachrow(...))`` in place of src/gbtworkerfunctions.jl:200
-    gives (StatsBase.skewness with Julia's Float32 mean).  With ``tblock=M``
-    the (nc, ni, nt/M) skewness of every block of M selected spectra (M must
-    divide nt: DimensionMismatch).  Files reach the GPU as getdata reads them
-    (window_on_device).  Float32 data only: any other element type (host
-    array, device tensor, 8/16-bit SIGPROC file) is a TypeError."""
-    idxs = sanitizeidxs(idxs)
+def _read_moment(name, takes, fname, idxs, device, on_device, on_host, to_host):
+    """The reader of getskewness and getmoments: a device tensor goes to
+    ``on_device(x, win)``; a file reaches the GPU as getdata reads it
+    (window_on_device) and its result comes back through ``to_host``; a host
+    array, or a file window_on_device leaves alone, goes to ``on_host(a, win)``.
+    Float32 only: ``name`` and ``takes`` word the TypeError.  ``idxs``: sanitized."""
     if _is_tensor(fname):
-        return engine.skewness(fname, to_window(idxs, fname.shape), tblock=tblock)
+        return on_device(fname, to_window(idxs, fname.shape))
     if isinstance(fname, (str, bytes)) or hasattr(fname, "__fspath__"):
         got = window_on_device(fname, idxs, device)
         if got is not None:
@@ -714,7 +711,7 @@ def getskewness(fname, idxs=(COLON, COLON, COLON), device=0, tblock=None):
 
             x, rwin = got
             with torch.cuda.device(x.device):
-                return engine.fb_to_numpy(engine.skewness(x, rwin, tblock=tblock))
+                return to_host(on_device(x, rwin))
         # not Float32, or an empty window: the host array tells which
         if readers.ishdf5(fname):
             a, idxs = readers.fbh5_read(fname, idxs), (COLON, COLON, COLON)
@@ -724,10 +721,23 @@ def getskewness(fname, idxs=(COLON, COLON, COLON), device=0, tblock=None):
         a = fname
     a = np.asarray(a)
     if a.dtype != np.float32:
-        raise TypeError(f"getskewness: element type {a.dtype} is not supported; skewness takes "
-                        "Float32 (float32) data only")
-    return engine.skewness_host(np.asfortranarray(a), to_window(idxs, a.shape), device=device,
-                                tblock=tblock)
+        engine._need_f32(name, a.dtype, takes)
+    return on_host(np.asfortranarray(a), to_window(idxs, a.shape))
+
+
+def getskewness(fname, idxs=(COLON, COLON, COLON), device=0, tblock=None):
+    """Skewness of every (channel, IF) row over time, Float64 (nc, ni): what
+    ``map(skewness, eachrow(...))`` in place of src/gbtworkerfunctions.jl:200
+    gives (StatsBase.skewness with Julia's Float32 mean).  With ``tblock=M``
+    the (nc, ni, nt/M) skewness of every block of M selected spectra (M must
+    divide nt: DimensionMismatch).  Files reach the GPU as getdata reads them
+    (window_on_device).  Float32 data only: any other element type (host
+    array, device tensor, 8/16-bit SIGPROC file) is a TypeError."""
+    return _read_moment(
+        "getskewness", "skewness", fname, sanitizeidxs(idxs), device,
+        lambda x, win: engine.skewness(x, win, tblock=tblock),
+        lambda a, win: engine.skewness_host(a, win, device=device, tblock=tblock),
+        engine.fb_to_numpy)
 
 
 def getmoments(fname, idxs=(COLON, COLON, COLON), device=0, tblock=None, which=engine.MOMENTS):
@@ -743,30 +753,11 @@ def getmoments(fname, idxs=(COLON, COLON, COLON), device=0, tblock=None, which=e
     tensor, 8/16-bit SIGPROC file) is a TypeError."""
     idxs = sanitizeidxs(idxs)
     engine._which_planes(which)  # (the ValueError before any file is touched)
-    if _is_tensor(fname):
-        return engine.moments(fname, to_window(idxs, fname.shape), tblock=tblock, which=which)
-    if isinstance(fname, (str, bytes)) or hasattr(fname, "__fspath__"):
-        got = window_on_device(fname, idxs, device)
-        if got is not None:
-            import torch
-
-            x, rwin = got
-            with torch.cuda.device(x.device):
-                m = engine.moments(x, rwin, tblock=tblock, which=which)
-                return engine.Moments(*[None if t is None else engine.fb_to_numpy(t) for t in m])
-        # not Float32, or an empty window: the host array tells which
-        if readers.ishdf5(fname):
-            a, idxs = readers.fbh5_read(fname, idxs), (COLON, COLON, COLON)
-        else:
-            _, a = readers.fil_mmap(fname)
-    else:
-        a = fname
-    a = np.asarray(a)
-    if a.dtype != np.float32:
-        raise TypeError(f"getmoments: element type {a.dtype} is not supported; moments takes "
-                        "Float32 (float32) data only")
-    return engine.moments_host(np.asfortranarray(a), to_window(idxs, a.shape), device=device,
-                               tblock=tblock, which=which)
+    return _read_moment(
+        "getmoments", "moments", fname, idxs, device,
+        lambda x, win: engine.moments(x, win, tblock=tblock, which=which),
+        lambda a, win: engine.moments_host(a, win, device=device, tblock=tblock, which=which),
+        lambda m: engine.Moments(*[None if t is None else engine.fb_to_numpy(t) for t in m]))
 
 
 getinventory = readers.getinventory

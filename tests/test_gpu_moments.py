@@ -341,8 +341,10 @@ def test_null_planes_and_strided_planes_through_the_abi(pkg, eng, M, win, sub):
 @pytest.mark.parametrize("M,nt,win", [(None, 16, None), (None, 100, None), (None, 1030, None),
                                       (None, 600, [0, 6, 1, 0, 1, 1, 0, 600, 1]),
                                       (16, 64, None), (256, 768, None),
-                                      (16, 64, [0, 256, 2, 0, 1, 1, 0, 64, 1])],
-                         ids=["regs", "mid", "leaf", "twopass", "M16", "M256", "M16-channel-step"])
+                                      (16, 64, [0, 256, 2, 0, 1, 1, 0, 64, 1]),
+                                      (None, 100, [0, 256, 2, 0, 1, 1, 0, 100, 1])],
+                         ids=["regs", "mid", "leaf", "twopass", "M16", "M256", "M16-channel-step",
+                              "mid-channel-step"])
 def test_band(eng, orc, M, nt, win):
     """Three banks in one set of launches: each bank's planes are the bits of
     its own single call, and in the class of the path."""
@@ -368,6 +370,33 @@ def test_band(eng, orc, M, nt, win):
         assert two[k].var is None and two[k].skewness is None
         assert same_bits(host(eng, two[k].kurtosis), host(eng, ms[k].kurtosis))
         assert same_bits(host(eng, two[k].mean), host(eng, ms[k].mean))
+    if win is not None and win[2] == 2:
+        # channel step 2: no float4 columns, so with tblock the block-by-block
+        # form scatters into the per-plane band buffers; two planes are null
+        vk = eng.band_moments(xs, win, tblock=M, which=("var", "kurtosis"))
+        for k in range(3):
+            assert vk[k].mean is None and vk[k].skewness is None
+            assert same_bits(host(eng, vk[k].var), host(eng, ms[k].var))
+            assert same_bits(host(eng, vk[k].kurtosis), host(eng, ms[k].kurtosis))
+
+
+def test_whole_window_on_a_stream_without_scratch(eng):
+    """The library's scratch is per stream and the regs path needs none: on a
+    stream that has not leased any, a whole-window call still takes the one
+    lease of its workspace (empty here) and gives the default stream's bits."""
+    import torch
+
+    x = dev(eng, power_rows(np.random.default_rng(8), 256, 2, 16))
+    assert eng.moments_plan(x)["workspace_bytes"] == 0
+    want, sk = planes(eng, eng.moments(x)), host(eng, eng.skewness(x))
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    got, gs = eng.moments(x, stream=s), eng.skewness(x, stream=s)
+    s.synchronize()
+    got = planes(eng, got)
+    for name in PLANES:
+        assert same_bits(got[name], want[name]), name
+    assert same_bits(host(eng, gs), sk)
 
 
 def test_layers(pkg, eng, orc, tmp_path):
