@@ -48,9 +48,13 @@
 //               recipe in a second pass (k_kurt_pass, k_kurt_fold).
 //
 // Blocks of spectra (tblock = M, one result per block; the end of this file):
-//   M <= 32     k_kurtb_regs  : k_kurt_regs' body per (block, float4 column).
+//   M <= 32     k_kurtb_regs  : regs_recipe, the body of k_kurt_regs, per
+//               (block, float4 column).
 //   33..1024    k_kurtb_stream: one wave per (block, 256 channels), the leaf
-//               method finished in place by kurt_ratio (a block is one leaf).
+//               method (leaf_stream, leaf_central, the bodies of k_kurt_leaf)
+//               finished in place by kurt_ratio (a block is one leaf).
+// The block kernels add only their index arithmetic to those bodies: the
+// register form of a block is the whole-window call's bits by construction.
 //   otherwise   block by block through the paths above (api.hip).
 //
 // getskewness (StatsBase.skewness mapped over the same rows) is the same
@@ -74,6 +78,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "bldp_impl.h"
 
@@ -287,46 +292,55 @@ __device__ __forceinline__ void put_moved(double *const (&mo)[4], int64_t e, int
 // (plan option "kurt_exact": 1 = use the exact-count instantiation).  The
 // wave's 256 Float64 results go through LDS so every nt store instruction
 // writes 1 KiB contiguous (+2.5% on the 0000 band against each lane's 32 B as
-// two nt 16-byte stores).  regs_store writes one plane's four results of a
-// lane: `row` is the plane's nc results of this (bank, IF) row.
-__device__ __forceinline__ void regs_store(double *row, int64_t col, int64_t ncols,
-                                           const double (&r)[4]) {
-  d2v *o = reinterpret_cast<d2v *>(row + 4 * col);
-  if (ncols % 64 == 0 && (reinterpret_cast<uintptr_t>(row) & 15) == 0) {
-    // whole wave in range: transpose through this wave's 2 KiB of LDS so each
-    // store instruction writes 1 KiB contiguous (lane L: doubles 2L, 2L+1 of
-    // the wave's 256 outputs, then 128 + 2L, 129 + 2L)
+// two nt 16-byte stores).
+//
+// W results of a lane at o: 16-byte stores where the address allows them,
+// else one value at a time.
+template <int W>
+__device__ __forceinline__ void store_kurt(double *o, const double (&r)[W]) {
+  if constexpr (W == 4) {
+    if ((reinterpret_cast<uintptr_t>(o) & 15) == 0) {
+      __builtin_nontemporal_store(d2v{r[0], r[1]}, reinterpret_cast<d2v *>(o));
+      __builtin_nontemporal_store(d2v{r[2], r[3]}, reinterpret_cast<d2v *>(o) + 1);
+      return;
+    }
+  }
+#pragma unroll
+  for (int w = 0; w < W; ++w) o[w] = r[w];
+}
+// One plane's four results of a lane at o, the lane's own place in a row of
+// ncols float4 columns (the register kernels' store, whole-window and blocks).
+__device__ __forceinline__ void wave_store4(double *o, int64_t ncols, const double (&r)[4]) {
+  const int lane = threadIdx.x & 63;
+  // (ncols % 64 == 0: every wave is whole and lies in one row or block, and
+  // o - 4*lane is the first of its 256 outputs, a multiple of 32 bytes from
+  // the row's start)
+  if (ncols % 64 == 0 && (reinterpret_cast<uintptr_t>(o - 4 * lane) & 15) == 0) {
+    // transpose through this wave's 2 KiB of LDS so each store instruction
+    // writes 1 KiB contiguous (lane L: doubles 2L, 2L+1 of the wave's 256
+    // outputs, then 128 + 2L, 129 + 2L)
     __shared__ d2v st[4][128];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wave = threadIdx.x >> 6;
     st[wave][2 * lane] = d2v{r[0], r[1]};
     st[wave][2 * lane + 1] = d2v{r[2], r[3]};
     __builtin_amdgcn_wave_barrier();
     const d2v a0 = st[wave][lane], a1 = st[wave][64 + lane];
     __builtin_amdgcn_wave_barrier();  // (read before a next plane overwrites)
-    d2v *ow = reinterpret_cast<d2v *>(row + 4 * (col - lane));
+    d2v *ow = reinterpret_cast<d2v *>(o - 4 * lane);
     __builtin_nontemporal_store(a0, ow + lane);
     __builtin_nontemporal_store(a1, ow + 64 + lane);
-  } else if ((reinterpret_cast<uintptr_t>(o) & 15) == 0) {
-    __builtin_nontemporal_store(d2v{r[0], r[1]}, o);
-    __builtin_nontemporal_store(d2v{r[2], r[3]}, o + 1);
   } else {
-    double *od = row + 4 * col;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) od[w] = r[w];
+    store_kurt<4>(o, r);
   }
 }
+// The recipe on one float4 column p of cnt <= NTMAX spectra ld apart (a whole
+// window's, or one block's: the two forms are the same bits by construction).
+// The results go to element oe of `out`, or for ORD == kOrdAll of every plane
+// of `mo` that is not null.
 template <int NTMAX, bool EXACT, int ORD>
-__global__ __launch_bounds__(kB) void k_kurt_regs(const KurtArgs k) {
-  const int64_t ncols = k.nc / 4;
-  const int64_t ctiles = (ncols + kB - 1) / kB;
-  const int64_t b = blockIdx.x;
-  const int64_t ib = b / ctiles, col = (b % ctiles) * kB + threadIdx.x;
-  if (col >= ncols) return;
-  const int bank = (int)(ib / k.ni);
-  const int64_t i = ib - (int64_t)bank * k.ni;
-  const float *p = k.in[bank] + k.in_off + i * k.in_ld_i + 4 * col;
-  const int nt = EXACT ? NTMAX : (int)k.nt;
-  const int64_t ld = k.in_ld_t;
+__device__ __forceinline__ void regs_recipe(const float *p, int64_t ld, int cnt, double *out,
+                                            double *const (&mo)[4], int64_t oe, int64_t ncols) {
+  const int nt = EXACT ? NTMAX : cnt;
   float4 v[NTMAX];
 #pragma unroll
   for (int t = 0; t < NTMAX; ++t)
@@ -363,12 +377,12 @@ __global__ __launch_bounds__(kB) void k_kurt_regs(const KurtArgs k) {
     // plane after plane: 4 results live at a time, each plane with the wide store
 #pragma unroll
     for (int q = 0; q < 4; ++q)
-      if (k.mo[q]) {
+      if (mo[q]) {
         double r[4];
 #pragma unroll
         for (int w = 0; w < 4; ++w)
           r[w] = mom_plane(q, m[w], c2[w] / (double)nt, c3[w] / (double)nt, c4[w] / (double)nt);
-        regs_store(k.mo[q] + ib * k.nc, col, ncols, r);
+        wave_store4(mo[q] + oe, ncols, r);
       }
   } else {
     double r[4];
@@ -377,8 +391,20 @@ __global__ __launch_bounds__(kB) void k_kurt_regs(const KurtArgs k) {
       const double cm2 = c2[w] / (double)nt, cm4 = c4[w] / (double)nt;
       r[w] = mom_ratio<ORD>(cm2, cm4);
     }
-    regs_store(k.out + ib * k.nc, col, ncols, r);
+    wave_store4(out + oe, ncols, r);
   }
+}
+template <int NTMAX, bool EXACT, int ORD>
+__global__ __launch_bounds__(kB) void k_kurt_regs(const KurtArgs k) {
+  const int64_t ncols = k.nc / 4;
+  const int64_t ctiles = (ncols + kB - 1) / kB;
+  const int64_t b = blockIdx.x;
+  const int64_t ib = b / ctiles, col = (b % ctiles) * kB + threadIdx.x;
+  if (col >= ncols) return;
+  const int bank = (int)(ib / k.ni);
+  const int64_t i = ib - (int64_t)bank * k.ni;
+  const float *p = k.in[bank] + k.in_off + i * k.in_ld_i + 4 * col;
+  regs_recipe<NTMAX, EXACT, ORD>(p, k.in_ld_t, (int)k.nt, k.out, k.mo, ib * k.nc + 4 * col, ncols);
 }
 
 // ---------------------------------------------------------------------------
@@ -661,44 +687,12 @@ __device__ __forceinline__ void stw(T *p, const T (&v)[W]) {
   }
 }
 
-// The leaf's (mean, M2, M3, M4) about its own mean, from the power sums about
-// its first spectrum c, and its (sum, max, min).
-template <int W>
-__device__ __forceinline__ void leaf_store(const KurtArgs &k, const LeafAcc<W> &A, int64_t row,
-                                           int64_t col, int64_t slot, int64_t len) {
-  const int64_t n = k.nrow * k.nc, e = row * k.nc + W * col;
-  const double cnt = (double)len;
-  double mo[4][W];
-#pragma unroll
-  for (int w = 0; w < W; ++w) {
-    const double dl = A.a1[w] / cnt, dl2 = dl * dl;
-    mo[0][w] = A.c[w] + dl;
-    mo[1][w] = A.a2[w] - A.a1[w] * dl;
-    mo[2][w] = A.a3[w] - 3.0 * dl * A.a2[w] + 2.0 * cnt * dl2 * dl;
-    mo[3][w] = A.a4[w] - 4.0 * dl * A.a3[w] + 6.0 * dl2 * A.a2[w] - 3.0 * cnt * dl2 * dl2;
-  }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) stw<W, double>(k.pm + (q * k.nslot + slot) * n + e, mo[q]);
-  stw<W, float>(k.pf + slot * n + e, A.s);
-  stw<W, float>(k.pf + (k.nslot + slot) * n + e, A.hi);
-  stw<W, float>(k.pf + (2 * k.nslot + slot) * n + e, A.lo);
-}
-
+// A lane streams its W channels down len (<= 1024) spectra ld apart from p, a
+// leaf or a block of one leaf: the first spectrum starts the sums, then B
+// spectra per batch, the next batch's loads issued before this one is
+// processed, and a predicated tail.
 template <int W, int B>
-__global__ __launch_bounds__(kB) void k_kurt_leaf(const KurtArgs k) {
-  const int lane = threadIdx.x & 63;
-  const int64_t u = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int64_t seg = u % k.nseg, r = u / k.nseg;
-  const int64_t slot = r % k.nslot, row = r / k.nslot;
-  const int64_t col = seg * 64 + lane;
-  if (row >= k.nrow || col >= k.nc / W) return;
-  int64_t t0, len;
-  pw_leaf(k.nt, k.K, slot, t0, len);
-  if (len <= 0) return;
-  const int bank = (int)(row / k.ni);
-  const int64_t i = row - (int64_t)bank * k.ni;
-  const int64_t ld = k.in_ld_t;
-  const float *p = k.in[bank] + k.in_off + i * k.in_ld_i + W * col + t0 * ld;
+__device__ __forceinline__ LeafAcc<W> leaf_stream(const float *p, int64_t ld, int64_t len) {
   LeafAcc<W> A;
   {
     float x0[W];
@@ -735,7 +729,53 @@ __global__ __launch_bounds__(kB) void k_kurt_leaf(const KurtArgs k) {
     for (int q = 0; q < B; ++q)
       if (q < tail) leaf_step<W>(A, cur[q]);
   }
-  leaf_store<W>(k, A, row, col, slot, len);
+  return A;
+}
+
+// Channel w's power sums about the first spectrum c of cnt spectra -> its
+// mean and the central moments M2, M3, M4 about that mean.
+template <int W>
+__device__ __forceinline__ void leaf_central(const LeafAcc<W> &A, int w, double cnt, double &ma,
+                                             double &m2, double &m3, double &m4) {
+  const double dl = A.a1[w] / cnt, dl2 = dl * dl;
+  ma = A.c[w] + dl;
+  m2 = A.a2[w] - A.a1[w] * dl;
+  m3 = A.a3[w] - 3.0 * dl * A.a2[w] + 2.0 * cnt * dl2 * dl;
+  m4 = A.a4[w] - 4.0 * dl * A.a3[w] + 6.0 * dl2 * A.a2[w] - 3.0 * cnt * dl2 * dl2;
+}
+
+// The leaf's (mean, M2, M3, M4) about its own mean and its (sum, max, min).
+template <int W>
+__device__ __forceinline__ void leaf_store(const KurtArgs &k, const LeafAcc<W> &A, int64_t row,
+                                           int64_t col, int64_t slot, int64_t len) {
+  const int64_t n = k.nrow * k.nc, e = row * k.nc + W * col;
+  double mo[4][W];
+#pragma unroll
+  for (int w = 0; w < W; ++w)
+    leaf_central<W>(A, w, (double)len, mo[0][w], mo[1][w], mo[2][w], mo[3][w]);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) stw<W, double>(k.pm + (q * k.nslot + slot) * n + e, mo[q]);
+  stw<W, float>(k.pf + slot * n + e, A.s);
+  stw<W, float>(k.pf + (k.nslot + slot) * n + e, A.hi);
+  stw<W, float>(k.pf + (2 * k.nslot + slot) * n + e, A.lo);
+}
+
+template <int W, int B>
+__global__ __launch_bounds__(kB) void k_kurt_leaf(const KurtArgs k) {
+  const int lane = threadIdx.x & 63;
+  const int64_t u = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t seg = u % k.nseg, r = u / k.nseg;
+  const int64_t slot = r % k.nslot, row = r / k.nslot;
+  const int64_t col = seg * 64 + lane;
+  if (row >= k.nrow || col >= k.nc / W) return;
+  int64_t t0, len;
+  pw_leaf(k.nt, k.K, slot, t0, len);
+  if (len <= 0) return;
+  const int bank = (int)(row / k.ni);
+  const int64_t i = row - (int64_t)bank * k.ni;
+  const int64_t ld = k.in_ld_t;
+  const float *p = k.in[bank] + k.in_off + i * k.in_ld_i + W * col + t0 * ld;
+  leaf_store<W>(k, leaf_stream<W, B>(p, ld, len), row, col, slot, len);
 }
 
 // ---------------------------------------------------------------------------
@@ -1233,6 +1273,40 @@ int path_of(const KurtArgs &k) {
   return KP_TWOPASS;
 }
 
+// The moment order of a plan (4 kurtosis, 3 skewness, kOrdAll every plane) as
+// a compile-time constant: f(o) with o() == ORD.
+template <int V>
+using int_c = std::integral_constant<int, V>;
+template <typename F>
+auto with_order(int order, F &&f) {
+  if (order == 3) return f(int_c<3>{});
+  if (order == kOrdAll) return f(int_c<kOrdAll>{});
+  return f(int_c<4>{});
+}
+// Launch NAME<..., ORD> for the order of the plan `k` on the stream `s`.
+#define BLDP_KLAUNCH(grid, blk, shm, NAME, ...)                                        \
+  with_order(k.order, [&](auto o) {                                                   \
+    hipLaunchKernelGGL((NAME<__VA_ARGS__, o()>), grid, blk, shm, s, k);               \
+  })
+// The register kernel's <NTMAX, EXACT, ORD> for cnt <= 32 spectra (a window's
+// nt or a block's M): f(ntmax, exact, o), each a constant as o above.  Plan
+// option "kurt_exact" = 1 takes the straight-line forms at 16 and 32 spectra.
+// The exact form of 32 spectra has no kOrdAll instantiation: with a third
+// Float64 sum per channel it needs 256 VGPRs + 27 AGPRs (one wave per SIMD,
+// under the 2-workgroup cap order 4 just meets at 208); order kOrdAll takes
+// the counted form there (158 VGPRs).
+template <typename F>
+void with_regs_form(int64_t cnt, int order, F &&f) {
+  const bool exact = opt(OPT_KURT_EXACT) != 0;
+  with_order(order, [&](auto o) {
+    if (exact && cnt == 16) return f(int_c<16>{}, std::true_type{}, o);
+    if constexpr (o() != kOrdAll)
+      if (exact && cnt == 32) return f(int_c<32>{}, std::true_type{}, o);
+    if (cnt <= 16) return f(int_c<16>{}, std::false_type{}, o);
+    return f(int_c<32>{}, std::false_type{}, o);
+  });
+}
+
 // Workspace regions: A holds the leaf partials, B the first tree level's;
 // later tree levels alternate between them (each is smaller than A).
 struct KLayout {
@@ -1342,11 +1416,10 @@ hipError_t launch_tree(const KurtArgs &k, char *ws, const KLayout &L, hipStream_
     io.L -= q;
     first = false;
   }
-  if constexpr (MOM) {
-    if (k.order == 3) return launch_final<true, 3>(k, io, first, s);
-    if (k.order == kOrdAll) return launch_final<true, kOrdAll>(k, io, first, s);
-  }
-  return launch_final<MOM, 4>(k, io, first, s);
+  if constexpr (MOM)
+    return with_order(k.order, [&](auto o) { return launch_final<true, o()>(k, io, first, s); });
+  else
+    return launch_final<false, 4>(k, io, first, s);
 }
 
 }  // namespace
@@ -1404,28 +1477,6 @@ int kurtosis_path(const KurtArgs &k) { return path_of(k); }
 
 size_t kurtosis_ws_bytes(const KurtArgs &k) { return layout(k).total; }
 
-// Launch NAME<..., ORD> for the plan's moment order (4 kurtosis, 3 skewness).
-#define BLDP_KLAUNCH(grid, blk, shm, NAME, ...)                                \
-  do {                                                                        \
-    if (k.order == 3)                                                         \
-      hipLaunchKernelGGL((NAME<__VA_ARGS__, 3>), grid, blk, shm, s, k);       \
-    else if (k.order == kOrdAll)                                              \
-      hipLaunchKernelGGL((NAME<__VA_ARGS__, kOrdAll>), grid, blk, shm, s, k); \
-    else                                                                      \
-      hipLaunchKernelGGL((NAME<__VA_ARGS__, 4>), grid, blk, shm, s, k);       \
-  } while (0)
-// The exact-count forms of 32 spectra have no kOrdAll instantiation: with a
-// third Float64 sum per channel they need 256 VGPRs + 27 AGPRs (one wave per
-// SIMD, under the 2-workgroup cap order 4 just meets at 208); order kOrdAll
-// takes the counted form there (158 VGPRs).
-#define BLDP_KLAUNCH34(grid, blk, shm, NAME, ...)                              \
-  do {                                                                        \
-    if (k.order == 3)                                                         \
-      hipLaunchKernelGGL((NAME<__VA_ARGS__, 3>), grid, blk, shm, s, k);       \
-    else                                                                      \
-      hipLaunchKernelGGL((NAME<__VA_ARGS__, 4>), grid, blk, shm, s, k);       \
-  } while (0)
-
 hipError_t launch_kurtosis(KurtArgs &k, char *ws, hipStream_t s) {
   const int64_t n = k.nrow * k.nc;
   if (n == 0) return hipSuccess;
@@ -1444,16 +1495,10 @@ hipError_t launch_kurtosis(KurtArgs &k, char *ws, hipStream_t s) {
   const int64_t ncols = k.nc / 4;
   if (p == KP_REGS) {
     const dim3 g1((unsigned)(cdivk(ncols, kB) * k.nrow));
-    const bool exact = opt(OPT_KURT_EXACT) != 0;
     const unsigned shm = k.nt >= kKurtRegsCapLo && k.nt <= kKurtRegsCapHi ? kKurtRegsShm : 0;
-    if (exact && k.nt == 16)
-      BLDP_KLAUNCH(g1, block, shm, k_kurt_regs, 16, true);
-    else if (exact && k.nt == 32 && k.order != kOrdAll)
-      BLDP_KLAUNCH34(g1, block, shm, k_kurt_regs, 32, true);
-    else if (k.nt <= 16)
-      BLDP_KLAUNCH(g1, block, shm, k_kurt_regs, 16, false);
-    else
-      BLDP_KLAUNCH(g1, block, shm, k_kurt_regs, 32, false);
+    with_regs_form(k.nt, k.order, [&](auto ntmax, auto exact, auto o) {
+      hipLaunchKernelGGL((k_kurt_regs<ntmax(), exact(), o()>), g1, block, shm, s, k);
+    });
     return hipGetLastError();
   }
   if (p == KP_MID && opt(OPT_KURT_MID_CPL) == 2 && k.vec && cdivk(k.nt, 8) <= 48) {
@@ -1537,21 +1582,11 @@ hipError_t launch_kurtosis(KurtArgs &k, char *ws, hipStream_t s) {
     if (e != hipSuccess) return e;
   }
   const dim3 grid((unsigned)(cdivk(cdivk(k.nc, 64), 4 / k.ts) * k.nrow * k.nchunk));
-  if (k.order == 3)
-    hipLaunchKernelGGL(k_kurt_pass<3>, grid, block, 0, s, k);
-  else if (k.order == kOrdAll)
-    hipLaunchKernelGGL(k_kurt_pass<kOrdAll>, grid, block, 0, s, k);
-  else
-    hipLaunchKernelGGL(k_kurt_pass<4>, grid, block, 0, s, k);
-  if (k.nchunk > 1) {
-    const unsigned fg = (unsigned)std::min<int64_t>(cdivk(n, kB), 16384);
-    if (k.order == 3)
-      hipLaunchKernelGGL(k_kurt_fold<3>, dim3(fg), block, 0, s, k);
-    else if (k.order == kOrdAll)
-      hipLaunchKernelGGL(k_kurt_fold<kOrdAll>, dim3(fg), block, 0, s, k);
-    else
-      hipLaunchKernelGGL(k_kurt_fold<4>, dim3(fg), block, 0, s, k);
-  }
+  const unsigned fg = (unsigned)std::min<int64_t>(cdivk(n, kB), 16384);
+  with_order(k.order, [&](auto o) {
+    hipLaunchKernelGGL(k_kurt_pass<o()>, grid, block, 0, s, k);
+    if (k.nchunk > 1) hipLaunchKernelGGL(k_kurt_fold<o()>, dim3(fg), block, 0, s, k);
+  });
   return hipGetLastError();
 }
 
@@ -1582,46 +1617,11 @@ int64_t kurtosis_max_grid(const KurtArgs &k) {
 // out[k*out_bank + c + i*out_ld_i + b*out_ld_b].
 namespace {
 
-// 16-byte stores where the address allows them, else one value at a time
-template <int W>
-__device__ __forceinline__ void store_kurt(double *o, const double (&r)[W]) {
-  if constexpr (W == 4) {
-    if ((reinterpret_cast<uintptr_t>(o) & 15) == 0) {
-      __builtin_nontemporal_store(d2v{r[0], r[1]}, reinterpret_cast<d2v *>(o));
-      __builtin_nontemporal_store(d2v{r[2], r[3]}, reinterpret_cast<d2v *>(o) + 1);
-      return;
-    }
-  }
-#pragma unroll
-  for (int w = 0; w < W; ++w) o[w] = r[w];
-}
-
-// M <= NTMAX (<= 32): k_kurt_regs' body per (block, float4 column), the
-// recipe in the recipe's order, bit-identical to it.  The lanes of a (bank,
-// IF) row run over (block, column) pairs, column fastest, so narrow products
-// (the 0001 product: 128 columns) still fill their workgroups; when the
-// columns of a block are whole waves (nc % 256 == 0) a wave's 256 results are
-// contiguous and go through LDS to 1 KiB stores as in k_kurt_regs.
-// blk_store writes one plane's four results of a lane at o.
-__device__ __forceinline__ void blk_store(double *o, int64_t ncols, const double (&r)[4]) {
-  const int lane = threadIdx.x & 63;
-  // (ncols % 64 == 0: a wave lies in one block, per_row is whole waves, and
-  // o - 4*lane is the first of the wave's 256 outputs)
-  if (ncols % 64 == 0 && (reinterpret_cast<uintptr_t>(o - 4 * lane) & 15) == 0) {
-    __shared__ d2v st[4][128];
-    const int wave = threadIdx.x >> 6;
-    st[wave][2 * lane] = d2v{r[0], r[1]};
-    st[wave][2 * lane + 1] = d2v{r[2], r[3]};
-    __builtin_amdgcn_wave_barrier();
-    const d2v a0 = st[wave][lane], a1 = st[wave][64 + lane];
-    __builtin_amdgcn_wave_barrier();  // (read before a next plane overwrites)
-    d2v *ow = reinterpret_cast<d2v *>(o - 4 * lane);
-    __builtin_nontemporal_store(a0, ow + lane);
-    __builtin_nontemporal_store(a1, ow + 64 + lane);
-  } else {
-    store_kurt<4>(o, r);
-  }
-}
+// M <= NTMAX (<= 32): regs_recipe per (block, float4 column).  The lanes of a
+// (bank, IF) row run over (block, column) pairs, column fastest, so narrow
+// products (the 0001 product: 128 columns) still fill their workgroups; when
+// the columns of a block are whole waves (nc % 256 == 0) a wave's 256 results
+// are contiguous and wave_store4 takes them through LDS to 1 KiB stores.
 template <int NTMAX, bool EXACT, int ORD>
 __global__ __launch_bounds__(kB) void k_kurtb_regs(const KurtBlkArgs k) {
   const int64_t ncols = k.nc / 4;
@@ -1633,70 +1633,18 @@ __global__ __launch_bounds__(kB) void k_kurtb_regs(const KurtBlkArgs k) {
   const int64_t b = u / ncols, col = u - b * ncols;
   const int bank = (int)(row / k.ni);
   const int64_t i = row - (int64_t)bank * k.ni;
-  const int nt = EXACT ? NTMAX : (int)k.M;
   const int64_t ld = k.in_ld_t;
   const float *p = k.in[bank] + k.in_off + i * k.in_ld_i + b * k.M * ld + 4 * col;
-  float4 v[NTMAX];
-#pragma unroll
-  for (int t = 0; t < NTMAX; ++t)
-    if (EXACT || t < nt) v[t] = ldnt(p + t * ld);
-  // Base.sum: sequential Float32 from the block's first spectrum
-  f2v sa = {v[0].x, v[0].y}, sb = {v[0].z, v[0].w};
-#pragma unroll
-  for (int t = 1; t < NTMAX; ++t)
-    if (EXACT || t < nt) {
-      sa += f2v{v[t].x, v[t].y};
-      sb += f2v{v[t].z, v[t].w};
-    }
-  const float m[4] = {sa.x / (float)nt, sa.y / (float)nt, sb.x / (float)nt, sb.y / (float)nt};
-  double c2[4] = {0, 0, 0, 0}, c4[4] = {0, 0, 0, 0};
-  double c3[ORD == kOrdAll ? 4 : 1] = {};  // (order kOrdAll keeps both top moments)
-#pragma unroll
-  for (int t = 0; t < NTMAX; ++t)
-    if (EXACT || t < nt) {
-      const float x[4] = {v[t].x, v[t].y, v[t].z, v[t].w};
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        const float z = x[w] - m[w];  // StatsBase: z, z2 in Float32; Float64 moments
-        const float z2 = z * z;
-        c2[w] += (double)z2;
-        if constexpr (ORD == kOrdAll) {
-          c3[w] += (double)top_term<3>(z2, z);
-          c4[w] += (double)top_term<4>(z2, z);
-        } else {
-          c4[w] += (double)top_term<ORD>(z2, z);
-        }
-      }
-    }
   const int64_t oe = bank * k.out_bank + i * k.out_ld_i + b * k.out_ld_b + 4 * col;
-  if constexpr (ORD == kOrdAll) {
-    // plane after plane, as k_kurt_regs
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      if (k.mo[q]) {
-        double r[4];
-#pragma unroll
-        for (int w = 0; w < 4; ++w)
-          r[w] = mom_plane(q, m[w], c2[w] / (double)nt, c3[w] / (double)nt, c4[w] / (double)nt);
-        blk_store(k.mo[q] + oe, ncols, r);
-      }
-  } else {
-    double r[4];
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const double cm2 = c2[w] / (double)nt, cm4 = c4[w] / (double)nt;
-      r[w] = mom_ratio<ORD>(cm2, cm4);
-    }
-    blk_store(k.out + oe, ncols, r);
-  }
+  regs_recipe<NTMAX, EXACT, ORD>(p, ld, (int)k.M, k.out, k.mo, oe, ncols);
 }
 
 // 32 < M <= 1024: one wave per (block, 64 columns of W channels, bank x IF
-// row) streams the block once, as k_kurt_leaf streams a leaf (B spectra per
-// batch in flight): the sequential Float32 sum from the block's first
-// spectrum (-> Julia's m), max, min and the Float64 power sums about that
-// spectrum, moved to the block's own mean and finished by kurt_ratio.  No
-// tree, no workspace, no second pass; class "leaf" (exact z^2, z^4).
+// row) streams the block once with leaf_stream (a block is one leaf): the
+// sequential Float32 sum from the block's first spectrum (-> Julia's m), max,
+// min and the Float64 power sums about that spectrum, moved to the block's own
+// mean by leaf_central and finished by kurt_ratio.  No tree, no workspace, no
+// second pass; class "leaf" (exact z^2, z^4).
 template <int W, int B, int ORD>
 __global__ __launch_bounds__(kB) void k_kurtb_stream(const KurtBlkArgs k) {
   const int lane = threadIdx.x & 63;
@@ -1710,53 +1658,14 @@ __global__ __launch_bounds__(kB) void k_kurtb_stream(const KurtBlkArgs k) {
   const int64_t i = row - (int64_t)bank * k.ni;
   const int64_t ld = k.in_ld_t, len = k.M;
   const float *p = k.in[bank] + k.in_off + i * k.in_ld_i + b * len * ld + W * col;
-  LeafAcc<W> A;
-  {
-    float x0[W];
-    ldw<W>(p, x0);
-#pragma unroll
-    for (int w = 0; w < W; ++w) {
-      A.s[w] = A.hi[w] = A.lo[w] = x0[w];  // the sum starts from the first element
-      A.c[w] = (double)x0[w];
-      A.a1[w] = A.a2[w] = A.a3[w] = A.a4[w] = 0.0;
-    }
-  }
-  p += ld;
-  const int64_t rem = len - 1, nbt = rem / B;
-  float cur[B][W];
-  if (nbt > 0) {
-#pragma unroll
-    for (int j = 0; j < B; ++j) ldw<W>(p + j * ld, cur[j]);
-  }
-  for (int64_t bt = 0; bt < nbt; ++bt) {
-    p += B * ld;
-#pragma unroll
-    for (int j = 0; j < B; ++j) leaf_step<W>(A, cur[j]);
-    if (bt + 1 < nbt) {
-#pragma unroll
-      for (int j = 0; j < B; ++j) ldw<W>(p + j * ld, cur[j]);
-    }
-  }
-  const int tail = (int)(rem - nbt * B);
-  if (tail > 0) {
-#pragma unroll
-    for (int j = 0; j < B; ++j)
-      if (j < tail) ldw<W>(p + j * ld, cur[j]);
-#pragma unroll
-    for (int j = 0; j < B; ++j)
-      if (j < tail) leaf_step<W>(A, cur[j]);
-  }
-  // power sums about the first spectrum -> central moments about the block's
-  // own mean (leaf_store's step) -> the recipe's ratio about its Float32 m
-  const double cnt = (double)len;
+  const LeafAcc<W> A = leaf_stream<W, B>(p, ld, len);
+  // central moments about the block's own mean -> the recipe's ratio about
+  // its Float32 m
   double r[ORD == kOrdAll ? 4 : 1][W];  // (order kOrdAll: a row per plane)
 #pragma unroll
   for (int w = 0; w < W; ++w) {
-    const double dl = A.a1[w] / cnt, dl2 = dl * dl;
-    const double ma = A.c[w] + dl;
-    const double m2 = A.a2[w] - A.a1[w] * dl;
-    const double m3 = A.a3[w] - 3.0 * dl * A.a2[w] + 2.0 * cnt * dl2 * dl;
-    const double m4 = A.a4[w] - 4.0 * dl * A.a3[w] + 6.0 * dl2 * A.a2[w] - 3.0 * cnt * dl2 * dl2;
+    double ma, m2, m3, m4;
+    leaf_central<W>(A, w, (double)len, ma, m2, m3, m4);
     if constexpr (ORD == kOrdAll) {
       float m;
       r[MO_SKEW][w] = skew_ratio(len, A.s[w], ma, m2, m3, A.hi[w], A.lo[w], &r[MO_VAR][w], &m);
@@ -1817,15 +1726,9 @@ int64_t kurt_blocks_grid(const KurtBlkArgs &k) {
 hipError_t launch_kurt_blocks(const KurtBlkArgs &k, hipStream_t s) {
   const dim3 g((unsigned)kurt_blocks_grid(k)), block(kB);
   if (k.M <= 32) {
-    const bool exact = opt(OPT_KURT_EXACT) != 0;
-    if (exact && k.M == 16)
-      BLDP_KLAUNCH(g, block, 0, k_kurtb_regs, 16, true);
-    else if (exact && k.M == 32 && k.order != kOrdAll)
-      BLDP_KLAUNCH34(g, block, 0, k_kurtb_regs, 32, true);
-    else if (k.M <= 16)
-      BLDP_KLAUNCH(g, block, 0, k_kurtb_regs, 16, false);
-    else
-      BLDP_KLAUNCH(g, block, 0, k_kurtb_regs, 32, false);
+    with_regs_form(k.M, k.order, [&](auto ntmax, auto exact, auto o) {
+      hipLaunchKernelGGL((k_kurtb_regs<ntmax(), exact(), o()>), g, block, 0, s, k);
+    });
   } else if (k.leafw == 1) {
     BLDP_KLAUNCH(g, block, 0, k_kurtb_stream, 1, kLeafNB);
   } else {
@@ -1834,7 +1737,6 @@ hipError_t launch_kurt_blocks(const KurtBlkArgs &k, hipStream_t s) {
   return hipGetLastError();
 }
 #undef BLDP_KLAUNCH
-#undef BLDP_KLAUNCH34
 
 hipError_t launch_kurt_scatter(const double *src, int64_t nbank, int64_t ni, int64_t nc,
                                double *out, int64_t out_bank, int64_t out_ld_i, hipStream_t s) {
