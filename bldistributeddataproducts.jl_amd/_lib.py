@@ -14,15 +14,18 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG_DIR, "libbldp_hip.so")
 CSRC = os.path.join(PKG_DIR, "csrc")
 
-OPS = {"sum": 0, "mean": 1, "max": 2, "min": 3, "var": 4, "std": 5, "median": 6}
+OPS = {"sum": 0, "mean": 1, "max": 2, "min": 3, "var": 4, "std": 5, "median": 6, "mad": 8}
 # Statistics' var (corrected) / std / median over the fqavby channels of a
-# block: Float32 on the GPU, no time integration
-STAT_OPS = ("var", "std", "median")
+# block, and StatsBase's normalised mad (the median of |x - median| times
+# MAD_CONSTANT; code 7 is unassigned): Float32 on the GPU, no time integration
+STAT_OPS = ("var", "std", "median", "mad")
+MAD_CONSTANT = 1.4826022185056018  # 1 / quantile(Normal(), 3/4), StatsBase's mad_constant
 PATHS = {0: "vector", 1: "narrow", 2: "scalar", 3: "tile", 4: "interleaved", 5: "row",
          6: "narrow_mis", 7: "lane", 8: "moments", 9: "median_sort", 10: "median_select",
          11: "median_stream"}
 KURT_PATHS = {0: "regs", 1: "mid", 2: "leaf", 3: "twopass"}
-# tavfunc var / std / median (csrc/tstats.hip): blocks of <= 32 spectra in
+# tavfunc var / std / median / mad (csrc/tstats.hip; mad reports the median's
+# paths): blocks of <= 32 spectra in
 # registers, longer ones split over the time slices of a workgroup, and var /
 # std of blocks too few to fill the GPU also over workgroups (time chunks)
 TSTAT_PATHS = {0: "regs_moments", 1: "regs_median", 2: "split_moments", 3: "split_median",

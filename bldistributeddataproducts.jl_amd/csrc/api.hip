@@ -286,8 +286,8 @@ bool unaligned_vec_pays(int64_t F, bool rows16) {
   return F == 1 || (F % 4 == 0 && F <= 256);
 }
 
-int valid_op(int op) { return op >= BLDP_OP_SUM && op <= BLDP_OP_MEDIAN; }
-#define BLDP_OP_NAMES "0=sum 1=mean 2=max 3=min 4=var 5=std 6=median"
+int valid_op(int op) { return (op >= BLDP_OP_SUM && op <= BLDP_OP_MEDIAN) || op == BLDP_OP_MAD; }
+#define BLDP_OP_NAMES "0=sum 1=mean 2=max 3=min 4=var 5=std 6=median 8=mad"
 
 // Checks, window and plan of a reduce (shared by every reduce entry point and
 // by the prepared form): fills *a and *p; *empty when there is nothing to do.
@@ -298,10 +298,11 @@ int prepare_reduce(int nbank, const float *const *in, int64_t nchan, int64_t nif
   if (nbank < 1 || nbank > BLDP_MAX_BANKS)
     return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
   if (!valid_op(op)) return fail(BLDP_EINVAL, "unknown op %d (" BLDP_OP_NAMES ")", op);
-  // Statistics' var / std / median reduce the channel blocks only: fqav on the
-  // time axis after them would not be the statistic of the F x T block
+  // Statistics' var / std / median (and mad) reduce the channel blocks only: fqav
+  // on the time axis after them would not be the statistic of the F x T block
   if (stat_op(op) && tavby > 1)
-    return fail(BLDP_EINVAL, "tavby=%lld: var/std/median have no time integration (tavby <= 1)",
+    return fail(BLDP_EINVAL,
+                "tavby=%lld: var/std/median/mad have no time integration (tavby <= 1)",
                 (long long)tavby);
   Geo g;
   int rc = resolve_window(nchan, nif, ntime, win, &g);
@@ -623,7 +624,7 @@ int bldp_band_reduce_multi_f32(int nbank, const int *bank_dev, const float *cons
   if (nbank < 1 || nbank > BLDP_MAX_BANKS || !bank_dev || !in)
     return fail(BLDP_EINVAL, "bad bank arguments");
   if (stat_op(op))
-    return fail(BLDP_EINVAL, "var/std/median (op %d) run on one device: reduce each device's "
+    return fail(BLDP_EINVAL, "var/std/median/mad (op %d) run on one device: reduce each device's "
                              "banks with bldp_band_reduce_f32", op);
   if (flags & ~(BLDP_BAND_STAGED | BLDP_BAND_PEER_STORE))
     return fail(BLDP_EINVAL, "unknown flags 0x%x", flags);
@@ -1237,7 +1238,7 @@ static int tstat_prepare(int nbank, const float *const *in, int64_t nchan, int64
     return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
   if (!stat_op(op))
     return fail(BLDP_EINVAL,
-                "tstat: op %d is not 4=var 5=std 6=median (sum/mean/max/min over time: "
+                "tstat: op %d is not 4=var 5=std 6=median 8=mad (sum/mean/max/min over time: "
                 "bldp_reduce_* with tavby)",
                 op);
   Geo g;
@@ -1525,7 +1526,7 @@ int typed_reduce_args(int dtype, const void *in, int64_t nchan, int64_t nif, int
   if (!dtype_size(dtype)) return fail(BLDP_EINVAL, "unknown element type %d", dtype);
   if (!valid_op(op)) return fail(BLDP_EINVAL, "unknown op %d (" BLDP_OP_NAMES ")", op);
   if (stat_op(op))
-    return fail(BLDP_EINVAL, "median/var/std take Float32 on the GPU (element type %d)", dtype);
+    return fail(BLDP_EINVAL, "median/var/std/mad take Float32 on the GPU (element type %d)", dtype);
   Geo g;
   int rc = resolve_window(nchan, nif, ntime, win, &g);
   if (rc) return rc;

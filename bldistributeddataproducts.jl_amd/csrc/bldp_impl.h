@@ -151,7 +151,21 @@ __device__ __forceinline__ uint32_t xcd_order(uint32_t x, uint32_t X, int lg) {
 // plan_stats fills the launch geometry like plan_reduce (`words`: the channel
 // step is 1 and every bank pointer is dword-aligned) and returns BLDP_OK or,
 // with the message recorded, BLDP_EINVAL for a launch too large for one grid.
-inline bool stat_op(int op) { return op >= BLDP_OP_VAR && op <= BLDP_OP_MEDIAN; }
+// (op 7 is unassigned; BLDP_OP_MAD = 8 takes the median's kernels and plans)
+inline bool stat_op(int op) {
+  return (op >= BLDP_OP_VAR && op <= BLDP_OP_MEDIAN) || op == BLDP_OP_MAD;
+}
+inline bool median_op(int op) { return op == BLDP_OP_MEDIAN || op == BLDP_OP_MAD; }
+// mad: the median of |x - median(x)| times StatsBase's Float64 mad_constant
+// (1 / quantile(Normal(), 3/4)), the product rounded once more to Float32
+__device__ __forceinline__ float mad_scale(float m) {
+  return (float)((double)m * 1.4826022185056018);
+}
+// |x - c|, the difference rounded once (never fused into a neighbour)
+__device__ __forceinline__ float abs_dev(float x, float c) {
+#pragma clang fp contract(off)
+  return fabsf(__fsub_rn(x, c));
+}
 int plan_stats(RedArgs &a, int op, bool words, int xcd_lg, Plan *p);
 hipError_t launch_stats(const RedArgs &a, const Plan &p, int op, hipStream_t s);
 

@@ -378,8 +378,8 @@ extern "C" int bldp_reduce_host(int dev, int dtype, const void *in, int64_t ncha
   const int od = bldp_reduce_out_dtype(dtype, op);
   if (od < 0) return od;
   if (bldp::stat_op(op))  // (before anything is staged)
-    return bldp::set_error(BLDP_EINVAL, "median/var/std take Float32 on the GPU (element type %d)",
-                           dtype);
+    return bldp::set_error(BLDP_EINVAL,
+                           "median/var/std/mad take Float32 on the GPU (element type %d)", dtype);
   int64_t sh[3];
   int rc = bldp_reduce_shape(nchan, nif, ntime, win, fqavby, tavby, sh);
   if (rc) return rc;

@@ -32,6 +32,13 @@
 //              Four passes fix all 32 bits, so ties need nothing special.
 //              Keys stay in registers up to 4096 (PATH_MEDIAN_SELECT), else
 //              every pass reads the block again (PATH_MEDIAN_STREAM).
+//   mad        StatsBase's mad(x; normalize=true): c = median(x), m = the median
+//              (same rule, NaN wins) of |x - c| with the difference rounded
+//              once, result = Float32(Float64(m) * 1.4826022185056018).  The
+//              median's kernels with MAD set run their selection twice: the
+//              keys in registers become those of |x - c| in place (one read
+//              of the block), the stream form reads the block again and forms
+//              the deviations on the way.  Plans and paths are the median's.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -242,8 +249,40 @@ __device__ __forceinline__ float median_of(uint32_t k0, uint32_t k1, bool odd, b
 
 constexpr uint32_t kPadKey = 0xffffffffu;  // above every non-NaN key
 
-// L = next_pow2(F) >= 4 keys over L / 4 lanes, key e = 4 * lane + r.
-template <int L, bool VEC>
+// The bitonic network over the L keys of a group of L / 4 lanes (key e = 4 *
+// lane + r): runs of kk keys, ascending where (e & kk) == 0.
+template <int L>
+__device__ __forceinline__ void bitonic_sort4(uint32_t (&k)[4], const int lg) {
+#pragma unroll
+  for (int kk = 2; kk <= L; kk *= 2) {
+#pragma unroll
+    for (int j = kk / 2; j >= 1; j /= 2) {
+      if (j >= 4) {  // partner key e ^ j sits in lane ^ (j / 4), same r
+        const bool up = kk == L || ((4 * lg) & kk) == 0;
+        const bool low = (lg & (j / 4)) == 0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const uint32_t other = __shfl_xor(k[r], j / 4, 64);
+          k[r] = (low == up) ? min(k[r], other) : max(k[r], other);
+        }
+      } else {  // both keys in this lane
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if ((r & j) == 0) {
+            const bool up = kk == L || ((4 * lg + r) & kk) == 0;
+            const uint32_t lo = min(k[r], k[r | j]), hi = max(k[r], k[r | j]);
+            k[r] = up ? lo : hi;
+            k[r | j] = up ? hi : lo;
+          }
+      }
+    }
+  }
+}
+
+// L = next_pow2(F) >= 4 keys over L / 4 lanes, key e = 4 * lane + r.  MAD: the
+// sorted keys become those of |x - median| in place (the padding, which sorts
+// to e >= F, stays) and the network runs again.
+template <int L, bool VEC, bool MAD>
 __global__ __launch_bounds__(kBlock) void k_median_sort(const RedArgs a) {
   constexpr int LG = L / 4;
   const int lg = threadIdx.x % LG;
@@ -269,31 +308,7 @@ __global__ __launch_bounds__(kBlock) void k_median_sort(const RedArgs a) {
         k[r] = f2key(x);
       }
   }
-  // bitonic network: runs of kk keys, ascending where (e & kk) == 0
-#pragma unroll
-  for (int kk = 2; kk <= L; kk *= 2) {
-#pragma unroll
-    for (int j = kk / 2; j >= 1; j /= 2) {
-      if (j >= 4) {  // partner key e ^ j sits in lane ^ (j / 4), same r
-        const bool up = kk == L || ((4 * lg) & kk) == 0;
-        const bool low = (lg & (j / 4)) == 0;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const uint32_t other = __shfl_xor(k[r], j / 4, 64);
-          k[r] = (low == up) ? min(k[r], other) : max(k[r], other);
-        }
-      } else {  // both keys in this lane
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if ((r & j) == 0) {
-            const bool up = kk == L || ((4 * lg + r) & kk) == 0;
-            const uint32_t lo = min(k[r], k[r | j]), hi = max(k[r], k[r | j]);
-            k[r] = up ? lo : hi;
-            k[r | j] = up ? hi : lo;
-          }
-      }
-    }
-  }
+  bitonic_sort4<L>(k, lg);
   // ranks (F-1)/2 and F/2 (the same for odd F); the padding sorts above them
   const int q0 = (F - 1) / 2, q1 = F / 2;
   auto pick = [&](int q) {
@@ -302,11 +317,26 @@ __global__ __launch_bounds__(kBlock) void k_median_sort(const RedArgs a) {
     if (LG > 1) x = __shfl(x, (int)(threadIdx.x & 63) - lg + q / 4, 64);
     return x;
   };
-  const uint32_t k0 = pick(q0), k1 = pick(q1);
+  uint32_t k0 = pick(q0), k1 = pick(q1);
+  if (MAD) {
+    const float c = median_of(k0, k1, F & 1, false);  // (a NaN block: NaN below, whatever c is)
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (4 * lg + r < F) {
+        const float d = abs_dev(key2f(k[r]), c);
+        nan = nan || d != d;
+        k[r] = f2key(d);
+      }
+    bitonic_sort4<L>(k, lg);
+    k0 = pick(q0), k1 = pick(q1);
+  }
   const unsigned long long bal = __ballot(nan);
   const unsigned long long gmask = LG == 64 ? ~0ull : ((1ull << LG) - 1ull);
   const bool gnan = ((bal >> ((threadIdx.x & 63) - lg)) & gmask) != 0;
-  if (ok && lg == 0) *o = median_of(k0, k1, F & 1, gnan);
+  if (ok && lg == 0) {
+    const float m = median_of(k0, k1, F & 1, gnan);
+    *o = MAD ? mad_scale(m) : m;
+  }
 }
 
 // Count digit d of the lanes with pred in the wave's histogram h.  The digits
@@ -328,7 +358,10 @@ __device__ __forceinline__ void hist_add(uint32_t *h, uint32_t d, bool pred) {
   if (pred) atomicAdd(&h[d], 1u);
 }
 
-template <bool VEC, bool REG>
+// MAD: the four passes run twice, the second time over |x - c| with c the
+// median the first found: the register keys are transformed in place (REG),
+// or the block is read again and the deviations formed on the way (!REG).
+template <bool VEC, bool REG, bool MAD>
 __global__ __launch_bounds__(kBlock) void k_median_select(const RedArgs a) {
   __shared__ uint32_t hist[2][256];
   __shared__ uint32_t wtot[2][4];
@@ -339,16 +372,22 @@ __global__ __launch_bounds__(kBlock) void k_median_select(const RedArgs a) {
   float *o = nullptr;
   if (!stat_group(a, blockIdx.x, p, o)) return;  // (uniform)
   const int64_t F = a.F, n = VEC ? F / 4 : F;    // items: float4s or values
+  float cen = 0.0f;  // MAD, second round: the block's median
+  bool dev = false;  // MAD, second round (uniform): the keys are those of |x - cen|
   // item `it` (uniform loop index) of this thread: VEC 4 keys, else 1
   auto load = [&](int64_t it, uint32_t *k, bool &nan) {
     const int64_t idx = it * kBlock + tid;
     if (idx >= n) return false;
     if (VEC) {
-      const float4 x = ld4(p + 4 * idx);
+      float4 x = ld4(p + 4 * idx);
+      if (MAD && dev)
+        x = make_float4(abs_dev(x.x, cen), abs_dev(x.y, cen), abs_dev(x.z, cen),
+                        abs_dev(x.w, cen));
       nan = nan || x.x != x.x || x.y != x.y || x.z != x.z || x.w != x.w;
       k[0] = f2key(x.x), k[1] = f2key(x.y), k[2] = f2key(x.z), k[3] = f2key(x.w);
     } else {
-      const float x = p[idx * a.in_cs];
+      float x = p[idx * a.in_cs];
+      if (MAD && dev) x = abs_dev(x, cen);
       nan = nan || x != x;
       k[0] = f2key(x);
     }
@@ -366,9 +405,29 @@ __global__ __launch_bounds__(kBlock) void k_median_select(const RedArgs a) {
   if (tid == 0) nanflag = 0;
   uint32_t pre0 = 0, pre1 = 0;                       // key bits fixed so far
   uint32_t r0 = (uint32_t)((F - 1) / 2), r1 = (uint32_t)(F / 2);  // rank among the prefix's keys
-  for (int pass = 0; pass < 4; ++pass) {
-    const int shift = 24 - 8 * pass;
-    const uint32_t mask = pass == 0 ? 0u : 0xffffffffu << (shift + 8);
+  for (int pass = 0; pass < (MAD ? 8 : 4); ++pass) {
+    if (MAD && pass == 4) {  // the median is known: the same four passes over |x - cen|
+      cen = median_of(pre0, pre1, F & 1, false);  // (a NaN block: NaN below, whatever cen is)
+      dev = true;
+      if (REG) {
+#pragma unroll
+        for (int it = 0; it < NREG; ++it) {
+          if ((int64_t)it * kBlock + tid < n) {
+#pragma unroll
+            for (int c = 0; c < KPI; ++c) {
+              const float d = abs_dev(key2f(keys[it * KPI + c]), cen);
+              nan = nan || d != d;
+              keys[it * KPI + c] = f2key(d);
+            }
+          }
+        }
+      }
+      pre0 = pre1 = 0;
+      r0 = (uint32_t)((F - 1) / 2), r1 = (uint32_t)(F / 2);
+    }
+    const int ps = MAD ? pass & 3 : pass;  // the pass of this selection
+    const int shift = 24 - 8 * ps;
+    const uint32_t mask = ps == 0 ? 0u : 0xffffffffu << (shift + 8);
     const bool same = pre0 == pre1;
     hist[0][tid] = 0;
     hist[1][tid] = 0;
@@ -393,7 +452,7 @@ __global__ __launch_bounds__(kBlock) void k_median_select(const RedArgs a) {
         for (int c = 0; c < KPI; ++c) count(k[c], valid);
       }
     }
-    if (pass == 0 && nan) nanflag = 1;
+    if (ps == 0 && nan) nanflag = 1;
     __syncthreads();
     // inclusive scan of the 256 bins: in the wave, then over the waves
     const uint32_t c0 = hist[0][tid], c1 = same ? c0 : hist[1][tid];
@@ -415,7 +474,10 @@ __global__ __launch_bounds__(kBlock) void k_median_select(const RedArgs a) {
     pre1 |= sel[1][0] << shift;
     r1 = sel[1][1];
   }
-  if (tid == 0) *o = median_of(pre0, pre1, F & 1, nanflag != 0);
+  if (tid == 0) {
+    const float m = median_of(pre0, pre1, F & 1, nanflag != 0);
+    *o = MAD ? mad_scale(m) : m;
+  }
 }
 
 }  // namespace
@@ -444,7 +506,7 @@ int plan_stats(RedArgs &a, int op, bool words, int xcd_lg, Plan *pp) {
   };
   // F = 1: fqav(A, n <= 1) returns A whatever f is (src/gbtworkerfunctions.jl:17),
   // which is what the median of one element copies
-  if (op == BLDP_OP_MEDIAN || F == 1) {
+  if (median_op(op) || F == 1) {  // (mad: the median's path, its selection run twice)
     if (F >= ((int64_t)1 << 31))
       return set_error(BLDP_EINVAL, "median: fqavby=%lld is beyond 2^31 - 1", (long long)F);
     if (F <= kSortMaxF) {
@@ -461,7 +523,8 @@ int plan_stats(RedArgs &a, int op, bool words, int xcd_lg, Plan *pp) {
   // one block per workgroup, or kBlock / lpg of them side by side
   a.ntiles = p.lpg == kBlock ? p.nout : (p.nout + kBlock / p.lpg - 1) / (kBlock / p.lpg);
   if (a.ntiles > INT32_MAX)
-    return set_error(BLDP_EINVAL, "median/var/std: %lld blocks of %lld are too many for one launch",
+    return set_error(BLDP_EINVAL,
+                     "median/var/std/mad: %lld blocks of %lld are too many for one launch",
                      (long long)p.nout, (long long)F);
   p.grid = a.ntiles;
   p.ws_bytes = 0;
@@ -491,6 +554,7 @@ hipError_t launch_stats(const RedArgs &a, const Plan &p, int op, hipStream_t s) 
   if (p.grid <= 0) return hipSuccess;
   const dim3 grid((unsigned)p.grid, (unsigned)a.nbank);
   const bool vec = a.k4 != 0;
+  const bool mad = op == BLDP_OP_MAD && a.F > 1;  // (F = 1: the copy, as every op)
 #define BLDP_VECSEL(KN, N) (vec ? KN<N, true> : KN<N, false>)
   switch (p.path) {
     case PATH_MOMENTS:
@@ -505,6 +569,9 @@ hipError_t launch_stats(const RedArgs &a, const Plan &p, int op, hipStream_t s) 
         case kBlock: return launch1(vec ? k_mom_block<true> : k_mom_block<false>, grid, s, a, op);
       }
       break;
+#undef BLDP_VECSEL
+#define BLDP_MEDSEL(KN, A, B) (mad ? KN<A, B, true> : KN<A, B, false>)
+#define BLDP_VECSEL(KN, N) (vec ? BLDP_MEDSEL(KN, N, true) : BLDP_MEDSEL(KN, N, false))
     case PATH_MEDIAN_SORT:
       switch (p.lpg) {  // lanes of 4 keys
         case 1: return launch1(BLDP_VECSEL(k_median_sort, 4), grid, s, a);
@@ -514,12 +581,14 @@ hipError_t launch_stats(const RedArgs &a, const Plan &p, int op, hipStream_t s) 
         case 16: return launch1(BLDP_VECSEL(k_median_sort, 64), grid, s, a);
       }
       break;
-#undef BLDP_VECSEL
     case PATH_MEDIAN_SELECT:
-      return launch1(vec ? k_median_select<true, true> : k_median_select<false, true>, grid, s, a);
+      return launch1(vec ? BLDP_MEDSEL(k_median_select, true, true)
+                         : BLDP_MEDSEL(k_median_select, false, true), grid, s, a);
     case PATH_MEDIAN_STREAM:
-      return launch1(vec ? k_median_select<true, false> : k_median_select<false, false>, grid, s,
-                     a);
+      return launch1(vec ? BLDP_MEDSEL(k_median_select, true, false)
+                         : BLDP_MEDSEL(k_median_select, false, false), grid, s, a);
+#undef BLDP_VECSEL
+#undef BLDP_MEDSEL
   }
   return hipErrorInvalidValue;
 }

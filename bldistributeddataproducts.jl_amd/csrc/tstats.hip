@@ -38,6 +38,10 @@
 //              pass also tells how many keys equal the selected one; rank T/2
 //              of an even block is that key again, or else the smallest key
 //              above it, found by a fifth pass.
+//   mad        (stats.hip's rule) the median's two forms with their selection
+//              run twice: the register form sorts the keys of |x - median| made
+//              from its sorted keys, the split form repeats its passes forming
+//              the deviations from the block as it re-reads it.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -112,7 +116,32 @@ constexpr uint32_t kPadKey = 0xffffffffu;  // above every non-NaN key
 // ---------------------------------------------------------------------------
 // T <= TP <= 32: the block in registers
 
-template <int TP, int CPL, bool MED>
+// Bitonic network over the time index of a lane's TP keys per column: runs of
+// kk keys, ascending where (e & kk) == 0; every index is a compile-time constant.
+template <int TP, int CPL>
+__device__ __forceinline__ void bitonic_cols(uint32_t (&k)[TP][CPL]) {
+#pragma unroll
+  for (int kk = 2; kk <= TP; kk *= 2) {
+#pragma unroll
+    for (int j = kk / 2; j >= 1; j /= 2) {
+#pragma unroll
+      for (int e = 0; e < TP; ++e) {
+        if ((e & j) == 0) {
+          const bool up = kk == TP || (e & kk) == 0;
+#pragma unroll
+          for (int c = 0; c < CPL; ++c) {
+            const uint32_t lo = min(k[e][c], k[e | j][c]), hi = max(k[e][c], k[e | j][c]);
+            k[e][c] = up ? lo : hi;
+            k[e | j][c] = up ? hi : lo;
+          }
+        }
+      }
+    }
+  }
+}
+
+// MED: 0 var / std, 1 median, 2 mad (the network runs again over |x - median|)
+template <int TP, int CPL, int MED>
 __global__ __launch_bounds__(kBlock) void k_tstat_regs(const TStatArgs a, const int op) {
   const int64_t tile = xcd_order(blockIdx.x, gridDim.x, a.xcd_lg);
   const int64_t item = tile * kBlock + threadIdx.x;
@@ -164,37 +193,40 @@ __global__ __launch_bounds__(kBlock) void k_tstat_regs(const TStatArgs a, const 
           k[t][c] = kPadKey;
         }
       }
-    // bitonic network over the time index: runs of kk keys, ascending where
-    // (e & kk) == 0; every index is a compile-time constant
-#pragma unroll
-    for (int kk = 2; kk <= TP; kk *= 2) {
-#pragma unroll
-      for (int j = kk / 2; j >= 1; j /= 2) {
-#pragma unroll
-        for (int e = 0; e < TP; ++e) {
-          if ((e & j) == 0) {
-            const bool up = kk == TP || (e & kk) == 0;
-#pragma unroll
-            for (int c = 0; c < CPL; ++c) {
-              const uint32_t lo = min(k[e][c], k[e | j][c]), hi = max(k[e][c], k[e | j][c]);
-              k[e][c] = up ? lo : hi;
-              k[e | j][c] = up ? hi : lo;
-            }
-          }
-        }
-      }
-    }
+    bitonic_cols<TP, CPL>(k);
     // ranks (T-1)/2 and T/2 (the same for odd T); the padding sorts above them
     const int q0 = (T - 1) / 2, q1 = T / 2;
-#pragma unroll
-    for (int c = 0; c < CPL; ++c) {
-      uint32_t k0 = 0, k1 = 0;
+    auto ranks = [&](int c, uint32_t &k0, uint32_t &k1) {
+      k0 = 0, k1 = 0;
 #pragma unroll
       for (int e = 0; e < TP; ++e) {
         k0 = e == q0 ? k[e][c] : k0;
         k1 = e == q1 ? k[e][c] : k1;
       }
-      o[c] = median_of(k0, k1, T & 1, nan[c]);
+    };
+    if constexpr (MED == 2) {
+      // the sorted keys (the padding is at e >= T) become those of |x - median|
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) {
+        uint32_t k0, k1;
+        ranks(c, k0, k1);
+        const float cen = median_of(k0, k1, T & 1, false);  // (a NaN block: NaN below)
+#pragma unroll
+        for (int e = 0; e < TP; ++e)
+          if (e < T) {
+            const float d = abs_dev(key2f(k[e][c]), cen);
+            nan[c] = nan[c] || d != d;
+            k[e][c] = f2key(d);
+          }
+      }
+      bitonic_cols<TP, CPL>(k);
+    }
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+      uint32_t k0, k1;
+      ranks(c, k0, k1);
+      const float m = median_of(k0, k1, T & 1, nan[c]);
+      o[c] = MED == 2 ? mad_scale(m) : m;
     }
   }
 }
@@ -373,34 +405,41 @@ __global__ __launch_bounds__(kBlock) void k_tstat_mom_finish(const TStatArgs a, 
       op == BLDP_OP_STD ? sqrtf(var) : var;
 }
 
-template <int CPL>
-__global__ __launch_bounds__(kBlock) void k_tstat_med_split(const TStatArgs a) {
-  __shared__ uint32_t hist[kMedCols][256];
-  __shared__ uint32_t rank[2][kMedCols];  // of the wanted key among the prefix's keys, by pass parity
-  __shared__ uint32_t seld[kMedCols];     // the digit selected by the pass
-  __shared__ uint32_t selc[kMedCols];     // how many of the prefix's keys have it
-  __shared__ uint32_t mingt[kMedCols];    // smallest key above the selected one
-  __shared__ int nanflag[kMedCols];
-  const SplitGeo g = split_geo(a);
+// k_tstat_med_split's LDS arrays, per workgroup column (<= kMedCols)
+struct MedShared {
+  uint32_t (*hist)[256];
+  uint32_t (*rank)[kMedCols];  // [2]: of the wanted key among the prefix's keys, by pass parity
+  uint32_t *seld;              // the digit selected by the pass
+  uint32_t *selc;              // how many of the prefix's keys have it
+  uint32_t *mingt;             // smallest key above the selected one
+  int *nanflag;
+};
+
+// The select of a workgroup's tile: four passes for pre = the key of rank
+// (T-1)/2 of every column, and for even T a fifth for sh.mingt.  DEV: the keys
+// are those of |x - cen| (mad's second selection; sh.nanflag is kept).
+template <int CPL, bool DEV>
+__device__ __forceinline__ void med_select(const TStatArgs &a, const SplitGeo &g, const float *p,
+                                           const MedShared &sh, const float (&cen)[CPL],
+                                           uint32_t (&pre)[CPL]) {
   const int tid = threadIdx.x;
   const int64_t T = a.T;
-  const float *p = a.in[blockIdx.y] + a.in_off + (g.ok ? g.cg : 0) * CPL * a.in_cs +
-                   g.i * a.in_ld_i + g.b * T * a.in_ld_t;
   const int lc0 = g.tx * CPL;  // this lane's first column of the workgroup's (lx * CPL <= kMedCols)
+  // the value whose key is counted
+  auto val = [&](float x, int c) { return DEV ? abs_dev(x, cen[c]) : x; };
   if (tid < kMedCols) {
-    rank[0][tid] = (uint32_t)((T - 1) / 2);
-    seld[tid] = 0;
-    selc[tid] = 0;
-    mingt[tid] = kPadKey;
-    nanflag[tid] = 0;
+    sh.rank[0][tid] = (uint32_t)((T - 1) / 2);
+    sh.seld[tid] = 0;
+    sh.selc[tid] = 0;
+    sh.mingt[tid] = kPadKey;
+    if (!DEV) sh.nanflag[tid] = 0;
   }
-  uint32_t pre[CPL];  // key bits fixed so far
 #pragma unroll
   for (int c = 0; c < CPL; ++c) pre[c] = 0;
   for (int pass = 0; pass < 4; ++pass) {
     const int shift = 24 - 8 * pass;
     const uint32_t mask = ~(0xffffffffu >> (8 * pass));  // the bits fixed so far
-    for (int k = tid; k < kMedCols * 256; k += kBlock) (&hist[0][0])[k] = 0;
+    for (int k = tid; k < kMedCols * 256; k += kBlock) (&sh.hist[0][0])[k] = 0;
     __syncthreads();
     if (g.ok) {
       // a run of equal digits is counted once (spectra share their exponent byte)
@@ -414,6 +453,7 @@ __global__ __launch_bounds__(kBlock) void k_tstat_med_split(const TStatArgs a) {
         ldcols<CPL>(p + t * a.in_ld_t, x);
 #pragma unroll
         for (int c = 0; c < CPL; ++c) {
+          x[c] = val(x[c], c);
           nan[c] = nan[c] || x[c] != x[c];
           const uint32_t key = f2key(x[c]);
           if ((key & mask) == pre[c]) {
@@ -421,7 +461,7 @@ __global__ __launch_bounds__(kBlock) void k_tstat_med_split(const TStatArgs a) {
             if (d == rd[c]) {
               ++rn[c];
             } else {
-              if (rn[c]) atomicAdd(&hist[lc0 + c][rd[c]], rn[c]);
+              if (rn[c]) atomicAdd(&sh.hist[lc0 + c][rd[c]], rn[c]);
               rd[c] = d;
               rn[c] = 1;
             }
@@ -430,8 +470,8 @@ __global__ __launch_bounds__(kBlock) void k_tstat_med_split(const TStatArgs a) {
       }
 #pragma unroll
       for (int c = 0; c < CPL; ++c) {
-        if (rn[c]) atomicAdd(&hist[lc0 + c][rd[c]], rn[c]);
-        if (pass == 0 && nan[c]) nanflag[lc0 + c] = 1;
+        if (rn[c]) atomicAdd(&sh.hist[lc0 + c][rd[c]], rn[c]);
+        if (pass == 0 && nan[c]) sh.nanflag[lc0 + c] = 1;
       }
     }
     __syncthreads();
@@ -439,9 +479,9 @@ __global__ __launch_bounds__(kBlock) void k_tstat_med_split(const TStatArgs a) {
     // each, a prefix over them, and the lane whose bins hold it walks them
     {
       const int col = tid / kScanLanes, part = tid % kScanLanes;
-      const uint32_t r = rank[pass & 1][col];
+      const uint32_t r = sh.rank[pass & 1][col];
       uint32_t mine = 0;
-      for (int j = 0; j < kScanBins; ++j) mine += hist[col][part * kScanBins + j];
+      for (int j = 0; j < kScanBins; ++j) mine += sh.hist[col][part * kScanBins + j];
       uint32_t incl = mine;
 #pragma unroll
       for (int w = 1; w < kScanLanes; w *= 2) {
@@ -451,23 +491,22 @@ __global__ __launch_bounds__(kBlock) void k_tstat_med_split(const TStatArgs a) {
       uint32_t acc = incl - mine;
       const bool here = mine && acc <= r && r < incl;
       for (int j = 0; j < kScanBins; ++j) {
-        const uint32_t n = hist[col][part * kScanBins + j];
+        const uint32_t n = sh.hist[col][part * kScanBins + j];
         if (here && acc <= r && r < acc + n) {
-          seld[col] = (uint32_t)(part * kScanBins + j);
-          selc[col] = n;
-          rank[(pass + 1) & 1][col] = r - acc;
+          sh.seld[col] = (uint32_t)(part * kScanBins + j);
+          sh.selc[col] = n;
+          sh.rank[(pass + 1) & 1][col] = r - acc;
         }
         acc += n;
       }
     }
     __syncthreads();
 #pragma unroll
-    for (int c = 0; c < CPL; ++c) pre[c] |= seld[lc0 + c] << shift;
+    for (int c = 0; c < CPL; ++c) pre[c] |= sh.seld[lc0 + c] << shift;
   }
   // pre = the key of rank (T-1)/2; selc of them are equal, and it is number
   // rank[0] among those (four passes: parity 0 again)
-  const bool odd = (T & 1) != 0;
-  if (!odd) {
+  if ((T & 1) == 0) {
     if (g.ok) {
       uint32_t mn[CPL];
 #pragma unroll
@@ -478,22 +517,57 @@ __global__ __launch_bounds__(kBlock) void k_tstat_med_split(const TStatArgs a) {
         ldcols<CPL>(p + t * a.in_ld_t, x);
 #pragma unroll
         for (int c = 0; c < CPL; ++c) {
-          const uint32_t key = f2key(x[c]);
+          const uint32_t key = f2key(val(x[c], c));
           if (key > pre[c]) mn[c] = min(mn[c], key);
         }
       }
 #pragma unroll
-      for (int c = 0; c < CPL; ++c) atomicMin(&mingt[lc0 + c], mn[c]);
+      for (int c = 0; c < CPL; ++c) atomicMin(&sh.mingt[lc0 + c], mn[c]);
     }
     __syncthreads();
+  }
+}
+
+// MAD: the select runs twice, over the keys of x for the columns' medians cen,
+// then over those of |x - cen|.
+template <int CPL, bool MAD>
+__global__ __launch_bounds__(kBlock) void k_tstat_med_split(const TStatArgs a) {
+  __shared__ uint32_t hist[kMedCols][256];
+  __shared__ uint32_t rank[2][kMedCols];
+  __shared__ uint32_t seld[kMedCols];
+  __shared__ uint32_t selc[kMedCols];
+  __shared__ uint32_t mingt[kMedCols];
+  __shared__ int nanflag[kMedCols];
+  const MedShared sh{hist, rank, seld, selc, mingt, nanflag};
+  const SplitGeo g = split_geo(a);
+  const int64_t T = a.T;
+  const float *p = a.in[blockIdx.y] + a.in_off + (g.ok ? g.cg : 0) * CPL * a.in_cs +
+                   g.i * a.in_ld_i + g.b * T * a.in_ld_t;
+  const int lc0 = g.tx * CPL;
+  const bool odd = (T & 1) != 0;
+  float cen[CPL];
+  uint32_t pre[CPL];  // key bits fixed so far
+#pragma unroll
+  for (int c = 0; c < CPL; ++c) cen[c] = 0.0f;
+  med_select<CPL, false>(a, g, p, sh, cen, pre);
+  // the key of rank T/2 of an even block: pre again, or the smallest above it
+  auto rank1 = [&](int c) {
+    const int lc = lc0 + c;
+    return sh.rank[0][lc] + 1 < sh.selc[lc] ? pre[c] : sh.mingt[lc];
+  };
+  if constexpr (MAD) {
+#pragma unroll
+    for (int c = 0; c < CPL; ++c)
+      cen[c] = median_of(pre[c], rank1(c), odd, false);  // (a NaN block: NaN below)
+    __syncthreads();  // (rank, selc and mingt are read: the second selection resets them)
+    med_select<CPL, true>(a, g, p, sh, cen, pre);
   }
   if (g.ok && g.ty == 0) {
     float *o = a.out + blockIdx.y * a.out_bank + g.cg * CPL + g.i * a.out_ld_i + g.b * a.out_ld_b;
 #pragma unroll
     for (int c = 0; c < CPL; ++c) {
-      const int lc = lc0 + c;
-      const uint32_t k1 = rank[0][lc] + 1 < selc[lc] ? pre[c] : mingt[lc];
-      o[c] = median_of(pre[c], k1, odd, nanflag[lc] != 0);
+      const float m = median_of(pre[c], rank1(c), odd, sh.nanflag[lc0 + c] != 0);
+      o[c] = MAD ? mad_scale(m) : m;
     }
   }
 }
@@ -509,7 +583,8 @@ int pow2_ceil_log2(int64_t n, int cap) {
 int plan_tstat(TStatArgs &a, int op, bool words, int num_cus, int xcd_lg, TStatPlan *pp) {
   TStatPlan p{};
   const int64_t T = a.T;
-  const bool med = op == BLDP_OP_MEDIAN;
+  const bool med = median_op(op);  // (mad: the median's path, its selection run twice)
+  const int rounds = op == BLDP_OP_MAD ? 2 : 1;
   a.vec = (words && a.in_cs == 1 && a.nc % 4 == 0) ? 1 : 0;  // float4 columns
   const int cpl = a.vec ? 4 : 1;
   a.ncg = a.nc / cpl;
@@ -526,7 +601,7 @@ int plan_tstat(TStatArgs &a, int op, bool words, int num_cus, int xcd_lg, TStatP
   if (T <= kRegMaxT) {
     p.path = med ? TSTAT_REGS_MEDIAN : TSTAT_REGS_MOMENTS;
     p.tsplit = 1;
-    p.passes = 1;
+    p.passes = rounds;
     const int64_t items = a.ncg * a.ni * a.nb;
     grid = (items + kBlock - 1) / kBlock;
     // the per-XCD tile order where neighbouring workgroups read neighbouring
@@ -560,14 +635,14 @@ int plan_tstat(TStatArgs &a, int op, bool words, int num_cus, int xcd_lg, TStatP
     a.ctiles = (a.ncg + ((int64_t)1 << lg) - 1) >> lg;
     p.path = med ? TSTAT_SPLIT_MEDIAN : a.nchunk > 1 ? TSTAT_CHUNK_MOMENTS : TSTAT_SPLIT_MOMENTS;
     p.tsplit = kBlock >> lg;
-    p.passes = med ? (T % 2 ? 4 : 5) : 2;
+    p.passes = med ? rounds * (T % 2 ? 4 : 5) : 2;
     grid = a.ctiles * a.nchunk * a.ni * a.nb;
     if (a.nchunk > 1)
       p.ws_bytes = (size_t)2 * a.nchunk * a.nbank * a.nb * a.ni * a.nc * sizeof(double);
   }
   if (grid > INT32_MAX)
     return set_error(BLDP_EINVAL,
-                     "tavfunc median/var/std: %lld blocks of %lld spectra are too many for one "
+                     "tavfunc median/var/std/mad: %lld blocks of %lld spectra are too many for one "
                      "launch",
                      (long long)a.nb, (long long)T);
   p.grid = grid;
@@ -588,11 +663,16 @@ hipError_t launch1(void (*kn)(Args...), dim3 grid, hipStream_t s, Args... args) 
   return hipGetLastError();
 }
 
+template <int TP, int CPL>
+hipError_t launch_regs_cpl(const TStatArgs &a, bool med, dim3 grid, int op, hipStream_t s) {
+  if (!med) return launch1(k_tstat_regs<TP, CPL, 0>, grid, s, a, op);
+  return launch1(op == BLDP_OP_MAD ? k_tstat_regs<TP, CPL, 2> : k_tstat_regs<TP, CPL, 1>, grid, s,
+                 a, op);
+}
 template <int TP>
 hipError_t launch_regs(const TStatArgs &a, bool med, dim3 grid, int op, hipStream_t s) {
-  if (a.vec)
-    return launch1(med ? k_tstat_regs<TP, 4, true> : k_tstat_regs<TP, 4, false>, grid, s, a, op);
-  return launch1(med ? k_tstat_regs<TP, 1, true> : k_tstat_regs<TP, 1, false>, grid, s, a, op);
+  return a.vec ? launch_regs_cpl<TP, 4>(a, med, grid, op, s)
+               : launch_regs_cpl<TP, 1>(a, med, grid, op, s);
 }
 }  // namespace
 
@@ -613,7 +693,9 @@ hipError_t launch_tstat(const TStatArgs &a, const TStatPlan &p, int op, hipStrea
     case TSTAT_SPLIT_MOMENTS:
       return launch1(a.vec ? k_tstat_mom_split<4> : k_tstat_mom_split<1>, grid, s, a, op);
     case TSTAT_SPLIT_MEDIAN:
-      return launch1(a.vec ? k_tstat_med_split<4> : k_tstat_med_split<1>, grid, s, a);
+      if (op == BLDP_OP_MAD)
+        return launch1(a.vec ? k_tstat_med_split<4, true> : k_tstat_med_split<1, true>, grid, s, a);
+      return launch1(a.vec ? k_tstat_med_split<4, false> : k_tstat_med_split<1, false>, grid, s, a);
     case TSTAT_CHUNK_MOMENTS: {
       if (!a.ws) return hipErrorInvalidValue;
       const hipStream_t st = s;

@@ -1202,8 +1202,9 @@ size_t dtype_size(int dtype) {
 }
 
 int typed_out_dtype(int dtype, int op) {
-  if (!dtype_size(dtype) || op < BLDP_OP_SUM || op > BLDP_OP_MEDIAN) return -1;
-  // Statistics' var / std / median: Float32 stays, everything else is Float64
+  if (!dtype_size(dtype) || ((op < BLDP_OP_SUM || op > BLDP_OP_MEDIAN) && op != BLDP_OP_MAD))
+    return -1;
+  // Statistics' var / std / median, and mad: Float32 stays, everything else is Float64
   if (stat_op(op)) return dtype == BLDP_DT_F32 ? BLDP_DT_F32 : BLDP_DT_F64;
   if (op == BLDP_OP_MAX || op == BLDP_OP_MIN) return dtype;
   if (dtype == BLDP_DT_F32) return BLDP_DT_F32;

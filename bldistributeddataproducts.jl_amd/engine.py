@@ -215,7 +215,7 @@ def _dtype_code(dt):
 
 
 def _check_stat(op: str, tavby, dtype=None) -> None:
-    """var / std / median: no time integration, Float32 on the GPU (TypeError,
+    """var / std / median / mad: no time integration, Float32 on the GPU (TypeError,
     as Julia's MethodError for an fqavfunc the call does not fit)."""
     if op not in _lib.STAT_OPS:
         return
@@ -229,7 +229,7 @@ def _check_stat(op: str, tavby, dtype=None) -> None:
 def out_dtype(dtype, op: str) -> np.dtype:
     """fqav's result element type for input `dtype` (Julia's; bldp_reduce_out_dtype):
     sum widens integers to (U)Int64, mean is Float64, max / min keep the type;
-    var / std / median are Float32 of Float32 and Float64 of anything else."""
+    var / std / median / mad are Float32 of Float32 and Float64 of anything else."""
     code = _dtype_code(dtype)
     if code is None:
         raise TypeError(f"unsupported element type {dtype}")
@@ -556,7 +556,7 @@ def band_reduce_multi(banks, fqavby=1, tavby=1, op="sum", win=None, root=0, out=
 def _tstat_op(op) -> int:
     if op not in _lib.STAT_OPS:
         raise _lib.ArgumentError(
-            _lib.BLDP_EINVAL, f"tstat takes var/std/median, not {op!r} (sum/mean/max/min over "
+            _lib.BLDP_EINVAL, f"tstat takes var/std/median/mad, not {op!r} (sum/mean/max/min over "
                               f"time: reduce with tavby)")
     return _lib.OPS[op]
 
@@ -585,9 +585,9 @@ def _tstat_out(out, dims, device):
 
 
 def tstat(x, tavby, op, win=None, out=None, stream=None):
-    """var / std / median of every block of ``tavby`` selected spectra of every
-    (channel, IF) column, on the GPU (bldp_tstat_f32): fqav's rule on the time
-    axis with Julia's Statistics.  x: a Float32 device filterbank tensor;
+    """var / std / median / mad of every block of ``tavby`` selected spectra of
+    every (channel, IF) column, on the GPU (bldp_tstat_f32): fqav's rule on the
+    time axis with Julia's Statistics (mad: StatsBase's normalised one).  x: a Float32 device filterbank tensor;
     returns a Julia-order (nc, ni, nt/tavby) Float32 device tensor (``out``
     when given: e.g. a bank's slot of a stitched product).  tavby <= 1 copies
     the window."""

@@ -79,7 +79,8 @@ def getdata(workers, fnames, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum
             tavfunc=None):
     """src/gbt.jl:69-79 (+ tavby): an array of per-bank (nchan/fqavby, nif,
     ntime/tavby) Float32 arrays, the same size as workers/fnames.  ``tavfunc``
-    as in WorkerFunctions.getdata (the time integration's own function).
+    as in WorkerFunctions.getdata (the time integration's own function);
+    both take ``"var" | "std" | "median" | "mad"`` as there.
     ``fqavfunc="argmax" | "argmin"``: per-bank int32 arrays of block offsets."""
     return _fanout(workers, fnames,
                    lambda w, f: W.getdata(f, idxs, fqavby, fqavfunc, tavby, device=int(w),
@@ -352,7 +353,7 @@ def _band_on_device(ws, fs, idxs, fqavby, op, tavby, nfpc, timings=None, staged=
     # filter 32008): the band's chunks read and decoded as one stream per GPU
     chunked = (not raw and all(g[0] == "h5" for g in geo) and len({g[1] for g in geo}) == 1
                and os.environ.get("BLDP_NATIVE_READ", "1") != "0")
-    # var / std / median run on one device (bldp_band_reduce_multi_f32 does not
+    # var / std / median / mad run on one device (bldp_band_reduce_multi_f32 does not
     # take them): with banks on several GPUs, or staged, the band goes bank by bank
     if op in _lib.STAT_OPS and (force_copy or {int(w) for w in ws} != {root}):
         raw = chunked = False
@@ -457,7 +458,9 @@ def getband(workers, fnames, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum
     from the reduce kernel (default: the environment's BLDP_BAND_PEER_STORE,
     else off: such banks are reduced on their GPU and copied into the slot).
     ``tavfunc`` as in WorkerFunctions.getdata: each bank's last stage writes
-    its slot of the stitched product.  ``fqavfunc="argmax" | "argmin"`` returns
+    its slot of the stitched product.  ``fqavfunc`` ``"var" | "std" | "median" |
+    "mad"`` run on one device: with banks on several GPUs the band goes bank
+    by bank, each reduced on its GPU.  ``fqavfunc="argmax" | "argmin"`` returns
     the vcat of the banks' int32 offset arrays (offsets are relative to each
     block, so stitching is concatenation; stitched on the host); an index
     product has no DC spike to patch (``despike_nfpc``: TypeError)."""

@@ -12,7 +12,8 @@ module BLDPHip
 using Statistics: mean, median, var, std
 
 export gpu_init, gpu_finalize, gpu_pin, gpu_unpin, gpu_fqav, gpu_reduce, gpu_kurtosis, gpu_band,
-       gpu_tstat, gpu_argext, gpu_skewness, gpu_moments, gpu_comm_id, gpu_comm_init, gpu_comm_destroy, gpu_band_gather
+       gpu_tstat, gpu_argext, gpu_skewness, gpu_moments, gpu_comm_id, gpu_comm_init, gpu_comm_destroy, gpu_band_gather,
+       mad
 
 const libbldp = get(ENV, "BLDP_LIB", joinpath(@__DIR__, "..", "libbldp_hip.so"))
 
@@ -35,8 +36,39 @@ opcode(f) = f === sum ? Cint(0) : f === mean ? Cint(1) : f === maximum ? Cint(2)
 # Statistics' var (corrected), std and median have kernels for Float32 data
 # (BLDP_OP_VAR / _STD / _MEDIAN, no time integration); arrays of any other
 # element type return nothing here, so the reference's host fqav runs.
+# `mad` is this module's (below): BLDP_OP_MAD = 8, code 7 is unassigned.
 opcode(f, A) = opcode(f) !== nothing ? opcode(f) : !(A isa Array{Float32,3}) ? nothing :
-               f === var ? Cint(4) : f === std ? Cint(5) : f === median ? Cint(6) : nothing
+               f === var ? Cint(4) : f === std ? Cint(5) : f === median ? Cint(6) :
+               f === mad ? Cint(8) : nothing
+
+# isless order of a float as unsigned order, and the median by the kernels'
+# rule: the middle element of an odd slice, a/2 + b/2 in the element type of
+# an even one, NaN when the slice holds a NaN.
+_madkey(x::T) where {T<:AbstractFloat} = (u = reinterpret(Unsigned, x); signbit(x) ? ~u : u | ~(typemax(u) >> 1))
+function _madmedian(v::AbstractVector{T}) where {T<:AbstractFloat}
+    any(isnan, v) && return T(NaN)
+    s = sort(v; by=_madkey)
+    n = length(s)
+    isodd(n) ? s[(n + 1) ÷ 2] : s[n ÷ 2] / 2 + s[n ÷ 2 + 1] / 2
+end
+function _mad(v::AbstractVector{T}) where {T<:AbstractFloat}
+    length(v) <= 1 && return isempty(v) ? T(NaN) : v[1]
+    c = _madmedian(v)
+    T(Float64(_madmedian(abs.(v .- c))) * 1.4826022185056018)
+end
+_mad(v::AbstractVector) = _mad(Float64.(v))
+
+"""
+    mad(X; dims)
+
+The normalised median absolute deviation of every slice of `X` along `dims`
+(StatsBase's `mad(x; normalize=true)`, which has no `dims`, written out over
+slices so that it works as a `fqavfunc` / `tavfunc` on the reference's generic
+host path): `c = median(x)`, `m = median(abs.(x .- c))`, result
+`T(Float64(m) * 1.4826022185056018)` for Float32 / Float64 data and the Float64
+product for anything else.  A slice holding a NaN, or more than half one
+infinity, gives NaN.  Float32 arrays take the GPU kernels (BLDP_OP_MAD)."""
+mad(X::AbstractArray; dims=:) = dims === Colon() ? _mad(vec(X)) : mapslices(_mad, X; dims=dims)
 
 function lasterror()
     buf = Vector{UInt8}(undef, 1024)
@@ -147,8 +179,9 @@ end
 
 Drop-in for `fqav(A, n; f)` (src/gbtworkerfunctions.jl:16-20): same
 pass-through for `n <= 1`, same DimensionMismatch, GPU for sum/mean/maximum/
-minimum (and, for Float32 arrays with `tavby <= 1`, var/std/median), the
-reference's host code for any other `f`."""
+minimum (and, for Float32 arrays with `tavby <= 1`, var/std/median/mad), the
+reference's host code for any other `f` (`mad` of other element types too:
+its `dims` method is what that code calls)."""
 function gpu_fqav(A, n::Integer; f=sum, tavby::Integer=1, dev::Integer=0)
     (n <= 1 && tavby <= 1) && return A
     if A isa Array{<:GPUElt,3} && opcode(f, A) !== nothing
@@ -297,12 +330,13 @@ function gpu_kurtosis(A::Array{T,3}; idxs::Tuple=(:, :, :), dev::Integer=0,
 end
 
 # tavfunc values with a time-axis kernel of their own (csrc/tstats.hip)
-statcode(f) = f === var ? Cint(4) : f === std ? Cint(5) : f === median ? Cint(6) : nothing
+statcode(f) = f === var ? Cint(4) : f === std ? Cint(5) : f === median ? Cint(6) :
+              f === mad ? Cint(8) : nothing
 
 """
     gpu_tstat(A::Array{Float32,3}, tavby; f=median, idxs=(:,:,:), dev=0) -> Array{Float32,3}
 
-`f` (Statistics' `var`, `std` or `median`) of every block of `tavby` selected
+`f` (Statistics' `var`, `std` or `median`, or this module's `mad`) of every block of `tavby` selected
 spectra of every (channel, IF) column, fqav's rule on axis 3:
 `R[c, i, b] = f(A[idxs...][c, i, (b-1)*tavby+1 : b*tavby])`, computed on GPU `dev`
 (bldp_tstat_host_f32: the window staged on the device).  `tavby` must divide
@@ -310,7 +344,7 @@ the selected spectra (DimensionMismatch); `tavby <= 1` returns the window."""
 function gpu_tstat(A::Array{Float32,3}, tavby::Integer; f=median, idxs::Tuple=(:, :, :),
                    dev::Integer=0)
     op = statcode(f)
-    op === nothing && throw(ArgumentError("gpu_tstat takes var, std or median, not $f"))
+    op === nothing && throw(ArgumentError("gpu_tstat takes var, std, median or mad, not $f"))
     win = window(idxs, size(A))
     shp = zeros(Int64, 3)
     GC.@preserve win check(ccall((:bldp_tstat_shape, libbldp), Cint,
@@ -334,7 +368,7 @@ C_NULL, element (c, i, b) written at `out[c + i*out_ld[1] + b*out_ld[2]]`
 function gpu_tstat(in::Ptr{Float32}, dims::NTuple{3,Integer}, tavby::Integer, out::Ptr{Float32};
                    f=median, win=Ptr{Int64}(C_NULL), out_ld=nothing, stream::Ptr{Cvoid}=C_NULL)
     op = statcode(f)
-    op === nothing && throw(ArgumentError("gpu_tstat takes var, std or median, not $f"))
+    op === nothing && throw(ArgumentError("gpu_tstat takes var, std, median or mad, not $f"))
     shp = zeros(Int64, 3)
     GC.@preserve win check(ccall((:bldp_tstat_shape, libbldp), Cint,
         (Int64, Int64, Int64, Ptr{Int64}, Int64, Ptr{Int64}),
@@ -388,7 +422,7 @@ array the worker has read, on GPU `dev`.  `tavfunc === nothing`: `fqavfunc`
 reduces the fqavby x tavby block (gpu_fqav).  `tavfunc` given: the time
 integration takes its own function,
 `tav(fqav(A[idxs...], fqavby; f=fqavfunc), tavby; f=tavfunc)`; either stage is
-skipped when its factor is <= 1.  var / std / median of Float32 data run in
+skipped when its factor is <= 1.  var / std / median / mad of Float32 data run in
 gpu_tstat, sum / mean / maximum / minimum in gpu_reduce, anything else (other
 element types, other functions) in Julia on the host.  `fqavfunc === argmax` /
 `argmin` of Float32 data with `tavby <= 1` run in gpu_argext and return the

@@ -7,16 +7,20 @@ Same names, argument meanings and error behaviour as the reference:
 * ``sanitizeidxs``          — :167-169 (re-exported from .idxs);
 * ``getdata(fname, idxs, fqavby=1, fqavfunc="sum")`` — :191-195, plus the
   additive ``tavby`` time integration and its own function ``tavfunc``
-  (var / std / median over blocks of spectra included, csrc/tstats.hip);
+  (var / std / median / mad over blocks of spectra included, csrc/tstats.hip);
 * ``getfbdata`` / ``getfbh5data`` — :171-177 / :179-189;
 * ``getkurtosis``            — :197-202;
 * ``getinventory`` / headers — :35-159 (host metadata, see .readers).
 
 ``fqavfunc`` is one of ``"sum" | "mean" | "max" | "min"`` (or the Python
 builtins ``sum``/``max``/``min``, ``numpy.sum``/``mean``/``max``/``min``), or
-one of the strings ``"var" | "std" | "median"``: Julia's ``Statistics`` (the
-corrected variance, its root, and the median with ``middle(a, b) = a/2 + b/2``
-of an even block) on the GPU for Float32 data, without time integration
+one of the strings ``"var" | "std" | "median" | "mad"``: Julia's ``Statistics``
+(the corrected variance, its root, and the median with ``middle(a, b) = a/2 +
+b/2`` of an even block) and StatsBase's normalised median absolute deviation
+(the median, by the same rule, of ``|x - median(x)|`` with the difference
+rounded once, times ``1.4826022185056018`` in Float64; a block holding a NaN,
+or more than half one infinity, gives NaN)
+on the GPU for Float32 data, without time integration
 (``tavby > 1`` is a TypeError); data of other element types get the same
 rules on the host in Float64, as Julia's result type is.  Only the strings
 select them: ``numpy.std`` is the population form, not Julia's.
@@ -127,12 +131,13 @@ def _host_generic(A: np.ndarray, n: int, f) -> np.ndarray:
 
 
 def _host_stat(a: np.ndarray, n: int, op: str, win=None, axis: int = 0) -> np.ndarray:
-    """Julia's var / std / median of every n channels (``axis=0``, fqavfunc) or
-    every n spectra (``axis=2``, tavfunc) in Float64, for the
+    """Julia's var / std / median / mad of every n channels (``axis=0``,
+    fqavfunc) or every n spectra (``axis=2``, tavfunc) in Float64, for the
     element types the GPU ops do not take (integers, Float64): the corrected
     two-pass variance about the mean, its root, and the median ordered by
     isless (-0.0 < 0.0), the middle element of an odd block, a/2 + b/2 of an
-    even one, NaN when the block holds a NaN."""
+    even one, NaN when the block holds a NaN; mad is that median of
+    |x - median(x)| times StatsBase's mad_constant (n <= 1: the block itself)."""
     a = np.asarray(a)
     if win is not None:
         a = a[np.ix_(*[win[3 * k] + win[3 * k + 2] * np.arange(win[3 * k + 1])
@@ -145,17 +150,24 @@ def _host_stat(a: np.ndarray, n: int, op: str, win=None, axis: int = 0) -> np.nd
     # the reduced axis first: blocks of n along it, whatever axis it was
     m = np.moveaxis(np.asarray(a, dtype=np.float64), axis, 0)
     R = np.asfortranarray(m).reshape((n, m.shape[0] // n) + m.shape[1:], order="F")
-    with np.errstate(invalid="ignore", divide="ignore"):
+
+    def median(R):
+        bits = R.view(np.int64)
+        key = np.where(bits < 0, bits ^ np.int64(0x7FFFFFFFFFFFFFFF), bits)  # isless order
+        S = np.take_along_axis(R, np.argsort(key, axis=0, kind="stable"), axis=0)
+        r = S[n // 2] if n % 2 else S[n // 2 - 1] / 2 + S[n // 2] / 2
+        return np.where(np.isnan(R).any(axis=0), np.nan, r)
+
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
         if op == "var":
             r = np.var(R, axis=0, ddof=1)
         elif op == "std":
             r = np.std(R, axis=0, ddof=1)
+        elif op == "mad" and n > 1:
+            # the median (NaN wins again: Inf - Inf) of |x - median(x)|, normalised
+            r = median(np.abs(R - median(R)[None])) * _lib.MAD_CONSTANT
         else:
-            bits = R.view(np.int64)
-            key = np.where(bits < 0, bits ^ np.int64(0x7FFFFFFFFFFFFFFF), bits)  # isless order
-            S = np.take_along_axis(R, np.argsort(key, axis=0, kind="stable"), axis=0)
-            r = S[n // 2] if n % 2 else S[n // 2 - 1] / 2 + S[n // 2] / 2
-            r = np.where(np.isnan(R).any(axis=0), np.nan, r)
+            r = median(R)
     return np.asfortranarray(np.moveaxis(r, 0, axis))
 
 
@@ -286,7 +298,7 @@ def fqav(A, n: int, f="sum"):
     op = _opname(f)
     if _is_tensor(A):
         if op is None:
-            raise TypeError("only sum/mean/max/min/var/std/median run on device tensors")
+            raise TypeError("only sum/mean/max/min/var/std/median/mad run on device tensors")
         return engine.reduce(A, n, 1, op)
     A = np.asarray(A)
     if op is None:
@@ -366,7 +378,7 @@ def _tav_ops(fqavby, fqavfunc, tavfunc):
         raise TypeError(f"tavfunc {tavfunc!r} is not one of {sorted(_lib.OPS)}")
     op1 = _opname(fqavfunc)
     if op1 is None and fqavby > 1:
-        raise TypeError("tavfunc needs fqavfunc in sum/mean/max/min/var/std/median")
+        raise TypeError("tavfunc needs fqavfunc in sum/mean/max/min/var/std/median/mad")
     return op1 or "sum", op2
 
 
@@ -612,7 +624,7 @@ def getdata_device(fname, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum", 
             return _tav_device(got[0], got[1], fqavby, op1, tavby, op2, out=out)
     op = _opname(fqavfunc)
     if op is None:
-        raise TypeError("the device path takes fqavfunc in sum/mean/max/min/var/std/median")
+        raise TypeError("the device path takes fqavfunc in sum/mean/max/min/var/std/median/mad")
     got = window_on_device(fname, idxs, device)
     if got is None:
         return None
@@ -632,13 +644,13 @@ def getdata(fname, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum", tavby=1
     device tensor (result stays on the device).
 
     ``tavfunc=None`` (default): ``fqavfunc`` reduces the fqavby x tavby block,
-    as ever.  ``tavfunc`` given (a name of ``fqavfunc``'s, var / std / median
-    included): the time integration takes its own function, fqav's rule on
+    as ever.  ``tavfunc`` given (a name of ``fqavfunc``'s, var / std / median /
+    mad included): the time integration takes its own function, fqav's rule on
     axis 3: ``R = tav(fqav(A, fqavby; f=fqavfunc), tavby; f=tavfunc)`` with
     ``R[c, i, b] = tavfunc(B[c, i, b*tavby : (b+1)*tavby])``.  Either stage is
     skipped when its factor is <= 1; tavby must divide the selected spectra
     (DimensionMismatch).  Float32 data stay on the GPU between the stages;
-    var / std / median of other element types are Float64 from the host.
+    var / std / median / mad of other element types are Float64 from the host.
 
     ``fqavfunc="argmax" | "argmin"``: an int32 array of each block's winner's
     0-based offset ``k + fqavby * tt`` (module docstring); no ``tavfunc``."""

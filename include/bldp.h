@@ -88,7 +88,8 @@ extern "C" {
  *    "typed_kurt"; (additive, same version) bldp_op gains BLDP_OP_VAR,
  *    BLDP_OP_STD, BLDP_OP_MEDIAN for the Float32 reduce entry points; the
  *    bldp_kurtosis_blocks_*, bldp_tstat_*, bldp_argext_*, bldp_skewness_* and
- *    bldp_moments_* entry points */
+ *    bldp_moments_* entry points; (additive, same version) BLDP_OP_MAD = 8
+ *    wherever BLDP_OP_MEDIAN is taken (7 stays unassigned and invalid) */
 #define BLDP_ABI_VERSION 5
 
 #if defined(BLDP_BUILD)
@@ -102,10 +103,17 @@ extern "C" {
  * three take Float32 data and no time integration (tavby <= 1, else
  * BLDP_EINVAL); Float32 in, Float32 out.  median orders by isless
  * (-0.0 < 0.0), returns the middle element of an odd block and
- * middle(a, b) = a/2 + b/2 of an even one, and NaN for a block holding a NaN. */
+ * middle(a, b) = a/2 + b/2 of an even one, and NaN for a block holding a NaN.
+ * BLDP_OP_MAD is the normalised median absolute deviation (StatsBase's
+ * mad(x; normalize=true)) under the same conditions: c = median(x), then the
+ * median (same rule, NaN wins again) of d = |x - c| with the difference
+ * rounded once to Float32, times 1.4826022185056018 in Float64 and rounded to
+ * Float32.  fqavby <= 1 copies the window, as for every op.  7 is unassigned
+ * and BLDP_EINVAL everywhere. */
 enum bldp_op {
   BLDP_OP_SUM = 0, BLDP_OP_MEAN = 1, BLDP_OP_MAX = 2, BLDP_OP_MIN = 3,
-  BLDP_OP_VAR = 4, BLDP_OP_STD = 5, BLDP_OP_MEDIAN = 6
+  BLDP_OP_VAR = 4, BLDP_OP_STD = 5, BLDP_OP_MEDIAN = 6,
+  BLDP_OP_MAD = 8
 };
 
 /* error codes */
@@ -151,7 +159,8 @@ BLDP_API int bldp_reduce_shape(int64_t nchan, int64_t nif, int64_t ntime, const 
  * these pointers.  info = {path (0 vector, 1 narrow, 2 scalar, 3 tile,
  * 4 interleaved, 5 row, 6 narrow_mis, 7 lane; var / std: 8 moments; median:
  * 9 bitonic sort of blocks <= 64, 10 radix select with the keys in registers,
- * 11 radix select re-reading the block), lanes per group (8-11: 256 = one
+ * 11 radix select re-reading the block; mad: the median's path for its shape,
+ * the selection run twice), lanes per group (8-11: 256 = one
  * workgroup per block), waves (row
  * path: workgroup slices) splitting T, float4 per lane per row, time chunks,
  * workgroups, workspace bytes, vector output stores}.  Launches nothing. */
@@ -462,8 +471,11 @@ BLDP_API int bldp_moments_host_f32(int dev, const float *in, int64_t nchan, int6
  * result is op of that block of column (c, i): BLDP_OP_VAR (the corrected
  * variance about the mean), BLDP_OP_STD (its root) or BLDP_OP_MEDIAN (ordered
  * by isless, the middle element of an odd block, a/2 + b/2 in Float32 of an
- * even one, NaN when the block holds a NaN).  A constant block gives exactly
- * +0.0 for var / std.  Any other op is BLDP_EINVAL (sum / mean / max / min over
+ * even one, NaN when the block holds a NaN) or BLDP_OP_MAD (the normalised
+ * median absolute deviation of enum bldp_op: the median of |x - median| by the
+ * same rule, times 1.4826022185056018 in Float64, rounded to Float32).  A
+ * constant block gives exactly
+ * +0.0 for var / std / mad.  Any other op is BLDP_EINVAL (sum / mean / max / min over
  * time are bldp_reduce_* with tavby); a tavby that does not divide nt is
  * BLDP_EDIM, a window outside the array BLDP_EBOUNDS.  tavby <= 1 copies the
  * window (fqav's n <= 1 rule, as bldp_reduce_f32 with fqavby = tavby = 1).
@@ -473,7 +485,11 @@ BLDP_API int bldp_moments_host_f32(int dev, const float *in, int64_t nchan, int6
  * columns with float4 loads: unit channel step, nc a multiple of 4); longer
  * blocks are split over the time slices of a workgroup that meet through LDS,
  * var / std in two passes with Float64 accumulators, the median by an 8-bit
- * radix select that re-reads the block every pass.  One launch, no workspace;
+ * radix select that re-reads the block every pass.  mad runs the median's
+ * selection twice in the same kernel (the register form on its registers, the
+ * split form re-reading the block and forming |x - median| on the fly) and
+ * reports the median's path with passes = 2 (registers), 8 (split, odd tavby)
+ * or 10 (split, even tavby).  One launch, no workspace;
  * var / std of blocks too few to fill the GPU are also cut into time chunks
  * across workgroups (three launches, Float64 partials in library scratch leased
  * for the call, added in a fixed order).
