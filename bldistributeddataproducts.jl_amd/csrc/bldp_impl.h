@@ -1,5 +1,6 @@
 // Internal launch interface shared by kernels.hip and api.hip (not part of the ABI).
 #pragma once
+#include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -113,18 +114,29 @@ enum Path { PATH_VEC = 0, PATH_NARROW = 1, PATH_SCALAR = 2, PATH_TILE = 3, PATH_
             PATH_MOMENTS = 8, PATH_MEDIAN_SORT = 9, PATH_MEDIAN_SELECT = 10,
             PATH_MEDIAN_STREAM = 11 };
 
+// The kernel a Float32 reduce plan starts: one value per k_reduce_* entry of
+// kernels.hip (plan_reduce chooses, launch_reduce switches on it).
+enum ReduceKernel { RK_VEC = 0, RK_WAVET, RK_IL, RK_ROW, RK_ROWS, RK_ROWT, RK_NARROW, RK_NARROWT,
+                    RK_NARROW_MIS, RK_LANE, RK_LANET, RK_LANES, RK_COL3, RK_TILE, RK_SCALAR,
+                    RK_COUNT };
+
 struct Plan {
   int path;
   int lpg;                   // lanes per output group (vector path; stats.hip: 256 = a workgroup)
-  bool lanet;                // lane path: k_reduce_lanet (NRW rows per lane) not k_reduce_lane
-  bool col3;                 // lane path at fqavby = 12: k_reduce_col3 (float4 columns)
   int64_t grid;             // blocks of 256 threads
   int64_t nout;              // outputs per bank
   size_t ws_bytes;           // partial workspace required (0 if nchunk == 1)
+  // plan_reduce only: the kernel and its launch, as launch_reduce starts them
+  int kernel;                // ReduceKernel
+  int nrw;                   // k_reduce_rowt / narrowt: rows per lane (their NRW)
+  uint32_t gx, gy, gz;       // grid
+  uint32_t block;            // threads per workgroup
+  uint32_t shm;              // dynamic LDS bytes
 };
 
-// Fill the launch geometry (path, lpg, ts, k4, nchunk, rows_per_chunk,
-// blocks_c, grid) for an args struct whose shape/stride fields are set.
+// Choose the kernel and fill its launch (the plan's kernel and geometry, and
+// ts, k4, nchunk, rows_per_chunk, blocks_c, ntiles, ... of the args, as that
+// kernel reads them) for an args struct whose shape/stride fields are set.
 // `aligned` says whether 16-byte vector loads of every group are legal;
 // `rows16` whether every bank pointer is 16-byte aligned and the IF/time
 // pitches are multiples of 4 floats (any channel offset and step); `words`
@@ -135,8 +147,25 @@ Plan plan_reduce(RedArgs &a, bool aligned, bool rows16, bool words, int num_cus,
 hipError_t launch_reduce(const RedArgs &a, const Plan &p, int op, hipStream_t s);
 // events the next launch_reduce's dispatches carry (null, null: none)
 void set_launch_events(hipEvent_t start, hipEvent_t stop);
-// those events, for a launch outside kernels.hip that carries both on one dispatch
+// those events, for the next dispatch (the start event is handed out once)
 void take_launch_events(hipEvent_t *start, hipEvent_t *stop);
+// One dispatch of kn; it carries the thread's timing events when they are set
+// (hipExtLaunchKernel).  shm: dynamic LDS bytes; a workgroup's allocation above
+// 64 KiB needs the kernel's attribute raised.
+template <typename... Args>
+hipError_t launch_kernel(void (*kn)(Args...), dim3 grid, dim3 block, unsigned shm, hipStream_t s,
+                         Args... args) {
+  if (shm > 65536u)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kn),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+  hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+  take_launch_events(&ev_start, &ev_stop);
+  if (ev_stop)
+    hipExtLaunchKernelGGL(kn, grid, block, shm, s, ev_start, ev_stop, 0, args...);
+  else
+    hipLaunchKernelGGL(kn, grid, block, shm, s, args...);
+  return hipGetLastError();
+}
 
 // Workgroup x of a launch of X in the per-XCD contiguous order over 2^lg
 // XCDs: x runs on XCD x % 2^lg and takes tile (x % 2^lg) * (X / 2^lg) +

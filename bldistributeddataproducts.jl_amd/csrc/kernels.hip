@@ -23,6 +23,7 @@
 
 #include <atomic>
 #include <cstring>
+#include <type_traits>
 
 #include "bldp_impl.h"
 
@@ -205,15 +206,6 @@ constexpr int64_t kIlXcdMaxPitch = (int64_t)128 << 20;
 constexpr int64_t kRowtXcdBytes = (int64_t)1 << 30;
 
 // (xcd_order itself: bldp_impl.h, shared with stats.hip)
-
-// The short-time-block kernels (k_reduce_rowt, k_reduce_narrowt,
-// k_reduce_lanet) also take tavby = 3 and 8, not only 1, 2, 4 (plan option
-// "t38"; the 512-channel 0001 product at tavby = 3 ran one 3-row block per
-// wave with half the waves idle: 2.4-2.7 TB/s).  narrowt: fqavby = 2 at
-// tavby = 3 only (fqavby = 1 lost 7% on the 0002 band; at tavby = 8
-// narrow_tile's one full batch sums in another order).
-// profiles/r03/ab_t38_r03t.json
-#define BLDP_T38_CASES(M, X) case 3: M(X, 3) case 8: M(X, 8)
 
 // Pairwise fold of the per-lane accumulators into acc[0].
 template <int OP>
@@ -1698,278 +1690,159 @@ int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // bldp_reduce_launch_timed): the start event takes the first dispatch's start
 // and the stop event the last dispatch's end, with no marker packets queued
 // between one launch and the next (a hipEventRecord pair costs a short launch
-// a few microseconds of command-processor time).
+// a few microseconds of command-processor time).  launch_kernel (bldp_impl.h)
+// takes them for every dispatch.
 thread_local hipEvent_t t_ev_start = nullptr, t_ev_stop = nullptr;
 
-// SH: dynamic LDS bytes, here an occupancy cap (kIlShm, kRowShm, ...): a
-// workgroup's allocation above 64 KiB needs the kernel's attribute raised.
-#define BLDP_LAUNCH(KN, GR, BL, SH, ST, ...)                                          \
-  do {                                                                                \
-    if ((SH) > 65536u)                                                                \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(KN),                   \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)(SH)); \
-    if (t_ev_stop) {                                                                  \
-      hipExtLaunchKernelGGL(KN, GR, BL, SH, ST, t_ev_start, t_ev_stop, 0, __VA_ARGS__); \
-      t_ev_start = nullptr;                                                           \
-    } else {                                                                          \
-      hipLaunchKernelGGL(KN, GR, BL, SH, ST, __VA_ARGS__);                            \
-    }                                                                                 \
-  } while (0)
-
-template <int OP>
-hipError_t launch_vec(const RedArgs &a, const Plan &p, hipStream_t s) {
-  const dim3 grid((unsigned)p.grid), block(kBlock);
-  const int k4c = (a.k4 == 1 || a.k4 == 2 || a.k4 == 4 || a.k4 == 3) ? a.k4 : 0;
-#define BLDP_VEC(L, K)                                                 \
-  if (p.lpg == L && k4c == K) {                                        \
-    BLDP_LAUNCH((k_reduce_vec<OP, L, K>), grid, block, kVecShm, s, a); \
-    return hipGetLastError();                                          \
-  }
-  BLDP_VEC(64, 1) BLDP_VEC(64, 2) BLDP_VEC(64, 4) BLDP_VEC(64, 0)
-  BLDP_VEC(32, 1) BLDP_VEC(32, 0) BLDP_VEC(16, 1) BLDP_VEC(16, 0)
-  BLDP_VEC(8, 1) BLDP_VEC(8, 0) BLDP_VEC(4, 1) BLDP_VEC(4, 0)
-  BLDP_VEC(2, 1) BLDP_VEC(2, 0) BLDP_VEC(1, 1) BLDP_VEC(1, 0)
-  BLDP_VEC(1, 3) BLDP_VEC(2, 3) BLDP_VEC(4, 3) BLDP_VEC(8, 3) BLDP_VEC(16, 3) BLDP_VEC(32, 3)
-  BLDP_VEC(64, 3)
-#undef BLDP_VEC
-  return hipErrorInvalidValue;
+// The values a template parameter of the reduce kernels takes, each list
+// stated once: the planner asks contains(), the dispatcher pick()s the
+// instantiation, so the two cannot disagree.
+template <int... V>
+struct Vals {
+  static constexpr bool contains(int64_t v) { return ((v == V) || ...); }
+};
+// f(std::integral_constant<int, v>) for the listed value equal to v; false
+// when none is (or f says so).
+template <int... V, typename Fn>
+bool pick(Vals<V...>, int64_t v, Fn &&f) {
+  return ((v == V && f(std::integral_constant<int, V>{})) || ...);
 }
 
+// k_reduce_vec: lanes per group, and the compiled float4-per-lane counts (0 =
+// the generic loop; 2 and 4 exist for whole-wave groups only: K4 is odd below)
+constexpr Vals<64, 32, 16, 8, 4, 2, 1> kVecLpg;
+constexpr Vals<1, 2, 4, 3> kVecK4;
+template <int LPG>
+using VecK4c = std::conditional_t<LPG == 64, Vals<1, 2, 4, 3, 0>, Vals<1, 3, 0>>;
+// k_reduce_row / rows / rowt: float4 per group (F = 4 .. 256); rows' slices
+constexpr Vals<1, 2, 4, 8, 16, 32, 64> kRowG4;
+constexpr Vals<2, 4> kRowSlices;
+// k_reduce_il / wavet: float4 per lane per row (F = 512 .. 4096)
+constexpr Vals<2, 4, 8, 16> kIlK4;
+constexpr Vals<1, 2> kNarrowF;
+constexpr Vals<2, 3, 5, 6, 7> kLaneF;
+constexpr Vals<3, 5, 6, 7, 12> kLanetF;
+// The short time blocks (tavby) of k_reduce_rowt, k_reduce_narrowt,
+// k_reduce_lanet / lanes / col3 and k_reduce_wavet: 1, 2, 4, and also tavby =
+// 3 and 8 (plan option "t38"; the 512-channel 0001 product at tavby = 3 ran
+// one 3-row block per wave with half the waves idle: 2.4-2.7 TB/s).  narrowt:
+// fqavby = 2 at tavby = 3 only (fqavby = 1 lost 7% on the 0002 band; at tavby
+// = 8 narrow_tile's one full batch sums in another order).
+// profiles/r03/ab_t38_r03t.json.  wavet: 3 only (T = 8: -8%, ab_t38_r03w)
+constexpr Vals<1, 2, 4> kShortT;
+constexpr Vals<1, 2, 4, 3, 8> kShortT38;
+constexpr Vals<1, 2, 4, 3> kWavetT;
+template <int F>
+using NarrowtT = std::conditional_t<F == 2, Vals<1, 2, 4, 3>, Vals<1, 2, 4>>;  // the (F, T) pairs
+// rows per lane (NRW) of k_reduce_rowt / narrowt: 4 exists at T <= 2 only
+template <int T>
+using RowsPerLane = std::conditional_t<(T <= 2), Vals<4, 8, 16>, Vals<8, 16>>;
+
+// T is a short time block of list `l`: beyond 1, 2, 4 only with option t38
+template <typename L>
+bool short_t(L l, int64_t T, bool t38) {
+  return l.contains(T) && (t38 || kShortT.contains(T));
+}
+bool narrowt_pair(int64_t F, int64_t T) {
+  return pick(kNarrowF, F, [&](auto f) { return NarrowtT<decltype(f)::value>::contains(T); });
+}
+
+// The plan's kernel (p.kernel) at the instantiation its template parameters
+// name, with the plan's launch (p.gx .. p.shm); then the finalize of a
+// time-chunked plan.  A value outside its list: hipErrorInvalidValue.
 template <int OP>
 hipError_t launch_op(const RedArgs &a, const Plan &p, hipStream_t s) {
-  hipError_t e = hipSuccess;
-  const dim3 grid((unsigned)p.grid), block(kBlock);
-  if (p.path == PATH_NARROW && a.tpb > 1) {  // short time blocks, several per workgroup
-    const dim3 g3((unsigned)(a.blocks_c * cdiv(cdiv(a.nto, a.tpb), 1 << a.tsub_log2)),
-                  (unsigned)a.ni, (unsigned)a.nbank);
-#define BLDP_NARROWT(FF, TT)                                                  \
-  if ((TT) <= 2 && a.tpb == 4 / (TT))                                         \
-    BLDP_LAUNCH((k_reduce_narrowt<OP, FF, TT, ((TT) <= 2 ? 4 : 16)>), g3, block, 0, s, a); \
-  else if (a.tpb == 8 / (TT))                                                 \
-    BLDP_LAUNCH((k_reduce_narrowt<OP, FF, TT, 8>), g3, block, 0, s, a);       \
-  else                                                                        \
-    BLDP_LAUNCH((k_reduce_narrowt<OP, FF, TT, 16>), g3, block, 0, s, a);
-    if (a.F == 1 && a.T == 1) { BLDP_NARROWT(1, 1) }
-    else if (a.F == 1 && a.T == 2) { BLDP_NARROWT(1, 2) }
-    else if (a.F == 1 && a.T == 4) { BLDP_NARROWT(1, 4) }
-    else if (a.F == 2 && a.T == 1) { BLDP_NARROWT(2, 1) }
-    else if (a.F == 2 && a.T == 2) { BLDP_NARROWT(2, 2) }
-    else if (a.F == 2 && a.T == 4) { BLDP_NARROWT(2, 4) }
-    else if (a.F == 2 && a.T == 3) { BLDP_NARROWT(2, 3) }
-    else return hipErrorInvalidValue;
-#undef BLDP_NARROWT
-    return hipGetLastError();
-  }
-  if (p.path == PATH_VEC && a.tpb > 1) {  // large groups, short time blocks: k_reduce_wavet
-    constexpr int NW = 4 * 4;  // time blocks per batch x batches: see k_reduce_wavet
-    (void)NW;
-    const int64_t rw = (int64_t)a.tpb;  // time blocks per wave
-    const dim3 g3((unsigned)(a.nco * cdiv(a.nto, 4 * rw)), (unsigned)a.ni, (unsigned)a.nbank);
-    const unsigned wb = (unsigned)(a.nbank * a.nco);  // bpack: one wave per (bank, group)
-    const dim3 g3b((unsigned)cdiv(a.nto, rw), (unsigned)a.ni, 1u);
-#define BLDP_WAVETL(K, T)                                                        \
-  if (a.bpack)                                                                   \
-    BLDP_LAUNCH((k_reduce_wavet<OP, K, T, true>), g3b, dim3(64 * wb), 0, s, a);  \
-  else                                                                           \
-    BLDP_LAUNCH((k_reduce_wavet<OP, K, T, false>), g3, block, 0, s, a);          \
-  break;
-#define BLDP_WAVET_T(K)                      \
-  switch (a.T) {                             \
-    case 1: BLDP_WAVETL(K, 1)                \
-    case 2: BLDP_WAVETL(K, 2)                \
-    case 4: BLDP_WAVETL(K, 4)                \
-    case 3: BLDP_WAVETL(K, 3)                \
-    default: return hipErrorInvalidValue;    \
-  }                                          \
-  break;
-    switch (a.k4) {
-      case 2: BLDP_WAVET_T(2)
-      case 4: BLDP_WAVET_T(4)
-      case 8: BLDP_WAVET_T(8)
-      case 16: BLDP_WAVET_T(16)
-      default: return hipErrorInvalidValue;
-    }
-#undef BLDP_WAVET_T
-#undef BLDP_WAVETL
-    return hipGetLastError();
-  }
-  if (p.path == PATH_LANE && p.col3) {  // fqavby = 12, short time blocks: k_reduce_col3
-    const dim3 g3((unsigned)(a.blocks_c * cdiv(a.nto, a.tpb)), (unsigned)a.ni, 1u);
-    const dim3 b3(kCol3Threads);
-    switch (a.T) {
-      case 1: BLDP_LAUNCH((k_reduce_col3<OP, 1>), g3, b3, 0, s, a); break;
-      case 2: BLDP_LAUNCH((k_reduce_col3<OP, 2>), g3, b3, 0, s, a); break;
-      case 3: BLDP_LAUNCH((k_reduce_col3<OP, 3>), g3, b3, 0, s, a); break;
-      case 4: BLDP_LAUNCH((k_reduce_col3<OP, 4>), g3, b3, 0, s, a); break;
-      case 8: BLDP_LAUNCH((k_reduce_col3<OP, 8>), g3, b3, 0, s, a); break;
-      default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
-  if (p.path == PATH_LANE && p.lanet) {  // short time blocks, small odd groups: k_reduce_lanet
-    const dim3 g3(a.bpack ? (unsigned)(a.blocks_c * cdiv(a.nto, a.tpb))
-                          : (unsigned)(a.blocks_c * cdiv(cdiv(a.nto, a.tpb), 1 << a.tsub_log2)),
-                  (unsigned)a.ni, a.bpack ? 1u : (unsigned)a.nbank);
-#define BLDP_LANETL(FF, TT)                                        \
-  if (a.bpack)                                                     \
-    BLDP_LAUNCH((k_reduce_lanes<OP, FF, TT>), g3, block, 0, s, a); \
-  else                                                             \
-    BLDP_LAUNCH((k_reduce_lanet<OP, FF, TT>), g3, block, 0, s, a); \
-  break;
-#define BLDP_LANET_T(FF)                   \
-  switch (a.T) {                           \
-    case 1: BLDP_LANETL(FF, 1)             \
-    case 2: BLDP_LANETL(FF, 2)             \
-    case 4: BLDP_LANETL(FF, 4)             \
-    BLDP_T38_CASES(BLDP_LANETL, FF)        \
-    default: return hipErrorInvalidValue;  \
-  }                                        \
-  break;
-    switch (a.F) {
-      case 3: BLDP_LANET_T(3)
-      case 5: BLDP_LANET_T(5)
-      case 6: BLDP_LANET_T(6)
-      case 7: BLDP_LANET_T(7)
-      case 12: BLDP_LANET_T(12)
-      default: return hipErrorInvalidValue;
-    }
-#undef BLDP_LANET_T
-#undef BLDP_LANETL
-    return hipGetLastError();
-  }
-  if (p.path == PATH_VEC_ROW && a.tpb > 1) {  // short time blocks, several per workgroup
-    const dim3 g3(a.bpack ? (unsigned)(a.blocks_c * cdiv(a.nto, a.tpb))
-                          : (unsigned)(a.blocks_c * cdiv(cdiv(a.nto, a.tpb), 1 << a.tsub_log2)),
-                  (unsigned)a.ni, (unsigned)(a.bpack ? a.nbank >> a.tsub_log2 : a.nbank));
-#define BLDP_ROWTK(G, T, N)                                                \
-  if (a.bpack)                                                             \
-    BLDP_LAUNCH((k_reduce_rowt<OP, G, T, N, true>), g3, block, kRowtShm, s, a);   \
-  else                                                                     \
-    BLDP_LAUNCH((k_reduce_rowt<OP, G, T, N, false>), g3, block, kRowtShm, s, a);  \
-  break;
-#define BLDP_ROWTN(T, N)                                                                    \
-  switch (a.F / 4) {                                                                        \
-    case 1: BLDP_ROWTK(1, T, N)    \
-    case 2: BLDP_ROWTK(2, T, N)    \
-    case 4: BLDP_ROWTK(4, T, N)    \
-    case 8: BLDP_ROWTK(8, T, N)    \
-    case 16: BLDP_ROWTK(16, T, N)  \
-    case 32: BLDP_ROWTK(32, T, N)  \
-    case 64: BLDP_ROWTK(64, T, N)  \
-    default: return hipErrorInvalidValue;                                                   \
-  }
-#define BLDP_ROWT(T)                 \
-  if ((T) <= 2 && a.tpb == 4 / (T)) { \
-    BLDP_ROWTN(T, ((T) <= 2 ? 4 : 8))  \
-  } else if (a.tpb == 8 / (T)) {     \
-    BLDP_ROWTN(T, 8)                 \
-  } else if (a.tpb == 16 / (T)) {    \
-    BLDP_ROWTN(T, 16)                \
-  } else {                           \
-    return hipErrorInvalidValue;     \
-  }
-#define BLDP_ROWTC(X, T) BLDP_ROWT(T) break;
-    switch (a.T) {
-      case 1: BLDP_ROWT(1) break;
-      case 2: BLDP_ROWT(2) break;
-      case 4: BLDP_ROWT(4) break;
-      BLDP_T38_CASES(BLDP_ROWTC, 0)
-      default: return hipErrorInvalidValue;
-    }
-#undef BLDP_ROWTC
-#undef BLDP_ROWT
-#undef BLDP_ROWTN
-#undef BLDP_ROWTK
-    return hipGetLastError();
-  }
-  if (p.path == PATH_VEC_ROW && a.rsplit > 1) {  // a block's rows over 2 / 4 slices
-    const dim3 g3((unsigned)a.blocks_c, (unsigned)(a.ni * a.nto), (unsigned)a.nbank);
-#define BLDP_ROWS(S)                                                                          \
-  switch (a.F / 4) {                                                                          \
-    case 1: BLDP_LAUNCH((k_reduce_rows<OP, 1, S>), g3, block, kRowShm, s, a); break;         \
-    case 2: BLDP_LAUNCH((k_reduce_rows<OP, 2, S>), g3, block, kRowShm, s, a); break;         \
-    case 4: BLDP_LAUNCH((k_reduce_rows<OP, 4, S>), g3, block, kRowShm, s, a); break;         \
-    case 8: BLDP_LAUNCH((k_reduce_rows<OP, 8, S>), g3, block, kRowShm, s, a); break;         \
-    case 16: BLDP_LAUNCH((k_reduce_rows<OP, 16, S>), g3, block, kRowShm, s, a); break;       \
-    case 32: BLDP_LAUNCH((k_reduce_rows<OP, 32, S>), g3, block, kRowShm, s, a); break;       \
-    case 64: BLDP_LAUNCH((k_reduce_rows<OP, 64, S>), g3, block, kRowShm, s, a); break;       \
-    default: return hipErrorInvalidValue;                                                     \
-  }
-    if (a.rsplit == 2) {
-      BLDP_ROWS(2)
-    } else if (a.rsplit == 4) {
-      BLDP_ROWS(4)
-    } else {
-      return hipErrorInvalidValue;
-    }
-#undef BLDP_ROWS
-    return hipGetLastError();
-  }
-  if (p.path == PATH_VEC_ROW) {
-    const dim3 g3((unsigned)a.blocks_c, (unsigned)(a.ni * a.nto), (unsigned)a.nbank);
-    switch (a.F / 4) {
-      case 1: BLDP_LAUNCH((k_reduce_row<OP, 1>), g3, block, kRowShm, s, a); break;
-      case 2: BLDP_LAUNCH((k_reduce_row<OP, 2>), g3, block, kRowShm, s, a); break;
-      case 4: BLDP_LAUNCH((k_reduce_row<OP, 4>), g3, block, kRowShm, s, a); break;
-      case 8: BLDP_LAUNCH((k_reduce_row<OP, 8>), g3, block, kRowShm, s, a); break;
-      case 16: BLDP_LAUNCH((k_reduce_row<OP, 16>), g3, block, kRowShm, s, a); break;
-      case 32: BLDP_LAUNCH((k_reduce_row<OP, 32>), g3, block, kRowShm, s, a); break;
-      case 64: BLDP_LAUNCH((k_reduce_row<OP, 64>), g3, block, kRowShm, s, a); break;
-      default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
-  if (p.path == PATH_VEC_IL) {
-    const dim3 g3((unsigned)a.blocks_c, (unsigned)(a.ni * a.nto), (unsigned)a.nbank);
-    switch (a.k4) {
-      case 2: BLDP_LAUNCH((k_reduce_il<OP, 2, il_gpw(2)>), g3, block, kIlShm, s, a); break;
-      case 4: BLDP_LAUNCH((k_reduce_il<OP, 4, kIlGpw>), g3, block, kIlShm, s, a); break;
-      case 8: BLDP_LAUNCH((k_reduce_il<OP, 8, kIlGpw>), g3, block, kIlShm, s, a); break;
-      case 16: BLDP_LAUNCH((k_reduce_il<OP, 16, kIlGpw>), g3, block, kIlShm, s, a); break;
-      default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  } else if (p.path == PATH_VEC) {
-    e = launch_vec<OP>(a, p, s);
-  } else if (p.path == PATH_NARROW) {
-    if (a.F == 1)
-      BLDP_LAUNCH((k_reduce_narrow<OP, 1>), grid, block, kNarrowShm, s, a);
-    else
-      BLDP_LAUNCH((k_reduce_narrow<OP, 2>), grid, block, kNarrowShm, s, a);
-    e = hipGetLastError();
-  } else if (p.path == PATH_NARROW_MIS) {
-    BLDP_LAUNCH((k_reduce_narrow_mis<OP, 1>), grid, block, 0, s, a);
-    e = hipGetLastError();
-  } else if (p.path == PATH_LANE) {
-    switch (a.F) {
-      case 2: BLDP_LAUNCH((k_reduce_lane<OP, 2>), grid, block, 0, s, a); break;
-      case 3: BLDP_LAUNCH((k_reduce_lane<OP, 3>), grid, block, 0, s, a); break;
-      case 5: BLDP_LAUNCH((k_reduce_lane<OP, 5>), grid, block, 0, s, a); break;
-      case 6: BLDP_LAUNCH((k_reduce_lane<OP, 6>), grid, block, 0, s, a); break;
-      case 7: BLDP_LAUNCH((k_reduce_lane<OP, 7>), grid, block, 0, s, a); break;
-      default: return hipErrorInvalidValue;
-    }
-    e = hipGetLastError();
-  } else if (p.path == PATH_TILE) {
-    if (a.in_cs == 1)
-      BLDP_LAUNCH((k_reduce_tile<OP, true>), grid, block, 0, s, a);
-    else
-      BLDP_LAUNCH((k_reduce_tile<OP, false>), grid, block, 0, s, a);
-    e = hipGetLastError();
-  } else {
-    BLDP_LAUNCH((k_reduce_scalar<OP>), grid, block, 0, s, a);
-    e = hipGetLastError();
+  hipError_t e = hipErrorInvalidValue;
+  const auto go = [&](void (*kn)(RedArgs)) {
+    e = launch_kernel(kn, dim3(p.gx, p.gy, p.gz), dim3(p.block), p.shm, s, a);
+    return true;
+  };
+  switch (p.kernel) {
+    case RK_VEC:
+      pick(kVecLpg, p.lpg, [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        return pick(VecK4c<L>{}, kVecK4.contains(a.k4) ? a.k4 : 0, [&](auto k) {
+          return go(k_reduce_vec<OP, L, decltype(k)::value>);
+        });
+      });
+      break;
+    case RK_WAVET:  // large groups, short time blocks
+      pick(kIlK4, a.k4, [&](auto k) {
+        return pick(kWavetT, a.T, [&](auto t) {
+          constexpr int K = decltype(k)::value, T = decltype(t)::value;
+          return go(a.bpack ? k_reduce_wavet<OP, K, T, true> : k_reduce_wavet<OP, K, T, false>);
+        });
+      });
+      break;
+    case RK_IL:
+      pick(kIlK4, a.k4, [&](auto k) {
+        constexpr int K = decltype(k)::value;
+        return go(k_reduce_il<OP, K, il_gpw(K)>);
+      });
+      break;
+    case RK_ROW:
+      pick(kRowG4, a.F / 4, [&](auto g) { return go(k_reduce_row<OP, decltype(g)::value>); });
+      break;
+    case RK_ROWS:  // a block's rows over 2 / 4 slices
+      pick(kRowG4, a.F / 4, [&](auto g) {
+        return pick(kRowSlices, a.rsplit, [&](auto sl) {
+          return go(k_reduce_rows<OP, decltype(g)::value, decltype(sl)::value>);
+        });
+      });
+      break;
+    case RK_ROWT:  // short time blocks, several per workgroup
+      pick(kRowG4, a.F / 4, [&](auto g) {
+        return pick(kShortT38, a.T, [&](auto t) {
+          constexpr int G = decltype(g)::value, T = decltype(t)::value;
+          return pick(RowsPerLane<T>{}, p.nrw, [&](auto n) {
+            constexpr int N = decltype(n)::value;
+            return go(a.bpack ? k_reduce_rowt<OP, G, T, N, true> : k_reduce_rowt<OP, G, T, N, false>);
+          });
+        });
+      });
+      break;
+    case RK_NARROW:
+      pick(kNarrowF, a.F, [&](auto f) { return go(k_reduce_narrow<OP, decltype(f)::value>); });
+      break;
+    case RK_NARROWT:  // short time blocks, several per workgroup
+      pick(kNarrowF, a.F, [&](auto f) {
+        constexpr int F = decltype(f)::value;
+        return pick(NarrowtT<F>{}, a.T, [&](auto t) {
+          constexpr int T = decltype(t)::value;
+          return pick(RowsPerLane<T>{}, p.nrw, [&](auto n) {
+            return go(k_reduce_narrowt<OP, F, T, decltype(n)::value>);
+          });
+        });
+      });
+      break;
+    case RK_NARROW_MIS: go(k_reduce_narrow_mis<OP, 1>); break;
+    case RK_LANE:
+      pick(kLaneF, a.F, [&](auto f) { return go(k_reduce_lane<OP, decltype(f)::value>); });
+      break;
+    case RK_LANET:  // short time blocks, small odd groups
+    case RK_LANES:  // ... with the lanes along the stitched row
+      pick(kLanetF, a.F, [&](auto f) {
+        return pick(kShortT38, a.T, [&](auto t) {
+          constexpr int F = decltype(f)::value, T = decltype(t)::value;
+          return go(p.kernel == RK_LANES ? k_reduce_lanes<OP, F, T> : k_reduce_lanet<OP, F, T>);
+        });
+      });
+      break;
+    case RK_COL3:  // fqavby = 12, short time blocks
+      pick(kShortT38, a.T, [&](auto t) { return go(k_reduce_col3<OP, decltype(t)::value>); });
+      break;
+    case RK_TILE: go(a.in_cs == 1 ? k_reduce_tile<OP, true> : k_reduce_tile<OP, false>); break;
+    case RK_SCALAR: go(k_reduce_scalar<OP>); break;
   }
   if (e != hipSuccess || a.nchunk == 1) return e;
   const int64_t nout = (int64_t)a.nbank * a.nto * a.ni * a.nco;
+  const dim3 block(kBlock);
   if (a.nchunk > 16) {
     const unsigned fg = (unsigned)std::min<int64_t>(cdiv(nout, 4), 16384);
-    BLDP_LAUNCH((k_reduce_finalize_w<OP>), dim3(fg), block, 0, s, a);
-  } else {
-    const unsigned fg = (unsigned)std::min<int64_t>(cdiv(nout, kBlock), 8192);
-    BLDP_LAUNCH((k_reduce_finalize<OP>), dim3(fg), block, 0, s, a);
+    return launch_kernel(k_reduce_finalize_w<OP>, dim3(fg), block, 0, s, a);
   }
-  return hipGetLastError();
+  const unsigned fg = (unsigned)std::min<int64_t>(cdiv(nout, kBlock), 8192);
+  return launch_kernel(k_reduce_finalize<OP>, dim3(fg), block, 0, s, a);
 }
 
 }  // namespace
@@ -2050,271 +1923,318 @@ void plan_opt_set(int k, int64_t v) { g_plan_opt.v[k].store(v, std::memory_order
 
 // Where the per-XCD tile order pays (the rule and its measurements: the
 // comment above kIlXcdMinT).  `bytes`: the launch's algorithmic traffic.
-bool xcd_order_pays(int path, const RedArgs &a, int64_t F, int64_t T, int64_t bytes) {
+bool xcd_order_pays(int kernel, const RedArgs &a, int64_t bytes) {
   const int64_t pitch = 4 * a.in_ld_t;  // bytes between a column's rows
-  switch (path) {
-    case PATH_VEC_IL: return T >= kIlXcdMinT && pitch <= kIlXcdMaxPitch;
-    case PATH_VEC_ROW:
-      if (a.tpb > 1) return bytes >= kRowtXcdBytes && pitch >= kRowXcdMinPitch;  // rowt
-      return T >= kIlXcdMinT && pitch >= kRowXcdMinPitch && pitch <= kIlXcdMaxPitch;  // row(s)
-    case PATH_NARROW:
-      if (a.tpb > 1) return F == 2 && bytes >= kRowtXcdBytes;  // narrowt
-      return true;  // narrow
-    case PATH_VEC:
-      if (a.tpb > 1) return false;  // wavet
-      return true;  // vec
-    case PATH_TILE: return false;
-    default: return false;
+  switch (kernel) {
+    case RK_IL: return a.T >= kIlXcdMinT && pitch <= kIlXcdMaxPitch;
+    case RK_ROWT: return bytes >= kRowtXcdBytes && pitch >= kRowXcdMinPitch;
+    case RK_ROW:
+    case RK_ROWS: return a.T >= kIlXcdMinT && pitch >= kRowXcdMinPitch && pitch <= kIlXcdMaxPitch;
+    case RK_NARROWT: return a.F == 2 && bytes >= kRowtXcdBytes;
+    case RK_NARROW: return true;
+    case RK_VEC: return true;
+    case RK_WAVET: return false;
+    case RK_TILE: return false;
+    default: return false;  // the lane kernels, narrow_mis, scalar
   }
 }
 
-Plan plan_reduce(RedArgs &a, bool aligned, bool rows16, bool words, int num_cus, int xcd_lg) {
-  Plan p{};
-  const int64_t F = a.F, T = a.T;
-  p.nout = a.nco * a.ni * a.nto;
-  const int64_t target_waves = (int64_t)num_cus * 16;  // ~4 waves per SIMD
-  int64_t tiles;  // independent wave/thread tiles before any time split
-  a.ts = 1;
-  a.k4 = 1;
-  a.tpb = 1;
-  a.tsub_log2 = 0;
-  a.rsplit = 1;
-  a.bpack = 0;
-  a.st_plain = 0;
+namespace {
+
+// What plan_reduce's steps share: the launch under construction and the
+// window's alignment classes (plan_reduce's parameters).
+struct Planning {
+  RedArgs &a;
+  Plan &p;
+  const bool aligned, rows16, words;
+  const int num_cus;
   const bool t38 = opt(OPT_T38) != 0;
-  if (opt(OPT_LANET) && words && a.in_cs == 1 && (T == 1 || T == 2 || T == 4 || (t38 && (T == 3 || T == 8))) &&
-      (F == 3 || F == 5 || F == 6 || F == 7 || F == 12) && a.ni <= 65535 && a.nbank <= 65535 &&
-      cdiv(a.nco + lanet_oalign_pad(), (int64_t)kBlock) * cdiv(a.nto, kLanetRows / T) <=
-          INT32_MAX) {
-    // small odd groups, short time blocks: one lane per group, NRW rows per lane
+
+  // groups of tpb time blocks, 2^sh of them per workgroup
+  int64_t tgroups(int64_t tpb, int sh = 0) const {
+    return cdiv(cdiv(a.nto, tpb), (int64_t)1 << sh);
+  }
+  // A 3-D launch of x * y * z workgroups, one per tile, becomes the plan's;
+  // false, with nothing changed, where a dimension does not fit a grid.
+  bool launch3(ReduceKernel k, int64_t x, int64_t y, int64_t z, unsigned block = kBlock,
+               unsigned shm = 0) {
+    if (x > INT32_MAX || y > 65535 || z > 65535) return false;
+    p.kernel = k;
+    p.gx = (uint32_t)x, p.gy = (uint32_t)y, p.gz = (uint32_t)z;
+    p.block = block;
+    p.shm = shm;
+    p.grid = a.ntiles = x * y * z;
+    return true;
+  }
+  // A 1-D launch over a.ntiles tiles (those beyond the grid: grid-stride loop).
+  void launch_stride(ReduceKernel k, unsigned shm = 0) {
+    p.kernel = k;
+    p.grid = std::min<int64_t>(a.ntiles, INT32_MAX);
+    p.gx = (uint32_t)p.grid, p.gy = p.gz = 1;
+    p.block = kBlock;
+    p.shm = shm;
+  }
+
+  // Small odd groups, short time blocks: one lane per group, 8 rows per lane
+  // (k_reduce_lanet), or one of its two forms for narrow rows.
+  bool lanet() {
+    const int64_t F = a.F, T = a.T;
+    if (!(opt(OPT_LANET) && words && a.in_cs == 1 && short_t(kShortT38, T, t38) &&
+          kLanetF.contains(F)))
+      return false;
+    const int64_t tpb = kLanetRows / T;
+    const int64_t bc = cdiv(a.nco + lanet_oalign_pad(), (int64_t)kBlock);
+    // (the grid of unpacked time groups must fit, whatever form follows)
+    if (bc * tgroups(tpb) > INT32_MAX || a.ni > 65535 || a.nbank > 65535) return false;
     p.path = PATH_LANE;
-    p.lanet = true;
-    a.tpb = (int32_t)(kLanetRows / T);
-    a.blocks_c = cdiv(a.nco + lanet_oalign_pad(), (int64_t)kBlock);
-    // narrow windows: 2 or 4 time groups per workgroup (the 0001 product at
-    // fqavby = 12: 42 groups a row kept 42 of 256 lanes busy)
-    if (opt(OPT_LANET_PACK))
-      a.tsub_log2 = a.nco + 15 <= 64 ? 2 : a.nco + 15 <= 128 ? 1 : 0;
     a.nchunk = 1;
     a.rows_per_chunk = T;
-    a.ntiles = a.blocks_c * cdiv(cdiv(a.nto, a.tpb), (int64_t)1 << a.tsub_log2) * a.ni * a.nbank;
-    // a stitched band of banks narrower than a workgroup: lanes along the
-    // product row (k_reduce_lanes, option lane_bpack)
-    const int64_t row = a.nbank * a.nco;
-    // (F = 12: 2.94 vs 2.90 ms on the 0001 band, not taken; F = 3 3.53 vs
-    // 4.21, profiles/r04/ab_t1_0001_r04h.json)
-    // (T <= 4: at T = 8, 2% slower on the 0001 band)
-    if (opt(OPT_LANE_BPACK) && F <= 7 && T <= 4 && a.nbank > 1 && a.out_bank == a.nco &&
-        a.nco + 15 < kBlock &&
-        row <= UINT32_MAX - kBlock && cdiv(row, (int64_t)kBlock) * cdiv(a.nto, a.tpb) <= INT32_MAX) {
-      a.bpack = 1;
-      a.tsub_log2 = 0;
-      a.blocks_c = cdiv(row, (int64_t)kBlock);
-      a.ntiles = a.blocks_c * cdiv(a.nto, a.tpb) * a.ni;
-    }
+    const int64_t prow = a.nbank * a.nco;  // groups of a stitched product row
     // fqavby = 12: float4 columns, three lanes a group (k_reduce_col3, option
     // col3); any output layout, several banks per workgroup
     // (rows of < 65536 groups: the 0000 product's 5.6M-group rows lost 3-5% at
     // T = 2..4, profiles/r04/ab_grid0_r04l.json)
-    if (opt(OPT_COL3) && F == 12 && (T == 1 || T == 2 || T == 3 || T == 4 || T == 8) &&
-        a.nco < 65536 &&
+    const int64_t tpb3 = 4 / T > 0 ? 4 / T : 1;
+    if (opt(OPT_COL3) && F == 12 && a.nco < 65536 &&
         3 * a.nco * a.nbank <= UINT32_MAX - kCol3Threads &&
-        cdiv(a.nbank * a.nco, (int64_t)64) * cdiv(a.nto, (int64_t)(4 / T > 0 ? 4 / T : 1)) <=
-            INT32_MAX) {
-      p.col3 = true;
-      a.bpack = 0;
-      a.tsub_log2 = 0;
-      a.tpb = (int32_t)(4 / T > 0 ? 4 / T : 1);
-      a.blocks_c = cdiv(a.nbank * a.nco, (int64_t)64);
-      a.ntiles = a.blocks_c * cdiv(a.nto, (int64_t)a.tpb) * a.ni;
+        launch3(RK_COL3, cdiv(prow, (int64_t)64) * tgroups(tpb3), a.ni, 1, kCol3Threads)) {
+      a.tpb = (int32_t)tpb3;
+      a.blocks_c = cdiv(prow, (int64_t)64);
+      return true;
     }
-    p.grid = a.ntiles;
-    p.ws_bytes = 0;
-    a.div = (float)(F * T);
-    return p;
+    a.tpb = (int32_t)tpb;
+    // a stitched band of banks narrower than a workgroup: lanes along the
+    // product row (k_reduce_lanes, option lane_bpack)
+    // (F = 12: 2.94 vs 2.90 ms on the 0001 band, not taken; F = 3 3.53 vs
+    // 4.21, profiles/r04/ab_t1_0001_r04h.json)
+    // (T <= 4: at T = 8, 2% slower on the 0001 band)
+    if (opt(OPT_LANE_BPACK) && F <= 7 && T <= 4 && a.nbank > 1 && a.out_bank == a.nco &&
+        a.nco + 15 < kBlock && prow <= UINT32_MAX - kBlock &&
+        launch3(RK_LANES, cdiv(prow, (int64_t)kBlock) * tgroups(tpb), a.ni, 1)) {
+      a.bpack = 1;
+      a.blocks_c = cdiv(prow, (int64_t)kBlock);
+      return true;
+    }
+    // narrow windows: 2 or 4 time groups per workgroup (the 0001 product at
+    // fqavby = 12: 42 groups a row kept 42 of 256 lanes busy)
+    if (opt(OPT_LANET_PACK)) a.tsub_log2 = a.nco + 15 <= 64 ? 2 : a.nco + 15 <= 128 ? 1 : 0;
+    a.blocks_c = bc;
+    return launch3(RK_LANET, bc * tgroups(tpb, a.tsub_log2), a.ni, a.nbank);
   }
-  if (aligned && F % 4 == 0) {
-    p.path = PATH_VEC;
-    const int64_t g4 = F / 4;
-    int lpg = 1;
-    while (lpg < 64 && g4 % (2 * lpg) == 0) lpg *= 2;
-    p.lpg = lpg;
-    a.k4 = (int32_t)(g4 / lpg);
-    const int64_t ctiles = cdiv(a.nco, 64 / lpg);
-    tiles = ctiles * a.ni * a.nto * a.nbank;
-    // rows a time-split wave needs at least: groups wider than the interleaved
-    // kernel's (G4 > 1024: one wave reads K4 > 16 float4 per lane per row) have
-    // enough work in one row (fqavby = 65536 at tavby = 8 was 272 waves)
-    const int64_t tsrows = (opt(OPT_WIDE_SPLIT) && a.k4 > 16) ? 1 : 8;
-    while (a.ts < 4 && tiles * a.ts < target_waves && T >= 2 * a.ts * tsrows) a.ts *= 2;
-    // no idle waves: a workgroup holds 4/ts column tiles, so narrow windows
-    // (fewer than 4 column tiles, e.g. the 512-channel 0001 product) split
-    // their time rows over the spare waves instead
-    if (opt(OPT_TS_FILL))
-      while (a.ts < 4 && ctiles < 4 / a.ts && T >= 2 * a.ts * 8) a.ts *= 2;
-    a.blocks_c = cdiv(ctiles, 4 / a.ts);
-    tiles *= a.ts;
-  } else if (aligned && (F == 1 || F == 2) && (a.nco * F) % 4 == 0) {
-    p.path = PATH_NARROW;
-    const int64_t nc4 = a.nco * F / 4;
-    a.blocks_c = cdiv(nc4, kBlock);
-    tiles = cdiv(nc4, 64) * a.ni * a.nto * a.nbank;
-  } else if (words && a.in_cs == 1 && opt(OPT_LANE) >= 1 &&
-             (F == 2 || F == 3 || F == 5 || F == 6 || F == 7) &&
-             (!rows16 || (opt(OPT_LANE3) && F == 3))) {
-    // small odd / not-multiple-of-4 groups: one lane per output
-    p.path = PATH_LANE;
-    a.blocks_c = cdiv(a.nco, kBlock);
-    tiles = cdiv(a.nco, 64) * a.ni * a.nto * a.nbank;
-  } else if (rows16 && a.in_cs == 1 && opt(OPT_NARROW_MIS) >= 1 && F == 1) {
-    // misaligned start, time integration: aligned columns realigned by shuffle
-    // (F = 2 on the same kernel lost to the tile path: 6.06 vs 5.83 ms on the
-    // 0000 band at c0 = 2, profiles/r02/ab_tile_narrow_mis.json; removed in
-    // round 5)
-    p.path = PATH_NARROW_MIS;
-    a.blocks_c = cdiv(a.nco * F, kMisSpan);
-    tiles = a.blocks_c * 4 * a.ni * a.nto * a.nbank;
-  } else if (rows16 && a.in_cs >= 1 && a.in_cs <= 8 && F <= (kSpan - 4) / a.in_cs + 1) {
-    p.path = PATH_TILE;
-    a.gpt = ((kSpan - 4) / a.in_cs + 1) / F;
-    a.blocks_c = cdiv(a.nco, a.gpt);
-    tiles = a.blocks_c * 4 * a.ni * a.nto * a.nbank;
-  } else {
-    p.path = PATH_SCALAR;
-    a.blocks_c = cdiv(a.nco, kBlock);
-    tiles = cdiv(a.nco, 64) * a.ni * a.nto * a.nbank;
+
+  // The base path by alignment and group size, its time split (ts waves of a
+  // tile, nchunk workgroups of a time block) and its 1-D grid-stride launch.
+  void base() {
+    const int64_t F = a.F, T = a.T;
+    const int64_t target_waves = (int64_t)num_cus * 16;  // ~4 waves per SIMD
+    int64_t tiles;  // independent wave/thread tiles before any time split
+    ReduceKernel k;
+    unsigned shm = 0;
+    if (aligned && F % 4 == 0) {
+      p.path = PATH_VEC;
+      k = RK_VEC, shm = kVecShm;
+      const int64_t g4 = F / 4;
+      int lpg = 1;
+      while (lpg < 64 && g4 % (2 * lpg) == 0) lpg *= 2;
+      p.lpg = lpg;
+      a.k4 = (int32_t)(g4 / lpg);
+      const int64_t ctiles = cdiv(a.nco, 64 / lpg);
+      tiles = ctiles * a.ni * a.nto * a.nbank;
+      // rows a time-split wave needs at least: groups wider than the interleaved
+      // kernel's (G4 > 1024: one wave reads K4 > 16 float4 per lane per row) have
+      // enough work in one row (fqavby = 65536 at tavby = 8 was 272 waves)
+      const int64_t tsrows = (opt(OPT_WIDE_SPLIT) && a.k4 > 16) ? 1 : 8;
+      while (a.ts < 4 && tiles * a.ts < target_waves && T >= 2 * a.ts * tsrows) a.ts *= 2;
+      // no idle waves: a workgroup holds 4/ts column tiles, so narrow windows
+      // (fewer than 4 column tiles, e.g. the 512-channel 0001 product) split
+      // their time rows over the spare waves instead
+      if (opt(OPT_TS_FILL))
+        while (a.ts < 4 && ctiles < 4 / a.ts && T >= 2 * a.ts * 8) a.ts *= 2;
+      a.blocks_c = cdiv(ctiles, 4 / a.ts);
+      tiles *= a.ts;
+    } else if (aligned && kNarrowF.contains(F) && (a.nco * F) % 4 == 0) {
+      p.path = PATH_NARROW;
+      k = RK_NARROW, shm = kNarrowShm;
+      const int64_t nc4 = a.nco * F / 4;
+      a.blocks_c = cdiv(nc4, kBlock);
+      tiles = cdiv(nc4, 64) * a.ni * a.nto * a.nbank;
+    } else if (words && a.in_cs == 1 && opt(OPT_LANE) >= 1 && kLaneF.contains(F) &&
+               (!rows16 || (opt(OPT_LANE3) && F == 3))) {
+      // small odd / not-multiple-of-4 groups: one lane per output
+      p.path = PATH_LANE;
+      k = RK_LANE;
+      a.blocks_c = cdiv(a.nco, kBlock);
+      tiles = cdiv(a.nco, 64) * a.ni * a.nto * a.nbank;
+    } else if (rows16 && a.in_cs == 1 && opt(OPT_NARROW_MIS) >= 1 && F == 1) {
+      // misaligned start, time integration: aligned columns realigned by shuffle
+      // (F = 2 on the same kernel lost to the tile path: 6.06 vs 5.83 ms on the
+      // 0000 band at c0 = 2, profiles/r02/ab_tile_narrow_mis.json; removed in
+      // round 5)
+      p.path = PATH_NARROW_MIS;
+      k = RK_NARROW_MIS;
+      a.blocks_c = cdiv(a.nco * F, kMisSpan);
+      tiles = a.blocks_c * 4 * a.ni * a.nto * a.nbank;
+    } else if (rows16 && a.in_cs >= 1 && a.in_cs <= 8 && F <= (kSpan - 4) / a.in_cs + 1) {
+      p.path = PATH_TILE;
+      k = RK_TILE;
+      a.gpt = ((kSpan - 4) / a.in_cs + 1) / F;
+      a.blocks_c = cdiv(a.nco, a.gpt);
+      tiles = a.blocks_c * 4 * a.ni * a.nto * a.nbank;
+    } else {
+      p.path = PATH_SCALAR;
+      k = RK_SCALAR;
+      a.blocks_c = cdiv(a.nco, kBlock);
+      tiles = cdiv(a.nco, 64) * a.ni * a.nto * a.nbank;
+    }
+    // Long time blocks with too few tiles: split the T rows across workgroups.
+    const int64_t rows_per_wave = cdiv(T, a.ts);
+    // float4 per lane in a wave's rows (wide groups: K4 of them per row)
+    const int64_t wave_work =
+        rows_per_wave * ((opt(OPT_WIDE_SPLIT) && p.path == PATH_VEC && a.k4 > 16) ? a.k4 : 1);
+    int64_t nchunk = 1;
+    if (tiles > 0 && tiles < target_waves && wave_work >= 128) {  // (empty windows: no split)
+      nchunk = std::min<int64_t>(cdiv(target_waves, tiles), wave_work / 64);
+      nchunk = std::min<int64_t>(nchunk, rows_per_wave);
+      nchunk = std::max<int64_t>(nchunk, 1);
+    }
+    a.rows_per_chunk = cdiv(T, nchunk);
+    if (a.rows_per_chunk < 1) a.rows_per_chunk = 1;
+    a.nchunk = (int32_t)std::max<int64_t>(1, cdiv(T, a.rows_per_chunk));
+    p.ws_bytes = a.nchunk > 1 ? (size_t)a.nchunk * a.nbank * p.nout * sizeof(float) : 0;
+    a.ntiles = a.blocks_c * a.ni * a.nchunk * a.nto * a.nbank;
+    launch_stride(k, shm);
   }
-  // Long time blocks with too few tiles: split the T rows across workgroups.
-  const int64_t rows_per_wave = cdiv(T, a.ts);
-  // float4 per lane in a wave's rows (wide groups: K4 of them per row)
-  const int64_t wave_work =
-      rows_per_wave * ((opt(OPT_WIDE_SPLIT) && p.path == PATH_VEC && a.k4 > 16) ? a.k4 : 1);
-  int64_t nchunk = 1;
-  if (tiles > 0 && tiles < target_waves && wave_work >= 128) {  // (empty windows: no split)
-    nchunk = std::min<int64_t>(cdiv(target_waves, tiles), wave_work / 64);
-    nchunk = std::min<int64_t>(nchunk, rows_per_wave);
-    nchunk = std::max<int64_t>(nchunk, 1);
+
+  // whole-wave groups of the vector path with no time split: what wavet and il take
+  bool wave_groups() const {
+    return p.kernel == RK_VEC && p.lpg == 64 && kIlK4.contains(a.k4) && a.ts == 1 && a.nchunk == 1;
   }
-  a.rows_per_chunk = cdiv(T, nchunk);
-  if (a.rows_per_chunk < 1) a.rows_per_chunk = 1;
-  a.nchunk = (int32_t)std::max<int64_t>(1, cdiv(T, a.rows_per_chunk));
-  p.ws_bytes = a.nchunk > 1 ? (size_t)a.nchunk * a.nbank * p.nout * sizeof(float) : 0;
-  a.ntiles = a.blocks_c * a.ni * a.nchunk * a.nto * a.nbank;
-  p.grid = std::min<int64_t>(a.ntiles, INT32_MAX);  // tiles beyond: grid-stride loop
+
   // large groups with short time blocks where the interleaved kernel is a
   // poor fit (few groups per row, or its 3-D grid too small): k_reduce_wavet
   // (path "vector", a.tpb = time blocks per wave)
-  if (opt(OPT_WAVET) && p.path == PATH_VEC && p.lpg == 64 &&
-      (a.k4 == 2 || a.k4 == 4 || a.k4 == 8 || a.k4 == 16) &&
-      (T == 1 || T == 2 || T == 4 || (t38 && T == 3)) &&  // (T = 8: -8%, ab_t38_r03w)
-      a.ts == 1 && a.nchunk == 1 &&
-      (a.nco < 4 || a.ni * a.nto > 65535) && a.ni <= 65535 &&
-      a.nbank <= 65535) {
+  bool wavet() {
+    const int64_t T = a.T;
+    if (!(opt(OPT_WAVET) && wave_groups() && short_t(kWavetT, T, t38) &&
+          (a.nco < 4 || a.ni * a.nto > 65535)))
+      return false;
     const int64_t tb = std::max<int64_t>(1, 16 / (T * a.k4)), rw = tb * (tb >= 2 ? 1 : 4);
-    if (a.nco * cdiv(a.nto, 4 * rw) <= INT32_MAX) {
-      a.tpb = (int32_t)rw;
-      a.ntiles = a.nco * cdiv(a.nto, 4 * rw) * a.ni * a.nbank;
-      // a stitched band whose product row is <= 16 groups: one workgroup per
-      // RW spectra with a wave per (bank, group), whole rows stored (wave_bpack)
-      if (opt(OPT_WAVE_BPACK) && a.nbank > 1 && a.nbank * a.nco <= 16 && a.out_bank == a.nco) {
-        a.bpack = 1;
-        a.ntiles = cdiv(a.nto, rw) * a.ni;
-      }
-      p.grid = a.ntiles;
-    }
+    if (!launch3(RK_WAVET, a.nco * cdiv(a.nto, 4 * rw), a.ni, a.nbank)) return false;
+    a.tpb = (int32_t)rw;  // time blocks per wave
+    // a stitched band whose product row is <= 16 groups: one workgroup per
+    // RW spectra with a wave per (bank, group), whole rows stored (wave_bpack)
+    if (opt(OPT_WAVE_BPACK) && a.nbank > 1 && a.nbank * a.nco <= 16 && a.out_bank == a.nco &&
+        launch3(RK_WAVET, cdiv(a.nto, rw), a.ni, 1, (unsigned)(64 * a.nbank * a.nco)))
+      a.bpack = 1;
+    return true;
   }
+
   // whole-time-block tiles of 512..4096-channel groups: interleaved kernel
   // (3-D grid, so every dimension must fit)
-  if (opt(OPT_VEC_IL) && p.path == PATH_VEC && p.lpg == 64 && a.tpb == 1 &&
-      (a.k4 == 2 || a.k4 == 4 || a.k4 == 8 || a.k4 == 16) && a.ts == 1 && a.nchunk == 1 &&
-      cdiv(a.nco, il_gpw(a.k4)) <= INT32_MAX && a.ni * a.nto <= 65535 && a.nbank <= 65535) {
+  bool il() {
+    if (!(opt(OPT_VEC_IL) && wave_groups())) return false;
+    const int64_t bc = cdiv(a.nco, il_gpw(a.k4));
+    if (!launch3(RK_IL, bc, a.ni * a.nto, a.nbank, kBlock, kIlShm)) return false;
     p.path = PATH_VEC_IL;
-    a.blocks_c = cdiv(a.nco, il_gpw(a.k4));
-    a.ntiles = a.blocks_c * a.ni * a.nto * a.nbank;
-    p.grid = a.ntiles;
+    a.blocks_c = bc;
+    return true;
   }
+
   // small power-of-two groups, whole time block per tile, no time split:
-  // the lean row kernel (3-D grid, so every dimension must fit)
-  if (opt(OPT_VEC_ROW) && p.path == PATH_VEC && a.k4 == 1 && a.ts == 1 && a.nchunk == 1 &&
-      F >= 4 && F <= 256 && (F & (F - 1)) == 0 && a.nbank <= 65535) {
-    const int64_t bc = cdiv(a.nco * (F / 4), kBlock);
-    // short time blocks: 16 / T of them per workgroup (k_reduce_rowt; grid x =
-    // column blocks x time groups, so long 0001-product windows fit too)
-    int64_t tpb = (T == 1 || T == 2 || T == 4 || (t38 && (T == 3 || T == 8))) ? 16 / T : 1;
-    if (opt(OPT_ROW_TPB) && tpb > 1 && a.nto > 1 && bc * cdiv(a.nto, tpb) <= INT32_MAX &&
-        a.ni <= 65535) {
-      p.path = PATH_VEC_ROW;
-      a.blocks_c = bc;
-      // <= 128 float4 columns: 2 or 4 time groups per workgroup (>= 64 lanes each)
-      const int64_t cols = a.nco * (F / 4);
-      a.tsub_log2 = opt(OPT_ROWT_PACK) ? (cols <= 64 ? 2 : cols <= 128 ? 1 : 0) : 0;
-      // small launches: 8 rows per lane (4 at T <= 2), more workgroups (option rowt_small);
-      // at T = 8 that is one time block per workgroup, i.e. k_reduce_row, whose
-      // 3-D grid must then hold (IF, time block) in y
-      // windows of <= 128 float4 columns (the 0001 product) take 8 rows too at
-      // T = 1 and at F >= 64 (option rowt_narrow8: 0001 band at T = 1, F = 4 / 8
-      // / 16 / 64 +1.2..6%, F = 64 T = 2 / 4 +4.5 / 1.8%; F = 16 T = 2, F = 8 T = 2
-      // and F = 4 T = 3 -1.7..4%: not taken; profiles/r04/ab_t1_0001_r04{j,k}.json,
-      // ab_grid1_r04p.json)
-      // Small launches at T <= 2 take 4 rows (0002 band T = 1 / 2, F = 4..256
-      // +2..6%, profiles/r04/ab_grid_r04x.json; the narrow 0001 windows stay on
-      // 8: 4 lost 2-5% there, ab_t1_0001_r04x.json)
-      const bool small = bc * cdiv(cdiv(a.nto, tpb), (int64_t)1 << a.tsub_log2) * a.ni *
-                             a.nbank < opt(OPT_ROWT_SMALL) * num_cus;
-      if ((small || (opt(OPT_ROWT_NARROW8) && cols <= 128 && (T == 1 || F >= 64))) &&
-          (8 / T > 1 || (bc <= INT32_MAX && a.ni * a.nto <= 65535)))
-        tpb = small && T <= 2 ? 4 / T : 8 / T;
-      if (tpb == 1) {  // k_reduce_row
-        a.tpb = 1;
-        a.tsub_log2 = 0;
-        a.ntiles = bc * a.ni * a.nto * a.nbank;
-      } else {
-        a.tpb = (int32_t)tpb;
-        a.ntiles = bc * cdiv(cdiv(a.nto, tpb), (int64_t)1 << a.tsub_log2) * a.ni * a.nbank;
-        // a stitched band of narrow banks whose row segments are < 128 bytes
-        // (the 0001 band at fqavby = 64: 32 bytes a bank): the lane sets take
-        // consecutive banks instead of time groups, so each product row gets
-        // whole segments of 2^tsub_log2 banks (option row_bpack)
-        const int64_t sets = (int64_t)1 << a.tsub_log2;
-        if (opt(OPT_ROW_BPACK) && a.tsub_log2 > 0 && cols == (kBlock >> a.tsub_log2) &&
-            a.nbank % sets == 0 && a.out_bank == a.nco && 4 * a.nco < 128 &&
-            bc * cdiv(a.nto, tpb) <= INT32_MAX) {
-          a.bpack = 1;
-          a.ntiles = bc * cdiv(a.nto, tpb) * a.ni * (a.nbank / sets);
-        }
-      }
-      p.grid = a.ntiles;
-    } else if (bc <= INT32_MAX && a.ni * a.nto <= 65535) {
-      p.path = PATH_VEC_ROW;
-      a.blocks_c = bc;
-      a.ntiles = a.blocks_c * a.ni * a.nto * a.nbank;
-      // launches of whole 16-row batches with < 64 tiles per CU: the block's
-      // rows split over 4 slices of the workgroup (2 for F = 256, whose
-      // slices each fold 64 columns), so that the launch does not end on a
-      // partial round of 64 KiB tiles (profiles/r04/ab_rows_r04c.json: one to
-      // eight 0002 files 5-11% faster; 0000 bands, 256+ tiles per CU, 9-27%
-      // slower split)
-      // (F >= 128: only below 16 tiles per CU, in 2 slices; the 0002 band at
-      // F = 128 / 256, 34 tiles per CU, lost 3-5% split, profiles/r04/
-      // ab_grid_r04l.json)
-      int64_t S = plan_opt(OPT_ROW_SPLIT);
-      if (T % 16 != 0)
-        S = 1;
-      else if (S < 0)
-        S = F >= 128 ? (a.ntiles < (int64_t)16 * num_cus ? 2 : 1)
-                     : (a.ntiles < (int64_t)64 * num_cus ? 4 : 1);
-      if (S == 2 || S == 4) {
-        a.rsplit = (int32_t)S;
-        a.blocks_c = cdiv(a.nco * (F / 4), kBlock / S);
-        a.ntiles = a.blocks_c * a.ni * a.nto * a.nbank;
-      }
-      p.grid = a.ntiles;
-    }
+  // the lean row kernels (3-D grid, so every dimension must fit)
+  bool row() {
+    if (!(opt(OPT_VEC_ROW) && p.kernel == RK_VEC && a.k4 == 1 && a.ts == 1 && a.nchunk == 1 &&
+          kRowG4.contains(a.F / 4) && a.nbank <= 65535))
+      return false;
+    const int64_t bc = cdiv(a.nco * (a.F / 4), kBlock);
+    if (!rowt(bc) && !row_rows(bc)) return false;
+    p.path = PATH_VEC_ROW;
+    return true;
   }
+
+  // short time blocks: 16 / T of them per workgroup (k_reduce_rowt; grid x =
+  // column blocks x time groups, so long 0001-product windows fit too)
+  bool rowt(int64_t bc) {
+    const int64_t F = a.F, T = a.T;
+    if (!(opt(OPT_ROW_TPB) && short_t(kShortT38, T, t38) && 16 / T > 1 && a.nto > 1 &&
+          bc * tgroups(16 / T) <= INT32_MAX && a.ni <= 65535))
+      return false;
+    // <= 128 float4 columns: 2 or 4 time groups per workgroup (>= 64 lanes each)
+    const int64_t cols = a.nco * (F / 4);
+    const int sh = opt(OPT_ROWT_PACK) ? (cols <= 64 ? 2 : cols <= 128 ? 1 : 0) : 0;
+    // small launches: 8 rows per lane (4 at T <= 2), more workgroups (option rowt_small);
+    // at T = 8 that is one time block per workgroup, i.e. k_reduce_row, whose
+    // 3-D grid must then hold (IF, time block) in y
+    // windows of <= 128 float4 columns (the 0001 product) take 8 rows too at
+    // T = 1 and at F >= 64 (option rowt_narrow8: 0001 band at T = 1, F = 4 / 8
+    // / 16 / 64 +1.2..6%, F = 64 T = 2 / 4 +4.5 / 1.8%; F = 16 T = 2, F = 8 T = 2
+    // and F = 4 T = 3 -1.7..4%: not taken; profiles/r04/ab_t1_0001_r04{j,k}.json,
+    // ab_grid1_r04p.json)
+    // Small launches at T <= 2 take 4 rows (0002 band T = 1 / 2, F = 4..256
+    // +2..6%, profiles/r04/ab_grid_r04x.json; the narrow 0001 windows stay on
+    // 8: 4 lost 2-5% there, ab_t1_0001_r04x.json)
+    int nrw = 16;
+    const bool small = bc * tgroups(16 / T, sh) * a.ni * a.nbank < opt(OPT_ROWT_SMALL) * num_cus;
+    if ((small || (opt(OPT_ROWT_NARROW8) && cols <= 128 && (T == 1 || F >= 64))) &&
+        (8 / T > 1 || (bc <= INT32_MAX && a.ni * a.nto <= 65535)))
+      nrw = small && T <= 2 ? 4 : 8;
+    const int64_t tpb = nrw / T;
+    if (tpb == 1) return false;  // k_reduce_row (row_rows)
+    // a stitched band of narrow banks whose row segments are < 128 bytes
+    // (the 0001 band at fqavby = 64: 32 bytes a bank): the lane sets take
+    // consecutive banks instead of time groups, so each product row gets
+    // whole segments of 2^tsub_log2 banks (option row_bpack)
+    const int64_t sets = (int64_t)1 << sh;
+    if (opt(OPT_ROW_BPACK) && sh > 0 && cols == (kBlock >> sh) && a.nbank % sets == 0 &&
+        a.out_bank == a.nco && 4 * a.nco < 128 &&
+        launch3(RK_ROWT, bc * tgroups(tpb), a.ni, a.nbank / sets, kBlock, kRowtShm))
+      a.bpack = 1;
+    else if (!launch3(RK_ROWT, bc * tgroups(tpb, sh), a.ni, a.nbank, kBlock, kRowtShm))
+      return false;
+    p.nrw = nrw;
+    a.blocks_c = bc;
+    a.tpb = (int32_t)tpb;
+    a.tsub_log2 = sh;
+    return true;
+  }
+
+  // one time block per workgroup: k_reduce_row, or k_reduce_rows with the
+  // block's rows over 2 / 4 slices of the workgroup
+  bool row_rows(int64_t bc) {
+    const int64_t F = a.F, T = a.T;
+    if (!launch3(RK_ROW, bc, a.ni * a.nto, a.nbank, kBlock, kRowShm)) return false;
+    a.blocks_c = bc;
+    // launches of whole 16-row batches with < 64 tiles per CU: the block's
+    // rows split over 4 slices of the workgroup (2 for F = 256, whose
+    // slices each fold 64 columns), so that the launch does not end on a
+    // partial round of 64 KiB tiles (profiles/r04/ab_rows_r04c.json: one to
+    // eight 0002 files 5-11% faster; 0000 bands, 256+ tiles per CU, 9-27%
+    // slower split)
+    // (F >= 128: only below 16 tiles per CU, in 2 slices; the 0002 band at
+    // F = 128 / 256, 34 tiles per CU, lost 3-5% split, profiles/r04/
+    // ab_grid_r04l.json)
+    int64_t S = plan_opt(OPT_ROW_SPLIT);
+    if (T % 16 != 0)
+      S = 1;
+    else if (S < 0)
+      S = F >= 128 ? (a.ntiles < (int64_t)16 * num_cus ? 2 : 1)
+                   : (a.ntiles < (int64_t)64 * num_cus ? 4 : 1);
+    if (!kRowSlices.contains(S)) return true;
+    const int64_t bcs = cdiv(a.nco * (F / 4), kBlock / S);
+    if (launch3(RK_ROWS, bcs, a.ni * a.nto, a.nbank, kBlock, kRowShm)) {
+      a.rsplit = (int32_t)S;
+      a.blocks_c = bcs;
+    }
+    return true;
+  }
+
   // narrow path, short time blocks: k_reduce_narrowt (grid as k_reduce_rowt's)
-  if (opt(OPT_NARROW_TPB) && p.path == PATH_NARROW && a.nchunk == 1 &&
-      (T == 1 || T == 2 || T == 4 || (t38 && T == 3 && F == 2)) &&
-      (opt(OPT_NARROW_TPB) >= 1 + (F == 1 && T == 1)) && a.nto > 1 && a.ni <= 65535 && a.nbank <= 65535) {
+  bool narrowt() {
+    const int64_t F = a.F, T = a.T;
+    if (!(opt(OPT_NARROW_TPB) && p.kernel == RK_NARROW && a.nchunk == 1 && narrowt_pair(F, T) &&
+          (t38 || kShortT.contains(T)) && (opt(OPT_NARROW_TPB) >= 1 + (F == 1 && T == 1)) &&
+          a.nto > 1))
+      return false;
     const int64_t cols = a.nco * F / 4;
     const int sh = cols <= 64 ? 2 : cols <= 128 ? 1 : 0;
     // fewer rows per lane (instead of 16) on launches under rowt_small (64)
@@ -2323,34 +2243,45 @@ Plan plan_reduce(RedArgs &a, bool aligned, bool rows16, bool words, int num_cus,
     // T = 1..4 +5..12%, the 0001 band F = 1 / 2 T = 1 +7 / 3%; 4 against 8 at
     // T = 1, 2 another 2..8% (0002 / 0001 bands); the 0000 band keeps 16
     // (profiles/r04/ab_grid_r04{o,w}.json, ab_t1_0001_r04{o,w}.json)
-    int64_t tpb = 16 / T;
-    if ((a.blocks_c * cdiv(cdiv(a.nto, tpb), (int64_t)1 << sh) * a.ni * a.nbank <
-             opt(OPT_ROWT_SMALL) * num_cus ||
-         (opt(OPT_ROWT_NARROW8) && cols <= 128 && T == 1)) && 8 / T >= 1)
-      tpb = T <= 2 ? 4 / T : 8 / T;
-    const int64_t x = a.blocks_c * cdiv(cdiv(a.nto, tpb), (int64_t)1 << sh);
-    if (x <= INT32_MAX) {
-      a.tpb = (int32_t)tpb;
-      a.tsub_log2 = sh;
-      a.ntiles = x * a.ni * a.nbank;
-      p.grid = a.ntiles;
-    }
+    int nrw = 16;
+    if (a.blocks_c * tgroups(16 / T, sh) * a.ni * a.nbank < opt(OPT_ROWT_SMALL) * num_cus ||
+        (opt(OPT_ROWT_NARROW8) && cols <= 128 && T == 1))
+      nrw = T <= 2 ? 4 : 8;
+    const int64_t tpb = nrw / T;
+    if (!launch3(RK_NARROWT, a.blocks_c * tgroups(tpb, sh), a.ni, a.nbank)) return false;
+    p.nrw = nrw;
+    a.tpb = (int32_t)tpb;
+    a.tsub_log2 = sh;
+    return true;
   }
-  // narrow-path vector stores
+};
+
+}  // namespace
+
+Plan plan_reduce(RedArgs &a, bool aligned, bool rows16, bool words, int num_cus, int xcd_lg) {
+  Plan p{};
+  const int64_t F = a.F, T = a.T;
+  p.nout = a.nco * a.ni * a.nto;
+  a.ts = 1;
+  a.k4 = 1;
+  a.tpb = 1;
+  a.tsub_log2 = 0;
+  a.rsplit = 1;
+  a.bpack = 0;
+  a.st_plain = 0;
+  a.div = (float)(F * T);
+  Planning pl{a, p, aligned, rows16, words, num_cus};
+  // the lane kernels for short time blocks come before every other path
+  // (their stores stay non-temporal and their tiles in launch order)
+  if (pl.lanet()) return p;
+  // the base path, then the one specialised form of it that applies
+  pl.base();
+  (void)(pl.wavet() || pl.il() || pl.row() || pl.narrowt());
+  // 16-byte row-segment stores of k_reduce_rowt, float4 (F = 1) / float2 (F = 2)
+  // stores of the narrow kernels: legal where the output's base and pitches allow
   a.vec_out = 0;
-  if (p.path == PATH_VEC_ROW && a.tpb > 1) {  // k_reduce_rowt's 16-byte row-segment stores
-    const uintptr_t op = (uintptr_t)a.out;
-    a.vec_out = (op % 16 == 0) && a.out_bank % 4 == 0 && a.out_ld_i % 4 == 0 &&
-                a.out_ld_t % 4 == 0;
-  }
-  if (p.path == PATH_NARROW_MIS) {  // float4 (F = 1) / float2 (F = 2) stores at aligned co
-    const int64_t w = 4 / F;            // outputs per lane
-    const uintptr_t op = (uintptr_t)a.out;
-    a.vec_out = (op % (4 * w) == 0) && a.out_bank % w == 0 && a.out_ld_i % w == 0 &&
-                a.out_ld_t % w == 0;
-  }
-  if (p.path == PATH_NARROW) {
-    const int64_t w = 4 / F;  // outputs per lane
+  if (p.kernel == RK_ROWT || p.path == PATH_NARROW || p.path == PATH_NARROW_MIS) {
+    const int64_t w = p.kernel == RK_ROWT ? 4 : 4 / F;  // outputs per lane
     const uintptr_t op = (uintptr_t)a.out;
     a.vec_out = (op % (4 * w) == 0) && a.out_bank % w == 0 && a.out_ld_i % w == 0 &&
                 a.out_ld_t % w == 0;
@@ -2358,13 +2289,10 @@ Plan plan_reduce(RedArgs &a, bool aligned, bool rows16, bool words, int num_cus,
   // output stores of the row / interleaved kernels: plain below 2 GB of
   // launch traffic, non-temporal above (option st_plain: 0 always nt, 1 (the
   // default) by that size rule, 2 always plain)
-  {
-    const int64_t bytes = 4 * a.nbank * a.ni * (a.nco * F * a.nto * T + a.nco * a.nto);
-    const int64_t o = opt(OPT_ST_PLAIN);
-    a.st_plain = o == 2 ? 1 : o == 0 ? 0 : (bytes < ((int64_t)2 << 30) ? 1 : 0);
-    a.xcd_lg = xcd_order_pays(p.path, a, F, T, bytes) ? xcd_lg : 0;
-  }
-  a.div = (float)(F * T);
+  const int64_t bytes = 4 * a.nbank * a.ni * (a.nco * F * a.nto * T + a.nco * a.nto);
+  const int64_t o = opt(OPT_ST_PLAIN);
+  a.st_plain = o == 2 ? 1 : o == 0 ? 0 : (bytes < ((int64_t)2 << 30) ? 1 : 0);
+  a.xcd_lg = xcd_order_pays(p.kernel, a, bytes) ? xcd_lg : 0;
   return p;
 }
 

@@ -537,36 +537,28 @@ int plan_stats(RedArgs &a, int op, bool words, int xcd_lg, Plan *pp) {
 
 
 namespace {
-// One dispatch; it carries the timing events of bldp_reduce_launch_timed when set.
-template <typename... Args>
-hipError_t launch1(void (*kn)(Args...), dim3 grid, hipStream_t s, Args... args) {
-  hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-  take_launch_events(&ev_start, &ev_stop);
-  if (ev_stop)
-    hipExtLaunchKernelGGL(kn, grid, dim3(kBlock), 0, s, ev_start, ev_stop, 0, args...);
-  else
-    hipLaunchKernelGGL(kn, grid, dim3(kBlock), 0, s, args...);
-  return hipGetLastError();
-}
 }  // namespace
 
 hipError_t launch_stats(const RedArgs &a, const Plan &p, int op, hipStream_t s) {
   if (p.grid <= 0) return hipSuccess;
   const dim3 grid((unsigned)p.grid, (unsigned)a.nbank);
+  const auto go = [&](auto *kn, auto... args) {
+    return launch_kernel(kn, grid, dim3(kBlock), 0, s, args...);
+  };
   const bool vec = a.k4 != 0;
   const bool mad = op == BLDP_OP_MAD && a.F > 1;  // (F = 1: the copy, as every op)
 #define BLDP_VECSEL(KN, N) (vec ? KN<N, true> : KN<N, false>)
   switch (p.path) {
     case PATH_MOMENTS:
       switch (p.lpg) {
-        case 1: return launch1(BLDP_VECSEL(k_mom_lanes, 1), grid, s, a, op);
-        case 2: return launch1(BLDP_VECSEL(k_mom_lanes, 2), grid, s, a, op);
-        case 4: return launch1(BLDP_VECSEL(k_mom_lanes, 4), grid, s, a, op);
-        case 8: return launch1(BLDP_VECSEL(k_mom_lanes, 8), grid, s, a, op);
-        case 16: return launch1(BLDP_VECSEL(k_mom_lanes, 16), grid, s, a, op);
-        case 32: return launch1(BLDP_VECSEL(k_mom_lanes, 32), grid, s, a, op);
-        case 64: return launch1(BLDP_VECSEL(k_mom_lanes, 64), grid, s, a, op);
-        case kBlock: return launch1(vec ? k_mom_block<true> : k_mom_block<false>, grid, s, a, op);
+        case 1: return go(BLDP_VECSEL(k_mom_lanes, 1), a, op);
+        case 2: return go(BLDP_VECSEL(k_mom_lanes, 2), a, op);
+        case 4: return go(BLDP_VECSEL(k_mom_lanes, 4), a, op);
+        case 8: return go(BLDP_VECSEL(k_mom_lanes, 8), a, op);
+        case 16: return go(BLDP_VECSEL(k_mom_lanes, 16), a, op);
+        case 32: return go(BLDP_VECSEL(k_mom_lanes, 32), a, op);
+        case 64: return go(BLDP_VECSEL(k_mom_lanes, 64), a, op);
+        case kBlock: return go(vec ? k_mom_block<true> : k_mom_block<false>, a, op);
       }
       break;
 #undef BLDP_VECSEL
@@ -574,19 +566,19 @@ hipError_t launch_stats(const RedArgs &a, const Plan &p, int op, hipStream_t s) 
 #define BLDP_VECSEL(KN, N) (vec ? BLDP_MEDSEL(KN, N, true) : BLDP_MEDSEL(KN, N, false))
     case PATH_MEDIAN_SORT:
       switch (p.lpg) {  // lanes of 4 keys
-        case 1: return launch1(BLDP_VECSEL(k_median_sort, 4), grid, s, a);
-        case 2: return launch1(BLDP_VECSEL(k_median_sort, 8), grid, s, a);
-        case 4: return launch1(BLDP_VECSEL(k_median_sort, 16), grid, s, a);
-        case 8: return launch1(BLDP_VECSEL(k_median_sort, 32), grid, s, a);
-        case 16: return launch1(BLDP_VECSEL(k_median_sort, 64), grid, s, a);
+        case 1: return go(BLDP_VECSEL(k_median_sort, 4), a);
+        case 2: return go(BLDP_VECSEL(k_median_sort, 8), a);
+        case 4: return go(BLDP_VECSEL(k_median_sort, 16), a);
+        case 8: return go(BLDP_VECSEL(k_median_sort, 32), a);
+        case 16: return go(BLDP_VECSEL(k_median_sort, 64), a);
       }
       break;
     case PATH_MEDIAN_SELECT:
-      return launch1(vec ? BLDP_MEDSEL(k_median_select, true, true)
-                         : BLDP_MEDSEL(k_median_select, false, true), grid, s, a);
+      return go(vec ? BLDP_MEDSEL(k_median_select, true, true)
+                    : BLDP_MEDSEL(k_median_select, false, true), a);
     case PATH_MEDIAN_STREAM:
-      return launch1(vec ? BLDP_MEDSEL(k_median_select, true, false)
-                         : BLDP_MEDSEL(k_median_select, false, false), grid, s, a);
+      return go(vec ? BLDP_MEDSEL(k_median_select, true, false)
+                    : BLDP_MEDSEL(k_median_select, false, false), a);
 #undef BLDP_VECSEL
 #undef BLDP_MEDSEL
   }

@@ -651,23 +651,12 @@ int plan_tstat(TStatArgs &a, int op, bool words, int num_cus, int xcd_lg, TStatP
 }
 
 namespace {
-// One dispatch; it carries the timing events of bldp_reduce_launch_timed when set.
-template <typename... Args>
-hipError_t launch1(void (*kn)(Args...), dim3 grid, hipStream_t s, Args... args) {
-  hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-  take_launch_events(&ev_start, &ev_stop);
-  if (ev_stop)
-    hipExtLaunchKernelGGL(kn, grid, dim3(kBlock), 0, s, ev_start, ev_stop, 0, args...);
-  else
-    hipLaunchKernelGGL(kn, grid, dim3(kBlock), 0, s, args...);
-  return hipGetLastError();
-}
 
 template <int TP, int CPL>
 hipError_t launch_regs_cpl(const TStatArgs &a, bool med, dim3 grid, int op, hipStream_t s) {
-  if (!med) return launch1(k_tstat_regs<TP, CPL, 0>, grid, s, a, op);
-  return launch1(op == BLDP_OP_MAD ? k_tstat_regs<TP, CPL, 2> : k_tstat_regs<TP, CPL, 1>, grid, s,
-                 a, op);
+  if (!med) return launch_kernel(k_tstat_regs<TP, CPL, 0>, grid, dim3(kBlock), 0, s, a, op);
+  return launch_kernel(op == BLDP_OP_MAD ? k_tstat_regs<TP, CPL, 2> : k_tstat_regs<TP, CPL, 1>, grid,
+                       dim3(kBlock), 0, s, a, op);
 }
 template <int TP>
 hipError_t launch_regs(const TStatArgs &a, bool med, dim3 grid, int op, hipStream_t s) {
@@ -679,6 +668,9 @@ hipError_t launch_regs(const TStatArgs &a, bool med, dim3 grid, int op, hipStrea
 hipError_t launch_tstat(const TStatArgs &a, const TStatPlan &p, int op, hipStream_t s) {
   if (p.grid <= 0) return hipSuccess;
   const dim3 grid((unsigned)p.grid, (unsigned)a.nbank);
+  const auto go = [&](auto *kn, auto... args) {
+    return launch_kernel(kn, grid, dim3(kBlock), 0, s, args...);
+  };
   switch (p.path) {
     case TSTAT_REGS_MOMENTS:
     case TSTAT_REGS_MEDIAN: {
@@ -691,11 +683,11 @@ hipError_t launch_tstat(const TStatArgs &a, const TStatPlan &p, int op, hipStrea
       break;
     }
     case TSTAT_SPLIT_MOMENTS:
-      return launch1(a.vec ? k_tstat_mom_split<4> : k_tstat_mom_split<1>, grid, s, a, op);
+      return go(a.vec ? k_tstat_mom_split<4> : k_tstat_mom_split<1>, a, op);
     case TSTAT_SPLIT_MEDIAN:
       if (op == BLDP_OP_MAD)
-        return launch1(a.vec ? k_tstat_med_split<4, true> : k_tstat_med_split<1, true>, grid, s, a);
-      return launch1(a.vec ? k_tstat_med_split<4, false> : k_tstat_med_split<1, false>, grid, s, a);
+        return go(a.vec ? k_tstat_med_split<4, true> : k_tstat_med_split<1, true>, a);
+      return go(a.vec ? k_tstat_med_split<4, false> : k_tstat_med_split<1, false>, a);
     case TSTAT_CHUNK_MOMENTS: {
       if (!a.ws) return hipErrorInvalidValue;
       const hipStream_t st = s;

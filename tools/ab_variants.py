@@ -171,15 +171,14 @@ VARIANTS = {
     # the per-XCD tile order (round 5 measurements; round 6: one rule,
     # kernels.hip xcd_order_pays, which these patch; the kurtosis / typed
     # forms, measured losers, were removed from the sources)
-    "tilexcd": {"patch": [(K, "    case PATH_TILE: return false;", "    case PATH_TILE: return true;")]},
-    "wavetxcd": {"patch": [(K, "      if (a.tpb > 1) return false;  // wavet",
-                            "      if (a.tpb > 1) return true;  // wavet")]},
-    "narrowtxcdoff": {"patch": [(K, "      if (a.tpb > 1) return F == 2 && bytes >= kRowtXcdBytes;  // narrowt",
-                                 "      if (a.tpb > 1) return false;  // narrowt")]},
+    "tilexcd": {"patch": [(K, "    case RK_TILE: return false;", "    case RK_TILE: return true;")]},
+    "wavetxcd": {"patch": [(K, "    case RK_WAVET: return false;", "    case RK_WAVET: return true;")]},
+    "narrowtxcdoff": {"patch": [(K, "    case RK_NARROWT: return a.F == 2 && bytes >= kRowtXcdBytes;",
+                                 "    case RK_NARROWT: return false;")]},
     "rowtxcdoff": {"patch": [(K, "constexpr int64_t kRowtXcdBytes = (int64_t)1 << 30;",
                               "constexpr int64_t kRowtXcdBytes = INT64_MAX;")]},
-    "narrowxcdoff": {"patch": [(K, "      return true;  // narrow", "      return false;  // narrow")]},
-    "vecxcdoff": {"patch": [(K, "      return true;  // vec", "      return false;  // vec")]},
+    "narrowxcdoff": {"patch": [(K, "    case RK_NARROW: return true;", "    case RK_NARROW: return false;")]},
+    "vecxcdoff": {"patch": [(K, "    case RK_VEC: return true;", "    case RK_VEC: return false;")]},
     "rowxcdoff": {"patch": [(K, "constexpr int64_t kRowXcdMinPitch = (int64_t)4 << 20;",
                              "constexpr int64_t kRowXcdMinPitch = INT64_MAX;")]},
     # k_kurt_i8 (8-bit getkurtosis, round 6): loads per batch, a wave cap
