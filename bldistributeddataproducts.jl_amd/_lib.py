@@ -20,6 +20,48 @@ OPS = {"sum": 0, "mean": 1, "max": 2, "min": 3, "var": 4, "std": 5, "median": 6,
 # MAD_CONSTANT; code 7 is unassigned): Float32 on the GPU, no time integration
 STAT_OPS = ("var", "std", "median", "mad")
 MAD_CONSTANT = 1.4826022185056018  # 1 / quantile(Normal(), 3/4), StatsBase's mad_constant
+
+
+def quantile_p(p) -> float:
+    """The probability of a quantile as a Float64 in [0, 1] (ValueError otherwise)."""
+    try:
+        q = float(p)
+    except (TypeError, ValueError):
+        raise ValueError(f"quantile: p={p!r} is not a number in [0, 1]") from None
+    if not 0.0 <= q <= 1.0:  # (NaN fails both comparisons)
+        raise ValueError(f"quantile: p={p!r} is outside [0, 1]")
+    return q
+
+
+def quantile(p):
+    """The fqavfunc / tavfunc of Statistics.quantile(block, p) (Julia's default,
+    type 7): the tuple ``("quantile", p)``, taken wherever ``"median"`` is.  It is
+    no entry of OPS: the library's bldp_quantile_* entry points carry p."""
+    return ("quantile", quantile_p(p))
+
+
+def quantile_of(op):
+    """p of a ``("quantile", p)`` function (checked: ValueError), else None."""
+    if isinstance(op, tuple) and len(op) == 2 and op[0] == "quantile":
+        return quantile_p(op[1])
+    return None
+
+
+def stat_op(op) -> bool:
+    """var / std / median / mad or a quantile: Float32 on the GPU, one axis."""
+    return (isinstance(op, str) and op in STAT_OPS) or quantile_of(op) is not None
+
+
+def quantile_rank(n: int, p: float):
+    """(j, g) of Statistics.quantile (type 7) for n >= 2 values: the 1-based lower
+    rank and the weight of the next, Float64 with every operation rounded once."""
+    p = float(p)
+    m = 1.0 + p * (1.0 - 1.0 - 1.0)
+    aleph = n * p + m
+    j = int(min(max(float(int(aleph)), 1.0), float(n - 1)))
+    return j, min(max(aleph - j, 0.0), 1.0)
+
+
 PATHS = {0: "vector", 1: "narrow", 2: "scalar", 3: "tile", 4: "interleaved", 5: "row",
          6: "narrow_mis", 7: "lane", 8: "moments", 9: "median_sort", 10: "median_select",
          11: "median_stream"}
@@ -125,6 +167,11 @@ SIGNATURES = {
     "bldp_tstat_f32": ([P, I64, I64, I64, P, I64, I, P, I64, I64, P], I),
     "bldp_band_tstat_f32": ([I, P, I64, I64, I64, P, I64, I, P, P], I),
     "bldp_tstat_host_f32": ([I, P, I64, I64, I64, P, I64, I, P], I),
+    "bldp_quantile_shape": ([I64, I64, I64, P, I, I64, P], I),
+    "bldp_quantile_plan_f32": ([P, I64, I64, I64, P, I, I64, D, P, P], I),
+    "bldp_quantile_f32": ([P, I64, I64, I64, P, I, I64, D, P, I64, I64, P], I),
+    "bldp_band_quantile_f32": ([I, P, I64, I64, I64, P, I, I64, D, P, P], I),
+    "bldp_quantile_host_f32": ([I, P, I64, I64, I64, P, I, I64, D, P], I),
     "bldp_argext_plan_f32": ([P, I64, I64, I64, P, I64, I64, I, P, P], I),
     "bldp_argext_f32": ([P, I64, I64, I64, P, I64, I64, I, P, P, I64, I64, P], I),
     "bldp_band_argext_f32": ([I, P, I64, I64, I64, P, I64, I64, I, P, P, P], I),

@@ -291,16 +291,22 @@ int valid_op(int op) { return (op >= BLDP_OP_SUM && op <= BLDP_OP_MEDIAN) || op 
 
 // Checks, window and plan of a reduce (shared by every reduce entry point and
 // by the prepared form): fills *a and *p; *empty when there is nothing to do.
+// qp: the probability of a quantile (the bldp_quantile_* entry points; op is
+// then kOpQuantile, which no caller's op can be).
 int prepare_reduce(int nbank, const float *const *in, int64_t nchan, int64_t nif, int64_t ntime,
                    const int64_t *win, int64_t fqavby, int64_t tavby, int op, float *out,
                    int64_t out_bank, int64_t out_ld_i, int64_t out_ld_t, bool stitched,
-                   bool query, RedArgs *ap, Plan *pp, bool *empty) {
+                   bool query, RedArgs *ap, Plan *pp, bool *empty, const double *qp = nullptr) {
   if (nbank < 1 || nbank > BLDP_MAX_BANKS)
     return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
-  if (!valid_op(op)) return fail(BLDP_EINVAL, "unknown op %d (" BLDP_OP_NAMES ")", op);
-  // Statistics' var / std / median (and mad) reduce the channel blocks only: fqav
-  // on the time axis after them would not be the statistic of the F x T block
-  if (stat_op(op) && tavby > 1)
+  if (qp)
+    op = kOpQuantile;
+  else if (!valid_op(op))
+    return fail(BLDP_EINVAL, "unknown op %d (" BLDP_OP_NAMES ")", op);
+  const bool stat = stat_op(op) || qp;
+  // Statistics' var / std / median (and mad, quantile) reduce the channel blocks
+  // only: fqav on the time axis after them would not be the statistic of the F x T block
+  if (stat && tavby > 1)
     return fail(BLDP_EINVAL,
                 "tavby=%lld: var/std/median/mad have no time integration (tavby <= 1)",
                 (long long)tavby);
@@ -318,6 +324,11 @@ int prepare_reduce(int nbank, const float *const *in, int64_t nchan, int64_t nif
   a.F = F;
   a.T = T;
   a.nbank = nbank;
+  if (qp && F > 1) {
+    int64_t q;
+    quantile_rank(F, *qp, &q, &a.qg);
+    a.qrank = (int32_t)q;
+  }
   if (stitched) {
     a.out_bank = a.nco;
     a.out_ld_i = nbank * a.nco;
@@ -343,7 +354,7 @@ int prepare_reduce(int nbank, const float *const *in, int64_t nchan, int64_t nif
   const bool aligned = (rows16 && vec_ok(g)) ||
                        (opt(OPT_UNALIGNED_VEC) >= 1 && words && g.cs == 1 &&
                         unaligned_vec_pays(F, rows16));
-  if (stat_op(op)) {
+  if (stat) {
     rc = plan_stats(a, op, words && g.cs == 1, xcd_log2_current(), pp);
     if (rc) return rc;
   } else {
@@ -366,7 +377,8 @@ int run_reduce(RedArgs a, const Plan &p, int op, hipStream_t s) {
     if (rc) return rc;
     a.ws = (float *)lease.ptr;
   }
-  hipError_t e = stat_op(op) ? launch_stats(a, p, op, s) : launch_reduce(a, p, op, s);
+  hipError_t e = stat_op(op) || op == kOpQuantile ? launch_stats(a, p, op, s)
+                                                  : launch_reduce(a, p, op, s);
   if (e != hipSuccess) return fail(BLDP_EHIP, "reduce launch: %s", hipGetErrorString(e));
   return BLDP_OK;
 }
@@ -374,13 +386,14 @@ int run_reduce(RedArgs a, const Plan &p, int op, hipStream_t s) {
 int reduce_impl(int nbank, const float *const *in, int64_t nchan, int64_t nif, int64_t ntime,
                 const int64_t *win, int64_t fqavby, int64_t tavby, int op, float *out,
                 int64_t out_bank, int64_t out_ld_i, int64_t out_ld_t, bool stitched,
-                hipStream_t s, int64_t *info) {
+                hipStream_t s, int64_t *info, const double *qp = nullptr) {
   RedArgs a;
   Plan p;
   bool empty = false;
   int rc = prepare_reduce(nbank, in, nchan, nif, ntime, win, fqavby, tavby, op, out, out_bank,
-                          out_ld_i, out_ld_t, stitched, info != nullptr, &a, &p, &empty);
+                          out_ld_i, out_ld_t, stitched, info != nullptr, &a, &p, &empty, qp);
   if (rc) return rc;
+  if (qp) op = kOpQuantile;
   if (info) {
     info[0] = p.path;
     info[1] = p.lpg;
@@ -390,6 +403,7 @@ int reduce_impl(int nbank, const float *const *in, int64_t nchan, int64_t nif, i
     info[5] = p.grid;
     info[6] = (int64_t)p.ws_bytes;
     info[7] = a.vec_out;
+    if (qp) info[6] = a.F > 1 ? a.qrank : -1;  // (no workspace: the slot carries the lower rank)
     return BLDP_OK;  // plan query only
   }
   if (empty) return BLDP_OK;
@@ -1233,10 +1247,13 @@ int bldp_band_moments_f32(int nbank, const float *const *in, int64_t nchan, int6
 static int tstat_prepare(int nbank, const float *const *in, int64_t nchan, int64_t nif,
                          int64_t ntime, const int64_t *win, int64_t tavby, int op, float *out,
                          int64_t out_bank, int64_t out_ld_i, int64_t out_ld_b, bool query,
-                         TStatArgs *ap, TStatPlan *pp, bool *copy, bool *empty) {
+                         TStatArgs *ap, TStatPlan *pp, bool *copy, bool *empty,
+                         const double *qp = nullptr) {
   if (nbank < 1 || nbank > BLDP_MAX_BANKS)
     return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
-  if (!stat_op(op))
+  if (qp)  // (the bldp_quantile_* entry points: kOpQuantile, which no caller's op can be)
+    op = kOpQuantile;
+  else if (!stat_op(op))
     return fail(BLDP_EINVAL,
                 "tstat: op %d is not 4=var 5=std 6=median 8=mad (sum/mean/max/min over time: "
                 "bldp_reduce_* with tavby)",
@@ -1263,6 +1280,11 @@ static int tstat_prepare(int nbank, const float *const *in, int64_t nchan, int64
   a.out_bank = out_bank;
   a.out_ld_i = out_ld_i;
   a.out_ld_b = out_ld_b;
+  if (qp && T > 1) {
+    int64_t q;
+    quantile_rank(T, *qp, &q, &a.qg);
+    a.qrank = (int32_t)q;
+  }
   *empty = a.nc == 0 || a.ni == 0 || a.nb == 0;
   if (!in) return fail(BLDP_EINVAL, "tstat: null input pointer array");
   bool words = true;
@@ -1291,13 +1313,15 @@ static int tstat_prepare(int nbank, const float *const *in, int64_t nchan, int64
 
 static int tstat_run(int nbank, const float *const *in, int64_t nchan, int64_t nif, int64_t ntime,
                      const int64_t *win, int64_t tavby, int op, float *out, int64_t out_bank,
-                     int64_t out_ld_i, int64_t out_ld_b, void *stream) {
+                     int64_t out_ld_i, int64_t out_ld_b, void *stream,
+                     const double *qp = nullptr) {
   TStatArgs a;
   TStatPlan p;
   bool copy = false, empty = false;
   int rc = tstat_prepare(nbank, in, nchan, nif, ntime, win, tavby, op, out, out_bank, out_ld_i,
-                         out_ld_b, false, &a, &p, &copy, &empty);
+                         out_ld_b, false, &a, &p, &copy, &empty, qp);
   if (rc || empty) return rc;
+  if (qp) op = kOpQuantile;
   hipStream_t s = (hipStream_t)stream;
   if (copy)  // the window itself: the reduce's F = T = 1 copy
     return reduce_impl(nbank, in, nchan, nif, ntime, win, 1, 1, BLDP_OP_SUM, out, out_bank,
@@ -1318,16 +1342,17 @@ int bldp_tstat_shape(int64_t nchan, int64_t nif, int64_t ntime, const int64_t *w
   return bldp_reduce_shape(nchan, nif, ntime, win, 1, tavby, dims);
 }
 
-int bldp_tstat_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
-                        const int64_t *win, int64_t tavby, int op, const float *out,
-                        int64_t info[8]) {
+// bldp_tstat_plan_f32, and with qp the time-axis plan of bldp_quantile_plan_f32
+static int tstat_plan(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                      const int64_t *win, int64_t tavby, int op, const float *out,
+                      int64_t info[8], const double *qp) {
   if (!info) return fail(BLDP_EINVAL, "null info");
   TStatArgs a;
   TStatPlan p;
   bool copy = false, empty = false;
   const float *ins[1] = {in};
   int rc = tstat_prepare(1, ins, nchan, nif, ntime, win, tavby, op, (float *)out, 0, 0, 0, true,
-                         &a, &p, &copy, &empty);
+                         &a, &p, &copy, &empty, qp);
   if (rc) return rc;
   if (copy) {  // the plan of the copy (bldp_reduce_plan_f32 of F = T = 1), path -1
     rc = bldp_reduce_plan_f32(in, nchan, nif, ntime, win, 1, 1, BLDP_OP_SUM, out, info);
@@ -1335,6 +1360,7 @@ int bldp_tstat_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t nti
     const int64_t grid = info[5], ws = info[6];
     info[0] = -1, info[1] = 1, info[2] = 1, info[3] = 1, info[4] = grid, info[5] = ws;
     info[6] = a.nb, info[7] = 0;
+    if (qp) info[5] = -1;  // (no rank: the window itself)
     return BLDP_OK;
   }
   info[0] = p.path;
@@ -1345,7 +1371,14 @@ int bldp_tstat_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t nti
   info[5] = (int64_t)p.ws_bytes;
   info[6] = a.nb;
   info[7] = p.tsplit > 1 ? ((int64_t)1 << a.lx_log2) : 0;
+  if (qp) info[5] = a.qrank;  // (no workspace: the slot carries the lower rank)
   return BLDP_OK;
+}
+
+int bldp_tstat_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                        const int64_t *win, int64_t tavby, int op, const float *out,
+                        int64_t info[8]) {
+  return tstat_plan(in, nchan, nif, ntime, win, tavby, op, out, info, nullptr);
 }
 
 int bldp_tstat_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win,
@@ -1366,6 +1399,69 @@ int bldp_band_tstat_f32(int nbank, const float *const *in, int64_t nchan, int64_
   // the vcat of the banks: bank k's channels at k*nc of every (IF, block) row
   return tstat_run(nbank, in, nchan, nif, ntime, win, tavby, op, out, d[0], nbank * d[0],
                    nbank * d[0] * d[1], stream);
+}
+
+// ---- quantile(p): an order statistic of blocks of channels or of spectra -----
+// The checks every bldp_quantile_* entry point makes before anything else.
+static int quantile_check(int axis, double p) {
+  if (axis != 0 && axis != 2)
+    return fail(BLDP_EINVAL,
+                "quantile: axis %d is not 0 (blocks of n channels) or 2 (blocks of n spectra)",
+                axis);
+  if (!(p >= 0.0 && p <= 1.0)) return fail(BLDP_EINVAL, "quantile: p=%g is outside [0, 1]", p);
+  return BLDP_OK;
+}
+
+int bldp_quantile_shape(int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win, int axis,
+                        int64_t n, int64_t dims[3]) {
+  const int rc = quantile_check(axis, 0.0);
+  if (rc) return rc;
+  return bldp_reduce_shape(nchan, nif, ntime, win, axis == 0 ? n : 1, axis == 0 ? 1 : n, dims);
+}
+
+int bldp_quantile_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                           const int64_t *win, int axis, int64_t n, double p, const float *out,
+                           int64_t info[8]) {
+  if (!info) return fail(BLDP_EINVAL, "null info");
+  int rc = quantile_check(axis, p);
+  if (rc) return rc;
+  if (axis == 2) return tstat_plan(in, nchan, nif, ntime, win, n, 0, out, info, &p);
+  int64_t sh[3];
+  rc = bldp_reduce_shape(nchan, nif, ntime, win, n, 1, sh);
+  if (rc) return rc;
+  const float *ins[1] = {in};
+  return reduce_impl(1, ins, nchan, nif, ntime, win, n, 1, 0, (float *)out, sh[0] * sh[1] * sh[2],
+                     sh[0], sh[0] * sh[1], false, nullptr, info, &p);
+}
+
+int bldp_quantile_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                      const int64_t *win, int axis, int64_t n, double p, float *out,
+                      int64_t out_ld_i, int64_t out_ld_t, void *stream) {
+  const int rc = quantile_check(axis, p);
+  if (rc) return rc;
+  const float *ins[1] = {in};
+  if (axis == 2)
+    return tstat_run(1, ins, nchan, nif, ntime, win, n, 0, out, 0, out_ld_i, out_ld_t, stream, &p);
+  return reduce_impl(1, ins, nchan, nif, ntime, win, n, 1, 0, out, 0, out_ld_i, out_ld_t, false,
+                     (hipStream_t)stream, nullptr, &p);
+}
+
+int bldp_band_quantile_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                           int64_t ntime, const int64_t *win, int axis, int64_t n, double p,
+                           float *out, void *stream) {
+  int rc = quantile_check(axis, p);
+  if (rc) return rc;
+  if (axis == 0)
+    return reduce_impl(nbank, in, nchan, nif, ntime, win, n, 1, 0, out, 0, 0, 0, true,
+                       (hipStream_t)stream, nullptr, &p);
+  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
+    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
+  int64_t d[3];
+  rc = bldp_tstat_shape(nchan, nif, ntime, win, n, d);
+  if (rc) return rc;
+  // the vcat of the banks, as bldp_band_tstat_f32
+  return tstat_run(nbank, in, nchan, nif, ntime, win, n, 0, out, d[0], nbank * d[0],
+                   nbank * d[0] * d[1], stream, &p);
 }
 
 // ---- fqavfunc argmax / argmin: the winner's offset in every F x T block ------

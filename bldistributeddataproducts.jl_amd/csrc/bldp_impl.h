@@ -82,6 +82,8 @@ struct RedArgs {
   int32_t st_plain;        // row / il / rowt output stores plain (1) or non-temporal (0)
   int32_t xcd_lg;          // log2 XCDs of the per-XCD tile order (xcd_order), 0 = off
   float div;               // F*T, the mean divisor
+  int32_t qrank;           // quantile: the lower rank j - 1 (0-based; the upper is qrank + 1 < F)
+  double qg;               // quantile: the weight g of the upper rank
 };
 
 // Runtime plan options (bldp_plan_option): process-wide overrides of the
@@ -184,7 +186,21 @@ __device__ __forceinline__ uint32_t xcd_order(uint32_t x, uint32_t X, int lg) {
 inline bool stat_op(int op) {
   return (op >= BLDP_OP_VAR && op <= BLDP_OP_MEDIAN) || op == BLDP_OP_MAD;
 }
-inline bool median_op(int op) { return op == BLDP_OP_MEDIAN || op == BLDP_OP_MAD; }
+// quantile(p) is no op of the ABI (its entry points carry p, not an op): inside
+// the library it travels as kOpQuantile with the rank and weight in the args.
+constexpr int kOpQuantile = 64;
+// the ops that take the median's kernels and plans
+inline bool median_op(int op) {
+  return op == BLDP_OP_MEDIAN || op == BLDP_OP_MAD || op == kOpQuantile;
+}
+// What the median's kernels select (their compile-time selector): ranks
+// (n-1)/2 and n/2 once, the same twice (mad), or the run-time ranks qrank and
+// qrank + 1 joined by quantile_of.
+enum Sel { SEL_MEDIAN = 0, SEL_MAD = 1, SEL_QUANTILE = 2 };
+// The 0-based lower rank j - 1 and the weight g of Statistics.quantile(x, p)
+// of n >= 2 values (type 7), in Float64 with every operation rounded once
+// (host.hip); the upper rank is always *rank + 1 <= n - 1.
+void quantile_rank(int64_t n, double p, int64_t *rank, double *g);
 // mad: the median of |x - median(x)| times StatsBase's Float64 mad_constant
 // (1 / quantile(Normal(), 3/4)), the product rounded once more to Float32
 __device__ __forceinline__ float mad_scale(float m) {
@@ -194,6 +210,28 @@ __device__ __forceinline__ float mad_scale(float m) {
 __device__ __forceinline__ float abs_dev(float x, float c) {
 #pragma clang fp contract(off)
   return fabsf(__fsub_rn(x, c));
+}
+// Statistics' quantile from the keys' values a = v[j], b = v[j + 1] and the
+// weight g: a + g * (b - a) with the difference rounded once to Float32 and
+// the product and the sum once each in Float64 where both are finite, else
+// (1 - g) * a + g * b (NaN for a zero weight next to an infinity: the formula
+// as it stands); the result rounded to Float32.  Never fused: the products
+// and sums are written as operators under the pragma, because hipcc contracts
+// by default and __dmul_rn / __dadd_rn are ordinary operators of a header
+// compiled without it (they came out as v_fmac_f64 here).
+__device__ __forceinline__ float quantile_mix(float a, float b, double g) {
+#pragma clang fp contract(off)
+  double r;
+  if (isfinite(a) && isfinite(b)) {
+    const float d = b - a;
+    const double gd = g * (double)d;
+    r = (double)a + gd;
+  } else {
+    const double w = 1.0 - g;
+    const double wa = w * (double)a, gb = g * (double)b;
+    r = wa + gb;
+  }
+  return (float)r;
 }
 int plan_stats(RedArgs &a, int op, bool words, int xcd_lg, Plan *p);
 hipError_t launch_stats(const RedArgs &a, const Plan &p, int op, hipStream_t s);
@@ -234,6 +272,8 @@ struct TStatArgs {
   int32_t nchunk;
   int64_t tchunk;
   double *ws;
+  int32_t qrank;  // quantile: the lower rank j - 1 (0-based; the upper is qrank + 1 < T)
+  double qg;      // quantile: the weight g of the upper rank
 };
 enum TStatPath { TSTAT_REGS_MOMENTS = 0, TSTAT_REGS_MEDIAN = 1, TSTAT_SPLIT_MOMENTS = 2,
                  TSTAT_SPLIT_MEDIAN = 3, TSTAT_CHUNK_MOMENTS = 4 };

@@ -320,6 +320,54 @@ extern "C" int bldp_tstat_host_f32(int dev, const float *in, int64_t nchan, int6
   });
 }
 
+// Statistics.quantile's index and weight (type 7, alpha = beta = 1) for n >= 2
+// values: m = 1 + p (1 - alpha - beta), aleph = n p + m, j = clamp(trunc(aleph),
+// 1, n - 1), g = clamp(aleph - j, 0, 1), every operation rounded once (a fused
+// n p + m would move g by an ulp); *rank is j - 1.
+void bldp::quantile_rank(int64_t n, double p, int64_t *rank, double *g) {
+#pragma clang fp contract(off)
+  const double m = 1.0 + p * (1.0 - 1.0 - 1.0);
+  const double np = (double)n * p;
+  const double aleph = np + m;
+  const double j = std::min(std::max(std::trunc(aleph), 1.0), (double)(n - 1));
+  *rank = (int64_t)j - 1;
+  *g = std::min(std::max(aleph - j, 0.0), 1.0);
+}
+
+// The same staging for quantile(p) over blocks of n channels (axis 0) or n
+// spectra (axis 2): the window's rows go to the device once (in window order),
+// the dense product of bldp_quantile_shape comes back.
+extern "C" int bldp_quantile_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                      int64_t ntime, const int64_t *win, int axis, int64_t n,
+                                      double p, float *out) {
+  // (every argument check, before any staging)
+  int64_t info[8], sh[3];
+  int rc = bldp_quantile_plan_f32(nullptr, nchan, nif, ntime, win, axis, n, p, nullptr, info);
+  if (rc) return rc;
+  rc = bldp_quantile_shape(nchan, nif, ntime, win, axis, n, sh);
+  if (rc) return rc;
+  const int64_t nn = n <= 1 ? 1 : n;
+  const int64_t nc = axis == 0 ? sh[0] * nn : sh[0], ni = sh[1];
+  const int64_t nt = axis == 2 ? sh[2] * nn : sh[2], nout = sh[0] * sh[1] * sh[2];
+  if (nout == 0) return BLDP_OK;
+  if (!out || !in) return bldp::set_error(BLDP_EINVAL, "quantile: null pointer");
+  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
+  return with_stager(dev, [&](bldp::Stager *sg) -> int {
+    float *dbuf, *dout;
+    int r = bldp::stager_buffer(sg, 0, (size_t)(h.span * ni * nt) * 4, (void **)&dbuf);
+    if (!r) r = bldp::stager_buffer(sg, 2, (size_t)nout * sizeof(float), (void **)&dout);
+    if (!r) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
+    if (r) return r;
+    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
+    r = bldp_quantile_f32(dbuf, h.span, ni, nt, dwin, axis, n, p, dout, sh[0], sh[0] * ni,
+                          sg->st[0]);
+    if (r) return r;
+    HCHK(hipMemcpyAsync(out, dout, (size_t)nout * sizeof(float), hipMemcpyDeviceToHost,
+                        sg->st[0]));
+    return BLDP_OK;
+  });
+}
+
 // The same staging for fqavfunc argmax / argmin: the window's rows go to the
 // device once (in window order), the (nco, ni, nto) offsets, and the winners'
 // bits when val is given, come back.

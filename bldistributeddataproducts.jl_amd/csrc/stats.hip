@@ -39,6 +39,13 @@
 //              keys in registers become those of |x - c| in place (one read
 //              of the block), the stream form reads the block again and forms
 //              the deviations on the way.  Plans and paths are the median's.
+//   quantile   Statistics.quantile(x, p) (type 7): the host turns (F, p) into
+//              the lower rank q = j - 1 and the weight g (RedArgs qrank, qg);
+//              the median's kernels with SEL_QUANTILE select ranks q and q + 1
+//              where the median's take (F-1)/2 and F/2, and quantile_of joins
+//              them: a + g (b - a), the difference rounded once to Float32, the
+//              rest once each in Float64; NaN wins.  Plans and paths are the
+//              median's.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -247,6 +254,12 @@ __device__ __forceinline__ float median_of(uint32_t k0, uint32_t k1, bool odd, b
   return odd ? key2f(k0) : middle(key2f(k0), key2f(k1));
 }
 
+// Ranks q and q + 1 of a block joined with weight g (bldp_impl.h quantile_mix)
+__device__ __forceinline__ float quantile_of(uint32_t k0, uint32_t k1, double g, bool nan) {
+  if (nan) return __uint_as_float(0x7fc00000u);
+  return quantile_mix(key2f(k0), key2f(k1), g);
+}
+
 constexpr uint32_t kPadKey = 0xffffffffu;  // above every non-NaN key
 
 // The bitonic network over the L keys of a group of L / 4 lanes (key e = 4 *
@@ -281,9 +294,11 @@ __device__ __forceinline__ void bitonic_sort4(uint32_t (&k)[4], const int lg) {
 
 // L = next_pow2(F) >= 4 keys over L / 4 lanes, key e = 4 * lane + r.  MAD: the
 // sorted keys become those of |x - median| in place (the padding, which sorts
-// to e >= F, stays) and the network runs again.
-template <int L, bool VEC, bool MAD>
+// to e >= F, stays) and the network runs again.  SEL_QUANTILE: the ranks are
+// a.qrank and the next.
+template <int L, bool VEC, Sel SEL>
 __global__ __launch_bounds__(kBlock) void k_median_sort(const RedArgs a) {
+  constexpr bool MAD = SEL == SEL_MAD;
   constexpr int LG = L / 4;
   const int lg = threadIdx.x % LG;
   const int64_t tile = xcd_order(blockIdx.x, gridDim.x, a.xcd_lg);
@@ -310,7 +325,8 @@ __global__ __launch_bounds__(kBlock) void k_median_sort(const RedArgs a) {
   }
   bitonic_sort4<L>(k, lg);
   // ranks (F-1)/2 and F/2 (the same for odd F); the padding sorts above them
-  const int q0 = (F - 1) / 2, q1 = F / 2;
+  const int q0 = SEL == SEL_QUANTILE ? a.qrank : (F - 1) / 2;
+  const int q1 = SEL == SEL_QUANTILE ? a.qrank + 1 : F / 2;
   auto pick = [&](int q) {
     const int r = q & 3;
     uint32_t x = r == 0 ? k[0] : r == 1 ? k[1] : r == 2 ? k[2] : k[3];
@@ -334,8 +350,12 @@ __global__ __launch_bounds__(kBlock) void k_median_sort(const RedArgs a) {
   const unsigned long long gmask = LG == 64 ? ~0ull : ((1ull << LG) - 1ull);
   const bool gnan = ((bal >> ((threadIdx.x & 63) - lg)) & gmask) != 0;
   if (ok && lg == 0) {
-    const float m = median_of(k0, k1, F & 1, gnan);
-    *o = MAD ? mad_scale(m) : m;
+    if constexpr (SEL == SEL_QUANTILE) {
+      *o = quantile_of(k0, k1, a.qg, gnan);
+    } else {
+      const float m = median_of(k0, k1, F & 1, gnan);
+      *o = MAD ? mad_scale(m) : m;
+    }
   }
 }
 
@@ -361,8 +381,10 @@ __device__ __forceinline__ void hist_add(uint32_t *h, uint32_t d, bool pred) {
 // MAD: the four passes run twice, the second time over |x - c| with c the
 // median the first found: the register keys are transformed in place (REG),
 // or the block is read again and the deviations formed on the way (!REG).
-template <bool VEC, bool REG, bool MAD>
+// SEL_QUANTILE: the two ranks start at a.qrank and the next.
+template <bool VEC, bool REG, Sel SEL>
 __global__ __launch_bounds__(kBlock) void k_median_select(const RedArgs a) {
+  constexpr bool MAD = SEL == SEL_MAD;
   __shared__ uint32_t hist[2][256];
   __shared__ uint32_t wtot[2][4];
   __shared__ uint32_t sel[2][2];  // per rank: its digit, its rank among that digit's keys
@@ -404,7 +426,9 @@ __global__ __launch_bounds__(kBlock) void k_median_select(const RedArgs a) {
   }
   if (tid == 0) nanflag = 0;
   uint32_t pre0 = 0, pre1 = 0;                       // key bits fixed so far
-  uint32_t r0 = (uint32_t)((F - 1) / 2), r1 = (uint32_t)(F / 2);  // rank among the prefix's keys
+  // rank among the prefix's keys
+  uint32_t r0 = SEL == SEL_QUANTILE ? (uint32_t)a.qrank : (uint32_t)((F - 1) / 2);
+  uint32_t r1 = SEL == SEL_QUANTILE ? (uint32_t)a.qrank + 1u : (uint32_t)(F / 2);
   for (int pass = 0; pass < (MAD ? 8 : 4); ++pass) {
     if (MAD && pass == 4) {  // the median is known: the same four passes over |x - cen|
       cen = median_of(pre0, pre1, F & 1, false);  // (a NaN block: NaN below, whatever cen is)
@@ -475,8 +499,12 @@ __global__ __launch_bounds__(kBlock) void k_median_select(const RedArgs a) {
     r1 = sel[1][1];
   }
   if (tid == 0) {
-    const float m = median_of(pre0, pre1, F & 1, nanflag != 0);
-    *o = MAD ? mad_scale(m) : m;
+    if constexpr (SEL == SEL_QUANTILE) {
+      *o = quantile_of(pre0, pre1, a.qg, nanflag != 0);
+    } else {
+      const float m = median_of(pre0, pre1, F & 1, nanflag != 0);
+      *o = MAD ? mad_scale(m) : m;
+    }
   }
 }
 
@@ -506,7 +534,8 @@ int plan_stats(RedArgs &a, int op, bool words, int xcd_lg, Plan *pp) {
   };
   // F = 1: fqav(A, n <= 1) returns A whatever f is (src/gbtworkerfunctions.jl:17),
   // which is what the median of one element copies
-  if (median_op(op) || F == 1) {  // (mad: the median's path, its selection run twice)
+  // (mad: the median's path, its selection run twice; quantile: its ranks moved)
+  if (median_op(op) || F == 1) {
     if (F >= ((int64_t)1 << 31))
       return set_error(BLDP_EINVAL, "median: fqavby=%lld is beyond 2^31 - 1", (long long)F);
     if (F <= kSortMaxF) {
@@ -524,7 +553,7 @@ int plan_stats(RedArgs &a, int op, bool words, int xcd_lg, Plan *pp) {
   a.ntiles = p.lpg == kBlock ? p.nout : (p.nout + kBlock / p.lpg - 1) / (kBlock / p.lpg);
   if (a.ntiles > INT32_MAX)
     return set_error(BLDP_EINVAL,
-                     "median/var/std/mad: %lld blocks of %lld are too many for one launch",
+                     "median/var/std/mad/quantile: %lld blocks of %lld are too many for one launch",
                      (long long)p.nout, (long long)F);
   p.grid = a.ntiles;
   p.ws_bytes = 0;
@@ -546,7 +575,11 @@ hipError_t launch_stats(const RedArgs &a, const Plan &p, int op, hipStream_t s) 
     return launch_kernel(kn, grid, dim3(kBlock), 0, s, args...);
   };
   const bool vec = a.k4 != 0;
-  const bool mad = op == BLDP_OP_MAD && a.F > 1;  // (F = 1: the copy, as every op)
+  // (F = 1: the copy, as every op)
+  const Sel sel = a.F <= 1 ? SEL_MEDIAN
+                           : op == BLDP_OP_MAD ? SEL_MAD : op == kOpQuantile ? SEL_QUANTILE : SEL_MEDIAN;
+  if (sel == SEL_QUANTILE && (a.qrank < 0 || (int64_t)a.qrank + 1 >= a.F))
+    return hipErrorInvalidValue;  // (the upper rank must be a key of the block)
 #define BLDP_VECSEL(KN, N) (vec ? KN<N, true> : KN<N, false>)
   switch (p.path) {
     case PATH_MOMENTS:
@@ -562,7 +595,9 @@ hipError_t launch_stats(const RedArgs &a, const Plan &p, int op, hipStream_t s) 
       }
       break;
 #undef BLDP_VECSEL
-#define BLDP_MEDSEL(KN, A, B) (mad ? KN<A, B, true> : KN<A, B, false>)
+#define BLDP_MEDSEL(KN, A, B)               \
+  (sel == SEL_MAD ? KN<A, B, SEL_MAD>       \
+                  : sel == SEL_QUANTILE ? KN<A, B, SEL_QUANTILE> : KN<A, B, SEL_MEDIAN>)
 #define BLDP_VECSEL(KN, N) (vec ? BLDP_MEDSEL(KN, N, true) : BLDP_MEDSEL(KN, N, false))
     case PATH_MEDIAN_SORT:
       switch (p.lpg) {  // lanes of 4 keys

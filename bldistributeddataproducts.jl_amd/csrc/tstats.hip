@@ -42,6 +42,11 @@
 //              run twice: the register form sorts the keys of |x - median| made
 //              from its sorted keys, the split form repeats its passes forming
 //              the deviations from the block as it re-reads it.
+//   quantile   (stats.hip's rule) the median's two forms selecting the run-time
+//              ranks q = TStatArgs.qrank and q + 1: the register form's chain
+//              compares against them, the split form selects rank q and always
+//              runs its fifth pass (rank q + 1 is the same key again or the
+//              smallest above it); quantile_of joins the two with weight qg.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -111,6 +116,11 @@ __device__ __forceinline__ float median_of(uint32_t k0, uint32_t k1, bool odd, b
   if (nan) return __uint_as_float(0x7fc00000u);
   return odd ? key2f(k0) : middle(key2f(k0), key2f(k1));
 }
+// Ranks q and q + 1 of a block joined with weight g (bldp_impl.h quantile_mix)
+__device__ __forceinline__ float quantile_of(uint32_t k0, uint32_t k1, double g, bool nan) {
+  if (nan) return __uint_as_float(0x7fc00000u);
+  return quantile_mix(key2f(k0), key2f(k1), g);
+}
 constexpr uint32_t kPadKey = 0xffffffffu;  // above every non-NaN key
 
 // ---------------------------------------------------------------------------
@@ -140,7 +150,8 @@ __device__ __forceinline__ void bitonic_cols(uint32_t (&k)[TP][CPL]) {
   }
 }
 
-// MED: 0 var / std, 1 median, 2 mad (the network runs again over |x - median|)
+// MED: 0 var / std, 1 median, 2 mad (the network runs again over |x - median|),
+// 3 quantile (ranks a.qrank and the next, wave-uniform, compared in the chain)
 template <int TP, int CPL, int MED>
 __global__ __launch_bounds__(kBlock) void k_tstat_regs(const TStatArgs a, const int op) {
   const int64_t tile = xcd_order(blockIdx.x, gridDim.x, a.xcd_lg);
@@ -195,7 +206,8 @@ __global__ __launch_bounds__(kBlock) void k_tstat_regs(const TStatArgs a, const 
       }
     bitonic_cols<TP, CPL>(k);
     // ranks (T-1)/2 and T/2 (the same for odd T); the padding sorts above them
-    const int q0 = (T - 1) / 2, q1 = T / 2;
+    const int q0 = MED == 3 ? a.qrank : (T - 1) / 2;
+    const int q1 = MED == 3 ? a.qrank + 1 : T / 2;
     auto ranks = [&](int c, uint32_t &k0, uint32_t &k1) {
       k0 = 0, k1 = 0;
 #pragma unroll
@@ -225,8 +237,12 @@ __global__ __launch_bounds__(kBlock) void k_tstat_regs(const TStatArgs a, const 
     for (int c = 0; c < CPL; ++c) {
       uint32_t k0, k1;
       ranks(c, k0, k1);
-      const float m = median_of(k0, k1, T & 1, nan[c]);
-      o[c] = MED == 2 ? mad_scale(m) : m;
+      if constexpr (MED == 3) {
+        o[c] = quantile_of(k0, k1, a.qg, nan[c]);
+      } else {
+        const float m = median_of(k0, k1, T & 1, nan[c]);
+        o[c] = MED == 2 ? mad_scale(m) : m;
+      }
     }
   }
 }
@@ -415,20 +431,23 @@ struct MedShared {
   int *nanflag;
 };
 
-// The select of a workgroup's tile: four passes for pre = the key of rank
-// (T-1)/2 of every column, and for even T a fifth for sh.mingt.  DEV: the keys
-// are those of |x - cen| (mad's second selection; sh.nanflag is kept).
+// The select of a workgroup's tile: four passes for pre = the key of rank q
+// (the median's (T-1)/2) of every column, and where the next rank is wanted
+// too (`upper`: the median of an even T, every quantile) a fifth for sh.mingt.
+// DEV: the keys are those of |x - cen| (mad's second selection; sh.nanflag is
+// kept).
 template <int CPL, bool DEV>
 __device__ __forceinline__ void med_select(const TStatArgs &a, const SplitGeo &g, const float *p,
                                            const MedShared &sh, const float (&cen)[CPL],
-                                           uint32_t (&pre)[CPL]) {
+                                           uint32_t (&pre)[CPL], const uint32_t q,
+                                           const bool upper) {
   const int tid = threadIdx.x;
   const int64_t T = a.T;
   const int lc0 = g.tx * CPL;  // this lane's first column of the workgroup's (lx * CPL <= kMedCols)
   // the value whose key is counted
   auto val = [&](float x, int c) { return DEV ? abs_dev(x, cen[c]) : x; };
   if (tid < kMedCols) {
-    sh.rank[0][tid] = (uint32_t)((T - 1) / 2);
+    sh.rank[0][tid] = q;
     sh.seld[tid] = 0;
     sh.selc[tid] = 0;
     sh.mingt[tid] = kPadKey;
@@ -504,9 +523,9 @@ __device__ __forceinline__ void med_select(const TStatArgs &a, const SplitGeo &g
 #pragma unroll
     for (int c = 0; c < CPL; ++c) pre[c] |= sh.seld[lc0 + c] << shift;
   }
-  // pre = the key of rank (T-1)/2; selc of them are equal, and it is number
+  // pre = the key of rank q; selc of them are equal, and it is number
   // rank[0] among those (four passes: parity 0 again)
-  if ((T & 1) == 0) {
+  if (upper) {
     if (g.ok) {
       uint32_t mn[CPL];
 #pragma unroll
@@ -528,10 +547,11 @@ __device__ __forceinline__ void med_select(const TStatArgs &a, const SplitGeo &g
   }
 }
 
-// MAD: the select runs twice, over the keys of x for the columns' medians cen,
-// then over those of |x - cen|.
-template <int CPL, bool MAD>
+// SEL_MAD: the select runs twice, over the keys of x for the columns' medians
+// cen, then over those of |x - cen|.  SEL_QUANTILE: rank a.qrank and the next.
+template <int CPL, Sel SEL>
 __global__ __launch_bounds__(kBlock) void k_tstat_med_split(const TStatArgs a) {
+  constexpr bool MAD = SEL == SEL_MAD;
   __shared__ uint32_t hist[kMedCols][256];
   __shared__ uint32_t rank[2][kMedCols];
   __shared__ uint32_t seld[kMedCols];
@@ -545,12 +565,14 @@ __global__ __launch_bounds__(kBlock) void k_tstat_med_split(const TStatArgs a) {
                    g.i * a.in_ld_i + g.b * T * a.in_ld_t;
   const int lc0 = g.tx * CPL;
   const bool odd = (T & 1) != 0;
+  const uint32_t q = SEL == SEL_QUANTILE ? (uint32_t)a.qrank : (uint32_t)((T - 1) / 2);
+  const bool upper = SEL == SEL_QUANTILE || !odd;
   float cen[CPL];
   uint32_t pre[CPL];  // key bits fixed so far
 #pragma unroll
   for (int c = 0; c < CPL; ++c) cen[c] = 0.0f;
-  med_select<CPL, false>(a, g, p, sh, cen, pre);
-  // the key of rank T/2 of an even block: pre again, or the smallest above it
+  med_select<CPL, false>(a, g, p, sh, cen, pre, q, upper);
+  // the key of the next rank (T/2 of an even block): pre again, or the smallest above it
   auto rank1 = [&](int c) {
     const int lc = lc0 + c;
     return sh.rank[0][lc] + 1 < sh.selc[lc] ? pre[c] : sh.mingt[lc];
@@ -560,14 +582,18 @@ __global__ __launch_bounds__(kBlock) void k_tstat_med_split(const TStatArgs a) {
     for (int c = 0; c < CPL; ++c)
       cen[c] = median_of(pre[c], rank1(c), odd, false);  // (a NaN block: NaN below)
     __syncthreads();  // (rank, selc and mingt are read: the second selection resets them)
-    med_select<CPL, true>(a, g, p, sh, cen, pre);
+    med_select<CPL, true>(a, g, p, sh, cen, pre, q, upper);
   }
   if (g.ok && g.ty == 0) {
     float *o = a.out + blockIdx.y * a.out_bank + g.cg * CPL + g.i * a.out_ld_i + g.b * a.out_ld_b;
 #pragma unroll
     for (int c = 0; c < CPL; ++c) {
-      const float m = median_of(pre[c], rank1(c), odd, sh.nanflag[lc0 + c] != 0);
-      o[c] = MAD ? mad_scale(m) : m;
+      if constexpr (SEL == SEL_QUANTILE) {
+        o[c] = quantile_of(pre[c], rank1(c), a.qg, sh.nanflag[lc0 + c] != 0);
+      } else {
+        const float m = median_of(pre[c], rank1(c), odd, sh.nanflag[lc0 + c] != 0);
+        o[c] = MAD ? mad_scale(m) : m;
+      }
     }
   }
 }
@@ -583,7 +609,8 @@ int pow2_ceil_log2(int64_t n, int cap) {
 int plan_tstat(TStatArgs &a, int op, bool words, int num_cus, int xcd_lg, TStatPlan *pp) {
   TStatPlan p{};
   const int64_t T = a.T;
-  const bool med = median_op(op);  // (mad: the median's path, its selection run twice)
+  // (mad: the median's path, its selection run twice; quantile: its ranks moved)
+  const bool med = median_op(op);
   const int rounds = op == BLDP_OP_MAD ? 2 : 1;
   a.vec = (words && a.in_cs == 1 && a.nc % 4 == 0) ? 1 : 0;  // float4 columns
   const int cpl = a.vec ? 4 : 1;
@@ -635,14 +662,15 @@ int plan_tstat(TStatArgs &a, int op, bool words, int num_cus, int xcd_lg, TStatP
     a.ctiles = (a.ncg + ((int64_t)1 << lg) - 1) >> lg;
     p.path = med ? TSTAT_SPLIT_MEDIAN : a.nchunk > 1 ? TSTAT_CHUNK_MOMENTS : TSTAT_SPLIT_MOMENTS;
     p.tsplit = kBlock >> lg;
-    p.passes = med ? rounds * (T % 2 ? 4 : 5) : 2;
+    // (a quantile always takes the next rank too: the fifth pass)
+    p.passes = med ? rounds * (T % 2 && op != kOpQuantile ? 4 : 5) : 2;
     grid = a.ctiles * a.nchunk * a.ni * a.nb;
     if (a.nchunk > 1)
       p.ws_bytes = (size_t)2 * a.nchunk * a.nbank * a.nb * a.ni * a.nc * sizeof(double);
   }
   if (grid > INT32_MAX)
     return set_error(BLDP_EINVAL,
-                     "tavfunc median/var/std/mad: %lld blocks of %lld spectra are too many for one "
+                     "tavfunc median/var/std/mad/quantile: %lld blocks of %lld spectra are too many for one "
                      "launch",
                      (long long)a.nb, (long long)T);
   p.grid = grid;
@@ -655,8 +683,10 @@ namespace {
 template <int TP, int CPL>
 hipError_t launch_regs_cpl(const TStatArgs &a, bool med, dim3 grid, int op, hipStream_t s) {
   if (!med) return launch_kernel(k_tstat_regs<TP, CPL, 0>, grid, dim3(kBlock), 0, s, a, op);
-  return launch_kernel(op == BLDP_OP_MAD ? k_tstat_regs<TP, CPL, 2> : k_tstat_regs<TP, CPL, 1>, grid,
-                       dim3(kBlock), 0, s, a, op);
+  return launch_kernel(op == BLDP_OP_MAD ? k_tstat_regs<TP, CPL, 2>
+                                         : op == kOpQuantile ? k_tstat_regs<TP, CPL, 3>
+                                                             : k_tstat_regs<TP, CPL, 1>,
+                       grid, dim3(kBlock), 0, s, a, op);
 }
 template <int TP>
 hipError_t launch_regs(const TStatArgs &a, bool med, dim3 grid, int op, hipStream_t s) {
@@ -667,6 +697,8 @@ hipError_t launch_regs(const TStatArgs &a, bool med, dim3 grid, int op, hipStrea
 
 hipError_t launch_tstat(const TStatArgs &a, const TStatPlan &p, int op, hipStream_t s) {
   if (p.grid <= 0) return hipSuccess;
+  if (op == kOpQuantile && (a.qrank < 0 || (int64_t)a.qrank + 1 >= a.T))
+    return hipErrorInvalidValue;  // (the upper rank must be a key of the block)
   const dim3 grid((unsigned)p.grid, (unsigned)a.nbank);
   const auto go = [&](auto *kn, auto... args) {
     return launch_kernel(kn, grid, dim3(kBlock), 0, s, args...);
@@ -686,8 +718,11 @@ hipError_t launch_tstat(const TStatArgs &a, const TStatPlan &p, int op, hipStrea
       return go(a.vec ? k_tstat_mom_split<4> : k_tstat_mom_split<1>, a, op);
     case TSTAT_SPLIT_MEDIAN:
       if (op == BLDP_OP_MAD)
-        return go(a.vec ? k_tstat_med_split<4, true> : k_tstat_med_split<1, true>, a);
-      return go(a.vec ? k_tstat_med_split<4, false> : k_tstat_med_split<1, false>, a);
+        return go(a.vec ? k_tstat_med_split<4, SEL_MAD> : k_tstat_med_split<1, SEL_MAD>, a);
+      if (op == kOpQuantile)
+        return go(a.vec ? k_tstat_med_split<4, SEL_QUANTILE> : k_tstat_med_split<1, SEL_QUANTILE>,
+                  a);
+      return go(a.vec ? k_tstat_med_split<4, SEL_MEDIAN> : k_tstat_med_split<1, SEL_MEDIAN>, a);
     case TSTAT_CHUNK_MOMENTS: {
       if (!a.ws) return hipErrorInvalidValue;
       const hipStream_t st = s;

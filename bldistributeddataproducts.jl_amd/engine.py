@@ -26,6 +26,7 @@ __all__ = [
     "stitch",
     "despike", "kurtosis", "kurtosis_blocks_plan", "band_kurtosis", "synth", "plan", "reduce_host", "kurtosis_host",
     "tstat", "tstat_plan", "band_tstat", "tstat_host",
+    "quantile", "quantile_plan", "band_quantile", "quantile_host",
     "skewness", "skewness_plan", "band_skewness", "skewness_host",
     "Moments", "MOMENTS", "moments", "moments_plan", "band_moments", "moments_host",
     "argext", "argext_plan", "band_argext", "argext_host",
@@ -214,10 +215,16 @@ def _dtype_code(dt):
     return DTYPE_CODES.get(np.dtype(dt))
 
 
+def _no_quantile(op, what) -> None:
+    if _lib.quantile_of(op) is not None:
+        raise TypeError(f"{what} takes the ops of enum bldp_op; a quantile goes through "
+                        f"engine.quantile / band_quantile")
+
+
 def _check_stat(op: str, tavby, dtype=None) -> None:
     """var / std / median / mad: no time integration, Float32 on the GPU (TypeError,
     as Julia's MethodError for an fqavfunc the call does not fit)."""
-    if op not in _lib.STAT_OPS:
+    if not _lib.stat_op(op):
         return
     if int(tavby) > 1:
         raise TypeError(f"fqavfunc {op!r} has no time integration: tavby={tavby} needs "
@@ -233,6 +240,8 @@ def out_dtype(dtype, op: str) -> np.dtype:
     code = _dtype_code(dtype)
     if code is None:
         raise TypeError(f"unsupported element type {dtype}")
+    if _lib.quantile_of(op) is not None:  # (no op of the ABI: the median's types)
+        op = "median"
     rc = _lib.lib().bldp_reduce_out_dtype(code, _lib.OPS[op])
     _lib.check(min(rc, 0), "bldp_reduce_out_dtype")
     return DTYPE_OF_CODE[rc]
@@ -279,6 +288,8 @@ def reduce(x, fqavby=1, tavby=1, op="sum", win=None, out=None, stream=None):
     x: device filterbank tensor; win: 9-int window (see idxs.to_window) or
     None; returns a Julia-order (nc/F, ni, nt/T) device tensor."""
     _check_stat(op, tavby, x.dtype)
+    if _lib.quantile_of(op) is not None:
+        return quantile(x, fqavby, op[1], 0, win, out, stream)
     L = _lib.lib()
     shape = tuple(x.shape)
     _check_bounds(win, shape)
@@ -343,6 +354,7 @@ class PreparedReduce(_Prepared):
 
     def __init__(self, x, fqavby=1, tavby=1, op="sum", win=None, out=None):
         _check_stat(op, tavby, x.dtype)
+        _no_quantile(op, "PreparedReduce")
         torch = _torch()
         L = _lib.lib()
         shape = tuple(x.shape)
@@ -394,6 +406,9 @@ class PreparedKurtosis(_Prepared):
 
 def plan(x, fqavby=1, tavby=1, op="sum", win=None) -> dict:
     """Launch plan the library picks for this call (path, lanes/group, ...)."""
+    if _lib.quantile_of(op) is not None:
+        _check_stat(op, tavby)
+        return quantile_plan(x, fqavby, op[1], 0, win)
     L = _lib.lib()
     shape = tuple(x.shape)
     _check_bounds(win, shape)
@@ -444,6 +459,8 @@ def band_reduce(banks, fqavby=1, tavby=1, op="sum", win=None, out=None, stream=N
     """Reduce every bank of a band resident on ONE GPU and stitch them in bank
     order (reduce(vcat, ...), src/gbt.jl:103) in a single launch."""
     _check_stat(op, tavby)
+    if _lib.quantile_of(op) is not None:
+        return band_quantile(banks, fqavby, op[1], 0, win, out, stream)
     L = _lib.lib()
     banks, geo, out, ptrs, (keep, wp) = _band_args(banks, fqavby, tavby, win, out)
     nchan, nif, ntime = geo
@@ -464,6 +481,7 @@ class PreparedBandReduce:
 
     def __init__(self, banks, fqavby=1, tavby=1, op="sum", win=None, out=None):
         _check_stat(op, tavby)
+        _no_quantile(op, "PreparedBandReduce")
         L = _lib.lib()
         banks, geo, out, ptrs, (keep, wp) = _band_args(banks, fqavby, tavby, win, out)
         h = ctypes.c_void_p()
@@ -517,7 +535,7 @@ def band_reduce_multi(banks, fqavby=1, tavby=1, op="sum", win=None, root=0, out=
     opt-in until a multi-GPU node has run it) -- per-call arguments, not
     process state.  sum / mean / max / min only: var / std / median run on one
     device (GBT.getband then goes bank by bank)."""
-    if op in _lib.STAT_OPS:
+    if _lib.stat_op(op):
         raise TypeError(f"band_reduce_multi takes sum/mean/max/min, not {op!r}: reduce each "
                         f"device's banks with band_reduce")
     torch = _torch()
@@ -554,10 +572,10 @@ def band_reduce_multi(banks, fqavby=1, tavby=1, op="sum", win=None, root=0, out=
 
 
 def _tstat_op(op) -> int:
-    if op not in _lib.STAT_OPS:
+    if not isinstance(op, str) or op not in _lib.STAT_OPS:
         raise _lib.ArgumentError(
-            _lib.BLDP_EINVAL, f"tstat takes var/std/median/mad, not {op!r} (sum/mean/max/min over "
-                              f"time: reduce with tavby)")
+            _lib.BLDP_EINVAL, f"tstat takes var/std/median/mad or a quantile, not {op!r} "
+                              f"(sum/mean/max/min over time: reduce with tavby)")
     return _lib.OPS[op]
 
 
@@ -590,7 +608,9 @@ def tstat(x, tavby, op, win=None, out=None, stream=None):
     time axis with Julia's Statistics (mad: StatsBase's normalised one).  x: a Float32 device filterbank tensor;
     returns a Julia-order (nc, ni, nt/tavby) Float32 device tensor (``out``
     when given: e.g. a bank's slot of a stitched product).  tavby <= 1 copies
-    the window."""
+    the window.  ``op`` may be ``("quantile", p)``: ``quantile`` on axis 2."""
+    if _lib.quantile_of(op) is not None:
+        return quantile(x, tavby, op[1], 2, win, out, stream)
     L = _lib.lib()
     code = _tstat_op(op)
     shape = tuple(x.shape)
@@ -613,6 +633,8 @@ def tstat_plan(x, tavby, op, win=None) -> dict:
     slices of a workgroup splitting a block (1: the register form), passes over
     the block, workgroups, workspace bytes, blocks and the lanes along the
     channels of a split workgroup."""
+    if _lib.quantile_of(op) is not None:
+        return quantile_plan(x, tavby, op[1], 2, win)
     L = _lib.lib()
     code = _tstat_op(op)
     shape = tuple(x.shape)
@@ -633,6 +655,8 @@ def band_tstat(banks, tavby, op, win=None, out=None, stream=None):
     """``tstat`` of every bank of a band resident on ONE GPU, stitched in bank
     order (the vcat of the per-bank results) in one launch
     (bldp_band_tstat_f32): a dense (nbank*nc, ni, nt/tavby) Float32 tensor."""
+    if _lib.quantile_of(op) is not None:
+        return band_quantile(banks, tavby, op[1], 2, win, out, stream)
     L = _lib.lib()
     code = _tstat_op(op)
     banks, geo, out, ptrs, (keep, wp) = _band_args(banks, 1, tavby, win, out)
@@ -648,6 +672,8 @@ def band_tstat(banks, tavby, op, win=None, out=None, stream=None):
 def tstat_host(a: np.ndarray, tavby, op, win=None, device=0) -> np.ndarray:
     """Host Fortran-ordered Float32 array in, (nc, ni, nt/tavby) Float32 host
     array out (bldp_tstat_host_f32: the window's rows staged on ``device``)."""
+    if _lib.quantile_of(op) is not None:
+        return quantile_host(a, tavby, op[1], 2, win, device)
     L = _lib.lib()
     code = _tstat_op(op)
     a = np.asarray(a)
@@ -661,6 +687,102 @@ def tstat_host(a: np.ndarray, tavby, op, win=None, device=0) -> np.ndarray:
                                a.shape[1], a.shape[2], wp, int(tavby), code,
                                out.ctypes.data if out.size else None)
     _lib.check(rc, "bldp_tstat_host_f32")
+    return out
+
+
+def _quantile_args(p, axis):
+    """(p, axis) of a quantile call, checked before any GPU work."""
+    p = _lib.quantile_p(p)
+    if axis not in (0, 2):
+        raise ValueError(f"quantile: axis {axis!r} is not 0 (blocks of channels) or 2 (blocks "
+                         f"of spectra)")
+    return p, int(axis)
+
+
+def quantile(x, n, p, axis=0, win=None, out=None, stream=None):
+    """Statistics.quantile(block, p) (type 7) of every block of ``n`` channels
+    (axis 0, the blocks of ``reduce``) or of ``n`` selected spectra (axis 2, the
+    blocks of ``tstat``) of a Float32 device filterbank tensor, on the GPU
+    (bldp_quantile_f32): the median's kernels selecting ranks j - 1 and j.  A
+    block holding a NaN gives NaN; n <= 1 copies the window.  Returns a
+    Julia-order (nc/n, ni, nt) or (nc, ni, nt/n) Float32 device tensor (``out``
+    when given, laid out as ``tstat`` takes it)."""
+    p, axis = _quantile_args(p, axis)
+    L = _lib.lib()
+    shape = tuple(x.shape)
+    _check_bounds(win, shape)
+    dims = out_shape(shape, win, n if axis == 0 else 1, n if axis == 2 else 1)
+    ptr, nchan, nif, ntime = _abi_dims(x)
+    if out is None:
+        out = fb_empty(*dims, device=x.device)
+    optr, ld_i, ld_t = _tstat_out(out, dims, x.device)
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    rc = L.bldp_quantile_f32(ptr, nchan, nif, ntime, wp, axis, int(n), p, optr, ld_i, ld_t,
+                             _lib.stream_ptr(stream))
+    _lib.check(rc, "bldp_quantile_f32")
+    return out
+
+
+def quantile_plan(x, n, p, axis=0, win=None) -> dict:
+    """Launch plan of ``quantile(x, n, p, axis, win)`` (bldp_quantile_plan_f32):
+    the median's plan of that axis and shape (the keys of ``plan`` on axis 0, of
+    ``tstat_plan`` on axis 2) with ``rank``, the 0-based lower rank j - 1 (-1 for
+    the copy of n <= 1), in place of the workspace bytes."""
+    p, axis = _quantile_args(p, axis)
+    L = _lib.lib()
+    shape = tuple(x.shape)
+    _check_bounds(win, shape)
+    ptr, nchan, nif, ntime = _abi_dims(x)
+    info = (ctypes.c_int64 * 8)()
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    _lib.check(L.bldp_quantile_plan_f32(ptr, nchan, nif, ntime, wp, axis, int(n), p, None, info),
+               "bldp_quantile_plan_f32")
+    if axis == 0:
+        keys = ["path", "lanes_per_group", "time_split_waves", "float4_per_lane", "time_chunks",
+                "workgroups", "rank", "vec_out"]
+        paths = _lib.PATHS
+    else:
+        keys = ["path", "channels_per_lane", "time_split_lanes", "passes", "workgroups", "rank",
+                "blocks", "channel_lanes"]
+        paths = _lib.TSTAT_PATHS
+    d = dict(zip(keys, [int(v) for v in info]))
+    d["path"] = paths.get(d["path"], "copy")
+    return d
+
+
+def band_quantile(banks, n, p, axis=0, win=None, out=None, stream=None):
+    """``quantile`` of every bank of a band resident on ONE GPU, stitched in bank
+    order in one launch (bldp_band_quantile_f32): a dense Float32 tensor laid out
+    as ``band_reduce``'s (axis 0) or ``band_tstat``'s (axis 2)."""
+    p, axis = _quantile_args(p, axis)
+    L = _lib.lib()
+    banks, geo, out, ptrs, (keep, wp) = _band_args(banks, n if axis == 0 else 1,
+                                                   n if axis == 2 else 1, win, out)
+    if out.device != banks[0].device:
+        raise ValueError(f"out is on {out.device}, the banks on {banks[0].device}")
+    rc = L.bldp_band_quantile_f32(len(banks), ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp, axis,
+                                  int(n), p, out.data_ptr() if out.numel() else None,
+                                  _lib.stream_ptr(stream))
+    _lib.check(rc, "bldp_band_quantile_f32")
+    return out
+
+
+def quantile_host(a: np.ndarray, n, p, axis=0, win=None, device=0) -> np.ndarray:
+    """Host Fortran-ordered Float32 array in, dense Float32 host array out
+    (bldp_quantile_host_f32: the window's rows staged on ``device``)."""
+    p, axis = _quantile_args(p, axis)
+    L = _lib.lib()
+    a = np.asarray(a)
+    if a.dtype != np.float32 or not a.flags.f_contiguous or a.ndim != 3:
+        raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
+    _check_bounds(win, a.shape)
+    dims = out_shape(a.shape, win, n if axis == 0 else 1, n if axis == 2 else 1)
+    out = np.empty(dims, dtype=np.float32, order="F")
+    keep, wp = _lib.win_arg(_full_win(win, a.shape))
+    rc = L.bldp_quantile_host_f32(int(device), a.ctypes.data if a.size else None, a.shape[0],
+                                  a.shape[1], a.shape[2], wp, axis, int(n), p,
+                                  out.ctypes.data if out.size else None)
+    _lib.check(rc, "bldp_quantile_host_f32")
     return out
 
 
@@ -1201,6 +1323,8 @@ def reduce_host(a: np.ndarray, fqavby=1, tavby=1, op="sum", win=None, device=0) 
     """Host array in, host array out (bldp_reduce_host_f32): the window is
     streamed through the GPU and reduced there."""
     _check_stat(op, tavby)
+    if _lib.quantile_of(op) is not None:
+        return quantile_host(a, fqavby, op[1], 0, win, device)
     L = _lib.lib()
     a = np.asarray(a)
     if a.dtype != np.float32 or not a.flags.f_contiguous or a.ndim != 3:

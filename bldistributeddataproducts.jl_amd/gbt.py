@@ -355,7 +355,7 @@ def _band_on_device(ws, fs, idxs, fqavby, op, tavby, nfpc, timings=None, staged=
                and os.environ.get("BLDP_NATIVE_READ", "1") != "0")
     # var / std / median / mad run on one device (bldp_band_reduce_multi_f32 does not
     # take them): with banks on several GPUs, or staged, the band goes bank by bank
-    if op in _lib.STAT_OPS and (force_copy or {int(w) for w in ws} != {root}):
+    if _lib.stat_op(op) and (force_copy or {int(w) for w in ws} != {root}):
         raw = chunked = False
     # tavfunc (two stages, the window staying on its GPU in between): bank by
     # bank, each bank's last stage writing its slot (copied there from another GPU)

@@ -13,7 +13,7 @@ using Statistics: mean, median, var, std
 
 export gpu_init, gpu_finalize, gpu_pin, gpu_unpin, gpu_fqav, gpu_reduce, gpu_kurtosis, gpu_band,
        gpu_tstat, gpu_argext, gpu_skewness, gpu_moments, gpu_comm_id, gpu_comm_init, gpu_comm_destroy, gpu_band_gather,
-       mad
+       mad, quantile, gpu_quantile, gpu_quantile_plan, gpu_band_quantile
 
 const libbldp = get(ENV, "BLDP_LIB", joinpath(@__DIR__, "..", "libbldp_hip.so"))
 
@@ -379,6 +379,129 @@ function gpu_tstat(in::Ptr{Float32}, dims::NTuple{3,Integer}, tavby::Integer, ou
          Ptr{Cvoid}),
         in, dims[1], dims[2], dims[3], win, tavby, op, out, ld[1], ld[2], stream))
     (shp[1], shp[2], shp[3])
+end
+
+# ---- quantile(p): bldp_quantile_* (no op code: the entry points carry p) -------
+_checkp(p) = (0 <= p <= 1) || throw(ArgumentError("quantile: p=$p is outside [0, 1]"))
+
+# Statistics.quantile's default (type 7) by the kernels' rule (include/bldp.h):
+# isless order, the index and weight in Float64, a + g * (b - a) with the
+# difference rounded in the element type where both are finite, else
+# (1 - g) * a + g * b; NaN when the slice holds a NaN (Statistics throws there).
+function _quantile(v::AbstractVector{T}, p::Real) where {T<:AbstractFloat}
+    n = length(v)
+    n <= 1 && return isempty(v) ? T(NaN) : v[1]
+    any(isnan, v) && return T(NaN)
+    s = sort(v; by=_madkey)
+    pp = Float64(p)
+    m = 1.0 + pp * (1.0 - 1.0 - 1.0)
+    aleph = n * pp + m
+    j = clamp(trunc(Int, aleph), 1, n - 1)
+    g = clamp(aleph - j, 0.0, 1.0)
+    a, b = s[j], s[j + 1]
+    r = isfinite(a) && isfinite(b) ? Float64(a) + g * Float64(b - a) :
+        (1.0 - g) * Float64(a) + g * Float64(b)
+    T(r)
+end
+_quantile(v::AbstractVector, p::Real) = _quantile(Float64.(v), p)
+
+"""
+    quantile(X, p; dims)
+
+`Statistics.quantile(slice, p)` (the default definition, type 7) of every slice
+of `X` along `dims`, which Statistics' own method does not take; this module's
+function, in the style of `mad(X; dims)` (qualify it as `BLDPHip.quantile` next
+to `using Statistics`).  A Float32 (nchan, nif, ntime) array with `dims = 1` or
+`dims = 3` runs on the GPU (bldp_quantile_host_f32, one block of `size(X, dims)`
+per slice); anything else takes the same rule on the host.  A slice holding a
+NaN gives NaN.  `quantile(X, 0.5; dims)` of an even slice is `a + 0.5 (b - a)`,
+which may differ from `median`'s `a/2 + b/2` in the last bit."""
+function quantile(X::AbstractArray, p::Real; dims=:, dev::Integer=0)
+    _checkp(p)
+    dims === Colon() && return _quantile(vec(X), p)
+    if X isa Array{Float32,3} && (dims == 1 || dims == 3) && size(X, dims) > 1
+        return gpu_quantile(X, size(X, dims), p; axis=dims - 1, dev)
+    end
+    mapslices(v -> _quantile(v, p), X; dims=dims)
+end
+
+"""
+    gpu_quantile(A::Array{Float32,3}, n, p; axis=0, idxs=(:,:,:), dev=0) -> Array{Float32,3}
+
+quantile(p) of every block of `n` selected channels (`axis = 0`, an fqavfunc) or
+`n` selected spectra (`axis = 2`, a tavfunc) of the window, computed on GPU
+`dev` (bldp_quantile_host_f32: the window staged on the device).  `n` must
+divide the axis (DimensionMismatch); `n <= 1` returns the window."""
+function gpu_quantile(A::Array{Float32,3}, n::Integer, p::Real; axis::Integer=0,
+                      idxs::Tuple=(:, :, :), dev::Integer=0)
+    _checkp(p)
+    win = window(idxs, size(A))
+    shp = zeros(Int64, 3)
+    GC.@preserve win check(ccall((:bldp_quantile_shape, libbldp), Cint,
+        (Int64, Int64, Int64, Ptr{Int64}, Cint, Int64, Ptr{Int64}),
+        size(A, 1), size(A, 2), size(A, 3), win, axis, n, shp))
+    out = Array{Float32,3}(undef, shp...)
+    GC.@preserve A win out check(ccall((:bldp_quantile_host_f32, libbldp), Cint,
+        (Cint, Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Cint, Int64, Float64, Ptr{Float32}),
+        dev, A, size(A, 1), size(A, 2), size(A, 3), win, axis, n, p, out))
+    out
+end
+
+"""
+    gpu_quantile(in::Ptr{Float32}, dims, n, p, out::Ptr{Float32}; axis=0, win=C_NULL,
+                 out_ld=nothing, stream=C_NULL)
+
+The same on DEVICE memory (bldp_quantile_f32; asynchronous on `stream`): output
+element (c, i, t) written at `out[c + i*out_ld[1] + t*out_ld[2]]` (0-based;
+dense by default).  Returns the output's dims."""
+function gpu_quantile(in::Ptr{Float32}, dims::NTuple{3,Integer}, n::Integer, p::Real,
+                      out::Ptr{Float32}; axis::Integer=0, win=Ptr{Int64}(C_NULL), out_ld=nothing,
+                      stream::Ptr{Cvoid}=C_NULL)
+    _checkp(p)
+    shp = zeros(Int64, 3)
+    GC.@preserve win check(ccall((:bldp_quantile_shape, libbldp), Cint,
+        (Int64, Int64, Int64, Ptr{Int64}, Cint, Int64, Ptr{Int64}),
+        dims[1], dims[2], dims[3], win, axis, n, shp))
+    ld = out_ld === nothing ? (shp[1], shp[1] * shp[2]) : out_ld
+    GC.@preserve win check(ccall((:bldp_quantile_f32, libbldp), Cint,
+        (Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Cint, Int64, Float64, Ptr{Float32}, Int64,
+         Int64, Ptr{Cvoid}),
+        in, dims[1], dims[2], dims[3], win, axis, n, p, out, ld[1], ld[2], stream))
+    (shp[1], shp[2], shp[3])
+end
+
+"""
+    gpu_quantile_plan(dims, n, p; axis=0, win=C_NULL) -> Vector{Int64}
+
+The launch plan of that call (bldp_quantile_plan_f32; needs no GPU): the
+median's plan of the axis and shape, the 0-based lower rank in its
+workspace-bytes slot (the 7th entry on axis 0, the 6th on axis 2)."""
+function gpu_quantile_plan(dims::NTuple{3,Integer}, n::Integer, p::Real; axis::Integer=0,
+                           win=Ptr{Int64}(C_NULL))
+    _checkp(p)
+    info = zeros(Int64, 8)
+    GC.@preserve win check(ccall((:bldp_quantile_plan_f32, libbldp), Cint,
+        (Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Cint, Int64, Float64, Ptr{Float32},
+         Ptr{Int64}),
+        C_NULL, dims[1], dims[2], dims[3], win, axis, n, p, C_NULL, info))
+    info
+end
+
+"""
+    gpu_band_quantile(banks::Vector{Ptr{Float32}}, dims, n, p, out::Ptr{Float32}; axis=0,
+                      win=C_NULL, stream=C_NULL)
+
+quantile(p) of every bank of a band resident on one GPU, stitched in bank order
+in one launch (bldp_band_quantile_f32); `out` is the dense vcat of the banks."""
+function gpu_band_quantile(banks::Vector{Ptr{Float32}}, dims::NTuple{3,Integer}, n::Integer,
+                           p::Real, out::Ptr{Float32}; axis::Integer=0, win=Ptr{Int64}(C_NULL),
+                           stream::Ptr{Cvoid}=C_NULL)
+    _checkp(p)
+    GC.@preserve banks win check(ccall((:bldp_band_quantile_f32, libbldp), Cint,
+        (Cint, Ptr{Ptr{Float32}}, Int64, Int64, Int64, Ptr{Int64}, Cint, Int64, Float64,
+         Ptr{Float32}, Ptr{Cvoid}),
+        length(banks), banks, dims[1], dims[2], dims[3], win, axis, n, p, out, stream))
+    nothing
 end
 
 # fqavfunc values whose result is a position (csrc/argext.hip, enum bldp_argop)

@@ -14,6 +14,9 @@ Same names, argument meanings and error behaviour as the reference:
 
 ``fqavfunc`` is one of ``"sum" | "mean" | "max" | "min"`` (or the Python
 builtins ``sum``/``max``/``min``, ``numpy.sum``/``mean``/``max``/``min``), or
+the tuple ``("quantile", p)`` (``quantile(p)`` makes it: Statistics.quantile of
+every block, Julia's default type 7, by the rule of include/bldp.h; a bad ``p``
+is a ValueError before any GPU work), or
 one of the strings ``"var" | "std" | "median" | "mad"``: Julia's ``Statistics``
 (the corrected variance, its root, and the median with ``middle(a, b) = a/2 +
 b/2`` of an even block) and StatsBase's normalised median absolute deviation
@@ -72,11 +75,20 @@ class FRange:
         return self.first + self.step * np.arange(self.length, dtype=np.float64)
 
 
-def _opname(f) -> str | None:
+def _opname(f):
+    """The GPU op of an fqavfunc / tavfunc: a name of _lib.OPS, the tuple
+    ``("quantile", p)`` (p checked here: ValueError before any GPU work), or
+    None for a host callable."""
     if isinstance(f, str):
         if f not in _lib.OPS:
-            raise ValueError(f"fqavfunc {f!r} not one of {sorted(_lib.OPS)}")
+            raise ValueError(f"fqavfunc {f!r} not one of {sorted(_lib.OPS)} or "
+                             f"(\"quantile\", p)")
         return f
+    if isinstance(f, tuple):
+        p = _lib.quantile_of(f)
+        if p is None:
+            raise ValueError(f"fqavfunc {f!r} is not (\"quantile\", p)")
+        return ("quantile", p)
     names = {sum: "sum", max: "max", min: "min", np.sum: "sum", np.mean: "mean",
              np.max: "max", np.min: "min", np.amax: "max", np.amin: "min"}
     return names.get(f)
@@ -137,7 +149,9 @@ def _host_stat(a: np.ndarray, n: int, op: str, win=None, axis: int = 0) -> np.nd
     two-pass variance about the mean, its root, and the median ordered by
     isless (-0.0 < 0.0), the middle element of an odd block, a/2 + b/2 of an
     even one, NaN when the block holds a NaN; mad is that median of
-    |x - median(x)| times StatsBase's mad_constant (n <= 1: the block itself)."""
+    |x - median(x)| times StatsBase's mad_constant (n <= 1: the block itself).
+    ``("quantile", p)``: Statistics.quantile (type 7) by the rule of
+    include/bldp.h with every step in Float64 (d a Float64 difference)."""
     a = np.asarray(a)
     if win is not None:
         a = a[np.ix_(*[win[3 * k] + win[3 * k + 2] * np.arange(win[3 * k + 1])
@@ -158,8 +172,22 @@ def _host_stat(a: np.ndarray, n: int, op: str, win=None, axis: int = 0) -> np.nd
         r = S[n // 2] if n % 2 else S[n // 2 - 1] / 2 + S[n // 2] / 2
         return np.where(np.isnan(R).any(axis=0), np.nan, r)
 
+    def quantile(R, p):
+        j, g = _lib.quantile_rank(n, p)
+        bits = R.view(np.int64)
+        key = np.where(bits < 0, bits ^ np.int64(0x7FFFFFFFFFFFFFFF), bits)  # isless order
+        S = np.take_along_axis(R, np.argsort(key, axis=0, kind="stable"), axis=0)
+        lo, hi = S[j - 1], S[j]
+        fin = np.isfinite(lo) & np.isfinite(hi)
+        r = np.where(fin, lo + g * (hi - lo), (1.0 - g) * lo + g * hi)
+        return np.where(np.isnan(R).any(axis=0), np.nan, r)
+
     with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
-        if op == "var":
+        if _lib.quantile_of(op) is not None and n > 1:
+            r = quantile(R, op[1])
+        elif _lib.quantile_of(op) is not None:
+            r = R[0]
+        elif op == "var":
             r = np.var(R, axis=0, ddof=1)
         elif op == "std":
             r = np.std(R, axis=0, ddof=1)
@@ -298,7 +326,8 @@ def fqav(A, n: int, f="sum"):
     op = _opname(f)
     if _is_tensor(A):
         if op is None:
-            raise TypeError("only sum/mean/max/min/var/std/median/mad run on device tensors")
+            raise TypeError("only sum/mean/max/min/var/std/median/mad and (\"quantile\", p) run "
+                            "on device tensors")
         return engine.reduce(A, n, 1, op)
     A = np.asarray(A)
     if op is None:
@@ -322,7 +351,7 @@ def _reduce_host(a, fqavby, tavby, op, win, device):
     if engine._dtype_code(a.dtype) is None:
         raise TypeError(f"fqav: element type {a.dtype} is not supported (Float32, Float64, "
                         f"8- to 64-bit integers)")
-    if op in _lib.STAT_OPS:
+    if _lib.stat_op(op):
         return _host_stat(a, fqavby, op, win)
     return engine.reduce_host_typed(a, fqavby, tavby, op, win, device=device)
 
@@ -373,12 +402,14 @@ def _reduce_array(x, idxs, fqavby, fqavfunc, tavby, device, tavfunc=None):
 def _tav_ops(fqavby, fqavfunc, tavfunc):
     """The two ops of getdata(...; tavfunc): R = tav(fqav(A, fqavby; f=fqavfunc),
     tavby; f=tavfunc), tav being fqav's rule on axis 3."""
-    op2 = _opname(tavfunc) if isinstance(tavfunc, str) or callable(tavfunc) else None
+    op2 = _opname(tavfunc) if isinstance(tavfunc, (str, tuple)) or callable(tavfunc) else None
     if op2 is None:
-        raise TypeError(f"tavfunc {tavfunc!r} is not one of {sorted(_lib.OPS)}")
+        raise TypeError(f"tavfunc {tavfunc!r} is not one of {sorted(_lib.OPS)} or "
+                        f"(\"quantile\", p)")
     op1 = _opname(fqavfunc)
     if op1 is None and fqavby > 1:
-        raise TypeError("tavfunc needs fqavfunc in sum/mean/max/min/var/std/median/mad")
+        raise TypeError("tavfunc needs fqavfunc in sum/mean/max/min/var/std/median/mad or "
+                        "(\"quantile\", p)")
     return op1 or "sum", op2
 
 
@@ -392,7 +423,7 @@ def _tav_device(x, win, fqavby, op1, tavby, op2, out=None):
         return engine.reduce(x, fqavby, 1, op1 if fqavby > 1 else "sum", win, out=out)
     if fqavby > 1:
         x, win = engine.reduce(x, fqavby, 1, op1, win), None
-    if op2 in _lib.STAT_OPS:
+    if _lib.stat_op(op2):
         return engine.tstat(x, tavby, op2, win, out=out)
     return engine.reduce(x, 1, tavby, op2, win, out=out)
 
@@ -412,7 +443,7 @@ def _tav_host(a, win, fqavby, op1, tavby, op2, device):
                                          for k in range(3)])])
     if tavby <= 1:
         return a
-    if op2 in _lib.STAT_OPS:
+    if _lib.stat_op(op2):
         return _host_stat(a, tavby, op2, axis=2)
     return _reduce_host(np.asfortranarray(a), 1, tavby, op2, None, device)
 
@@ -624,7 +655,8 @@ def getdata_device(fname, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum", 
             return _tav_device(got[0], got[1], fqavby, op1, tavby, op2, out=out)
     op = _opname(fqavfunc)
     if op is None:
-        raise TypeError("the device path takes fqavfunc in sum/mean/max/min/var/std/median/mad")
+        raise TypeError("the device path takes fqavfunc in sum/mean/max/min/var/std/median/mad or "
+                        "(\"quantile\", p)")
     got = window_on_device(fname, idxs, device)
     if got is None:
         return None

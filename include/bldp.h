@@ -89,7 +89,8 @@ extern "C" {
  *    BLDP_OP_STD, BLDP_OP_MEDIAN for the Float32 reduce entry points; the
  *    bldp_kurtosis_blocks_*, bldp_tstat_*, bldp_argext_*, bldp_skewness_* and
  *    bldp_moments_* entry points; (additive, same version) BLDP_OP_MAD = 8
- *    wherever BLDP_OP_MEDIAN is taken (7 stays unassigned and invalid) */
+ *    wherever BLDP_OP_MEDIAN is taken (7 stays unassigned and invalid);
+ *    (additive, same version) the bldp_quantile_* entry points */
 #define BLDP_ABI_VERSION 5
 
 #if defined(BLDP_BUILD)
@@ -523,6 +524,68 @@ BLDP_API int bldp_band_tstat_f32(int nbank, const float *const *in, int64_t ncha
 BLDP_API int bldp_tstat_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
                                  int64_t ntime, const int64_t *win, int64_t tavby, int op,
                                  float *out);
+
+/* quantile(p): Statistics.quantile(x, p) (Julia's default, type 7, alpha = beta
+ * = 1) of every block of n channels (axis = 0: fqavfunc, the blocks and the
+ * output of bldp_reduce_* with fqavby = n, tavby <= 1) or of n spectra (axis =
+ * 2: tavfunc, the blocks and the output of bldp_tstat_*) of a Float32 window.
+ * The entry points carrying `int op` have no room for p, so quantile has this
+ * family of its own and is no value of enum bldp_op.  Additive in ABI 5.
+ *
+ * The rule, for a block x of n >= 2 values and a Float64 p in [0, 1]:
+ *  1. v[1..n] = x ordered by isless (-0.0 < 0.0, -Inf lowest, +Inf highest);
+ *  2. in Float64, every operation rounded once (never fused):
+ *     m = 1 + p * (1 - 1 - 1), aleph = n * p + m,
+ *     j = clamp(trunc(aleph), 1, n - 1), g = clamp(aleph - j, 0, 1);
+ *  3. a = v[j], b = v[j + 1] (the second is always taken, also when g == 0);
+ *  4. a and b both finite: d = b - a rounded once to Float32,
+ *     r = Float64(a) + g * Float64(d), a Float64 product then a Float64 sum;
+ *  5. otherwise r = (1 - g) * Float64(a) + g * Float64(b), not fused either:
+ *     g == 0 next to an infinite b, or g == 1 next to an infinite a, is NaN
+ *     (0 * Inf), the formula as it stands;
+ *  6. the result is Float32(r);
+ *  7. a block holding a NaN gives NaN (Julia throws; a kernel cannot, and the
+ *     median's "NaN wins" applies);
+ *  8. n <= 1 copies the window, as fqav does for every function.
+ * quantile(0.5) of an even block is a + 0.5 (b - a), not the median's
+ * middle(a, b) = a/2 + b/2: the two may differ in the last bit.
+ *
+ * The kernels, plans and limits are the median's of the same axis and shape (a
+ * quantile selects ranks j - 1 and j, 0-based, where the median selects
+ * (n-1)/2 and n/2); the time axis' split form always makes its fifth pass.
+ * p outside [0, 1] or NaN, or an axis other than 0 and 2, is BLDP_EINVAL; an n
+ * that does not divide the axis is BLDP_EDIM, a window outside the array
+ * BLDP_EBOUNDS; all before any launch.
+ *
+ * bldp_quantile_shape: dims = {nc / n, ni, nt} (axis 0) or {nc, ni, nt / n}
+ * (axis 2); pure host.
+ * bldp_quantile_plan_f32: info as the median's plan of that axis reports it
+ * (axis 0: bldp_reduce_plan_f32, axis 2: bldp_tstat_plan_f32), except that the
+ * workspace-bytes slot, which the median never uses (info[6] on axis 0,
+ * info[5] on axis 2), carries the 0-based lower rank j - 1 (-1 for the copy of
+ * n <= 1).  Launches nothing and needs no GPU (pointers may be null).
+ * bldp_quantile_f32: device pointers, asynchronous on `stream`; output element
+ * (c, i, t) at out[c + i*out_ld_i + t*out_ld_t] (elements).
+ * bldp_band_quantile_f32: in[] is a HOST array of device pointers of banks with
+ * one geometry; out is laid out as bldp_band_reduce_f32's (axis 0) or
+ * bldp_band_tstat_f32's (axis 2); one launch for the band.
+ * bldp_quantile_host_f32: host in, host dense out (the dims of
+ * bldp_quantile_shape); the window's rows are staged on device `dev`.
+ * Synchronous. */
+BLDP_API int bldp_quantile_shape(int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win,
+                                 int axis, int64_t n, int64_t dims[3]);
+BLDP_API int bldp_quantile_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                                    const int64_t *win, int axis, int64_t n, double p,
+                                    const float *out, int64_t info[8]);
+BLDP_API int bldp_quantile_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                               const int64_t *win, int axis, int64_t n, double p, float *out,
+                               int64_t out_ld_i, int64_t out_ld_t, void *stream);
+BLDP_API int bldp_band_quantile_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                                    int64_t ntime, const int64_t *win, int axis, int64_t n,
+                                    double p, float *out, void *stream);
+BLDP_API int bldp_quantile_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                    int64_t ntime, const int64_t *win, int axis, int64_t n,
+                                    double p, float *out);
 
 /* fqavfunc argmax / argmin (fqav(A, n; f=argmax), the position half of Julia's
  * findmax / findmin): where in each block of the reduce the extreme lies.  For
