@@ -10,7 +10,7 @@ The directory name is not a Python identifier; load it with
 """
 from . import _lib, band, engine, fbh5, filestream, gbt, h5chunks, idxs, readers, worker  # noqa: F401
 from ._lib import ArgumentError, BLDPError, BoundsError, DimensionMismatch, ReadError  # noqa: F401
-from ._lib import quantile  # noqa: F401
+from ._lib import quantile, quantiles  # noqa: F401
 from .idxs import COLON, JRange, sanitizeidxs  # noqa: F401
 from .worker import FRange, fqav, getmoments, getskewness  # noqa: F401
 
@@ -18,6 +18,6 @@ GBT = gbt
 GBT.WorkerFunctions = worker
 WorkerFunctions = worker
 
-__all__ = ["GBT", "WorkerFunctions", "fqav", "quantile", "getskewness", "getmoments", "JRange", "FRange", "COLON",
+__all__ = ["GBT", "WorkerFunctions", "fqav", "quantile", "quantiles", "getskewness", "getmoments", "JRange", "FRange", "COLON",
            "sanitizeidxs",
            "engine", "band", "DimensionMismatch", "BoundsError", "BLDPError", "ReadError"]

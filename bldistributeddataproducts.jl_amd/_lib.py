@@ -47,9 +47,37 @@ def quantile_of(op):
     return None
 
 
+MAX_QUANTILES = 8  # BLDP_MAX_QUANTILES: probabilities one launch takes (engine batches more)
+
+
+def quantiles(ps):
+    """The fqavfunc / tavfunc of Julia's vector form ``quantile(block, [p1, ...,
+    pK])``: the tuple ``("quantiles", (p1, ..., pK))``, K >= 1, each p checked as
+    ``quantile`` checks its one (ValueError; so are an empty or non-iterable
+    ``ps``).  The result has K planes on a new last axis, plane k bit for bit
+    what ``quantile(ps[k])`` gives, from one read and one selection of every
+    block; ``ps`` may be unsorted and may repeat."""
+    try:
+        ps = tuple(ps)
+    except TypeError:
+        raise ValueError(f"quantiles: ps={ps!r} is not a sequence of numbers in [0, 1]") from None
+    if not ps:
+        raise ValueError("quantiles: ps is empty")
+    return ("quantiles", tuple(quantile_p(p) for p in ps))
+
+
+def quantiles_of(op):
+    """The tuple of p's of a ``("quantiles", ps)`` function (checked: ValueError),
+    else None."""
+    if isinstance(op, tuple) and len(op) == 2 and op[0] == "quantiles":
+        return quantiles(op[1])[1]
+    return None
+
+
 def stat_op(op) -> bool:
-    """var / std / median / mad or a quantile: Float32 on the GPU, one axis."""
-    return (isinstance(op, str) and op in STAT_OPS) or quantile_of(op) is not None
+    """var / std / median / mad, a quantile or quantiles: Float32 on the GPU, one axis."""
+    return ((isinstance(op, str) and op in STAT_OPS) or quantile_of(op) is not None
+            or quantiles_of(op) is not None)
 
 
 def quantile_rank(n: int, p: float):
@@ -172,6 +200,11 @@ SIGNATURES = {
     "bldp_quantile_f32": ([P, I64, I64, I64, P, I, I64, D, P, I64, I64, P], I),
     "bldp_band_quantile_f32": ([I, P, I64, I64, I64, P, I, I64, D, P, P], I),
     "bldp_quantile_host_f32": ([I, P, I64, I64, I64, P, I, I64, D, P], I),
+    "bldp_quantiles_shape": ([I64, I64, I64, P, I, I64, I, P], I),
+    "bldp_quantiles_plan_f32": ([P, I64, I64, I64, P, I, I64, I, P, P, P], I),
+    "bldp_quantiles_f32": ([P, I64, I64, I64, P, I, I64, I, P, P, I64, I64, I64, P], I),
+    "bldp_band_quantiles_f32": ([I, P, I64, I64, I64, P, I, I64, I, P, P, P], I),
+    "bldp_quantiles_host_f32": ([I, P, I64, I64, I64, P, I, I64, I, P, P], I),
     "bldp_argext_plan_f32": ([P, I64, I64, I64, P, I64, I64, I, P, P], I),
     "bldp_argext_f32": ([P, I64, I64, I64, P, I64, I64, I, P, P, I64, I64, P], I),
     "bldp_band_argext_f32": ([I, P, I64, I64, I64, P, I64, I64, I, P, P, P], I),

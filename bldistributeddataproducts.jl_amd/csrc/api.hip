@@ -292,18 +292,22 @@ int valid_op(int op) { return (op >= BLDP_OP_SUM && op <= BLDP_OP_MEDIAN) || op 
 // Checks, window and plan of a reduce (shared by every reduce entry point and
 // by the prepared form): fills *a and *p; *empty when there is nothing to do.
 // qp: the probability of a quantile (the bldp_quantile_* entry points; op is
-// then kOpQuantile, which no caller's op can be).
+// then kOpQuantile, which no caller's op can be).  qset: the plan of
+// bldp_quantiles_* (kOpQuantiles: the median's; the caller builds the QSet).
 int prepare_reduce(int nbank, const float *const *in, int64_t nchan, int64_t nif, int64_t ntime,
                    const int64_t *win, int64_t fqavby, int64_t tavby, int op, float *out,
                    int64_t out_bank, int64_t out_ld_i, int64_t out_ld_t, bool stitched,
-                   bool query, RedArgs *ap, Plan *pp, bool *empty, const double *qp = nullptr) {
+                   bool query, RedArgs *ap, Plan *pp, bool *empty, const double *qp = nullptr,
+                   bool qset = false) {
   if (nbank < 1 || nbank > BLDP_MAX_BANKS)
     return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
-  if (qp)
+  if (qset)  // (the bldp_quantiles_* entry points: the ranks travel in a QSet)
+    op = kOpQuantiles;
+  else if (qp)
     op = kOpQuantile;
   else if (!valid_op(op))
     return fail(BLDP_EINVAL, "unknown op %d (" BLDP_OP_NAMES ")", op);
-  const bool stat = stat_op(op) || qp;
+  const bool stat = stat_op(op) || qp || qset;
   // Statistics' var / std / median (and mad, quantile) reduce the channel blocks
   // only: fqav on the time axis after them would not be the statistic of the F x T block
   if (stat && tavby > 1)
@@ -1462,6 +1466,155 @@ int bldp_band_quantile_f32(int nbank, const float *const *in, int64_t nchan, int
   // the vcat of the banks, as bldp_band_tstat_f32
   return tstat_run(nbank, in, nchan, nif, ntime, win, n, 0, out, d[0], nbank * d[0],
                    nbank * d[0] * d[1], stream, &p);
+}
+
+// ---- quantiles(ps): several quantiles of every block from one selection ------
+// The checks every bldp_quantiles_* entry point makes before anything else.
+static int quantiles_check(int axis, int np, const double *p) {
+  int rc = quantile_check(axis, 0.0);
+  if (rc) return rc;
+  if (np < 1 || np > BLDP_MAX_QUANTILES)
+    return fail(BLDP_EINVAL, "quantiles: np=%d outside 1..%d (batch longer lists)", np,
+                BLDP_MAX_QUANTILES);
+  if (!p) return fail(BLDP_EINVAL, "quantiles: null p");
+  for (int k = 0; k < np; ++k)
+    if (!(p[k] >= 0.0 && p[k] <= 1.0))
+      return fail(BLDP_EINVAL, "quantiles: p[%d]=%g is outside [0, 1]", k, p[k]);
+  return BLDP_OK;
+}
+
+// Every entry point of the family.  Plane k of the output starts at out + k *
+// out_ld_q and is laid out as the quantile entry point of the same kind lays
+// its one out (stitched: bldp_band_quantile_f32's dense product).  info: the
+// plan query (nothing is launched).
+static int quantiles_run(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                         int64_t ntime, const int64_t *win, int axis, int64_t n, int np,
+                         const double *p, float *out, int64_t out_ld_i, int64_t out_ld_t,
+                         int64_t out_ld_q, bool stitched, void *stream, int64_t *info) {
+  int rc = quantiles_check(axis, np, p);
+  if (rc) return rc;
+  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
+    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
+  int64_t d[3];
+  rc = bldp_quantile_shape(nchan, nif, ntime, win, axis, n, d);
+  if (rc) return rc;
+  int64_t bank = 0;
+  if (stitched) {  // the vcat of the banks: dense planes one after the other
+    bank = d[0];
+    out_ld_i = nbank * d[0];
+    out_ld_t = out_ld_i * d[1];
+    out_ld_q = out_ld_t * d[2];
+  }
+  const bool empty = d[0] == 0 || d[1] == 0 || d[2] == 0;
+  if (!info && !empty && np > 1 &&
+      out_ld_q < (d[2] - 1) * out_ld_t + (d[1] - 1) * out_ld_i + (stitched ? nbank : 1) * d[0])
+    return fail(BLDP_EINVAL, "quantiles: planes %lld elements apart overlap for a (%lld, %lld, "
+                "%lld) plane with strides (%lld, %lld)", (long long)out_ld_q, (long long)d[0],
+                (long long)d[1], (long long)d[2], (long long)out_ld_i, (long long)out_ld_t);
+  hipStream_t s = (hipStream_t)stream;
+  if (n <= 1) {
+    // the window itself in every plane, as the quantile entry point copies it
+    if (info) {
+      const float *ins[1] = {in ? in[0] : nullptr};
+      if (axis == 2) {
+        rc = tstat_plan(ins[0], nchan, nif, ntime, win, n, BLDP_OP_MEDIAN, nullptr, info, nullptr);
+      } else {
+        rc = reduce_impl(1, ins, nchan, nif, ntime, win, n, 1, BLDP_OP_MEDIAN, nullptr,
+                         d[0] * d[1] * d[2], d[0], d[0] * d[1], false, nullptr, info);
+      }
+      info[8] = 0;
+      info[9] = 1;
+      return rc;
+    }
+    for (int k = 0; k < np && !rc; ++k) {
+      float *o = out ? out + k * out_ld_q : nullptr;
+      if (axis == 2)
+        rc = tstat_run(nbank, in, nchan, nif, ntime, win, n, 0, o, bank, out_ld_i, out_ld_t,
+                       stream, &p[k]);
+      else
+        rc = reduce_impl(nbank, in, nchan, nif, ntime, win, n, 1, 0, o, bank, out_ld_i, out_ld_t,
+                         stitched, s, nullptr, &p[k]);
+    }
+    return rc;
+  }
+  QSet qs;
+  quantile_set(n, np, p, out_ld_q, &qs);
+  if (axis == 0) {
+    RedArgs a;
+    Plan pl;
+    bool none = false;
+    rc = prepare_reduce(nbank, in, nchan, nif, ntime, win, n, 1, 0, out, bank, out_ld_i, out_ld_t,
+                        stitched, info != nullptr, &a, &pl, &none, nullptr, true);
+    if (rc) return rc;
+    if (info) {
+      info[0] = pl.path, info[1] = pl.lpg, info[2] = a.ts, info[3] = a.k4, info[4] = a.nchunk;
+      info[5] = pl.grid, info[6] = (int64_t)pl.ws_bytes, info[7] = a.vec_out;
+      info[8] = qs.nr, info[9] = stats_q_reads(pl);
+      return BLDP_OK;
+    }
+    if (none) return BLDP_OK;
+    const hipError_t e = launch_stats_q(a, pl, qs, s);
+    if (e != hipSuccess) return fail(BLDP_EHIP, "quantiles launch: %s", hipGetErrorString(e));
+    return BLDP_OK;
+  }
+  TStatArgs a;
+  TStatPlan pl;
+  bool copy = false, none = false;
+  rc = tstat_prepare(nbank, in, nchan, nif, ntime, win, n, 0, out, bank, out_ld_i, out_ld_t,
+                     info != nullptr, &a, &pl, &copy, &none, &p[0]);
+  if (rc) return rc;
+  bool words = true;
+  for (int b = 0; b < nbank; ++b) words = words && aligned4(in[b]);
+  rc = plan_tstat_q(a, qs.nlow, words, num_cus_current(), xcd_log2_current(), &pl);
+  if (rc) return rc;
+  if (info) {
+    info[0] = pl.path, info[1] = pl.cpl, info[2] = pl.tsplit, info[3] = pl.passes;
+    info[4] = pl.grid, info[5] = (int64_t)pl.ws_bytes, info[6] = a.nb;
+    info[7] = pl.tsplit > 1 ? ((int64_t)1 << a.lx_log2) : 0;
+    info[8] = qs.nr, info[9] = pl.passes;
+    return BLDP_OK;
+  }
+  if (none) return BLDP_OK;
+  const hipError_t e = launch_tstat_q(a, pl, qs, s);
+  if (e != hipSuccess) return fail(BLDP_EHIP, "quantiles launch: %s", hipGetErrorString(e));
+  return BLDP_OK;
+}
+
+int bldp_quantiles_shape(int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win, int axis,
+                         int64_t n, int np, int64_t dims[4]) {
+  if (!dims) return fail(BLDP_EINVAL, "null dims");
+  if (np < 1 || np > BLDP_MAX_QUANTILES)
+    return fail(BLDP_EINVAL, "quantiles: np=%d outside 1..%d (batch longer lists)", np,
+                BLDP_MAX_QUANTILES);
+  const int rc = bldp_quantile_shape(nchan, nif, ntime, win, axis, n, dims);
+  if (rc) return rc;
+  dims[3] = np;
+  return BLDP_OK;
+}
+
+int bldp_quantiles_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                            const int64_t *win, int axis, int64_t n, int np, const double *p,
+                            const float *out, int64_t info[10]) {
+  if (!info) return fail(BLDP_EINVAL, "null info");
+  const float *ins[1] = {in};
+  return quantiles_run(1, ins, nchan, nif, ntime, win, axis, n, np, p, (float *)out, 0, 0, 0,
+                       true, nullptr, info);
+}
+
+int bldp_quantiles_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                       const int64_t *win, int axis, int64_t n, int np, const double *p,
+                       float *out, int64_t out_ld_i, int64_t out_ld_t, int64_t out_ld_q,
+                       void *stream) {
+  const float *ins[1] = {in};
+  return quantiles_run(1, ins, nchan, nif, ntime, win, axis, n, np, p, out, out_ld_i, out_ld_t,
+                       out_ld_q, false, stream, nullptr);
+}
+
+int bldp_band_quantiles_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                            int64_t ntime, const int64_t *win, int axis, int64_t n, int np,
+                            const double *p, float *out, void *stream) {
+  return quantiles_run(nbank, in, nchan, nif, ntime, win, axis, n, np, p, out, 0, 0, 0, true,
+                       stream, nullptr);
 }
 
 // ---- fqavfunc argmax / argmin: the winner's offset in every F x T block ------

@@ -190,13 +190,16 @@ inline bool stat_op(int op) {
 // the library it travels as kOpQuantile with the rank and weight in the args.
 constexpr int kOpQuantile = 64;
 // the ops that take the median's kernels and plans
+// quantiles(ps), the bldp_quantiles_* entry points: several quantiles of every
+// block from one selection; the ranks travel in a QSet beside the args.
+constexpr int kOpQuantiles = 65;
 inline bool median_op(int op) {
-  return op == BLDP_OP_MEDIAN || op == BLDP_OP_MAD || op == kOpQuantile;
+  return op == BLDP_OP_MEDIAN || op == BLDP_OP_MAD || op == kOpQuantile || op == kOpQuantiles;
 }
 // What the median's kernels select (their compile-time selector): ranks
 // (n-1)/2 and n/2 once, the same twice (mad), or the run-time ranks qrank and
-// qrank + 1 joined by quantile_of.
-enum Sel { SEL_MEDIAN = 0, SEL_MAD = 1, SEL_QUANTILE = 2 };
+// qrank + 1 joined by quantile_of, or the ranks of a QSet joined plane by plane.
+enum Sel { SEL_MEDIAN = 0, SEL_MAD = 1, SEL_QUANTILE = 2, SEL_QUANTILES = 3 };
 // The 0-based lower rank j - 1 and the weight g of Statistics.quantile(x, p)
 // of n >= 2 values (type 7), in Float64 with every operation rounded once
 // (host.hip); the upper rank is always *rank + 1 <= n - 1.
@@ -233,8 +236,32 @@ __device__ __forceinline__ float quantile_mix(float a, float b, double g) {
   }
   return (float)r;
 }
+// The rank set of quantiles(ps) for blocks of n >= 2 values: a by-value kernel
+// argument of the SEL_QUANTILES instantiations alone (RedArgs and TStatArgs,
+// which every hot reduce kernel carries, stay as they are).  Plane k of the
+// output is quantile_of(key of rank[lo[k]], key of rank[hi[k]], g[k]) and lies
+// k * out_ld_q elements after plane 0.
+struct QSet {
+  int32_t np;                             // planes: 1 .. BLDP_MAX_QUANTILES
+  int32_t nr;                             // distinct ranks
+  int32_t nlow;                           // distinct lower ranks
+  int32_t rank[2 * BLDP_MAX_QUANTILES];   // {j_k - 1, j_k} over all k: sorted, distinct, 0-based
+  int32_t low[BLDP_MAX_QUANTILES];        // {j_k - 1} over all k: sorted, distinct
+  uint8_t lo[BLDP_MAX_QUANTILES];         // plane k: where rank[] holds j_k - 1
+  uint8_t hi[BLDP_MAX_QUANTILES];         // ... and j_k
+  uint8_t lsel[BLDP_MAX_QUANTILES];       // ... and where low[] holds j_k - 1
+  double g[BLDP_MAX_QUANTILES];           // plane k: the weight of the upper rank
+  int64_t out_ld_q;                       // plane stride of the output (elements)
+};
+// Builds it with quantile_rank (host.hip); 1 <= np <= BLDP_MAX_QUANTILES, every
+// p in [0, 1], n >= 2.
+void quantile_set(int64_t n, int np, const double *p, int64_t out_ld_q, QSet *qs);
 int plan_stats(RedArgs &a, int op, bool words, int xcd_lg, Plan *p);
 hipError_t launch_stats(const RedArgs &a, const Plan &p, int op, hipStream_t s);
+// kOpQuantiles: the median's plan (plan_stats) launched with the rank set
+hipError_t launch_stats_q(const RedArgs &a, const Plan &p, const QSet &qs, hipStream_t s);
+// reads of the block a quantiles launch of that plan makes (any rank set)
+int stats_q_reads(const Plan &p);
 
 // argmax / argmin of every F x T block (argext.hip): the offset k + F * tt of the
 // winner in its block (column-major, channel fastest), first occurrence, NaN
@@ -290,6 +317,11 @@ struct TStatPlan {
 // message recorded, BLDP_EINVAL for a launch too large for one grid.
 int plan_tstat(TStatArgs &a, int op, bool words, int num_cus, int xcd_lg, TStatPlan *p);
 hipError_t launch_tstat(const TStatArgs &a, const TStatPlan &p, int op, hipStream_t s);
+// kOpQuantiles: plan_tstat's median plan, its split form re-tiled for nlow
+// distinct lower ranks (tstats.hip: ranks per sweep, columns per workgroup,
+// p->passes = the reads of the block), and its launch with the rank set
+int plan_tstat_q(TStatArgs &a, int nlow, bool words, int num_cus, int xcd_lg, TStatPlan *p);
+hipError_t launch_tstat_q(const TStatArgs &a, const TStatPlan &p, const QSet &qs, hipStream_t s);
 
 hipError_t launch_stitch(int nbank, const float *g, int64_t nc, int64_t nrows, float *out,
                          hipStream_t s);

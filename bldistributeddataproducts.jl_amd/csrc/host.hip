@@ -368,6 +368,69 @@ extern "C" int bldp_quantile_host_f32(int dev, const float *in, int64_t nchan, i
   });
 }
 
+// The rank set of quantiles(ps) (bldp_impl.h QSet): quantile_rank per plane,
+// then the sorted distinct ranks {j - 1, j}, the sorted distinct lower ranks,
+// and where each plane's two ranks lie in them.
+void bldp::quantile_set(int64_t n, int np, const double *p, int64_t out_ld_q, QSet *qs) {
+  QSet s{};
+  s.np = np;
+  s.out_ld_q = out_ld_q;
+  int32_t lower[BLDP_MAX_QUANTILES], all[2 * BLDP_MAX_QUANTILES];
+  for (int k = 0; k < np; ++k) {
+    int64_t r;
+    quantile_rank(n, p[k], &r, &s.g[k]);
+    lower[k] = (int32_t)r;
+    s.low[k] = lower[k];
+    all[2 * k] = lower[k];
+    all[2 * k + 1] = lower[k] + 1;
+  }
+  std::sort(all, all + 2 * np);
+  s.nr = (int32_t)(std::unique(all, all + 2 * np) - all);
+  std::copy(all, all + s.nr, s.rank);
+  std::sort(s.low, s.low + np);
+  s.nlow = (int32_t)(std::unique(s.low, s.low + np) - s.low);
+  std::fill(s.low + s.nlow, s.low + BLDP_MAX_QUANTILES, 0);
+  for (int k = 0; k < np; ++k) {
+    s.lo[k] = (uint8_t)(std::lower_bound(s.rank, s.rank + s.nr, lower[k]) - s.rank);
+    s.hi[k] = (uint8_t)(std::lower_bound(s.rank, s.rank + s.nr, lower[k] + 1) - s.rank);
+    s.lsel[k] = (uint8_t)(std::lower_bound(s.low, s.low + s.nlow, lower[k]) - s.low);
+  }
+  *qs = s;
+}
+
+// The same staging for quantiles(ps): the window's rows go to the device once,
+// the np dense planes of bldp_quantiles_shape come back.
+extern "C" int bldp_quantiles_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                       int64_t ntime, const int64_t *win, int axis, int64_t n,
+                                       int np, const double *p, float *out) {
+  // (every argument check, before any staging)
+  int64_t info[10], sh[4];
+  int rc = bldp_quantiles_plan_f32(nullptr, nchan, nif, ntime, win, axis, n, np, p, nullptr, info);
+  if (rc) return rc;
+  rc = bldp_quantiles_shape(nchan, nif, ntime, win, axis, n, np, sh);
+  if (rc) return rc;
+  const int64_t nn = n <= 1 ? 1 : n;
+  const int64_t nc = axis == 0 ? sh[0] * nn : sh[0], ni = sh[1];
+  const int64_t nt = axis == 2 ? sh[2] * nn : sh[2], plane = sh[0] * sh[1] * sh[2];
+  if (plane == 0) return BLDP_OK;
+  if (!out || !in) return bldp::set_error(BLDP_EINVAL, "quantiles: null pointer");
+  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
+  return with_stager(dev, [&](bldp::Stager *sg) -> int {
+    float *dbuf, *dout;
+    int r = bldp::stager_buffer(sg, 0, (size_t)(h.span * ni * nt) * 4, (void **)&dbuf);
+    if (!r) r = bldp::stager_buffer(sg, 2, (size_t)(plane * np) * sizeof(float), (void **)&dout);
+    if (!r) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
+    if (r) return r;
+    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
+    r = bldp_quantiles_f32(dbuf, h.span, ni, nt, dwin, axis, n, np, p, dout, sh[0], sh[0] * ni,
+                           plane, sg->st[0]);
+    if (r) return r;
+    HCHK(hipMemcpyAsync(out, dout, (size_t)(plane * np) * sizeof(float), hipMemcpyDeviceToHost,
+                        sg->st[0]));
+    return BLDP_OK;
+  });
+}
+
 // The same staging for fqavfunc argmax / argmin: the window's rows go to the
 // device once (in window order), the (nco, ni, nto) offsets, and the winners'
 // bits when val is given, come back.

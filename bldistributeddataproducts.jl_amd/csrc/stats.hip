@@ -46,6 +46,25 @@
 //              them: a + g (b - a), the difference rounded once to Float32, the
 //              rest once each in Float64; NaN wins.  Plans and paths are the
 //              median's.
+//   quantiles  quantiles(ps): K <= 8 quantiles of every block from ONE selection.
+//              The host turns (F, ps) into a QSet (bldp_impl.h): the sorted
+//              distinct ranks {j_k - 1, j_k} (<= 16) and, per plane, which two
+//              of them it joins and with what weight; it is a kernel argument
+//              of these instantiations alone.  Plane k is written k *
+//              out_ld_q elements after plane 0 and is, bit for bit, the
+//              quantile instantiation's result for ps[k].
+//              k_median_sort with SEL_QUANTILES sorts once and then picks and
+//              stores plane by plane.  k_quantiles_select is k_median_select's
+//              radix select for R ranks: still four passes over keys loaded
+//              once (registers) or four reads of the block (stream), whatever
+//              K is.  Per rank the prefix fixed so far and the rank among that
+//              prefix's keys live in LDS.  The ranks are sorted, so their
+//              prefixes are too: equal prefixes are adjacent, each distinct
+//              one gets a slot of 256 counters (<= 16 slots, 16 KiB), a key
+//              matches at most one slot and is counted at slot * 256 + digit
+//              with hist_add's leader trick.  The waves then scan one slot
+//              each and settle every rank of that slot.  Plans and paths are
+//              the median's; reads of the block: 1, 1 and 4.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -295,9 +314,15 @@ __device__ __forceinline__ void bitonic_sort4(uint32_t (&k)[4], const int lg) {
 // L = next_pow2(F) >= 4 keys over L / 4 lanes, key e = 4 * lane + r.  MAD: the
 // sorted keys become those of |x - median| in place (the padding, which sorts
 // to e >= F, stays) and the network runs again.  SEL_QUANTILE: the ranks are
-// a.qrank and the next.
-template <int L, bool VEC, Sel SEL>
-__global__ __launch_bounds__(kBlock) void k_median_sort(const RedArgs a) {
+// a.qrank and the next.  SEL_QUANTILES: one more argument, the QSet (QS is empty
+// for every other selector: their signature is (RedArgs)); the planes' ranks
+// are picked and stored one plane after the other.
+template <typename T>
+__device__ __forceinline__ const T &first_arg(const T &x) {
+  return x;
+}
+template <int L, bool VEC, Sel SEL, typename... QS>
+__global__ __launch_bounds__(kBlock) void k_median_sort(const RedArgs a, const QS... qs) {
   constexpr bool MAD = SEL == SEL_MAD;
   constexpr int LG = L / 4;
   const int lg = threadIdx.x % LG;
@@ -349,7 +374,13 @@ __global__ __launch_bounds__(kBlock) void k_median_sort(const RedArgs a) {
   const unsigned long long bal = __ballot(nan);
   const unsigned long long gmask = LG == 64 ? ~0ull : ((1ull << LG) - 1ull);
   const bool gnan = ((bal >> ((threadIdx.x & 63) - lg)) & gmask) != 0;
-  if (ok && lg == 0) {
+  if constexpr (SEL == SEL_QUANTILES) {
+    const QSet &s = first_arg(qs...);
+    for (int kq = 0; kq < s.np; ++kq) {  // (uniform: pick shuffles, whole waves)
+      const uint32_t ka = pick(s.rank[s.lo[kq]]), kb = pick(s.rank[s.hi[kq]]);
+      if (ok && lg == 0) o[kq * s.out_ld_q] = quantile_of(ka, kb, s.g[kq], gnan);
+    }
+  } else if (ok && lg == 0) {
     if constexpr (SEL == SEL_QUANTILE) {
       *o = quantile_of(k0, k1, a.qg, gnan);
     } else {
@@ -508,6 +539,139 @@ __global__ __launch_bounds__(kBlock) void k_median_select(const RedArgs a) {
   }
 }
 
+// quantiles(ps): k_median_select's select for the qs.nr sorted ranks of a QSet
+// at once (the file's head).  State per rank in LDS: pre, the key bits fixed
+// so far, and rem, its rank among the keys with that prefix (two copies by
+// pass parity: a pass reads one and writes the other).  Every pass: wave 0
+// lists the distinct prefixes (slots), everyone counts its keys at slot * 256 +
+// digit, wave w scans slots w, w + 4, ... (4 bins a lane) and settles their
+// ranks.  REG: the keys stay in registers, else every pass reads the block.
+template <bool VEC, bool REG>
+__global__ __launch_bounds__(kBlock) void k_quantiles_select(const RedArgs a, const QSet qs) {
+  constexpr int NR = 2 * BLDP_MAX_QUANTILES;
+  __shared__ uint32_t hist[NR * 256];
+  __shared__ uint32_t pre[NR];
+  __shared__ uint32_t rem[2][NR];
+  __shared__ uint32_t dpre[NR];    // the distinct prefixes, ascending
+  __shared__ int sfirst[NR + 1];   // slot s holds ranks sfirst[s] .. sfirst[s + 1] - 1
+  __shared__ int nslot;
+  __shared__ int nanflag;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float *p = nullptr;
+  float *o = nullptr;
+  if (!stat_group(a, blockIdx.x, p, o)) return;  // (uniform)
+  const int64_t F = a.F, n = VEC ? F / 4 : F;    // items: float4s or values
+  const int nr = qs.nr;
+  auto load = [&](int64_t it, uint32_t *k, bool &nan) {
+    const int64_t idx = it * kBlock + tid;
+    if (idx >= n) return false;
+    if (VEC) {
+      const float4 x = ld4(p + 4 * idx);
+      nan = nan || x.x != x.x || x.y != x.y || x.z != x.z || x.w != x.w;
+      k[0] = f2key(x.x), k[1] = f2key(x.y), k[2] = f2key(x.z), k[3] = f2key(x.w);
+    } else {
+      const float x = p[idx * a.in_cs];
+      nan = nan || x != x;
+      k[0] = f2key(x);
+    }
+    return true;
+  };
+  constexpr int KPI = VEC ? 4 : 1;                // keys per item
+  constexpr int NREG = VEC ? 4 : 16;              // items a lane keeps (REG)
+  const int64_t nit = (n + kBlock - 1) / kBlock;  // items per thread (uniform)
+  uint32_t keys[16];
+  bool nan = false;
+  if (REG) {
+#pragma unroll
+    for (int it = 0; it < NREG; ++it) (void)load(it, &keys[it * KPI], nan);
+  }
+  if (tid < NR) {
+    pre[tid] = 0;
+    rem[0][tid] = tid < nr ? (uint32_t)qs.rank[tid] : 0u;
+  }
+  if (tid == 0) nanflag = 0;
+  for (int pass = 0; pass < 4; ++pass) {
+    const int shift = 24 - 8 * pass, par = pass & 1;
+    const uint32_t mask = pass == 0 ? 0u : 0xffffffffu << (shift + 8);
+    __syncthreads();  // (pre and rem of the pass before)
+    if (wave == 0) {
+      const uint32_t mine = lane < nr ? pre[lane] : 0u;
+      const uint32_t prev = __shfl_up(mine, 1, 64);
+      const bool head = lane < nr && (lane == 0 || mine != prev);
+      const unsigned long long hb = __ballot(head);
+      if (head) {
+        const int s = __popcll(hb & ((1ull << lane) - 1ull));
+        dpre[s] = mine;
+        sfirst[s] = lane;
+      }
+      if (lane == 0) {
+        nslot = __popcll(hb);
+        sfirst[__popcll(hb)] = nr;
+      }
+    }
+    __syncthreads();
+    const int ns = nslot;  // (uniform, 1 .. nr)
+    for (int k = tid; k < ns * 256; k += kBlock) hist[k] = 0;
+    __syncthreads();
+    // a key has the prefix of at most one slot
+    auto count = [&](uint32_t key, bool valid) {
+      const uint32_t pk = key & mask;
+      int sl = -1;
+      for (int s = 0; s < ns; ++s) sl = pk == dpre[s] ? s : sl;
+      hist_add(hist, (uint32_t)(sl < 0 ? 0 : sl) * 256u + ((key >> shift) & 255u),
+               valid && sl >= 0);
+    };
+    if (REG) {
+#pragma unroll
+      for (int it = 0; it < NREG; ++it) {
+        const bool valid = (int64_t)it * kBlock + tid < n;
+#pragma unroll
+        for (int c = 0; c < KPI; ++c) count(keys[it * KPI + c], valid);
+      }
+    } else {
+      for (int64_t it = 0; it < nit; ++it) {
+        uint32_t k[4] = {0, 0, 0, 0};
+        const bool valid = load(it, k, nan);
+#pragma unroll
+        for (int c = 0; c < KPI; ++c) count(k[c], valid);
+      }
+    }
+    if (pass == 0 && nan) nanflag = 1;
+    __syncthreads();
+    for (int s = wave; s < ns; s += kBlock / 64) {  // (uniform in the wave)
+      const uint32_t *h = hist + s * 256 + 4 * lane;
+      const uint32_t c0 = h[0], c1 = h[1], c2 = h[2], c3 = h[3];
+      const uint32_t tot = (c0 + c1) + (c2 + c3);
+      uint32_t incl = tot;
+#pragma unroll
+      for (int w = 1; w < 64; w *= 2) {
+        const uint32_t u = __shfl_up(incl, w, 64);
+        if (lane >= w) incl += u;
+      }
+      const uint32_t excl = incl - tot;
+      for (int r = sfirst[s]; r < sfirst[s + 1]; ++r) {
+        const uint32_t want = rem[par][r];
+        if (excl <= want && want < incl) {  // (one lane: the bins holding the rank)
+          uint32_t acc = excl, d = 0;
+          if (want >= acc + c0) {
+            acc += c0, d = 1;
+            if (want >= acc + c1) {
+              acc += c1, d = 2;
+              if (want >= acc + c2) acc += c2, d = 3;
+            }
+          }
+          pre[r] |= (uint32_t)(4 * lane + d) << shift;
+          rem[par ^ 1][r] = want - acc;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < qs.np)
+    o[tid * qs.out_ld_q] =
+        quantile_of(pre[qs.lo[tid]], pre[qs.hi[tid]], qs.g[tid], nanflag != 0);
+}
+
 }  // namespace
 
 int plan_stats(RedArgs &a, int op, bool words, int xcd_lg, Plan *pp) {
@@ -616,6 +780,43 @@ hipError_t launch_stats(const RedArgs &a, const Plan &p, int op, hipStream_t s) 
                     : BLDP_MEDSEL(k_median_select, false, false), a);
 #undef BLDP_VECSEL
 #undef BLDP_MEDSEL
+  }
+  return hipErrorInvalidValue;
+}
+
+int stats_q_reads(const Plan &p) { return p.path == PATH_MEDIAN_STREAM ? 4 : 1; }
+
+hipError_t launch_stats_q(const RedArgs &a, const Plan &p, const QSet &qs, hipStream_t s) {
+  if (p.grid <= 0) return hipSuccess;
+  // (every rank must be a key of the block; the kernels index by these counts)
+  if (a.F < 2 || qs.np < 1 || qs.np > BLDP_MAX_QUANTILES || qs.nr < 1 ||
+      qs.nr > 2 * BLDP_MAX_QUANTILES)
+    return hipErrorInvalidValue;
+  for (int r = 0; r < qs.nr; ++r)
+    if (qs.rank[r] < 0 || qs.rank[r] >= a.F || (r && qs.rank[r] <= qs.rank[r - 1]))
+      return hipErrorInvalidValue;
+  for (int k = 0; k < qs.np; ++k)
+    if (qs.lo[k] >= qs.nr || qs.hi[k] >= qs.nr) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)p.grid, (unsigned)a.nbank);
+  const auto go = [&](auto *kn) { return launch_kernel(kn, grid, dim3(kBlock), 0, s, a, qs); };
+  const bool vec = a.k4 != 0;
+#define BLDP_QSORT(N) \
+  (vec ? k_median_sort<N, true, SEL_QUANTILES, QSet> : k_median_sort<N, false, SEL_QUANTILES, QSet>)
+  switch (p.path) {
+    case PATH_MEDIAN_SORT:
+      switch (p.lpg) {  // lanes of 4 keys
+        case 1: return go(BLDP_QSORT(4));
+        case 2: return go(BLDP_QSORT(8));
+        case 4: return go(BLDP_QSORT(16));
+        case 8: return go(BLDP_QSORT(32));
+        case 16: return go(BLDP_QSORT(64));
+      }
+      break;
+#undef BLDP_QSORT
+    case PATH_MEDIAN_SELECT:
+      return go(vec ? k_quantiles_select<true, true> : k_quantiles_select<false, true>);
+    case PATH_MEDIAN_STREAM:
+      return go(vec ? k_quantiles_select<true, false> : k_quantiles_select<false, false>);
   }
   return hipErrorInvalidValue;
 }

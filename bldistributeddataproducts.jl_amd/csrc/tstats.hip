@@ -47,6 +47,23 @@
 //              compares against them, the split form selects rank q and always
 //              runs its fifth pass (rank q + 1 is the same key again or the
 //              smallest above it); quantile_of joins the two with weight qg.
+//   quantiles  (stats.hip's rule) K <= 8 quantiles from one selection, the ranks
+//              in a QSet (bldp_impl.h), a kernel argument of these
+//              instantiations alone; plane k lies k * out_ld_q after plane 0.
+//              Register form (k_tstat_regs, MED = 4): one sort, then the
+//              unrolled chain and a store per plane.  One read of the block.
+//              Split form (k_tquantiles_split): the L distinct lower ranks
+//              j_k - 1 are selected as the quantile form selects its one, each
+//              followed by "the same key again or the smallest key above it".
+//              Pass 0 builds one histogram per column and serves all L ranks.
+//              Passes 1 to 3 and the pass for the smallest key above run in
+//              sweeps of G = min(L, 3) ranks, one histogram per (rank, column).
+//              L = 1 keeps the quantile form's tile, 32 columns a workgroup
+//              (32 KiB of LDS); L >= 2 takes 16 columns (G x 16 KiB = 32 or 48
+//              KiB, three workgroups a CU: 64-byte row segments, as the
+//              moments' narrowed tile).  Reads of the block: 1 + 4 ceil(L / G),
+//              that is 5, 5, 5, 9, 9, 9, 13, 13 for L = 1 .. 8 (K separate
+//              calls: 5 K).
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -151,9 +168,16 @@ __device__ __forceinline__ void bitonic_cols(uint32_t (&k)[TP][CPL]) {
 }
 
 // MED: 0 var / std, 1 median, 2 mad (the network runs again over |x - median|),
-// 3 quantile (ranks a.qrank and the next, wave-uniform, compared in the chain)
-template <int TP, int CPL, int MED>
-__global__ __launch_bounds__(kBlock) void k_tstat_regs(const TStatArgs a, const int op) {
+// 3 quantile (ranks a.qrank and the next, wave-uniform, compared in the chain),
+// 4 quantiles (one more argument, the QSet: QS is empty for every other MED,
+// whose signature is (TStatArgs, int); the chain and a store per plane)
+template <typename T>
+__device__ __forceinline__ const T &first_arg(const T &x) {
+  return x;
+}
+template <int TP, int CPL, int MED, typename... QS>
+__global__ __launch_bounds__(kBlock) void k_tstat_regs(const TStatArgs a, const int op,
+                                                       const QS... qs) {
   const int64_t tile = xcd_order(blockIdx.x, gridDim.x, a.xcd_lg);
   const int64_t item = tile * kBlock + threadIdx.x;
   if (item >= a.ncg * a.ni * a.nb) return;  // (no shuffle or barrier below)
@@ -232,6 +256,25 @@ __global__ __launch_bounds__(kBlock) void k_tstat_regs(const TStatArgs a, const 
           }
       }
       bitonic_cols<TP, CPL>(k);
+    }
+    if constexpr (MED == 4) {
+      const QSet &s = first_arg(qs...);
+      for (int kq = 0; kq < s.np; ++kq) {  // (uniform)
+        const int qa = s.rank[s.lo[kq]], qb = s.rank[s.hi[kq]];
+        const double g = s.g[kq];
+        float *const oq = o + kq * s.out_ld_q;
+#pragma unroll
+        for (int c = 0; c < CPL; ++c) {
+          uint32_t ka = 0, kb = 0;
+#pragma unroll
+          for (int e = 0; e < TP; ++e) {
+            ka = e == qa ? k[e][c] : ka;
+            kb = e == qb ? k[e][c] : kb;
+          }
+          oq[c] = quantile_of(ka, kb, g, nan[c]);
+        }
+      }
+      return;
     }
 #pragma unroll
     for (int c = 0; c < CPL; ++c) {
@@ -598,6 +641,188 @@ __global__ __launch_bounds__(kBlock) void k_tstat_med_split(const TStatArgs a) {
   }
 }
 
+// quantiles(ps), T > 32 (the file's head): the qs.nlow distinct lower ranks
+// qs.low[] of every column of a tile of COLS = 32 (G = 1) or 16 columns, G
+// ranks a sweep.  Per (lower rank l, column) in LDS: pre, the key bits fixed so
+// far; rem, the rank among that prefix's keys (two copies by pass parity: a
+// pass reads one and writes the other; four passes end in copy 0); selc, how
+// many keys equal the selected one; mingt, the smallest key above it.
+template <int CPL, int G>
+__global__ __launch_bounds__(kBlock) void k_tquantiles_split(const TStatArgs a, const QSet qs) {
+  constexpr int COLS = G == 1 ? kMedCols : kMedCols / 2;
+  constexpr int SCANL = kBlock / COLS;  // lanes scanning one column's histogram
+  constexpr int SCANB = 256 / SCANL;    // bins each of them sums
+  constexpr int NQ = BLDP_MAX_QUANTILES;
+  __shared__ uint32_t hist[G][COLS][256];
+  __shared__ uint32_t pre_s[NQ][COLS];
+  __shared__ uint32_t rem_s[2][NQ][COLS];
+  __shared__ uint32_t selc_s[NQ][COLS];
+  __shared__ uint32_t mingt_s[NQ][COLS];
+  __shared__ int nanflag[COLS];
+  const int tid = threadIdx.x;
+  const SplitGeo g = split_geo(a);  // (lx * CPL <= COLS: plan_tstat_q)
+  const int64_t T = a.T;
+  const float *p = a.in[blockIdx.y] + a.in_off + (g.ok ? g.cg : 0) * CPL * a.in_cs +
+                   g.i * a.in_ld_i + g.b * T * a.in_ld_t;
+  const int lc0 = g.tx * CPL;  // this lane's first column of the workgroup's
+  const int nlow = qs.nlow;
+  for (int k = tid; k < NQ * COLS; k += kBlock) {
+    const int l = k / COLS;
+    (&pre_s[0][0])[k] = 0;
+    (&rem_s[0][0][0])[k] = l < nlow ? (uint32_t)qs.low[l] : 0u;
+    (&selc_s[0][0])[k] = 0;
+    (&mingt_s[0][0])[k] = kPadKey;
+  }
+  if (tid < COLS) nanflag[tid] = 0;
+  // Counts the digits (key >> shift) & 255 of the keys whose bits under mask
+  // are pr[j][c] into hist[j] (j < ng), for this lane's columns over its time
+  // slice.  A run of equal digits is counted once (spectra share their
+  // exponent byte).  Pass 0: mask = 0 and ng = 1, every key counts, and NaNs
+  // are noted.
+  auto count = [&](const int ng, const int shift, const uint32_t mask,
+                   const uint32_t (&pr)[G][CPL], const bool first) {
+    for (int k = tid; k < ng * COLS * 256; k += kBlock) (&hist[0][0][0])[k] = 0;
+    __syncthreads();
+    if (g.ok) {
+      uint32_t rd[G][CPL], rn[G][CPL];
+      bool nan[CPL];
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) {
+        nan[c] = false;
+#pragma unroll
+        for (int j = 0; j < G; ++j) rd[j][c] = 0, rn[j][c] = 0;
+      }
+#pragma unroll 4
+      for (int64_t t = g.ty; t < T; t += g.ny) {
+        float x[CPL];
+        ldcols<CPL>(p + t * a.in_ld_t, x);
+#pragma unroll
+        for (int c = 0; c < CPL; ++c) {
+          nan[c] = nan[c] || x[c] != x[c];
+          const uint32_t key = f2key(x[c]);
+          const uint32_t d = (key >> shift) & 255u;
+#pragma unroll
+          for (int j = 0; j < G; ++j) {
+            if (j < ng && (key & mask) == pr[j][c]) {
+              if (d == rd[j][c]) {
+                ++rn[j][c];
+              } else {
+                if (rn[j][c]) atomicAdd(&hist[j][lc0 + c][rd[j][c]], rn[j][c]);
+                rd[j][c] = d;
+                rn[j][c] = 1;
+              }
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) {
+#pragma unroll
+        for (int j = 0; j < G; ++j)
+          if (rn[j][c]) atomicAdd(&hist[j][lc0 + c][rd[j][c]], rn[j][c]);
+        if (first && nan[c]) nanflag[lc0 + c] = 1;
+      }
+    }
+    __syncthreads();
+  };
+  // The bin of hist[j] holding lower rank l of every column: SCANL lanes a
+  // column sum SCANB bins each, a prefix over them, and the lane whose bins
+  // hold the rank walks them.
+  auto settle = [&](const int j, const int l, const int shift, const int par) {
+    const int col = tid / SCANL, part = tid % SCANL;
+    const uint32_t r = rem_s[par][l][col];
+    uint32_t mine = 0;
+    for (int b = 0; b < SCANB; ++b) mine += hist[j][col][part * SCANB + b];
+    uint32_t incl = mine;
+#pragma unroll
+    for (int w = 1; w < SCANL; w *= 2) {
+      const uint32_t u = __shfl_up(incl, w, SCANL);
+      if (part >= w) incl += u;
+    }
+    uint32_t acc = incl - mine;
+    const bool here = mine && acc <= r && r < incl;
+    for (int b = 0; b < SCANB; ++b) {
+      const uint32_t n = hist[j][col][part * SCANB + b];
+      if (here && acc <= r && r < acc + n) {
+        pre_s[l][col] |= (uint32_t)(part * SCANB + b) << shift;
+        selc_s[l][col] = n;
+        rem_s[par ^ 1][l][col] = r - acc;
+      }
+      acc += n;
+    }
+  };
+  uint32_t pr[G][CPL];
+#pragma unroll
+  for (int j = 0; j < G; ++j)
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) pr[j][c] = 0;
+  // pass 0: one histogram a column, every lower rank reads it
+  count(1, 24, 0u, pr, true);  // (its first barrier covers the setup above)
+  for (int l = 0; l < nlow; ++l) settle(0, l, 24, 0);
+  __syncthreads();
+  for (int l0 = 0; l0 < nlow; l0 += G) {
+    const int ng = nlow - l0 < G ? nlow - l0 : G;  // ranks of this sweep (uniform)
+    for (int pass = 1; pass < 4; ++pass) {
+      const int shift = 24 - 8 * pass;
+#pragma unroll
+      for (int j = 0; j < G; ++j)
+#pragma unroll
+        for (int c = 0; c < CPL; ++c) pr[j][c] = j < ng ? pre_s[l0 + j][lc0 + c] : 0u;
+      count(ng, shift, ~(0xffffffffu >> (8 * pass)), pr, false);
+#pragma unroll
+      for (int j = 0; j < G; ++j)
+        if (j < ng) settle(j, l0 + j, shift, pass & 1);
+      __syncthreads();
+    }
+    // pre_s = the keys of the sweep's ranks; the smallest key above each
+#pragma unroll
+    for (int j = 0; j < G; ++j)
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) pr[j][c] = j < ng ? pre_s[l0 + j][lc0 + c] : kPadKey;
+    if (g.ok) {
+      uint32_t mn[G][CPL];
+#pragma unroll
+      for (int j = 0; j < G; ++j)
+#pragma unroll
+        for (int c = 0; c < CPL; ++c) mn[j][c] = kPadKey;
+#pragma unroll 4
+      for (int64_t t = g.ty; t < T; t += g.ny) {
+        float x[CPL];
+        ldcols<CPL>(p + t * a.in_ld_t, x);
+#pragma unroll
+        for (int c = 0; c < CPL; ++c) {
+          const uint32_t key = f2key(x[c]);
+#pragma unroll
+          for (int j = 0; j < G; ++j)
+            if (key > pr[j][c]) mn[j][c] = min(mn[j][c], key);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < G; ++j)
+        if (j < ng) {
+#pragma unroll
+          for (int c = 0; c < CPL; ++c) atomicMin(&mingt_s[l0 + j][lc0 + c], mn[j][c]);
+        }
+    }
+    __syncthreads();
+  }
+  if (g.ok && g.ty == 0) {
+    float *o = a.out + blockIdx.y * a.out_bank + g.cg * CPL + g.i * a.out_ld_i + g.b * a.out_ld_b;
+    for (int kq = 0; kq < qs.np; ++kq) {
+      const int l = qs.lsel[kq];
+      const double w = qs.g[kq];
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) {
+        const int lc = lc0 + c;
+        // the key of the next rank: the same again, or the smallest above it
+        const uint32_t ka = pre_s[l][lc];
+        const uint32_t kb = rem_s[0][l][lc] + 1 < selc_s[l][lc] ? ka : mingt_s[l][lc];
+        o[kq * qs.out_ld_q + c] = quantile_of(ka, kb, w, nanflag[lc] != 0);
+      }
+    }
+  }
+}
+
 int pow2_ceil_log2(int64_t n, int cap) {
   int l = 0;
   while (l < cap && ((int64_t)1 << l) < n) ++l;
@@ -678,7 +903,40 @@ int plan_tstat(TStatArgs &a, int op, bool words, int num_cus, int xcd_lg, TStatP
   return BLDP_OK;
 }
 
+// k_tquantiles_split: lower ranks per sweep, and the columns of a workgroup
+static int sweep_ranks(int nlow) { return std::min(std::max(nlow, 1), 3); }
+static int sweep_cols(int nlow) { return nlow <= 1 ? kMedCols : kMedCols / 2; }
+
+int plan_tstat_q(TStatArgs &a, int nlow, bool words, int num_cus, int xcd_lg, TStatPlan *pp) {
+  const int rc = plan_tstat(a, kOpQuantiles, words, num_cus, xcd_lg, pp);
+  if (rc) return rc;
+  if (pp->path != TSTAT_SPLIT_MEDIAN) {
+    pp->passes = 1;
+    return BLDP_OK;
+  }
+  // the median's tile, narrowed to the columns whose histograms fit
+  const int cols = sweep_cols(nlow), G = sweep_ranks(nlow);
+  int lg = a.lx_log2;
+  while (lg > 0 && (pp->cpl << lg) > cols) --lg;
+  a.lx_log2 = lg;
+  a.ctiles = (a.ncg + ((int64_t)1 << lg) - 1) >> lg;
+  pp->tsplit = kBlock >> lg;
+  pp->passes = 1 + 4 * ((std::max(nlow, 1) + G - 1) / G);
+  pp->grid = a.ctiles * a.ni * a.nb;
+  if (pp->grid > INT32_MAX)
+    return set_error(BLDP_EINVAL,
+                     "tavfunc quantiles: %lld blocks of %lld spectra are too many for one launch",
+                     (long long)a.nb, (long long)a.T);
+  return BLDP_OK;
+}
+
 namespace {
+
+template <int TP>
+hipError_t launch_regs_q(const TStatArgs &a, const QSet &qs, dim3 grid, hipStream_t s) {
+  return launch_kernel(a.vec ? k_tstat_regs<TP, 4, 4, QSet> : k_tstat_regs<TP, 1, 4, QSet>, grid,
+                       dim3(kBlock), 0, s, a, 0, qs);
+}
 
 template <int TP, int CPL>
 hipError_t launch_regs_cpl(const TStatArgs &a, bool med, dim3 grid, int op, hipStream_t s) {
@@ -736,6 +994,40 @@ hipError_t launch_tstat(const TStatArgs &a, const TStatPlan &p, int op, hipStrea
                          dim3(kBlock), 0, st, a, op);
       return hipGetLastError();
     }
+  }
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_tstat_q(const TStatArgs &a, const TStatPlan &p, const QSet &qs, hipStream_t s) {
+  if (p.grid <= 0) return hipSuccess;
+  // (every rank must be a key of the block; the kernels index by these counts)
+  if (a.T < 2 || qs.np < 1 || qs.np > BLDP_MAX_QUANTILES || qs.nr < 1 ||
+      qs.nr > 2 * BLDP_MAX_QUANTILES || qs.nlow < 1 || qs.nlow > BLDP_MAX_QUANTILES)
+    return hipErrorInvalidValue;
+  for (int r = 0; r < qs.nr; ++r)
+    if (qs.rank[r] < 0 || qs.rank[r] >= a.T) return hipErrorInvalidValue;
+  for (int l = 0; l < qs.nlow; ++l)
+    if (qs.low[l] < 0 || (int64_t)qs.low[l] + 1 >= a.T) return hipErrorInvalidValue;
+  for (int k = 0; k < qs.np; ++k)
+    if (qs.lo[k] >= qs.nr || qs.hi[k] >= qs.nr || qs.lsel[k] >= qs.nlow)
+      return hipErrorInvalidValue;
+  const dim3 grid((unsigned)p.grid, (unsigned)a.nbank);
+  if (p.path == TSTAT_REGS_MEDIAN) {
+    if (a.T <= 2) return launch_regs_q<2>(a, qs, grid, s);
+    if (a.T <= 4) return launch_regs_q<4>(a, qs, grid, s);
+    if (a.T <= 8) return launch_regs_q<8>(a, qs, grid, s);
+    if (a.T <= 16) return launch_regs_q<16>(a, qs, grid, s);
+    if (a.T <= 32) return launch_regs_q<32>(a, qs, grid, s);
+    return hipErrorInvalidValue;
+  }
+  if (p.path != TSTAT_SPLIT_MEDIAN) return hipErrorInvalidValue;
+  // (the tile's columns have a histogram each: plan_tstat_q)
+  if (((a.vec ? 4 : 1) << a.lx_log2) > sweep_cols(qs.nlow)) return hipErrorInvalidValue;
+  const auto go = [&](auto *kn) { return launch_kernel(kn, grid, dim3(kBlock), 0, s, a, qs); };
+  switch (sweep_ranks(qs.nlow)) {
+    case 1: return go(a.vec ? k_tquantiles_split<4, 1> : k_tquantiles_split<1, 1>);
+    case 2: return go(a.vec ? k_tquantiles_split<4, 2> : k_tquantiles_split<1, 2>);
+    case 3: return go(a.vec ? k_tquantiles_split<4, 3> : k_tquantiles_split<1, 3>);
   }
   return hipErrorInvalidValue;
 }

@@ -27,6 +27,8 @@ __all__ = [
     "despike", "kurtosis", "kurtosis_blocks_plan", "band_kurtosis", "synth", "plan", "reduce_host", "kurtosis_host",
     "tstat", "tstat_plan", "band_tstat", "tstat_host",
     "quantile", "quantile_plan", "band_quantile", "quantile_host",
+    "quantiles", "quantiles_plan", "band_quantiles", "quantiles_host", "planes_empty",
+    "planes_to_numpy",
     "skewness", "skewness_plan", "band_skewness", "skewness_host",
     "Moments", "MOMENTS", "moments", "moments_plan", "band_moments", "moments_host",
     "argext", "argext_plan", "band_argext", "argext_host",
@@ -144,7 +146,10 @@ def fb_to_numpy(t, pinned=False) -> np.ndarray:
     """Device tensor (Julia order) -> Fortran-ordered numpy array.  With
     ``pinned`` the copy goes through the library's pinned slot ring
     (device_to_host: DMA at PCIe speed instead of torch's staged copy into
-    pageable memory, ~7 GB/s) into ordinary memory the array owns."""
+    pageable memory, ~7 GB/s) into ordinary memory the array owns.  A 4-D plane
+    tensor (``quantiles``) goes through ``planes_to_numpy``."""
+    if t.dim() == 4:
+        return planes_to_numpy(t)
     torch = _torch()
     c = t.permute(2, 1, 0).contiguous() if t.dim() == 3 else t.t().contiguous()
     if pinned and c.is_cuda:
@@ -216,7 +221,7 @@ def _dtype_code(dt):
 
 
 def _no_quantile(op, what) -> None:
-    if _lib.quantile_of(op) is not None:
+    if _lib.quantile_of(op) is not None or _lib.quantiles_of(op) is not None:
         raise TypeError(f"{what} takes the ops of enum bldp_op; a quantile goes through "
                         f"engine.quantile / band_quantile")
 
@@ -240,8 +245,8 @@ def out_dtype(dtype, op: str) -> np.dtype:
     code = _dtype_code(dtype)
     if code is None:
         raise TypeError(f"unsupported element type {dtype}")
-    if _lib.quantile_of(op) is not None:  # (no op of the ABI: the median's types)
-        op = "median"
+    if _lib.quantile_of(op) is not None or _lib.quantiles_of(op) is not None:
+        op = "median"  # (no op of the ABI: the median's types)
     rc = _lib.lib().bldp_reduce_out_dtype(code, _lib.OPS[op])
     _lib.check(min(rc, 0), "bldp_reduce_out_dtype")
     return DTYPE_OF_CODE[rc]
@@ -290,6 +295,8 @@ def reduce(x, fqavby=1, tavby=1, op="sum", win=None, out=None, stream=None):
     _check_stat(op, tavby, x.dtype)
     if _lib.quantile_of(op) is not None:
         return quantile(x, fqavby, op[1], 0, win, out, stream)
+    if _lib.quantiles_of(op) is not None:
+        return quantiles(x, fqavby, op[1], 0, win, out, stream)
     L = _lib.lib()
     shape = tuple(x.shape)
     _check_bounds(win, shape)
@@ -409,6 +416,9 @@ def plan(x, fqavby=1, tavby=1, op="sum", win=None) -> dict:
     if _lib.quantile_of(op) is not None:
         _check_stat(op, tavby)
         return quantile_plan(x, fqavby, op[1], 0, win)
+    if _lib.quantiles_of(op) is not None:
+        _check_stat(op, tavby)
+        return quantiles_plan(x, fqavby, op[1], 0, win)
     L = _lib.lib()
     shape = tuple(x.shape)
     _check_bounds(win, shape)
@@ -461,6 +471,8 @@ def band_reduce(banks, fqavby=1, tavby=1, op="sum", win=None, out=None, stream=N
     _check_stat(op, tavby)
     if _lib.quantile_of(op) is not None:
         return band_quantile(banks, fqavby, op[1], 0, win, out, stream)
+    if _lib.quantiles_of(op) is not None:
+        return band_quantiles(banks, fqavby, op[1], 0, win, out, stream)
     L = _lib.lib()
     banks, geo, out, ptrs, (keep, wp) = _band_args(banks, fqavby, tavby, win, out)
     nchan, nif, ntime = geo
@@ -611,6 +623,8 @@ def tstat(x, tavby, op, win=None, out=None, stream=None):
     the window.  ``op`` may be ``("quantile", p)``: ``quantile`` on axis 2."""
     if _lib.quantile_of(op) is not None:
         return quantile(x, tavby, op[1], 2, win, out, stream)
+    if _lib.quantiles_of(op) is not None:
+        return quantiles(x, tavby, op[1], 2, win, out, stream)
     L = _lib.lib()
     code = _tstat_op(op)
     shape = tuple(x.shape)
@@ -635,6 +649,8 @@ def tstat_plan(x, tavby, op, win=None) -> dict:
     channels of a split workgroup."""
     if _lib.quantile_of(op) is not None:
         return quantile_plan(x, tavby, op[1], 2, win)
+    if _lib.quantiles_of(op) is not None:
+        return quantiles_plan(x, tavby, op[1], 2, win)
     L = _lib.lib()
     code = _tstat_op(op)
     shape = tuple(x.shape)
@@ -657,6 +673,8 @@ def band_tstat(banks, tavby, op, win=None, out=None, stream=None):
     (bldp_band_tstat_f32): a dense (nbank*nc, ni, nt/tavby) Float32 tensor."""
     if _lib.quantile_of(op) is not None:
         return band_quantile(banks, tavby, op[1], 2, win, out, stream)
+    if _lib.quantiles_of(op) is not None:
+        return band_quantiles(banks, tavby, op[1], 2, win, out, stream)
     L = _lib.lib()
     code = _tstat_op(op)
     banks, geo, out, ptrs, (keep, wp) = _band_args(banks, 1, tavby, win, out)
@@ -674,6 +692,8 @@ def tstat_host(a: np.ndarray, tavby, op, win=None, device=0) -> np.ndarray:
     array out (bldp_tstat_host_f32: the window's rows staged on ``device``)."""
     if _lib.quantile_of(op) is not None:
         return quantile_host(a, tavby, op[1], 2, win, device)
+    if _lib.quantiles_of(op) is not None:
+        return quantiles_host(a, tavby, op[1], 2, win, device)
     L = _lib.lib()
     code = _tstat_op(op)
     a = np.asarray(a)
@@ -783,6 +803,164 @@ def quantile_host(a: np.ndarray, n, p, axis=0, win=None, device=0) -> np.ndarray
                                   a.shape[1], a.shape[2], wp, axis, int(n), p,
                                   out.ctypes.data if out.size else None)
     _lib.check(rc, "bldp_quantile_host_f32")
+    return out
+
+
+def planes_empty(nchan, nif, ntime, nplanes, device=None):
+    """Uninitialised (nchan, nif, ntime, nplanes) Float32 tensor on the GPU whose
+    every ``r[..., k]`` is laid out as ``fb_empty`` makes a product: the planes
+    lie one after the other (the layout of ``quantiles``)."""
+    torch = _torch()
+    return torch.empty((int(nplanes), int(ntime), int(nif), int(nchan)), dtype=torch.float32,
+                       device=device or "cuda").permute(3, 2, 1, 0)
+
+
+def planes_to_numpy(t) -> np.ndarray:
+    """A 4-D plane tensor (``planes_empty``'s axes) -> Fortran-ordered numpy array."""
+    h = t.permute(3, 2, 1, 0).contiguous().cpu().numpy()
+    return np.asfortranarray(h.transpose(3, 2, 1, 0))
+
+
+def _quantiles_args(ps, axis):
+    """(ps, axis) of a quantiles call, checked before any GPU work."""
+    ps = _lib.quantiles(ps)[1]
+    return ps, _quantile_args(0.0, axis)[1]
+
+
+def _p_batches(ps):
+    """ps in launches of <= _lib.MAX_QUANTILES: (first plane, ctypes double array)."""
+    m = _lib.MAX_QUANTILES
+    return [(k, (ctypes.c_double * len(ps[k:k + m]))(*ps[k:k + m])) for k in range(0, len(ps), m)]
+
+
+def _planes_out(out, dims, K, device):
+    """A caller's 4-D ``out`` of a quantiles call, checked before any launch: a
+    Float32 (\\*dims, K) tensor on ``device`` whose planes are laid out as
+    ``_tstat_out`` takes a product and do not overlap; returns (pointer, out_ld_i,
+    out_ld_t, out_ld_q)."""
+    torch = _torch()
+    if not isinstance(out, torch.Tensor):
+        raise TypeError("out must be a device tensor")
+    if out.dim() != 4 or tuple(out.shape) != (*dims, K):
+        raise ValueError(f"out is {tuple(out.shape)}, expected {(*dims, K)}")
+    optr, ld_i, ld_t = _tstat_out(out[..., 0], dims, device)
+    nc, ni, nt = dims
+    extent = max(nt - 1, 0) * ld_t + max(ni - 1, 0) * ld_i + nc
+    ld_q = out.stride(3) if K > 1 else extent
+    if ld_q < extent:
+        raise ValueError(f"out strides {out.stride()}: the planes overlap")
+    return optr, ld_i, ld_t, ld_q
+
+
+def quantiles(x, n, ps, axis=0, win=None, out=None, stream=None):
+    """``quantile`` for several probabilities at once (bldp_quantiles_f32): every
+    block is read and its ranks selected once, and plane ``r[..., k]`` is bit for
+    bit ``quantile(x, n, ps[k], axis, win)``.  ``ps``: any non-empty sequence,
+    unsorted and repeats allowed; more than ``_lib.MAX_QUANTILES`` of them go in
+    several launches into the one output.  Returns a (nc/n, ni, nt, K) or (nc,
+    ni, nt/n, K) Float32 device tensor laid out plane after plane
+    (``planes_empty``; ``out`` when given)."""
+    ps, axis = _quantiles_args(ps, axis)
+    L = _lib.lib()
+    shape = tuple(x.shape)
+    _check_bounds(win, shape)
+    dims = out_shape(shape, win, n if axis == 0 else 1, n if axis == 2 else 1)
+    ptr, nchan, nif, ntime = _abi_dims(x)
+    if out is None:
+        out = planes_empty(*dims, len(ps), device=x.device)
+    optr, ld_i, ld_t, ld_q = _planes_out(out, dims, len(ps), x.device)
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    for k0, arr in _p_batches(ps):
+        rc = L.bldp_quantiles_f32(ptr, nchan, nif, ntime, wp, axis, int(n), len(arr), arr,
+                                  optr + 4 * k0 * ld_q if optr else None, ld_i, ld_t, ld_q,
+                                  _lib.stream_ptr(stream))
+        _lib.check(rc, "bldp_quantiles_f32")
+    return out
+
+
+def quantiles_plan(x, n, ps, axis=0, win=None) -> dict:
+    """Launch plan of ``quantiles(x, n, ps, axis, win)`` (bldp_quantiles_plan_f32)
+    for at most ``_lib.MAX_QUANTILES`` probabilities (one launch): the median's
+    plan of that axis and shape (the keys of ``plan`` on axis 0, of ``tstat_plan``
+    on axis 2, where the split form reports its own passes, workgroups and
+    channel lanes) plus ``ranks``, the count of distinct ranks selected (0 for the
+    copy of n <= 1), and ``reads``, how often the block is read."""
+    ps, axis = _quantiles_args(ps, axis)
+    L = _lib.lib()
+    shape = tuple(x.shape)
+    _check_bounds(win, shape)
+    ptr, nchan, nif, ntime = _abi_dims(x)
+    info = (ctypes.c_int64 * 10)()
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    arr = (ctypes.c_double * len(ps))(*ps)
+    _lib.check(L.bldp_quantiles_plan_f32(ptr, nchan, nif, ntime, wp, axis, int(n), len(ps), arr,
+                                         None, info), "bldp_quantiles_plan_f32")
+    if axis == 0:
+        keys = ["path", "lanes_per_group", "time_split_waves", "float4_per_lane", "time_chunks",
+                "workgroups", "workspace_bytes", "vec_out", "ranks", "reads"]
+        paths = _lib.PATHS
+    else:
+        keys = ["path", "channels_per_lane", "time_split_lanes", "passes", "workgroups",
+                "workspace_bytes", "blocks", "channel_lanes", "ranks", "reads"]
+        paths = _lib.TSTAT_PATHS
+    d = dict(zip(keys, [int(v) for v in info]))
+    d["path"] = paths.get(d["path"], "copy")
+    return d
+
+
+def band_quantiles(banks, n, ps, axis=0, win=None, out=None, stream=None):
+    """``quantiles`` of every bank of a band resident on ONE GPU, stitched in bank
+    order (bldp_band_quantiles_f32, one launch per <= ``_lib.MAX_QUANTILES``
+    probabilities): a dense (nbank*nc', ni, nt', K) Float32 tensor whose plane k
+    is ``band_quantile(banks, n, ps[k], axis, win)``."""
+    ps, axis = _quantiles_args(ps, axis)
+    L = _lib.lib()
+    K = len(ps)
+    banks = list(banks)
+    if not banks:
+        raise ValueError("no banks")
+    fq, tv = (n, 1) if axis == 0 else (1, n)
+    if out is None:
+        _check_bounds(win, tuple(banks[0].shape))
+        nco, ni, nto = out_shape(tuple(banks[0].shape), win, fq, tv)
+        out = planes_empty(len(banks) * nco, ni, nto, K, device=banks[0].device)
+    elif out.dim() != 4 or out.shape[3] != K:
+        raise ValueError(f"out is {tuple(out.shape)}, expected {K} planes on a fourth axis")
+    # (plane 0 is checked as band_quantile's out is)
+    banks, geo, first, ptrs, (keep, wp) = _band_args(banks, fq, tv, win, out[..., 0])
+    plane = first.numel()
+    if K > 1 and plane and out.stride(3) != plane:
+        raise ValueError("out must be dense: plane k at k * nbank*nco*ni*nto elements")
+    if out.device != banks[0].device:
+        raise ValueError(f"out is on {out.device}, the banks on {banks[0].device}")
+    for k0, arr in _p_batches(ps):
+        rc = L.bldp_band_quantiles_f32(len(banks), ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp,
+                                       axis, int(n), len(arr), arr,
+                                       out.data_ptr() + 4 * k0 * plane if plane else None,
+                                       _lib.stream_ptr(stream))
+        _lib.check(rc, "bldp_band_quantiles_f32")
+    return out
+
+
+def quantiles_host(a: np.ndarray, n, ps, axis=0, win=None, device=0) -> np.ndarray:
+    """Host Fortran-ordered Float32 array in, Fortran-ordered (…, K) Float32 host
+    array out (bldp_quantiles_host_f32: the window's rows staged on ``device``,
+    once per <= ``_lib.MAX_QUANTILES`` probabilities)."""
+    ps, axis = _quantiles_args(ps, axis)
+    L = _lib.lib()
+    a = np.asarray(a)
+    if a.dtype != np.float32 or not a.flags.f_contiguous or a.ndim != 3:
+        raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
+    _check_bounds(win, a.shape)
+    dims = out_shape(a.shape, win, n if axis == 0 else 1, n if axis == 2 else 1)
+    out = np.empty((*dims, len(ps)), dtype=np.float32, order="F")
+    keep, wp = _lib.win_arg(_full_win(win, a.shape))
+    plane = dims[0] * dims[1] * dims[2]
+    for k0, arr in _p_batches(ps):
+        rc = L.bldp_quantiles_host_f32(int(device), a.ctypes.data if a.size else None, a.shape[0],
+                                       a.shape[1], a.shape[2], wp, axis, int(n), len(arr), arr,
+                                       out.ctypes.data + 4 * k0 * plane if out.size else None)
+        _lib.check(rc, "bldp_quantiles_host_f32")
     return out
 
 
@@ -1325,6 +1503,8 @@ def reduce_host(a: np.ndarray, fqavby=1, tavby=1, op="sum", win=None, device=0) 
     _check_stat(op, tavby)
     if _lib.quantile_of(op) is not None:
         return quantile_host(a, fqavby, op[1], 0, win, device)
+    if _lib.quantiles_of(op) is not None:
+        return quantiles_host(a, fqavby, op[1], 0, win, device)
     L = _lib.lib()
     a = np.asarray(a)
     if a.dtype != np.float32 or not a.flags.f_contiguous or a.ndim != 3:

@@ -473,6 +473,11 @@ def getband(workers, fnames, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum
         raise ValueError("stitch must be 'device' or 'host'")
     wcol = [list(w)] if w.ndim == 1 else [list(w[:, j]) for j in range(w.shape[1])]
     fcol = [list(f)] if f.ndim == 1 else [list(f[:, j]) for j in range(f.shape[1])]
+    for fn in (fqavfunc, tavfunc):
+        if isinstance(fn, tuple) and _lib.quantiles_of(fn) is not None:
+            raise TypeError("getband stitches 3-D products: the planes of quantiles(ps) of a "
+                            "band on one GPU come from engine.band_quantiles, the banks' own "
+                            "from GBT.getdata")
     aop = W._check_argop(fqavfunc, tavfunc)
     if aop is not None and despike_nfpc:
         raise TypeError(f"fqavfunc {aop!r} gives block offsets: despike_nfpc does not apply")

@@ -13,7 +13,8 @@ using Statistics: mean, median, var, std
 
 export gpu_init, gpu_finalize, gpu_pin, gpu_unpin, gpu_fqav, gpu_reduce, gpu_kurtosis, gpu_band,
        gpu_tstat, gpu_argext, gpu_skewness, gpu_moments, gpu_comm_id, gpu_comm_init, gpu_comm_destroy, gpu_band_gather,
-       mad, quantile, gpu_quantile, gpu_quantile_plan, gpu_band_quantile
+       mad, quantile, gpu_quantile, gpu_quantile_plan, gpu_band_quantile,
+       gpu_quantiles, gpu_quantiles_plan, gpu_band_quantiles
 
 const libbldp = get(ENV, "BLDP_LIB", joinpath(@__DIR__, "..", "libbldp_hip.so"))
 
@@ -501,6 +502,106 @@ function gpu_band_quantile(banks::Vector{Ptr{Float32}}, dims::NTuple{3,Integer},
         (Cint, Ptr{Ptr{Float32}}, Int64, Int64, Int64, Ptr{Int64}, Cint, Int64, Float64,
          Ptr{Float32}, Ptr{Cvoid}),
         length(banks), banks, dims[1], dims[2], dims[3], win, axis, n, p, out, stream))
+    nothing
+end
+
+# ---- quantiles(ps): bldp_quantiles_* (several quantiles from one selection) -----
+const MAX_QUANTILES = 8  # BLDP_MAX_QUANTILES: probabilities one launch takes
+
+function _checkps(ps)
+    isempty(ps) && throw(ArgumentError("quantiles: ps is empty"))
+    foreach(_checkp, ps)
+    collect(Float64, ps)
+end
+
+"""
+    gpu_quantiles(A::Array{Float32,3}, n, ps; axis=0, idxs=(:,:,:), dev=0) -> Array{Float32,4}
+
+`quantile(block, ps)` (Julia's vector form) of every block of `n` selected
+channels (`axis = 0`) or `n` selected spectra (`axis = 2`) of the window, on
+GPU `dev` (bldp_quantiles_host_f32): every block is read and its ranks selected
+once.  The result has `length(ps)` planes on a new last axis; plane `k` is bit
+for bit `gpu_quantile(A, n, ps[k]; axis, idxs, dev)`.  `ps` may be unsorted and
+may repeat; more than $(MAX_QUANTILES) go in several calls into the one array."""
+function gpu_quantiles(A::Array{Float32,3}, n::Integer, ps; axis::Integer=0,
+                       idxs::Tuple=(:, :, :), dev::Integer=0)
+    pv = _checkps(ps)
+    win = window(idxs, size(A))
+    shp = zeros(Int64, 4)
+    GC.@preserve win check(ccall((:bldp_quantiles_shape, libbldp), Cint,
+        (Int64, Int64, Int64, Ptr{Int64}, Cint, Int64, Cint, Ptr{Int64}),
+        size(A, 1), size(A, 2), size(A, 3), win, axis, n, 1, shp))
+    out = Array{Float32,4}(undef, shp[1], shp[2], shp[3], length(pv))
+    plane = shp[1] * shp[2] * shp[3]
+    for k0 in 1:MAX_QUANTILES:length(pv)
+        part = pv[k0:min(k0 + MAX_QUANTILES - 1, length(pv))]
+        GC.@preserve A win out part check(ccall((:bldp_quantiles_host_f32, libbldp), Cint,
+            (Cint, Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Cint, Int64, Cint,
+             Ptr{Float64}, Ptr{Float32}),
+            dev, A, size(A, 1), size(A, 2), size(A, 3), win, axis, n, length(part), part,
+            pointer(out, (k0 - 1) * plane + 1)))
+    end
+    out
+end
+
+"""
+    gpu_quantiles(in::Ptr{Float32}, dims, n, ps, out::Ptr{Float32}; axis=0, win=C_NULL,
+                  out_ld=nothing, stream=C_NULL)
+
+The same on DEVICE memory for at most $(MAX_QUANTILES) probabilities
+(bldp_quantiles_f32; asynchronous on `stream`): element (c, i, t) of plane k at
+`out[c + i*out_ld[1] + t*out_ld[2] + k*out_ld[3]]` (0-based; dense by default).
+Returns the output's dims."""
+function gpu_quantiles(in::Ptr{Float32}, dims::NTuple{3,Integer}, n::Integer, ps,
+                       out::Ptr{Float32}; axis::Integer=0, win=Ptr{Int64}(C_NULL), out_ld=nothing,
+                       stream::Ptr{Cvoid}=C_NULL)
+    pv = _checkps(ps)
+    shp = zeros(Int64, 4)
+    GC.@preserve win check(ccall((:bldp_quantiles_shape, libbldp), Cint,
+        (Int64, Int64, Int64, Ptr{Int64}, Cint, Int64, Cint, Ptr{Int64}),
+        dims[1], dims[2], dims[3], win, axis, n, length(pv), shp))
+    ld = out_ld === nothing ? (shp[1], shp[1] * shp[2], shp[1] * shp[2] * shp[3]) : out_ld
+    GC.@preserve win pv check(ccall((:bldp_quantiles_f32, libbldp), Cint,
+        (Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Cint, Int64, Cint, Ptr{Float64},
+         Ptr{Float32}, Int64, Int64, Int64, Ptr{Cvoid}),
+        in, dims[1], dims[2], dims[3], win, axis, n, length(pv), pv, out, ld[1], ld[2], ld[3],
+        stream))
+    (shp[1], shp[2], shp[3], shp[4])
+end
+
+"""
+    gpu_quantiles_plan(dims, n, ps; axis=0, win=C_NULL) -> Vector{Int64}
+
+The launch plan of that call (bldp_quantiles_plan_f32; needs no GPU): the
+median's plan of the axis and shape in the first eight entries, then the count
+of distinct ranks selected and the count of reads of the block."""
+function gpu_quantiles_plan(dims::NTuple{3,Integer}, n::Integer, ps; axis::Integer=0,
+                            win=Ptr{Int64}(C_NULL))
+    pv = _checkps(ps)
+    info = zeros(Int64, 10)
+    GC.@preserve win pv check(ccall((:bldp_quantiles_plan_f32, libbldp), Cint,
+        (Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Cint, Int64, Cint, Ptr{Float64},
+         Ptr{Float32}, Ptr{Int64}),
+        C_NULL, dims[1], dims[2], dims[3], win, axis, n, length(pv), pv, C_NULL, info))
+    info
+end
+
+"""
+    gpu_band_quantiles(banks::Vector{Ptr{Float32}}, dims, n, ps, out::Ptr{Float32}; axis=0,
+                       win=C_NULL, stream=C_NULL)
+
+quantiles(ps), at most $(MAX_QUANTILES), of every bank of a band resident on one
+GPU, stitched in bank order in one launch (bldp_band_quantiles_f32); `out` holds
+the dense planes of the vcat of the banks one after the other."""
+function gpu_band_quantiles(banks::Vector{Ptr{Float32}}, dims::NTuple{3,Integer}, n::Integer,
+                            ps, out::Ptr{Float32}; axis::Integer=0, win=Ptr{Int64}(C_NULL),
+                            stream::Ptr{Cvoid}=C_NULL)
+    pv = _checkps(ps)
+    GC.@preserve banks win pv check(ccall((:bldp_band_quantiles_f32, libbldp), Cint,
+        (Cint, Ptr{Ptr{Float32}}, Int64, Int64, Int64, Ptr{Int64}, Cint, Int64, Cint,
+         Ptr{Float64}, Ptr{Float32}, Ptr{Cvoid}),
+        length(banks), banks, dims[1], dims[2], dims[3], win, axis, n, length(pv), pv, out,
+        stream))
     nothing
 end
 

@@ -17,6 +17,10 @@ builtins ``sum``/``max``/``min``, ``numpy.sum``/``mean``/``max``/``min``), or
 the tuple ``("quantile", p)`` (``quantile(p)`` makes it: Statistics.quantile of
 every block, Julia's default type 7, by the rule of include/bldp.h; a bad ``p``
 is a ValueError before any GPU work), or
+the tuple ``("quantiles", (p1, ..., pK))`` (``quantiles(ps)`` makes it: Julia's
+vector form, every block read and selected once; the result has K planes on a
+new last axis, plane k bit for bit ``("quantile", pk)``'s; as ``tavfunc`` it is
+the last stage, as ``fqavfunc`` it takes no ``tavfunc``: TypeError), or
 one of the strings ``"var" | "std" | "median" | "mad"``: Julia's ``Statistics``
 (the corrected variance, its root, and the median with ``middle(a, b) = a/2 +
 b/2`` of an even block) and StatsBase's normalised median absolute deviation
@@ -77,17 +81,20 @@ class FRange:
 
 def _opname(f):
     """The GPU op of an fqavfunc / tavfunc: a name of _lib.OPS, the tuple
-    ``("quantile", p)`` (p checked here: ValueError before any GPU work), or
-    None for a host callable."""
+    ``("quantile", p)`` or ``("quantiles", ps)`` (every p checked here:
+    ValueError before any GPU work), or None for a host callable."""
     if isinstance(f, str):
         if f not in _lib.OPS:
             raise ValueError(f"fqavfunc {f!r} not one of {sorted(_lib.OPS)} or "
                              f"(\"quantile\", p)")
         return f
     if isinstance(f, tuple):
+        ps = _lib.quantiles_of(f)
+        if ps is not None:
+            return ("quantiles", ps)
         p = _lib.quantile_of(f)
         if p is None:
-            raise ValueError(f"fqavfunc {f!r} is not (\"quantile\", p)")
+            raise ValueError(f"fqavfunc {f!r} is not (\"quantile\", p) or (\"quantiles\", ps)")
         return ("quantile", p)
     names = {sum: "sum", max: "max", min: "min", np.sum: "sum", np.mean: "mean",
              np.max: "max", np.min: "min", np.amax: "max", np.amin: "min"}
@@ -151,7 +158,12 @@ def _host_stat(a: np.ndarray, n: int, op: str, win=None, axis: int = 0) -> np.nd
     even one, NaN when the block holds a NaN; mad is that median of
     |x - median(x)| times StatsBase's mad_constant (n <= 1: the block itself).
     ``("quantile", p)``: Statistics.quantile (type 7) by the rule of
-    include/bldp.h with every step in Float64 (d a Float64 difference)."""
+    include/bldp.h with every step in Float64 (d a Float64 difference).
+    ``("quantiles", ps)``: that per p, the K results on a new last axis."""
+    ps = _lib.quantiles_of(op)
+    if ps is not None:
+        planes = [_host_stat(a, n, ("quantile", p), win, axis) for p in ps]
+        return np.asfortranarray(np.stack(planes, axis=-1))
     a = np.asarray(a)
     if win is not None:
         a = a[np.ix_(*[win[3 * k] + win[3 * k + 2] * np.arange(win[3 * k + 1])
@@ -312,7 +324,8 @@ def fqav(A, n: int, f="sum"):
     if isinstance(A, (JRange, FRange)):
         return fqav_range(A, n)
     if n <= 1:
-        return A
+        ps = _lib.quantiles_of(f) if isinstance(f, tuple) else None
+        return A if ps is None else _planes(A, len(ps))
     aop = _argop(f)
     if aop is not None:  # where in each block of n the extreme lies (int32 offsets)
         if _is_tensor(A):
@@ -336,7 +349,21 @@ def fqav(A, n: int, f="sum"):
     if a3.ndim != 3:
         raise ValueError("fqav arrays are at most 3-D (nchan, nif, ntime)")
     out = _reduce_host(a3, n, 1, op, None, 0)
-    return out.reshape((out.shape[0],) + A.shape[1:], order="F")
+    # (quantiles: the planes' axis stays last)
+    return out.reshape((out.shape[0],) + A.shape[1:] + out.shape[3:], order="F")
+
+
+def _planes(A, K: int):
+    """fqav's n <= 1 rule for quantiles(ps): the array itself in each of K planes
+    on a new last axis, in its own element type, plane after plane."""
+    if _is_tensor(A):
+        import torch
+
+        r = torch.empty((K,) + tuple(reversed(A.shape)), dtype=A.dtype, device=A.device)
+        r = r.permute(*reversed(range(r.dim())))
+        r.copy_(A.unsqueeze(-1).expand(r.shape))
+        return r
+    return np.asfortranarray(np.stack([np.asarray(A)] * K, axis=-1))
 
 
 def _reduce_host(a, fqavby, tavby, op, win, device):
@@ -362,6 +389,11 @@ def _check_argop(fqavfunc, tavfunc):
     aop = _argop(fqavfunc)
     if aop is not None and tavfunc is not None:
         raise TypeError(f"fqavfunc {aop!r} gives block offsets: it takes tavby, not a tavfunc")
+    # quantiles(ps) gives K planes, which no second stage takes: it is the last stage
+    if tavfunc is not None and isinstance(fqavfunc, tuple) and \
+            _lib.quantiles_of(fqavfunc) is not None:
+        raise TypeError("fqavfunc quantiles(ps) gives a plane per p: it takes no tavfunc (as "
+                        "tavfunc it is the last stage, after any fqavfunc)")
     return aop
 
 
@@ -392,10 +424,11 @@ def _reduce_array(x, idxs, fqavby, fqavfunc, tavby, device, tavfunc=None):
         if engine._dtype_code(a.dtype) is None:
             raise TypeError(f"element type {a.dtype} is not supported")
         engine._check_bounds(win, a.shape)
-        if win is None:
-            return a
-        ax = [win[3 * k] + win[3 * k + 2] * np.arange(win[3 * k + 1]) for k in range(3)]
-        return np.asfortranarray(a[np.ix_(*ax)])
+        if win is not None:
+            ax = [win[3 * k] + win[3 * k + 2] * np.arange(win[3 * k + 1]) for k in range(3)]
+            a = np.asfortranarray(a[np.ix_(*ax)])
+        ps = _lib.quantiles_of(op)
+        return a if ps is None else _planes(a, len(ps))
     return _reduce_host(a, fqavby, tavby, op, win, device)
 
 
@@ -418,8 +451,9 @@ def _tav_device(x, win, fqavby, op1, tavby, op2, out=None):
     is the reduce with tavby = 1 (skipped for fqavby <= 1, its result a
     temporary device tensor), stage 2 the reduce with fqavby = 1 for
     sum / mean / max / min and engine.tstat for var / std / median (skipped
-    for tavby <= 1: fqav's n <= 1 rule)."""
-    if tavby <= 1:
+    for tavby <= 1: fqav's n <= 1 rule; quantiles(ps) then copies stage 1's
+    result into its planes)."""
+    if tavby <= 1 and _lib.quantiles_of(op2) is None:
         return engine.reduce(x, fqavby, 1, op1 if fqavby > 1 else "sum", win, out=out)
     if fqavby > 1:
         x, win = engine.reduce(x, fqavby, 1, op1, win), None
@@ -442,7 +476,8 @@ def _tav_host(a, win, fqavby, op1, tavby, op2, device):
         a = np.asfortranarray(a[np.ix_(*[win[3 * k] + win[3 * k + 2] * np.arange(win[3 * k + 1])
                                          for k in range(3)])])
     if tavby <= 1:
-        return a
+        ps = _lib.quantiles_of(op2)
+        return a if ps is None else _planes(a, len(ps))
     if _lib.stat_op(op2):
         return _host_stat(a, tavby, op2, axis=2)
     return _reduce_host(np.asfortranarray(a), 1, tavby, op2, None, device)
@@ -638,7 +673,7 @@ def window_on_device(fname, idxs, device=0):
 def getdata_device(fname, idxs=(COLON, COLON, COLON), fqavby=1, fqavfunc="sum", tavby=1,
                    device=0, out=None, tavfunc=None):
     """getdata with the result left on GPU ``device`` (a Julia-order Float32
-    tensor), written into ``out`` when given — e.g. a bank's slot of a stitched
+    tensor; quantiles(ps): the 4-D plane tensor), written into ``out`` when given — e.g. a bank's slot of a stitched
     band product (GBT.getband); None when the data are not Float32.  With
     ``tavfunc`` (as getdata) the last stage writes ``out``."""
     if _check_argop(fqavfunc, tavfunc) is not None:

@@ -90,7 +90,8 @@ extern "C" {
  *    bldp_kurtosis_blocks_*, bldp_tstat_*, bldp_argext_*, bldp_skewness_* and
  *    bldp_moments_* entry points; (additive, same version) BLDP_OP_MAD = 8
  *    wherever BLDP_OP_MEDIAN is taken (7 stays unassigned and invalid);
- *    (additive, same version) the bldp_quantile_* entry points */
+ *    (additive, same version) the bldp_quantile_* entry points;
+ *    (additive, same version) the bldp_quantiles_* entry points */
 #define BLDP_ABI_VERSION 5
 
 #if defined(BLDP_BUILD)
@@ -586,6 +587,74 @@ BLDP_API int bldp_band_quantile_f32(int nbank, const float *const *in, int64_t n
 BLDP_API int bldp_quantile_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
                                     int64_t ntime, const int64_t *win, int axis, int64_t n,
                                     double p, float *out);
+
+/* quantiles(ps): np quantiles of every block from ONE read and one selection,
+ * Julia's vector form quantile(v, [p1, ..., pK]).  The result is np planes;
+ * plane k is, bit for bit, what bldp_quantile_* returns for p[k] on the same
+ * window: rules 1 to 8 above applied per plane, NaN wins in every plane, and
+ * n <= 1 copies the window into every plane.  In Julia terms
+ * stack([fqav(A, n; f = x -> quantile(x, p)) for p in ps]) with the new axis
+ * last.  The planes are in the caller's order: p[] may be unsorted and may
+ * repeat.  Additive in ABI 5.
+ *
+ * The host turns (n, p[]) into the sorted distinct 0-based ranks {j_k - 1, j_k}
+ * (at most 2 np) and, per plane, which two of them it joins with which weight
+ * g_k; the kernels select the keys of those ranks once and write every plane.
+ * The median's kernels of that axis and shape do it:
+ *   axis 0, n <= 64 and axis 2, n <= 32: one sort in registers, then a pick and
+ *     a store per plane (1 read of the block);
+ *   axis 0, 64 < n <= 4096: the radix select of all ranks in the same four
+ *     passes over keys loaded once (1 read); ranks whose fixed prefixes agree
+ *     share a 256-bin histogram, at most 16 of them (16 KiB of LDS);
+ *   axis 0, n > 4096: the same, the block read once per pass (4 reads, not
+ *     4 np);
+ *   axis 2, n > 32: pass 0 builds one histogram per column for all ranks; then
+ *     the distinct lower ranks j_k - 1 go three per sweep of passes 1 to 3 and
+ *     a pass for the smallest key above each (the upper rank is the same key
+ *     again or that one), 16 columns a workgroup (48 KiB of LDS; one lower
+ *     rank: 32 columns, 32 KiB, the quantile's own tiling).  Reads of the
+ *     block: 1 + 4 ceil(L / 3) for L distinct lower ranks, that is 5, 5, 5, 9,
+ *     9, 9, 13, 13 for L = 1 .. 8, where np separate calls read it 5 np times.
+ *
+ * One launch takes 1 <= np <= BLDP_MAX_QUANTILES probabilities; callers with
+ * more batch them.  np outside that, any p[k] outside [0, 1] or NaN, a null p
+ * or an axis other than 0 and 2 is BLDP_EINVAL; an n that does not divide the
+ * axis is BLDP_EDIM, a window outside the array BLDP_EBOUNDS; all before any
+ * launch.
+ *
+ * bldp_quantiles_shape: dims = {nc / n, ni, nt, np} (axis 0) or {nc, ni,
+ * nt / n, np} (axis 2); pure host.
+ * bldp_quantiles_plan_f32: info[0..7] as the median's plan of that axis and
+ * shape reports it (axis 0: bldp_reduce_plan_f32; axis 2: bldp_tstat_plan_f32,
+ * with the passes, workgroups and channel lanes of the tiling above),
+ * info[8] = the count of distinct ranks (0 for the copy of n <= 1), info[9] =
+ * the reads of the block.  Launches nothing and needs no GPU (pointers may be
+ * null).
+ * bldp_quantiles_f32: device pointers, asynchronous on `stream`; element (c, i,
+ * t) of plane k at out[c + i*out_ld_i + t*out_ld_t + k*out_ld_q] (elements;
+ * planes must not overlap: BLDP_EINVAL).
+ * bldp_band_quantiles_f32: as bldp_band_quantile_f32, np dense planes of the
+ * stitched product one after the other.
+ * bldp_quantiles_host_f32: host in, host dense out (the dims of
+ * bldp_quantiles_shape, plane k at k * dims[0]*dims[1]*dims[2]); the window's
+ * rows are staged on device `dev` once.  Synchronous. */
+#define BLDP_MAX_QUANTILES 8
+BLDP_API int bldp_quantiles_shape(int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win,
+                                  int axis, int64_t n, int np, int64_t dims[4]);
+BLDP_API int bldp_quantiles_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                                     const int64_t *win, int axis, int64_t n, int np,
+                                     const double *p, const float *out, int64_t info[10]);
+BLDP_API int bldp_quantiles_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                                const int64_t *win, int axis, int64_t n, int np, const double *p,
+                                float *out, int64_t out_ld_i, int64_t out_ld_t, int64_t out_ld_q,
+                                void *stream);
+BLDP_API int bldp_band_quantiles_f32(int nbank, const float *const *in, int64_t nchan,
+                                     int64_t nif, int64_t ntime, const int64_t *win, int axis,
+                                     int64_t n, int np, const double *p, float *out,
+                                     void *stream);
+BLDP_API int bldp_quantiles_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                     int64_t ntime, const int64_t *win, int axis, int64_t n,
+                                     int np, const double *p, float *out);
 
 /* fqavfunc argmax / argmin (fqav(A, n; f=argmax), the position half of Julia's
  * findmax / findmin): where in each block of the reduce the extreme lies.  For
