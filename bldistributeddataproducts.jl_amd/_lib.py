@@ -205,6 +205,11 @@ SIGNATURES = {
     "bldp_quantiles_f32": ([P, I64, I64, I64, P, I, I64, I, P, P, I64, I64, I64, P], I),
     "bldp_band_quantiles_f32": ([I, P, I64, I64, I64, P, I, I64, I, P, P, P], I),
     "bldp_quantiles_host_f32": ([I, P, I64, I64, I64, P, I, I64, I, P, P], I),
+    "bldp_outliers_shape": ([I64, I64, I64, P, I, I64, P, P], I),
+    "bldp_outliers_plan_f32": ([P, I64, I64, I64, P, I, I64, I, P], I),
+    "bldp_outliers_f32": ([P, I64, I64, I64, P, I, I64, D, P, P, P, P, I64, I64, P], I),
+    "bldp_band_outliers_f32": ([I, P, I64, I64, I64, P, I, I64, D, P, P, P, P, P], I),
+    "bldp_outliers_host_f32": ([I, P, I64, I64, I64, P, I, I64, D, P, P, P, P], I),
     "bldp_argext_plan_f32": ([P, I64, I64, I64, P, I64, I64, I, P, P], I),
     "bldp_argext_f32": ([P, I64, I64, I64, P, I64, I64, I, P, P, I64, I64, P], I),
     "bldp_band_argext_f32": ([I, P, I64, I64, I64, P, I64, I64, I, P, P, P], I),

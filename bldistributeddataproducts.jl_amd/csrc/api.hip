@@ -8,6 +8,7 @@
 //     :174,:185 -> BoundsError) => BLDP_EBOUNDS;
 //   * everything else that Julia would reject by type or @assert => BLDP_EINVAL.
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -1615,6 +1616,158 @@ int bldp_band_quantiles_f32(int nbank, const float *const *in, int64_t nchan, in
                             const double *p, float *out, void *stream) {
   return quantiles_run(nbank, in, nchan, nif, ntime, win, axis, n, np, p, out, 0, 0, 0, true,
                        stream, nullptr);
+}
+
+// ---- outliers: median, mad, count and flags of every block from one launch ----
+// The checks every bldp_outliers_* entry point makes before anything else.
+static int outliers_check(int axis, int64_t n, double nsigma) {
+  if (axis != 0 && axis != 2)
+    return fail(BLDP_EINVAL,
+                "outliers: axis %d is not 0 (blocks of n channels) or 2 (blocks of n spectra)",
+                axis);
+  if (n < 2)
+    return fail(BLDP_EINVAL, "outliers: n=%lld: a block of fewer than 2 values has no scale",
+                (long long)n);
+  if (!(nsigma >= 0.0) || std::isinf(nsigma))
+    return fail(BLDP_EINVAL, "outliers: nsigma=%g is not a finite number >= 0", nsigma);
+  return BLDP_OK;
+}
+
+int bldp_outliers_shape(int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win, int axis,
+                        int64_t n, int64_t dims[3], int64_t mask_dims[3]) {
+  if (!dims || !mask_dims) return fail(BLDP_EINVAL, "null dims");
+  int rc = outliers_check(axis, n, 0.0);
+  if (rc) return rc;
+  rc = bldp_quantile_shape(nchan, nif, ntime, win, axis, n, dims);
+  if (rc) return rc;
+  mask_dims[0] = axis == 0 ? dims[0] * n : dims[0];
+  mask_dims[1] = dims[1];
+  mask_dims[2] = axis == 2 ? dims[2] * n : dims[2];
+  return BLDP_OK;
+}
+
+// Every entry point of the family.  med, mad and count: element (c', i, t') of
+// bank b at [b*bank + c' + i*out_ld_i + t'*out_ld_t] (stitched: the dense vcat
+// of the banks, as bldp_band_quantile_f32's product; the mask is then the vcat
+// of the banks' windows).  info: the plan query (nothing is launched).
+static int outliers_run(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                        int64_t ntime, const int64_t *win, int axis, int64_t n, double nsigma,
+                        float *med, float *mad, uint32_t *count, uint8_t *mask, int64_t out_ld_i,
+                        int64_t out_ld_t, bool stitched, void *stream, int64_t *info,
+                        bool want_mask) {
+  int rc = outliers_check(axis, n, nsigma);
+  if (rc) return rc;
+  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
+    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
+  int64_t d[3], md[3];
+  rc = bldp_outliers_shape(nchan, nif, ntime, win, axis, n, d, md);
+  if (rc) return rc;
+  int64_t bank = 0;
+  if (stitched) {
+    bank = d[0];
+    out_ld_i = nbank * d[0];
+    out_ld_t = out_ld_i * d[1];
+  }
+  const bool empty = d[0] == 0 || d[1] == 0 || d[2] == 0;
+  if (!info && !empty) {
+    if (!in) return fail(BLDP_EINVAL, "outliers: null input pointer array");
+    for (int b = 0; b < nbank; ++b)
+      if (!in[b]) return fail(BLDP_EINVAL, "outliers: null input pointer (bank %d)", b);
+    if (!med && !mad && !count && !mask)
+      return fail(BLDP_EINVAL, "outliers: every output is null");
+    if ((med || mad || count) &&
+        (out_ld_i < d[0] || out_ld_t < (d[1] - 1) * out_ld_i + d[0]))
+      return fail(BLDP_EINVAL,
+                  "outliers: out strides (%lld, %lld) overlap for a (%lld, %lld, %lld) result",
+                  (long long)out_ld_i, (long long)out_ld_t, (long long)d[0], (long long)d[1],
+                  (long long)d[2]);
+    // the outputs may not overlap each other or the input arrays
+    const int64_t span =
+        (nbank - 1) * bank + (d[2] - 1) * out_ld_t + (d[1] - 1) * out_ld_i + d[0];
+    const void *ptr[4] = {med, mad, count, mask};
+    const size_t len[4] = {(size_t)span * 4, (size_t)span * 4, (size_t)span * 4,
+                           (size_t)(nbank * md[0] * md[1] * md[2])};
+    static const char *const name[4] = {"med", "mad", "count", "mask"};
+    for (int q = 0; q < 4; ++q) {
+      if (!ptr[q]) continue;
+      for (int r = q + 1; r < 4; ++r)
+        if (ptr[r] && spans_overlap(ptr[q], len[q], ptr[r], len[r]))
+          return fail(BLDP_EINVAL, "outliers: outputs %s and %s overlap", name[q], name[r]);
+      for (int b = 0; b < nbank; ++b)
+        if (spans_overlap(ptr[q], len[q], in[b], (size_t)(nchan * nif * ntime) * sizeof(float)))
+          return fail(BLDP_EINVAL, "outliers: output %s overlaps the input (bank %d)", name[q], b);
+    }
+  }
+  OutlArgs oa{};
+  oa.nsigma = std::fabs(nsigma);  // (-0.0: the threshold's key must be +0.0's)
+  oa.med = med, oa.mad = mad, oa.count = count, oa.mask = mask;
+  oa.mask_bank = stitched ? md[0] : 0;
+  oa.mask_ld_i = nbank * md[0];
+  oa.mask_ld_t = oa.mask_ld_i * md[1];
+  const bool wm = info ? want_mask : mask != nullptr;
+  const float *none_in[BLDP_MAX_BANKS] = {};
+  if (!in) in = none_in;  // (the plan query takes null pointers)
+  hipStream_t s = (hipStream_t)stream;
+  if (axis == 0) {
+    RedArgs a;
+    Plan pl;
+    bool none = false;
+    rc = prepare_reduce(nbank, in, nchan, nif, ntime, win, n, 1, BLDP_OP_MAD, nullptr, bank,
+                        out_ld_i, out_ld_t, false, true, &a, &pl, &none);
+    if (rc) return rc;
+    if (info) {
+      info[0] = pl.path, info[1] = pl.lpg, info[2] = a.ts, info[3] = a.k4, info[4] = a.nchunk;
+      info[5] = pl.grid, info[6] = (int64_t)pl.ws_bytes, info[7] = a.vec_out;
+      info[8] = stats_outl_reads(pl, wm), info[9] = wm ? 1 : 0;
+      return BLDP_OK;
+    }
+    if (none) return BLDP_OK;
+    const hipError_t e = launch_stats_outl(a, pl, oa, s);
+    if (e != hipSuccess) return fail(BLDP_EHIP, "outliers launch: %s", hipGetErrorString(e));
+    return BLDP_OK;
+  }
+  TStatArgs a;
+  TStatPlan pl;
+  bool copy = false, none = false;
+  rc = tstat_prepare(nbank, in, nchan, nif, ntime, win, n, BLDP_OP_MAD, nullptr, bank, out_ld_i,
+                     out_ld_t, true, &a, &pl, &copy, &none);
+  if (rc) return rc;
+  if (info) {
+    info[0] = pl.path, info[1] = pl.cpl, info[2] = pl.tsplit, info[3] = pl.passes;
+    info[4] = pl.grid, info[5] = (int64_t)pl.ws_bytes, info[6] = a.nb;
+    info[7] = pl.tsplit > 1 ? ((int64_t)1 << a.lx_log2) : 0;
+    info[8] = tstat_outl_reads(pl, wm), info[9] = wm ? 1 : 0;
+    return BLDP_OK;
+  }
+  if (none) return BLDP_OK;
+  const hipError_t e = launch_tstat_outl(a, pl, oa, s);
+  if (e != hipSuccess) return fail(BLDP_EHIP, "outliers launch: %s", hipGetErrorString(e));
+  return BLDP_OK;
+}
+
+int bldp_outliers_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                           const int64_t *win, int axis, int64_t n, int want_mask,
+                           int64_t info[10]) {
+  if (!info) return fail(BLDP_EINVAL, "null info");
+  const float *ins[1] = {in};
+  return outliers_run(1, ins, nchan, nif, ntime, win, axis, n, 0.0, nullptr, nullptr, nullptr,
+                      nullptr, 0, 0, true, nullptr, info, want_mask != 0);
+}
+
+int bldp_outliers_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                      const int64_t *win, int axis, int64_t n, double nsigma, float *med,
+                      float *mad, uint32_t *count, uint8_t *mask, int64_t out_ld_i,
+                      int64_t out_ld_t, void *stream) {
+  const float *ins[1] = {in};
+  return outliers_run(1, ins, nchan, nif, ntime, win, axis, n, nsigma, med, mad, count, mask,
+                      out_ld_i, out_ld_t, false, stream, nullptr, false);
+}
+
+int bldp_band_outliers_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                           int64_t ntime, const int64_t *win, int axis, int64_t n, double nsigma,
+                           float *med, float *mad, uint32_t *count, uint8_t *mask, void *stream) {
+  return outliers_run(nbank, in, nchan, nif, ntime, win, axis, n, nsigma, med, mad, count, mask,
+                      0, 0, true, stream, nullptr, false);
 }
 
 // ---- fqavfunc argmax / argmin: the winner's offset in every F x T block ------

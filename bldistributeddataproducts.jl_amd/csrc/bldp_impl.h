@@ -199,7 +199,8 @@ inline bool median_op(int op) {
 // What the median's kernels select (their compile-time selector): ranks
 // (n-1)/2 and n/2 once, the same twice (mad), or the run-time ranks qrank and
 // qrank + 1 joined by quantile_of, or the ranks of a QSet joined plane by plane.
-enum Sel { SEL_MEDIAN = 0, SEL_MAD = 1, SEL_QUANTILE = 2, SEL_QUANTILES = 3 };
+// SEL_OUTLIERS: mad's two selections, then the flags of an OutlArgs.
+enum Sel { SEL_MEDIAN = 0, SEL_MAD = 1, SEL_QUANTILE = 2, SEL_QUANTILES = 3, SEL_OUTLIERS = 4 };
 // The 0-based lower rank j - 1 and the weight g of Statistics.quantile(x, p)
 // of n >= 2 values (type 7), in Float64 with every operation rounded once
 // (host.hip); the upper rank is always *rank + 1 <= n - 1.
@@ -256,12 +257,44 @@ struct QSet {
 // Builds it with quantile_rank (host.hip); 1 <= np <= BLDP_MAX_QUANTILES, every
 // p in [0, 1], n >= 2.
 void quantile_set(int64_t n, int np, const double *p, int64_t out_ld_q, QSet *qs);
+// outliers (the bldp_outliers_* entry points): what the SEL_OUTLIERS
+// instantiations of the median's kernels write beside their args, a by-value
+// kernel argument of those alone (as QSet).  med, mad and count are laid out as
+// the args lay out `out` (which these launches leave null): element e of `out`
+// is element e of each.  mask is the window's flags: element (c, i, t) of bank b
+// at mask[b * mask_bank + c + i * mask_ld_i + t * mask_ld_t].  A null pointer is
+// neither formed nor stored.
+struct OutlArgs {
+  double nsigma;  // finite, >= +0.0
+  float *med, *mad;
+  uint32_t *count;
+  uint8_t *mask;
+  int64_t mask_bank, mask_ld_i, mask_ld_t;
+};
+// The threshold of a block whose scaled mad is s: Float32(nsigma * Float64(s)),
+// one product rounded once (NaN for a NaN s, and for 0 * Inf: nothing is flagged)
+__device__ __forceinline__ float outl_thr(double nsigma, float s) {
+  return (float)(nsigma * (double)s);
+}
+// four flags (0 / 1) at m .. m + 3: one dword where the address allows it
+__device__ __forceinline__ void outl_store4(uint8_t *m, bool f0, bool f1, bool f2, bool f3) {
+  if (((uintptr_t)m & 3u) == 0) {
+    *reinterpret_cast<uint32_t *>(m) =
+        (uint32_t)f0 | ((uint32_t)f1 << 8) | ((uint32_t)f2 << 16) | ((uint32_t)f3 << 24);
+  } else {
+    m[0] = f0, m[1] = f1, m[2] = f2, m[3] = f3;
+  }
+}
 int plan_stats(RedArgs &a, int op, bool words, int xcd_lg, Plan *p);
 hipError_t launch_stats(const RedArgs &a, const Plan &p, int op, hipStream_t s);
 // kOpQuantiles: the median's plan (plan_stats) launched with the rank set
 hipError_t launch_stats_q(const RedArgs &a, const Plan &p, const QSet &qs, hipStream_t s);
 // reads of the block a quantiles launch of that plan makes (any rank set)
 int stats_q_reads(const Plan &p);
+// outliers: mad's plan (plan_stats with BLDP_OP_MAD) launched with the OutlArgs
+hipError_t launch_stats_outl(const RedArgs &a, const Plan &p, const OutlArgs &oa, hipStream_t s);
+// reads of the block an outliers launch of that plan makes
+int stats_outl_reads(const Plan &p, bool mask);
 
 // argmax / argmin of every F x T block (argext.hip): the offset k + F * tt of the
 // winner in its block (column-major, channel fastest), first occurrence, NaN
@@ -322,6 +355,11 @@ hipError_t launch_tstat(const TStatArgs &a, const TStatPlan &p, int op, hipStrea
 // p->passes = the reads of the block), and its launch with the rank set
 int plan_tstat_q(TStatArgs &a, int nlow, bool words, int num_cus, int xcd_lg, TStatPlan *p);
 hipError_t launch_tstat_q(const TStatArgs &a, const TStatPlan &p, const QSet &qs, hipStream_t s);
+// outliers: mad's plan (plan_tstat with BLDP_OP_MAD) launched with the OutlArgs,
+// and the reads of the block that launch makes
+hipError_t launch_tstat_outl(const TStatArgs &a, const TStatPlan &p, const OutlArgs &oa,
+                             hipStream_t s);
+int tstat_outl_reads(const TStatPlan &p, bool mask);
 
 hipError_t launch_stitch(int nbank, const float *g, int64_t nc, int64_t nrows, float *out,
                          hipStream_t s);

@@ -431,6 +431,50 @@ extern "C" int bldp_quantiles_host_f32(int dev, const float *in, int64_t nchan, 
   });
 }
 
+// The same staging for outliers: the window's rows go to the device once, the
+// dense planes of bldp_outliers_shape that the caller asked for come back.
+extern "C" int bldp_outliers_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                      int64_t ntime, const int64_t *win, int axis, int64_t n,
+                                      double nsigma, float *med, float *mad, uint32_t *count,
+                                      uint8_t *mask) {
+  // (every argument check, before any staging)
+  int64_t info[10], sh[3], ms[3];
+  int rc = bldp_outliers_plan_f32(nullptr, nchan, nif, ntime, win, axis, n, mask != nullptr, info);
+  if (rc) return rc;
+  if (!(nsigma >= 0.0) || std::isinf(nsigma))
+    return bldp::set_error(BLDP_EINVAL, "outliers: nsigma=%g is not a finite number >= 0", nsigma);
+  rc = bldp_outliers_shape(nchan, nif, ntime, win, axis, n, sh, ms);
+  if (rc) return rc;
+  const int64_t nc = ms[0], ni = ms[1], nt = ms[2], plane = sh[0] * sh[1] * sh[2];
+  if (plane == 0) return BLDP_OK;
+  if (!in) return bldp::set_error(BLDP_EINVAL, "outliers: null input pointer");
+  if (!med && !mad && !count && !mask)
+    return bldp::set_error(BLDP_EINVAL, "outliers: every output is null");
+  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
+  return with_stager(dev, [&](bldp::Stager *sg) -> int {
+    // the staged outputs: three planes of 4-byte elements, then the mask
+    const size_t pb = (size_t)plane * 4, mb = mask ? (size_t)(nc * ni * nt) : 0;
+    float *dbuf;
+    char *dout;
+    int r = bldp::stager_buffer(sg, 0, (size_t)(h.span * ni * nt) * 4, (void **)&dbuf);
+    if (!r) r = bldp::stager_buffer(sg, 2, 3 * pb + mb, (void **)&dout);
+    if (!r) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
+    if (r) return r;
+    float *dmed = med ? (float *)dout : nullptr, *dmad = mad ? (float *)(dout + pb) : nullptr;
+    uint32_t *dcount = count ? (uint32_t *)(dout + 2 * pb) : nullptr;
+    uint8_t *dmask = mask ? (uint8_t *)(dout + 3 * pb) : nullptr;
+    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
+    r = bldp_outliers_f32(dbuf, h.span, ni, nt, dwin, axis, n, nsigma, dmed, dmad, dcount, dmask,
+                          sh[0], sh[0] * ni, sg->st[0]);
+    if (r) return r;
+    if (med) HCHK(hipMemcpyAsync(med, dmed, pb, hipMemcpyDeviceToHost, sg->st[0]));
+    if (mad) HCHK(hipMemcpyAsync(mad, dmad, pb, hipMemcpyDeviceToHost, sg->st[0]));
+    if (count) HCHK(hipMemcpyAsync(count, dcount, pb, hipMemcpyDeviceToHost, sg->st[0]));
+    if (mask) HCHK(hipMemcpyAsync(mask, dmask, mb, hipMemcpyDeviceToHost, sg->st[0]));
+    return BLDP_OK;
+  });
+}
+
 // The same staging for fqavfunc argmax / argmin: the window's rows go to the
 // device once (in window order), the (nco, ni, nto) offsets, and the winners'
 // bits when val is given, come back.

@@ -65,6 +65,18 @@
 //              with hist_add's leader trick.  The waves then scan one slot
 //              each and settle every rank of that slot.  Plans and paths are
 //              the median's; reads of the block: 1, 1 and 4.
+//   outliers   (the bldp_outliers_* entry points) c = median(x), s = mad(x) as
+//              above, thr = Float32(nsigma * Float64(s)); sample i is flagged
+//              when |x_i - c| > thr, strictly, and never when c or s is NaN.
+//              The median's kernels with SEL_OUTLIERS run mad's two selections
+//              and then write what the trailing OutlArgs (bldp_impl.h) asks for:
+//              the median, the scaled mad, the count of flagged samples and the
+//              flags.  Sort and register-select forms: the keys held are those
+//              of |x - c|, compared against the threshold's key and counted over
+//              the lane group (xor-shuffles) or the workgroup (LDS); the mask
+//              reloads the block for the positions (1 read, 2 with a mask).
+//              Stream form: one more pass over the block (9 reads).  Plans and
+//              paths are mad's.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -118,6 +130,14 @@ __device__ __forceinline__ bool stat_group(const RedArgs &a, int64_t g, const fl
   p = a.in[b] + a.in_off + co * a.F * a.in_cs + i * a.in_ld_i + t * a.in_ld_t;
   o = a.out + b * a.out_bank + co + i * a.out_ld_i + t * a.out_ld_t;
   return true;
+}
+
+// outliers: where the mask holds the first element of block g of bank blockIdx.y
+__device__ __forceinline__ uint8_t *outl_mask(const RedArgs &a, const OutlArgs &oa, int64_t g) {
+  int64_t co, r, i, t;
+  divmod(g, a.nco, r, co);
+  divmod(r, a.ni, t, i);
+  return oa.mask + blockIdx.y * oa.mask_bank + co * a.F + i * oa.mask_ld_i + t * oa.mask_ld_t;
 }
 
 // ---------------------------------------------------------------------------
@@ -316,14 +336,17 @@ __device__ __forceinline__ void bitonic_sort4(uint32_t (&k)[4], const int lg) {
 // to e >= F, stays) and the network runs again.  SEL_QUANTILE: the ranks are
 // a.qrank and the next.  SEL_QUANTILES: one more argument, the QSet (QS is empty
 // for every other selector: their signature is (RedArgs)); the planes' ranks
-// are picked and stored one plane after the other.
+// are picked and stored one plane after the other.  SEL_OUTLIERS: mad's two
+// sorts, then the trailing OutlArgs' outputs: the sorted keys of |x - median|
+// above the threshold's are counted over the group, and the mask reloads the
+// lane's elements for their positions.
 template <typename T>
 __device__ __forceinline__ const T &first_arg(const T &x) {
   return x;
 }
 template <int L, bool VEC, Sel SEL, typename... QS>
 __global__ __launch_bounds__(kBlock) void k_median_sort(const RedArgs a, const QS... qs) {
-  constexpr bool MAD = SEL == SEL_MAD;
+  constexpr bool MAD = SEL == SEL_MAD || SEL == SEL_OUTLIERS;
   constexpr int LG = L / 4;
   const int lg = threadIdx.x % LG;
   const int64_t tile = xcd_order(blockIdx.x, gridDim.x, a.xcd_lg);
@@ -354,13 +377,26 @@ __global__ __launch_bounds__(kBlock) void k_median_sort(const RedArgs a, const Q
   const int q1 = SEL == SEL_QUANTILE ? a.qrank + 1 : F / 2;
   auto pick = [&](int q) {
     const int r = q & 3;
-    uint32_t x = r == 0 ? k[0] : r == 1 ? k[1] : r == 2 ? k[2] : k[3];
+    uint32_t x;
+    if constexpr (SEL == SEL_OUTLIERS) {
+      // (copies: choosing among the addresses of k, which is written again
+      // below, kept k in scratch at L = 4)
+      const uint32_t k0 = k[0], k1 = k[1], k2 = k[2], k3 = k[3];
+      x = r == 0 ? k0 : r == 1 ? k1 : r == 2 ? k2 : k3;
+    } else {
+      x = r == 0 ? k[0] : r == 1 ? k[1] : r == 2 ? k[2] : k[3];
+    }
     if (LG > 1) x = __shfl(x, (int)(threadIdx.x & 63) - lg + q / 4, 64);
     return x;
   };
   uint32_t k0 = pick(q0), k1 = pick(q1);
+  const unsigned long long gmask = LG == 64 ? ~0ull : ((1ull << LG) - 1ull);
+  float c = 0.0f;     // MAD: the block's median
+  bool nan0 = false;  // SEL_OUTLIERS: the block holds a NaN
   if (MAD) {
-    const float c = median_of(k0, k1, F & 1, false);  // (a NaN block: NaN below, whatever c is)
+    c = median_of(k0, k1, F & 1, false);  // (a NaN block: NaN below, whatever c is)
+    if constexpr (SEL == SEL_OUTLIERS)
+      nan0 = ((__ballot(nan) >> ((threadIdx.x & 63) - lg)) & gmask) != 0;
 #pragma unroll
     for (int r = 0; r < 4; ++r)
       if (4 * lg + r < F) {
@@ -372,9 +408,41 @@ __global__ __launch_bounds__(kBlock) void k_median_sort(const RedArgs a, const Q
     k0 = pick(q0), k1 = pick(q1);
   }
   const unsigned long long bal = __ballot(nan);
-  const unsigned long long gmask = LG == 64 ? ~0ull : ((1ull << LG) - 1ull);
   const bool gnan = ((bal >> ((threadIdx.x & 63) - lg)) & gmask) != 0;
-  if constexpr (SEL == SEL_QUANTILES) {
+  if constexpr (SEL == SEL_OUTLIERS) {
+    const OutlArgs &oa = first_arg(qs...);
+    const float sc = mad_scale(median_of(k0, k1, F & 1, gnan));
+    const float thr = outl_thr(oa.nsigma, sc);
+    const bool live = !gnan && thr == thr;  // (a NaN median or scale flags nothing)
+    const uint32_t kthr = f2key(thr);
+    uint32_t cnt = 0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) cnt += live && 4 * lg + r < F && k[r] > kthr;  // (padding: e >= F)
+#pragma unroll
+    for (int w = LG / 2; w >= 1; w /= 2) cnt += __shfl_xor(cnt, w, 64);
+    if (!ok) return;  // (no shuffle below)
+    if (lg == 0) {
+      const int64_t e = o - a.out;
+      if (oa.med) oa.med[e] = nan0 ? __uint_as_float(0x7fc00000u) : c;
+      if (oa.mad) oa.mad[e] = sc;
+      if (oa.count) oa.count[e] = cnt;
+    }
+    if (oa.mask) {
+      uint8_t *m = outl_mask(a, oa, tile * (kBlock / LG) + threadIdx.x / LG);
+      if (VEC) {
+        if (4 * lg < F) {
+          const float4 x = ld4(p + 4 * lg);
+          outl_store4(m + 4 * lg, live && abs_dev(x.x, c) > thr, live && abs_dev(x.y, c) > thr,
+                      live && abs_dev(x.z, c) > thr, live && abs_dev(x.w, c) > thr);
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (4 * lg + r < F)
+            m[4 * lg + r] = live && abs_dev(p[(int64_t)(4 * lg + r) * a.in_cs], c) > thr;
+      }
+    }
+  } else if constexpr (SEL == SEL_QUANTILES) {
     const QSet &s = first_arg(qs...);
     for (int kq = 0; kq < s.np; ++kq) {  // (uniform: pick shuffles, whole waves)
       const uint32_t ka = pick(s.rank[s.lo[kq]]), kb = pick(s.rank[s.hi[kq]]);
@@ -412,10 +480,14 @@ __device__ __forceinline__ void hist_add(uint32_t *h, uint32_t d, bool pred) {
 // MAD: the four passes run twice, the second time over |x - c| with c the
 // median the first found: the register keys are transformed in place (REG),
 // or the block is read again and the deviations formed on the way (!REG).
-// SEL_QUANTILE: the two ranks start at a.qrank and the next.
-template <bool VEC, bool REG, Sel SEL>
-__global__ __launch_bounds__(kBlock) void k_median_select(const RedArgs a) {
-  constexpr bool MAD = SEL == SEL_MAD;
+// SEL_QUANTILE: the two ranks start at a.qrank and the next.  SEL_OUTLIERS:
+// mad's eight passes, then the trailing OutlArgs' outputs (OA is empty for every
+// other selector): the register keys of |x - c| are counted against the
+// threshold's, or, for the mask and in the stream form, the block is read once
+// more, the deviations formed on the way.
+template <bool VEC, bool REG, Sel SEL, typename... OA>
+__global__ __launch_bounds__(kBlock) void k_median_select(const RedArgs a, const OA... oas) {
+  constexpr bool MAD = SEL == SEL_MAD || SEL == SEL_OUTLIERS;
   __shared__ uint32_t hist[2][256];
   __shared__ uint32_t wtot[2][4];
   __shared__ uint32_t sel[2][2];  // per rank: its digit, its rank among that digit's keys
@@ -460,9 +532,12 @@ __global__ __launch_bounds__(kBlock) void k_median_select(const RedArgs a) {
   // rank among the prefix's keys
   uint32_t r0 = SEL == SEL_QUANTILE ? (uint32_t)a.qrank : (uint32_t)((F - 1) / 2);
   uint32_t r1 = SEL == SEL_QUANTILE ? (uint32_t)a.qrank + 1u : (uint32_t)(F / 2);
+  bool nan0 = false;  // SEL_OUTLIERS: the block holds a NaN
   for (int pass = 0; pass < (MAD ? 8 : 4); ++pass) {
     if (MAD && pass == 4) {  // the median is known: the same four passes over |x - cen|
       cen = median_of(pre0, pre1, F & 1, false);  // (a NaN block: NaN below, whatever cen is)
+      // (pass 0's flag; pass 4 sets it again only behind its first barrier)
+      if constexpr (SEL == SEL_OUTLIERS) nan0 = nanflag != 0;
       dev = true;
       if (REG) {
 #pragma unroll
@@ -529,7 +604,49 @@ __global__ __launch_bounds__(kBlock) void k_median_select(const RedArgs a) {
     pre1 |= sel[1][0] << shift;
     r1 = sel[1][1];
   }
-  if (tid == 0) {
+  if constexpr (SEL == SEL_OUTLIERS) {
+    const OutlArgs &oa = first_arg(oas...);
+    const float sc = mad_scale(median_of(pre0, pre1, F & 1, nanflag != 0));
+    const float thr = outl_thr(oa.nsigma, sc);
+    const bool live = nanflag == 0 && thr == thr;  // (a NaN median or scale flags nothing)
+    const uint32_t kthr = f2key(thr);
+    uint32_t cnt = 0;
+    if (REG && !oa.mask) {
+#pragma unroll
+      for (int it = 0; it < NREG; ++it) {
+        const bool valid = (int64_t)it * kBlock + tid < n;
+#pragma unroll
+        for (int c = 0; c < KPI; ++c) cnt += live && valid && keys[it * KPI + c] > kthr;
+      }
+    } else {  // one more read: the keys of |x - cen| (dev is set) with their positions
+      uint8_t *m = oa.mask ? outl_mask(a, oa, blockIdx.x) : nullptr;
+      for (int64_t it = 0; it < nit; ++it) {
+        uint32_t k[4] = {0, 0, 0, 0};
+        bool unused = false;
+        if (!load(it, k, unused)) continue;
+        const int64_t idx = it * kBlock + tid;
+        bool f[KPI];
+#pragma unroll
+        for (int c = 0; c < KPI; ++c) f[c] = live && k[c] > kthr, cnt += f[c];
+        if (m) {
+          if constexpr (VEC)
+            outl_store4(m + 4 * idx, f[0], f[1], f[2], f[3]);
+          else
+            m[idx] = f[0];
+        }
+      }
+    }
+#pragma unroll
+    for (int w = 32; w >= 1; w /= 2) cnt += __shfl_xor(cnt, w, 64);
+    if (lane == 0) wtot[0][wave] = cnt;  // (free: the last pass's barrier is behind every reader)
+    __syncthreads();
+    if (tid == 0) {
+      const int64_t e = o - a.out;
+      if (oa.med) oa.med[e] = nan0 ? __uint_as_float(0x7fc00000u) : cen;
+      if (oa.mad) oa.mad[e] = sc;
+      if (oa.count) oa.count[e] = (wtot[0][0] + wtot[0][1]) + (wtot[0][2] + wtot[0][3]);
+    }
+  } else if (tid == 0) {
     if constexpr (SEL == SEL_QUANTILE) {
       *o = quantile_of(pre0, pre1, a.qg, nanflag != 0);
     } else {
@@ -785,6 +902,43 @@ hipError_t launch_stats(const RedArgs &a, const Plan &p, int op, hipStream_t s) 
 }
 
 int stats_q_reads(const Plan &p) { return p.path == PATH_MEDIAN_STREAM ? 4 : 1; }
+
+// mad's 8 reads and the flag pass; the register forms read once, and once more
+// for the positions of a mask
+int stats_outl_reads(const Plan &p, bool mask) {
+  return p.path == PATH_MEDIAN_STREAM ? 9 : mask ? 2 : 1;
+}
+
+hipError_t launch_stats_outl(const RedArgs &a, const Plan &p, const OutlArgs &oa, hipStream_t s) {
+  if (p.grid <= 0) return hipSuccess;
+  if (a.F < 2 || a.out || !(oa.nsigma >= 0.0 && oa.nsigma <= 1.7976931348623157e308))
+    return hipErrorInvalidValue;
+  const dim3 grid((unsigned)p.grid, (unsigned)a.nbank);
+  const auto go = [&](auto *kn) { return launch_kernel(kn, grid, dim3(kBlock), 0, s, a, oa); };
+  const bool vec = a.k4 != 0;
+#define BLDP_OSORT(N)                                         \
+  (vec ? k_median_sort<N, true, SEL_OUTLIERS, OutlArgs>       \
+       : k_median_sort<N, false, SEL_OUTLIERS, OutlArgs>)
+#define BLDP_OSEL(REG)                                        \
+  (vec ? k_median_select<true, REG, SEL_OUTLIERS, OutlArgs>   \
+       : k_median_select<false, REG, SEL_OUTLIERS, OutlArgs>)
+  switch (p.path) {
+    case PATH_MEDIAN_SORT:
+      switch (p.lpg) {  // lanes of 4 keys
+        case 1: return go(BLDP_OSORT(4));
+        case 2: return go(BLDP_OSORT(8));
+        case 4: return go(BLDP_OSORT(16));
+        case 8: return go(BLDP_OSORT(32));
+        case 16: return go(BLDP_OSORT(64));
+      }
+      break;
+    case PATH_MEDIAN_SELECT: return go(BLDP_OSEL(true));
+    case PATH_MEDIAN_STREAM: return go(BLDP_OSEL(false));
+  }
+#undef BLDP_OSORT
+#undef BLDP_OSEL
+  return hipErrorInvalidValue;
+}
 
 hipError_t launch_stats_q(const RedArgs &a, const Plan &p, const QSet &qs, hipStream_t s) {
   if (p.grid <= 0) return hipSuccess;

@@ -64,6 +64,15 @@
 //              moments' narrowed tile).  Reads of the block: 1 + 4 ceil(L / G),
 //              that is 5, 5, 5, 9, 9, 9, 13, 13 for L = 1 .. 8 (K separate
 //              calls: 5 K).
+//   outliers   (stats.hip's rule) mad's two selections, then what the trailing
+//              OutlArgs (bldp_impl.h) asks for: median, scaled mad, the count of
+//              samples with |x - c| > thr and the flags.  Register form
+//              (k_tstat_regs, MED = 5): the sorted keys of |x - c| against the
+//              threshold's key; the mask reloads the block (1 read, 2 with a
+//              mask; a lane's 4 columns pack their flags into a dword).  Split
+//              form (k_tstat_med_split, SEL_OUTLIERS): one more pass of the time
+//              slices over the block, their counts added in LDS (mad's reads
+//              and 1).
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -170,7 +179,10 @@ __device__ __forceinline__ void bitonic_cols(uint32_t (&k)[TP][CPL]) {
 // MED: 0 var / std, 1 median, 2 mad (the network runs again over |x - median|),
 // 3 quantile (ranks a.qrank and the next, wave-uniform, compared in the chain),
 // 4 quantiles (one more argument, the QSet: QS is empty for every other MED,
-// whose signature is (TStatArgs, int); the chain and a store per plane)
+// whose signature is (TStatArgs, int); the chain and a store per plane),
+// 5 outliers (mad's two sorts, then the trailing OutlArgs' outputs: the sorted
+// keys of |x - median| above the threshold's are counted, and the mask reloads
+// the block for their positions)
 template <typename T>
 __device__ __forceinline__ const T &first_arg(const T &x) {
   return x;
@@ -240,22 +252,64 @@ __global__ __launch_bounds__(kBlock) void k_tstat_regs(const TStatArgs a, const 
         k1 = e == q1 ? k[e][c] : k1;
       }
     };
-    if constexpr (MED == 2) {
+    float cen[CPL];  // mad, outliers: the columns' medians
+    bool nan0[CPL];  // outliers: the block holds a NaN
+    if constexpr (MED == 2 || MED == 5) {
       // the sorted keys (the padding is at e >= T) become those of |x - median|
 #pragma unroll
       for (int c = 0; c < CPL; ++c) {
         uint32_t k0, k1;
         ranks(c, k0, k1);
-        const float cen = median_of(k0, k1, T & 1, false);  // (a NaN block: NaN below)
+        cen[c] = median_of(k0, k1, T & 1, false);  // (a NaN block: NaN below)
+        nan0[c] = nan[c];
 #pragma unroll
         for (int e = 0; e < TP; ++e)
           if (e < T) {
-            const float d = abs_dev(key2f(k[e][c]), cen);
+            const float d = abs_dev(key2f(k[e][c]), cen[c]);
             nan[c] = nan[c] || d != d;
             k[e][c] = f2key(d);
           }
       }
       bitonic_cols<TP, CPL>(k);
+    }
+    if constexpr (MED == 5) {
+      const OutlArgs &oa = first_arg(qs...);
+      const int64_t eo = o - a.out;
+      float thr[CPL];
+      bool live[CPL];
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) {
+        uint32_t k0, k1;
+        ranks(c, k0, k1);
+        const float sc = mad_scale(median_of(k0, k1, T & 1, nan[c]));
+        thr[c] = outl_thr(oa.nsigma, sc);
+        live[c] = !nan[c] && thr[c] == thr[c];  // (a NaN median or scale flags nothing)
+        const uint32_t kthr = f2key(thr[c]);
+        uint32_t cnt = 0;
+#pragma unroll
+        for (int e = 0; e < TP; ++e) cnt += live[c] && e < T && k[e][c] > kthr;
+        if (oa.med) oa.med[eo + c] = nan0[c] ? __uint_as_float(0x7fc00000u) : cen[c];
+        if (oa.mad) oa.mad[eo + c] = sc;
+        if (oa.count) oa.count[eo + c] = cnt;
+      }
+      if (oa.mask) {
+        uint8_t *m = oa.mask + blockIdx.y * oa.mask_bank + cg * CPL + i * oa.mask_ld_i +
+                     b * a.T * oa.mask_ld_t;
+#pragma unroll
+        for (int t = 0; t < TP; ++t)
+          if (t < T) {
+            float x[CPL];
+            ldcols<CPL>(p + t * a.in_ld_t, x);
+            bool f[CPL];
+#pragma unroll
+            for (int c = 0; c < CPL; ++c) f[c] = live[c] && abs_dev(x[c], cen[c]) > thr[c];
+            if constexpr (CPL == 4)
+              outl_store4(m + t * oa.mask_ld_t, f[0], f[1], f[2], f[3]);
+            else
+              m[t * oa.mask_ld_t] = f[0];
+          }
+      }
+      return;
     }
     if constexpr (MED == 4) {
       const QSet &s = first_arg(qs...);
@@ -592,9 +646,12 @@ __device__ __forceinline__ void med_select(const TStatArgs &a, const SplitGeo &g
 
 // SEL_MAD: the select runs twice, over the keys of x for the columns' medians
 // cen, then over those of |x - cen|.  SEL_QUANTILE: rank a.qrank and the next.
-template <int CPL, Sel SEL>
-__global__ __launch_bounds__(kBlock) void k_tstat_med_split(const TStatArgs a) {
-  constexpr bool MAD = SEL == SEL_MAD;
+// SEL_OUTLIERS: mad's two selections, then one more pass over the block for the
+// trailing OutlArgs' outputs (OA is empty for every other selector): the time
+// slices form |x - cen|, store the flags and add their counts in LDS.
+template <int CPL, Sel SEL, typename... OA>
+__global__ __launch_bounds__(kBlock) void k_tstat_med_split(const TStatArgs a, const OA... oas) {
+  constexpr bool MAD = SEL == SEL_MAD || SEL == SEL_OUTLIERS;
   __shared__ uint32_t hist[kMedCols][256];
   __shared__ uint32_t rank[2][kMedCols];
   __shared__ uint32_t seld[kMedCols];
@@ -620,14 +677,68 @@ __global__ __launch_bounds__(kBlock) void k_tstat_med_split(const TStatArgs a) {
     const int lc = lc0 + c;
     return sh.rank[0][lc] + 1 < sh.selc[lc] ? pre[c] : sh.mingt[lc];
   };
+  bool nan0[CPL];  // SEL_OUTLIERS: the block holds a NaN
   if constexpr (MAD) {
 #pragma unroll
-    for (int c = 0; c < CPL; ++c)
+    for (int c = 0; c < CPL; ++c) {
       cen[c] = median_of(pre[c], rank1(c), odd, false);  // (a NaN block: NaN below)
+      nan0[c] = SEL == SEL_OUTLIERS && sh.nanflag[lc0 + c] != 0;
+    }
     __syncthreads();  // (rank, selc and mingt are read: the second selection resets them)
     med_select<CPL, true>(a, g, p, sh, cen, pre, q, upper);
   }
-  if (g.ok && g.ty == 0) {
+  if constexpr (SEL == SEL_OUTLIERS) {
+    __shared__ uint32_t cnt_s[kMedCols];
+    const OutlArgs &oa = first_arg(oas...);
+    float sc[CPL], thr[CPL];
+    bool live[CPL];
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+      const bool nan = sh.nanflag[lc0 + c] != 0;
+      sc[c] = mad_scale(median_of(pre[c], rank1(c), odd, nan));
+      thr[c] = outl_thr(oa.nsigma, sc[c]);
+      live[c] = !nan && thr[c] == thr[c];  // (a NaN median or scale flags nothing)
+    }
+    if (threadIdx.x < kMedCols) cnt_s[threadIdx.x] = 0;
+    __syncthreads();
+    if (g.ok) {
+      uint8_t *m = oa.mask ? oa.mask + blockIdx.y * oa.mask_bank + g.cg * CPL +
+                                 g.i * oa.mask_ld_i + g.b * T * oa.mask_ld_t
+                           : nullptr;
+      uint32_t cnt[CPL];
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) cnt[c] = 0;
+#pragma unroll 4
+      for (int64_t t = g.ty; t < T; t += g.ny) {
+        float x[CPL];
+        ldcols<CPL>(p + t * a.in_ld_t, x);
+        bool f[CPL];
+#pragma unroll
+        for (int c = 0; c < CPL; ++c)
+          f[c] = live[c] && abs_dev(x[c], cen[c]) > thr[c], cnt[c] += f[c];
+        if (m) {
+          if constexpr (CPL == 4)
+            outl_store4(m + t * oa.mask_ld_t, f[0], f[1], f[2], f[3]);
+          else
+            m[t * oa.mask_ld_t] = f[0];
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < CPL; ++c)
+        if (cnt[c]) atomicAdd(&cnt_s[lc0 + c], cnt[c]);
+    }
+    __syncthreads();
+    if (g.ok && g.ty == 0) {
+      const int64_t eo =
+          blockIdx.y * a.out_bank + g.cg * CPL + g.i * a.out_ld_i + g.b * a.out_ld_b;
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) {
+        if (oa.med) oa.med[eo + c] = nan0[c] ? __uint_as_float(0x7fc00000u) : cen[c];
+        if (oa.mad) oa.mad[eo + c] = sc[c];
+        if (oa.count) oa.count[eo + c] = cnt_s[lc0 + c];
+      }
+    }
+  } else if (g.ok && g.ty == 0) {
     float *o = a.out + blockIdx.y * a.out_bank + g.cg * CPL + g.i * a.out_ld_i + g.b * a.out_ld_b;
 #pragma unroll
     for (int c = 0; c < CPL; ++c) {
@@ -996,6 +1107,40 @@ hipError_t launch_tstat(const TStatArgs &a, const TStatPlan &p, int op, hipStrea
     }
   }
   return hipErrorInvalidValue;
+}
+
+// mad's reads and the flag pass; the register form reads once, and once more
+// for the positions of a mask
+int tstat_outl_reads(const TStatPlan &p, bool mask) {
+  return p.path == TSTAT_SPLIT_MEDIAN ? p.passes + 1 : mask ? 2 : 1;
+}
+
+namespace {
+template <int TP>
+hipError_t launch_regs_outl(const TStatArgs &a, const OutlArgs &oa, dim3 grid, hipStream_t s) {
+  return launch_kernel(a.vec ? k_tstat_regs<TP, 4, 5, OutlArgs> : k_tstat_regs<TP, 1, 5, OutlArgs>,
+                       grid, dim3(kBlock), 0, s, a, 0, oa);
+}
+}  // namespace
+
+hipError_t launch_tstat_outl(const TStatArgs &a, const TStatPlan &p, const OutlArgs &oa,
+                             hipStream_t s) {
+  if (p.grid <= 0) return hipSuccess;
+  if (a.T < 2 || a.out || !(oa.nsigma >= 0.0 && oa.nsigma <= 1.7976931348623157e308))
+    return hipErrorInvalidValue;
+  const dim3 grid((unsigned)p.grid, (unsigned)a.nbank);
+  if (p.path == TSTAT_REGS_MEDIAN) {
+    if (a.T <= 2) return launch_regs_outl<2>(a, oa, grid, s);
+    if (a.T <= 4) return launch_regs_outl<4>(a, oa, grid, s);
+    if (a.T <= 8) return launch_regs_outl<8>(a, oa, grid, s);
+    if (a.T <= 16) return launch_regs_outl<16>(a, oa, grid, s);
+    if (a.T <= 32) return launch_regs_outl<32>(a, oa, grid, s);
+    return hipErrorInvalidValue;
+  }
+  if (p.path != TSTAT_SPLIT_MEDIAN) return hipErrorInvalidValue;
+  return launch_kernel(a.vec ? k_tstat_med_split<4, SEL_OUTLIERS, OutlArgs>
+                             : k_tstat_med_split<1, SEL_OUTLIERS, OutlArgs>,
+                       grid, dim3(kBlock), 0, s, a, oa);
 }
 
 hipError_t launch_tstat_q(const TStatArgs &a, const TStatPlan &p, const QSet &qs, hipStream_t s) {

@@ -29,6 +29,7 @@ __all__ = [
     "quantile", "quantile_plan", "band_quantile", "quantile_host",
     "quantiles", "quantiles_plan", "band_quantiles", "quantiles_host", "planes_empty",
     "planes_to_numpy",
+    "OUTLIER_PLANES", "outliers", "outliers_plan", "band_outliers", "outliers_host",
     "skewness", "skewness_plan", "band_skewness", "skewness_host",
     "Moments", "MOMENTS", "moments", "moments_plan", "band_moments", "moments_host",
     "argext", "argext_plan", "band_argext", "argext_host",
@@ -962,6 +963,184 @@ def quantiles_host(a: np.ndarray, n, ps, axis=0, win=None, device=0) -> np.ndarr
                                        out.ctypes.data + 4 * k0 * plane if out.size else None)
         _lib.check(rc, "bldp_quantiles_host_f32")
     return out
+
+
+# The outputs of an outliers call, in the ABI's order; ``mask`` is asked for by
+# its own argument.
+OUTLIER_PLANES = ("median", "mad", "count")
+
+
+def _outliers_args(axis, nsigma, which):
+    """(axis, nsigma, flags of OUTLIER_PLANES) of an outliers call, checked before
+    any GPU work (ValueError)."""
+    if axis not in (0, 2):
+        raise ValueError(f"outliers: axis={axis!r} is not 0 (blocks of n channels) or 2 (blocks "
+                         f"of n spectra)")
+    try:
+        ns = float(nsigma)
+    except (TypeError, ValueError):
+        raise ValueError(f"outliers: nsigma={nsigma!r} is not a number") from None
+    if not (ns >= 0.0) or ns == float("inf"):
+        raise ValueError(f"outliers: nsigma={nsigma!r} is not a finite number >= 0")
+    if isinstance(which, str):
+        which = (which,)
+    which = tuple(which)
+    for w in which:
+        if w not in OUTLIER_PLANES:
+            raise ValueError(f"outliers: unknown output {w!r}; which takes names from "
+                             f"{OUTLIER_PLANES} (the mask: mask=True)")
+    return int(axis), ns, tuple(w in which for w in OUTLIER_PLANES)
+
+
+def _outliers_n(n, axis, nc, nt):
+    """The block length: ``None`` on axis 2 is the whole selected time range."""
+    if n is None:
+        if axis != 2:
+            raise ValueError("outliers: n=None (the whole selected time range) is for axis 2")
+        n = nt
+    n = int(n)
+    if n < 2:
+        raise _lib.ArgumentError(_lib.BLDP_EINVAL,
+                                 f"outliers: n={n}: a block of fewer than 2 values has no scale")
+    return n
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None and t.numel() else None
+
+
+def outliers(x, n, axis=2, nsigma=5.0, win=None, mask=False, which=OUTLIER_PLANES, stream=None):
+    """Median, mad, outlier count and outlier flags of every block of ``n``
+    selected channels (``axis=0``) or spectra (``axis=2``; ``n=None``: the whole
+    selected time range) from one launch (bldp_outliers_f32).  A sample is flagged
+    when ``|x - median| > Float32(nsigma * mad)``, strictly, with ``mad`` the
+    scaled median absolute deviation ``"mad"`` returns; a block whose median or
+    mad is NaN flags nothing (the rule of include/bldp.h).  Returns a dict of
+    device tensors: ``"median"`` and ``"mad"`` (Float32, bit for bit what the
+    ``"median"`` and ``"mad"`` statistics give), ``"count"`` (int32) for the names
+    in ``which``, each (nc/n, ni, nt) or (nc, ni, nt/n), and with ``mask=True``
+    ``"mask"``, the uint8 (nc, ni, nt) flags of the window.  Float32 tensors only."""
+    torch = _torch()
+    axis, ns, want = _outliers_args(axis, nsigma, which)
+    if x.dtype != torch.float32:
+        _need_f32("outliers", x.dtype, "outliers")
+    shape = tuple(x.shape)
+    _check_bounds(win, shape)
+    nc, ni, nt = window_shape(win, shape)
+    n = _outliers_n(n, axis, nc, nt)
+    dims = out_shape(shape, win, n if axis == 0 else 1, n if axis == 2 else 1)
+    ptr, nchan, nif, ntime = _abi_dims(x)
+    dts = (torch.float32, torch.float32, torch.int32)
+    outs = [fb_empty(*dims, device=x.device, dtype=dt) if w else None for w, dt in zip(want, dts)]
+    m = fb_empty(nc, ni, nt, device=x.device, dtype=torch.uint8) if mask else None
+    res = {k: o for k, o in zip(OUTLIER_PLANES, outs) if o is not None}
+    if m is not None:
+        res["mask"] = m
+    if not res:
+        raise ValueError("outliers: no output asked for (which is empty and mask is False)")
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    rc = _lib.lib().bldp_outliers_f32(ptr, nchan, nif, ntime, wp, axis, n, ns, *map(_ptr, outs),
+                                      _ptr(m), dims[0], dims[0] * dims[1], _lib.stream_ptr(stream))
+    _lib.check(rc, "bldp_outliers_f32")
+    return res
+
+
+def outliers_plan(x, n, axis=2, win=None, mask=False) -> dict:
+    """Launch plan of ``outliers(x, n, axis, win=win, mask=mask)``
+    (bldp_outliers_plan_f32): mad's plan of that axis and shape (the keys of
+    ``plan`` on axis 0, of ``tstat_plan`` on axis 2) plus ``reads``, how often the
+    block is read, and ``mask`` (1 when one is written)."""
+    axis, _, _ = _outliers_args(axis, 0.0, ())
+    shape = tuple(x.shape)
+    _check_bounds(win, shape)
+    nc, ni, nt = window_shape(win, shape)
+    n = _outliers_n(n, axis, nc, nt)
+    ptr, nchan, nif, ntime = _abi_dims(x)
+    info = (ctypes.c_int64 * 10)()
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    _lib.check(_lib.lib().bldp_outliers_plan_f32(ptr, nchan, nif, ntime, wp, axis, n,
+                                                 1 if mask else 0, info),
+               "bldp_outliers_plan_f32")
+    if axis == 0:
+        keys = ["path", "lanes_per_group", "time_split_waves", "float4_per_lane", "time_chunks",
+                "workgroups", "workspace_bytes", "vec_out", "reads", "mask"]
+        paths = _lib.PATHS
+    else:
+        keys = ["path", "channels_per_lane", "time_split_lanes", "passes", "workgroups",
+                "workspace_bytes", "blocks", "channel_lanes", "reads", "mask"]
+        paths = _lib.TSTAT_PATHS
+    d = dict(zip(keys, [int(v) for v in info]))
+    d["path"] = paths.get(d["path"], "copy")
+    return d
+
+
+def band_outliers(banks, n, axis=2, nsigma=5.0, win=None, mask=False, which=OUTLIER_PLANES,
+                  stream=None):
+    """``outliers`` of every bank of a band resident on ONE GPU, stitched in bank
+    order in one launch (bldp_band_outliers_f32): the dict of ``outliers`` with
+    dense (nbank*nc', ni, nt') planes and a (nbank*nc, ni, nt) mask, the vcat of
+    the banks' results."""
+    torch = _torch()
+    axis, ns, want = _outliers_args(axis, nsigma, which)
+    banks = list(banks)
+    if not banks:
+        raise ValueError("no banks")
+    for b in banks:
+        if b.dtype != torch.float32:
+            _need_f32("band_outliers", b.dtype, "outliers")
+    shape = tuple(banks[0].shape)
+    _check_bounds(win, shape)
+    nc, ni, nt = window_shape(win, shape)
+    n = _outliers_n(n, axis, nc, nt)
+    fq, tv = (n, 1) if axis == 0 else (1, n)
+    banks, geo, first, ptrs, (keep, wp) = _band_args(banks, fq, tv, win, None)
+    nb = len(banks)
+    dims = tuple(first.shape)
+    dts = (torch.float32, torch.float32, torch.int32)
+    outs = [fb_empty(*dims, device=first.device, dtype=dt) if w else None
+            for w, dt in zip(want, dts)]
+    m = fb_empty(nb * nc, ni, nt, device=first.device, dtype=torch.uint8) if mask else None
+    res = {k: o for k, o in zip(OUTLIER_PLANES, outs) if o is not None}
+    if m is not None:
+        res["mask"] = m
+    if not res:
+        raise ValueError("outliers: no output asked for (which is empty and mask is False)")
+    rc = _lib.lib().bldp_band_outliers_f32(nb, ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp, axis,
+                                           n, ns, *map(_ptr, outs), _ptr(m),
+                                           _lib.stream_ptr(stream))
+    _lib.check(rc, "bldp_band_outliers_f32")
+    return res
+
+
+def outliers_host(a: np.ndarray, n, axis=2, nsigma=5.0, win=None, mask=False,
+                  which=OUTLIER_PLANES, device=0) -> dict:
+    """Host Fortran-ordered Float32 array in, the dict of ``outliers`` as
+    Fortran-ordered host arrays out (bldp_outliers_host_f32: the window's rows
+    staged on ``device`` once).  Float32 arrays only."""
+    axis, ns, want = _outliers_args(axis, nsigma, which)
+    a = np.asarray(a)
+    if a.dtype != np.float32:
+        _need_f32("outliers_host", a.dtype, "outliers")
+    if not a.flags.f_contiguous or a.ndim != 3:
+        raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
+    _check_bounds(win, a.shape)
+    nc, ni, nt = window_shape(win, a.shape)
+    n = _outliers_n(n, axis, nc, nt)
+    dims = out_shape(a.shape, win, n if axis == 0 else 1, n if axis == 2 else 1)
+    dts = (np.float32, np.float32, np.int32)
+    outs = [np.empty(dims, dtype=dt, order="F") if w else None for w, dt in zip(want, dts)]
+    m = np.empty((nc, ni, nt), dtype=np.uint8, order="F") if mask else None
+    res = {k: o for k, o in zip(OUTLIER_PLANES, outs) if o is not None}
+    if m is not None:
+        res["mask"] = m
+    if not res:
+        raise ValueError("outliers: no output asked for (which is empty and mask is False)")
+    keep, wp = _lib.win_arg(_full_win(win, a.shape))
+    hp = [o.ctypes.data if o is not None and o.size else None for o in outs + [m]]
+    rc = _lib.lib().bldp_outliers_host_f32(int(device), a.ctypes.data if a.size else None,
+                                           a.shape[0], a.shape[1], a.shape[2], wp, axis, n, ns, *hp)
+    _lib.check(rc, "bldp_outliers_host_f32")
+    return res
 
 
 def _argext_op(op) -> int:

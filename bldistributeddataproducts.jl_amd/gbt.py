@@ -112,6 +112,16 @@ def getmoments(workers, fnames, idxs=(COLON, COLON, COLON), tblock=None,
                    lambda w, f: W.getmoments(f, idxs, device=int(w), tblock=tblock, which=which))
 
 
+def getoutliers(workers, fnames, idxs=(COLON, COLON, COLON), *, n=None, axis=2, nsigma=5.0,
+                mask=False):
+    """getkurtosis' fan-out (src/gbt.jl:81-88) with the robust outlier flagging
+    of WorkerFunctions.getoutliers: per-bank dicts of the median, mad and count
+    planes (and the mask with ``mask=True``) from one read of every file."""
+    return _fanout(workers, fnames,
+                   lambda w, f: W.getoutliers(f, idxs, n=n, axis=axis, nsigma=nsigma, mask=mask,
+                                              device=int(w)))
+
+
 def _chan_window(idxs, nchans):
     """(start0, count, step) of the channel index (idxs[0]) over nchans."""
     from .idxs import JRange, is_colon, sanitizeidxs

@@ -14,7 +14,8 @@ using Statistics: mean, median, var, std
 export gpu_init, gpu_finalize, gpu_pin, gpu_unpin, gpu_fqav, gpu_reduce, gpu_kurtosis, gpu_band,
        gpu_tstat, gpu_argext, gpu_skewness, gpu_moments, gpu_comm_id, gpu_comm_init, gpu_comm_destroy, gpu_band_gather,
        mad, quantile, gpu_quantile, gpu_quantile_plan, gpu_band_quantile,
-       gpu_quantiles, gpu_quantiles_plan, gpu_band_quantiles
+       gpu_quantiles, gpu_quantiles_plan, gpu_band_quantiles,
+       gpu_outliers, gpu_outliers_plan, gpu_band_outliers
 
 const libbldp = get(ENV, "BLDP_LIB", joinpath(@__DIR__, "..", "libbldp_hip.so"))
 
@@ -601,6 +602,109 @@ function gpu_band_quantiles(banks::Vector{Ptr{Float32}}, dims::NTuple{3,Integer}
         (Cint, Ptr{Ptr{Float32}}, Int64, Int64, Int64, Ptr{Int64}, Cint, Int64, Cint,
          Ptr{Float64}, Ptr{Float32}, Ptr{Cvoid}),
         length(banks), banks, dims[1], dims[2], dims[3], win, axis, n, length(pv), pv, out,
+        stream))
+    nothing
+end
+
+# ---- outliers: bldp_outliers_* (median, mad, count and flags from one launch) ----
+function _checknsigma(nsigma)
+    (nsigma >= 0 && isfinite(nsigma)) ||
+        throw(ArgumentError("outliers: nsigma=$nsigma is not a finite number >= 0"))
+    Float64(nsigma)
+end
+
+function _outliers_shape(dims, win, axis, n)
+    shp = zeros(Int64, 3)
+    mshp = zeros(Int64, 3)
+    GC.@preserve win check(ccall((:bldp_outliers_shape, libbldp), Cint,
+        (Int64, Int64, Int64, Ptr{Int64}, Cint, Int64, Ptr{Int64}, Ptr{Int64}),
+        dims[1], dims[2], dims[3], win, axis, n, shp, mshp))
+    shp, mshp
+end
+
+"""
+    gpu_outliers(A::Array{Float32,3}, n; axis=2, nsigma=5.0, idxs=(:,:,:), mask=false, dev=0)
+        -> (median, mad, count[, mask])
+
+The median, the scaled mad (`mad(block; normalize=true)`), the count of outliers
+and, with `mask=true`, the outlier flags of every block of `n` selected channels
+(`axis = 0`) or `n` selected spectra (`axis = 2`) of the window, on GPU `dev`
+(bldp_outliers_host_f32): a sample is flagged when `abs(x - median) >
+Float32(nsigma * mad)`, strictly, and a block whose median or mad is NaN flags
+nothing.  `median` and `mad` are `Float32`, `count` is `UInt32`, each sized as
+`gpu_quantile`'s result; `mask` is the window's `UInt8` array."""
+function gpu_outliers(A::Array{Float32,3}, n::Integer; axis::Integer=2, nsigma::Real=5.0,
+                      idxs::Tuple=(:, :, :), mask::Bool=false, dev::Integer=0)
+    ns = _checknsigma(nsigma)
+    win = window(idxs, size(A))
+    shp, mshp = _outliers_shape(size(A), win, axis, n)
+    med = Array{Float32,3}(undef, shp[1], shp[2], shp[3])
+    sc = Array{Float32,3}(undef, shp[1], shp[2], shp[3])
+    cnt = Array{UInt32,3}(undef, shp[1], shp[2], shp[3])
+    msk = mask ? Array{UInt8,3}(undef, mshp[1], mshp[2], mshp[3]) : nothing
+    GC.@preserve A win med sc cnt msk check(ccall((:bldp_outliers_host_f32, libbldp), Cint,
+        (Cint, Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Cint, Int64, Float64, Ptr{Float32},
+         Ptr{Float32}, Ptr{UInt32}, Ptr{UInt8}),
+        dev, A, size(A, 1), size(A, 2), size(A, 3), win, axis, n, ns, med, sc, cnt,
+        mask ? pointer(msk) : Ptr{UInt8}(C_NULL)))
+    mask ? (med, sc, cnt, msk) : (med, sc, cnt)
+end
+
+"""
+    gpu_outliers(in::Ptr{Float32}, dims, n, med, mad, count, mask; axis=2, nsigma=5.0,
+                 win=C_NULL, out_ld=nothing, stream=C_NULL)
+
+The same on DEVICE memory (bldp_outliers_f32; asynchronous on `stream`, one
+launch): element (c, i, t) of `med`, `mad` and `count` at `[c + i*out_ld[1] +
+t*out_ld[2]]` (0-based; dense by default), `mask` the dense window.  Any of the
+four pointers may be `C_NULL`: that output is neither formed nor stored.
+Returns the dims of the planes and of the mask."""
+function gpu_outliers(in::Ptr{Float32}, dims::NTuple{3,Integer}, n::Integer, med::Ptr{Float32},
+                      mad::Ptr{Float32}, count::Ptr{UInt32}, mask::Ptr{UInt8};
+                      axis::Integer=2, nsigma::Real=5.0, win=Ptr{Int64}(C_NULL), out_ld=nothing,
+                      stream::Ptr{Cvoid}=C_NULL)
+    ns = _checknsigma(nsigma)
+    shp, mshp = _outliers_shape(dims, win, axis, n)
+    ld = out_ld === nothing ? (shp[1], shp[1] * shp[2]) : out_ld
+    GC.@preserve win check(ccall((:bldp_outliers_f32, libbldp), Cint,
+        (Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Cint, Int64, Float64, Ptr{Float32},
+         Ptr{Float32}, Ptr{UInt32}, Ptr{UInt8}, Int64, Int64, Ptr{Cvoid}),
+        in, dims[1], dims[2], dims[3], win, axis, n, ns, med, mad, count, mask, ld[1], ld[2],
+        stream))
+    (shp[1], shp[2], shp[3]), (mshp[1], mshp[2], mshp[3])
+end
+
+"""
+    gpu_outliers_plan(dims, n; axis=2, win=C_NULL, mask=false) -> Vector{Int64}
+
+The launch plan of that call (bldp_outliers_plan_f32; needs no GPU): mad's plan
+of the axis and shape in the first eight entries, then the count of reads of the
+block and whether a mask is written."""
+function gpu_outliers_plan(dims::NTuple{3,Integer}, n::Integer; axis::Integer=2,
+                           win=Ptr{Int64}(C_NULL), mask::Bool=false)
+    info = zeros(Int64, 10)
+    GC.@preserve win check(ccall((:bldp_outliers_plan_f32, libbldp), Cint,
+        (Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Cint, Int64, Cint, Ptr{Int64}),
+        C_NULL, dims[1], dims[2], dims[3], win, axis, n, mask ? 1 : 0, info))
+    info
+end
+
+"""
+    gpu_band_outliers(banks::Vector{Ptr{Float32}}, dims, n, med, mad, count, mask; axis=2,
+                      nsigma=5.0, win=C_NULL, stream=C_NULL)
+
+outliers of every bank of a band resident on one GPU, stitched in bank order in
+one launch (bldp_band_outliers_f32): `med`, `mad` and `count` hold the dense
+vcat of the banks' planes, `mask` the vcat of their windows."""
+function gpu_band_outliers(banks::Vector{Ptr{Float32}}, dims::NTuple{3,Integer}, n::Integer,
+                           med::Ptr{Float32}, mad::Ptr{Float32}, count::Ptr{UInt32},
+                           mask::Ptr{UInt8}; axis::Integer=2, nsigma::Real=5.0,
+                           win=Ptr{Int64}(C_NULL), stream::Ptr{Cvoid}=C_NULL)
+    ns = _checknsigma(nsigma)
+    GC.@preserve banks win check(ccall((:bldp_band_outliers_f32, libbldp), Cint,
+        (Cint, Ptr{Ptr{Float32}}, Int64, Int64, Int64, Ptr{Int64}, Cint, Int64, Float64,
+         Ptr{Float32}, Ptr{Float32}, Ptr{UInt32}, Ptr{UInt8}, Ptr{Cvoid}),
+        length(banks), banks, dims[1], dims[2], dims[3], win, axis, n, ns, med, mad, count, mask,
         stream))
     nothing
 end

@@ -839,6 +839,29 @@ def getmoments(fname, idxs=(COLON, COLON, COLON), device=0, tblock=None, which=e
         lambda m: engine.Moments(*[None if t is None else engine.fb_to_numpy(t) for t in m]))
 
 
+def getoutliers(src, idxs=(COLON, COLON, COLON), *, n=None, axis=2, nsigma=5.0, mask=False,
+                device=0):
+    """Robust outlier flagging of every block of ``n`` selected channels
+    (``axis=0``) or spectra (``axis=2``; ``n=None``: the whole selected time
+    range) from ONE read of the data: a dict with ``"median"`` and ``"mad"``
+    (Float32, what the ``"median"`` and ``"mad"`` statistics give bit for bit),
+    ``"count"`` (int32), the samples of each block with ``|x - median| >
+    Float32(nsigma * mad)`` (strictly; a NaN median or mad flags nothing), each
+    (nc/n, ni, nt) or (nc, ni, nt/n), and with ``mask=True`` ``"mask"``, the uint8
+    (nc, ni, nt) flags of the window (engine.outliers; the rule of include/bldp.h).
+    Files reach the GPU as getdata reads them (window_on_device) and a host array
+    is staged there, both returning host arrays; a device tensor stays on the
+    device.  Float32 data only: any other element type (host array, device
+    tensor, 8/16-bit SIGPROC file) is a TypeError."""
+    engine._outliers_args(axis, nsigma, ())  # (the ValueError before any file is touched)
+    kw = dict(n=n, axis=axis, nsigma=nsigma, mask=mask)
+    return _read_moment(
+        "getoutliers", "outliers", src, sanitizeidxs(idxs), device,
+        lambda x, win: engine.outliers(x, win=win, **kw),
+        lambda a, win: engine.outliers_host(a, win=win, device=device, **kw),
+        lambda r: {k: engine.fb_to_numpy(t) for k, t in r.items()})
+
+
 getinventory = readers.getinventory
 getfbheader = readers.getfbheader
 getfbh5header = readers.getfbh5header

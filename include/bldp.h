@@ -91,7 +91,8 @@ extern "C" {
  *    bldp_moments_* entry points; (additive, same version) BLDP_OP_MAD = 8
  *    wherever BLDP_OP_MEDIAN is taken (7 stays unassigned and invalid);
  *    (additive, same version) the bldp_quantile_* entry points;
- *    (additive, same version) the bldp_quantiles_* entry points */
+ *    (additive, same version) the bldp_quantiles_* entry points;
+ *    (additive, same version) the bldp_outliers_* entry points */
 #define BLDP_ABI_VERSION 5
 
 #if defined(BLDP_BUILD)
@@ -655,6 +656,71 @@ BLDP_API int bldp_band_quantiles_f32(int nbank, const float *const *in, int64_t 
 BLDP_API int bldp_quantiles_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
                                      int64_t ntime, const int64_t *win, int axis, int64_t n,
                                      int np, const double *p, float *out);
+
+/* outliers: the median, the mad, the count of outliers and the outlier flags of
+ * every block from ONE launch.  Blocks, windows and geometry are those of
+ * bldp_quantile_*: n selected channels (axis 0) or n selected spectra (axis 2),
+ * n >= 2.  Additive in ABI 5.  For a block x[0 .. n-1]:
+ *  1. c = median(x): BLDP_OP_MEDIAN's bits.
+ *  2. d_i = |x_i - c|, the difference rounded once to Float32.
+ *  3. s = Float32(Float64(median(d)) * 1.4826022185056018): BLDP_OP_MAD's bits.
+ *  4. thr = Float32(nsigma * Float64(s)): one Float64 product, rounded once.
+ *  5. Sample i is flagged when d_i > thr, a strict Float32 compare: d_i == thr
+ *     is not flagged, s == 0 flags exactly the samples that differ from the
+ *     median, thr == +Inf flags nothing (nor does the NaN of 0 * Inf).
+ *  6. A NaN c or s flags nothing (a block holding a NaN, Inf - Inf deviations).
+ *  7. count = the flagged samples of the block (uint32).
+ *  8. mask[i] = 1 for a flagged sample, else 0 (uint8, dense over the window).
+ * Only this two-sided test exists.
+ *
+ * The median's kernels of that axis and shape do it, as mad's two selections
+ * and then one compare per element.  Reads of the block (info[8]):
+ *   axis 0, n <= 4096 and axis 2, n <= 32 (the block's keys in registers): 1
+ *     without a mask, 2 with one (the mask pass reads the block again for the
+ *     positions);
+ *   axis 0, n > 4096: 9 (mad's 8 and the flag pass);
+ *   axis 2, n > 32: mad's 8 (odd n) or 10 (even n), and 1.
+ *
+ * nsigma negative, NaN or infinite, n < 2 or an axis other than 0 and 2 is
+ * BLDP_EINVAL; an n that does not divide the axis is BLDP_EDIM, a window
+ * outside the array BLDP_EBOUNDS; so are (BLDP_EINVAL) four null outputs of a
+ * non-empty result and outputs that overlap each other or the input; all
+ * before any launch.
+ *
+ * bldp_outliers_shape: dims = bldp_quantile_shape's, mask_dims = the window's
+ * {nc, ni, nt}; pure host.
+ * bldp_outliers_plan_f32: info[0..7] as mad's plan of that axis and shape
+ * reports it (axis 0: bldp_reduce_plan_f32 with BLDP_OP_MAD; axis 2:
+ * bldp_tstat_plan_f32), info[8] = the reads of the block, info[9] = 1 when a
+ * mask is written, else 0.  Launches nothing and needs no GPU (the pointer may
+ * be null).
+ * bldp_outliers_f32: device pointers, asynchronous on `stream`, one launch, no
+ * workspace.  Element (c', i, t') of med, mad and count at [c' + i*out_ld_i +
+ * t'*out_ld_t] (elements); mask is the dense (nc, ni, nt) window, element (c, i,
+ * t) at mask[c + nc*(i + ni*t)].  Any output may be NULL and is then neither
+ * formed nor stored.
+ * bldp_band_outliers_f32: one launch for nbank banks; med, mad and count are
+ * laid out as bldp_band_quantile_f32's product, mask is the vcat of the banks'
+ * windows, (nbank*nc, ni, nt).
+ * bldp_outliers_host_f32: host in, host dense outs (any may be NULL); the
+ * window's rows are staged on device `dev` once.  Synchronous. */
+BLDP_API int bldp_outliers_shape(int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win,
+                                 int axis, int64_t n, int64_t dims[3], int64_t mask_dims[3]);
+BLDP_API int bldp_outliers_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                                    const int64_t *win, int axis, int64_t n, int want_mask,
+                                    int64_t info[10]);
+BLDP_API int bldp_outliers_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                               const int64_t *win, int axis, int64_t n, double nsigma, float *med,
+                               float *mad, uint32_t *count, uint8_t *mask, int64_t out_ld_i,
+                               int64_t out_ld_t, void *stream);
+BLDP_API int bldp_band_outliers_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                                    int64_t ntime, const int64_t *win, int axis, int64_t n,
+                                    double nsigma, float *med, float *mad, uint32_t *count,
+                                    uint8_t *mask, void *stream);
+BLDP_API int bldp_outliers_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                    int64_t ntime, const int64_t *win, int axis, int64_t n,
+                                    double nsigma, float *med, float *mad, uint32_t *count,
+                                    uint8_t *mask);
 
 /* fqavfunc argmax / argmin (fqav(A, n; f=argmax), the position half of Julia's
  * findmax / findmin): where in each block of the reduce the extreme lies.  For
