@@ -107,6 +107,10 @@ ARG_OPS = {"argmax": 0, "argmin": 1}
 # blocks of F <= 1024 over the lanes of a wave streaming the T rows, the same
 # with the rows split over the time slices of a workgroup, F > 1024 a workgroup
 ARGEXT_PATHS = {0: "lanes", 1: "lanes_tsplit", 2: "block"}
+# masked reduce (csrc/masked.hip): argext's paths, and how the flags are loaded:
+# a byte per element, one aligned dword per float4, one byte per row (stride 0
+# along the channels)
+MASK_LOADS = {0: "byte", 1: "dword", 2: "row"}
 
 BLDP_OK, BLDP_EINVAL, BLDP_EDIM, BLDP_EHIP, BLDP_ENOMEM, BLDP_EBOUNDS = 0, -1, -2, -3, -5, -6
 BLDP_ECOMM, BLDP_EIO = -7, -8
@@ -214,6 +218,10 @@ SIGNATURES = {
     "bldp_argext_f32": ([P, I64, I64, I64, P, I64, I64, I, P, P, I64, I64, P], I),
     "bldp_band_argext_f32": ([I, P, I64, I64, I64, P, I64, I64, I, P, P, P], I),
     "bldp_argext_host_f32": ([I, P, I64, I64, I64, P, I64, I64, I, P, P], I),
+    "bldp_masked_reduce_plan_f32": ([P, I64, I64, I64, P, I64, I64, P, P, P], I),
+    "bldp_masked_reduce_f32": ([P, I64, I64, I64, P, I64, I64, I, P, P, P, P, I64, I64, P], I),
+    "bldp_band_masked_reduce_f32": ([I, P, I64, I64, I64, P, I64, I64, I, P, P, P, P, P], I),
+    "bldp_masked_reduce_host_f32": ([I, P, I64, I64, I64, P, I64, I64, I, P, P, P, P], I),
     "bldp_fqav_range": ([D, D, I64, I64, P, P, P], I),
     "bldp_synth_f32": ([P, I64, I64, I64, I64, U64, I, P], I),
     "bldp_reduce_out_dtype": ([I, I], I),

@@ -1911,6 +1911,170 @@ int bldp_band_argext_f32(int nbank, const float *const *in, int64_t nchan, int64
                     nbank * d[0], nbank * d[0] * d[1], stream);
 }
 
+// ---- masked reduce: the sum / mean of a block's unflagged samples and their count ----
+// Checks, window and plan of a masked reduce (every entry point).  The outputs'
+// element (c', i, t') of bank b sits at [b*out_bank + c' + i*out_ld_i + t'*out_ld_t];
+// bank b's channel c is channel b*nc + c of the mask.  mask_ld NULL: the dense
+// (nbank*nc, ni, nt) mask.  query: the plan call (null pointers count as aligned).
+static int masked_prepare(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                          int64_t ntime, const int64_t *win, int64_t fqavby, int64_t tavby,
+                          int op, const uint8_t *mask, const int64_t *mask_ld, float *out,
+                          uint32_t *kept, int64_t out_bank, int64_t out_ld_i, int64_t out_ld_t,
+                          bool query, MaskedArgs *ap, Plan *pp, bool *empty) {
+  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
+    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
+  if (op != BLDP_OP_SUM && op != BLDP_OP_MEAN)
+    return fail(BLDP_EINVAL, "masked reduce: op %d is not sum (%d) or mean (%d)", op, BLDP_OP_SUM,
+                BLDP_OP_MEAN);
+  Geo g;
+  int rc = resolve_window(nchan, nif, ntime, win, &g);
+  if (rc) return rc;
+  int64_t F, T;
+  rc = resolve_factors(g, fqavby, tavby, &F, &T);
+  if (rc) return rc;
+  // kept is 31-bit (Python and the shim read Int32)
+  if (F > INT32_MAX / T)
+    return fail(BLDP_EINVAL, "masked reduce: blocks of fqavby x tavby = %lld x %lld elements are "
+                "beyond 2^31 - 1", (long long)F, (long long)T);
+  int64_t ld[3] = {1, nbank * g.nc, nbank * g.nc * g.ni};
+  if (mask_ld)
+    for (int ax = 0; ax < 3; ++ax) {
+      ld[ax] = mask_ld[ax];
+      if (ld[ax] < 0)
+        return fail(BLDP_EINVAL, "masked reduce: mask stride %d is negative (%lld)", ax,
+                    (long long)ld[ax]);
+    }
+  MaskedArgs &ma = *ap;
+  ma = MaskedArgs{};
+  RedArgs &a = ma.r;
+  a.nco = g.nc / F;
+  a.ni = g.ni;
+  a.nto = g.nt / T;
+  a.F = F;
+  a.T = T;
+  a.nbank = nbank;
+  a.out_bank = out_bank;
+  a.out_ld_i = out_ld_i;
+  a.out_ld_t = out_ld_t;
+  a.in_off = g.off;
+  a.in_cs = g.cs;
+  a.in_ld_i = g.ld_i;
+  a.in_ld_t = g.ld_t;
+  a.out = out;
+  ma.kept = kept;
+  ma.mask = mask;
+  ma.m_cs = ld[0], ma.m_ld_i = ld[1], ma.m_ld_t = ld[2];
+  ma.m_bank = g.nc * ld[0];
+  ma.mean = op == BLDP_OP_MEAN;
+  *empty = a.nco == 0 || a.ni == 0 || a.nto == 0;
+  if (!in) return fail(BLDP_EINVAL, "masked reduce: null input pointer array");
+  bool words = true;
+  for (int b = 0; b < nbank; ++b) {
+    a.in[b] = in[b];
+    words = words && aligned4(in[b]);
+  }
+  rc = plan_masked(ma, words && g.cs == 1, aligned4(mask), num_cus_current(), xcd_log2_current(),
+                   pp);
+  if (rc) return rc;
+  if (query || *empty) return BLDP_OK;
+  for (int b = 0; b < nbank; ++b)
+    if (!in[b]) return fail(BLDP_EINVAL, "masked reduce: null input pointer (bank %d)", b);
+  if (!out && !kept) return fail(BLDP_EINVAL, "masked reduce: out and kept are both null");
+  if (!mask) return fail(BLDP_EINVAL, "masked reduce: null mask pointer");
+  if (out_ld_i < a.nco || out_ld_t < (a.ni - 1) * out_ld_i + a.nco ||
+      (nbank > 1 && out_bank < a.nco))
+    return fail(BLDP_EINVAL,
+                "masked reduce: out strides (%lld, %lld) overlap for a (%lld, %lld, %lld) result",
+                (long long)out_ld_i, (long long)out_ld_t, (long long)a.nco, (long long)a.ni,
+                (long long)a.nto);
+  // the outputs may not overlap the window's elements, the mask's span, nor each other
+  int64_t lo = g.off, hi = g.off;  // lowest and highest element offset of the window
+  const int64_t span[3] = {(g.nc - 1) * g.cs, (g.ni - 1) * g.ld_i, (g.nt - 1) * g.ld_t};
+  for (int ax = 0; ax < 3; ++ax) (span[ax] < 0 ? lo : hi) += span[ax];
+  const int64_t last = (nbank - 1) * out_bank + (a.nco - 1) + (a.ni - 1) * out_ld_i +
+                       (a.nto - 1) * out_ld_t;  // of an output
+  const size_t obytes = 4 * (size_t)(last + 1), wbytes = 4 * (size_t)(hi - lo + 1);
+  const size_t mbytes =
+      (size_t)((nbank * g.nc - 1) * ld[0] + (g.ni - 1) * ld[1] + (g.nt - 1) * ld[2] + 1);
+  const void *optr[2] = {out, kept};
+  static const char *const name[2] = {"out", "kept"};
+  for (int q = 0; q < 2; ++q) {
+    if (!optr[q]) continue;
+    for (int b = 0; b < nbank; ++b)
+      if (spans_overlap(optr[q], obytes, in[b] + lo, wbytes))
+        return fail(BLDP_EINVAL, "masked reduce: %s overlaps the input window (bank %d)", name[q],
+                    b);
+    if (spans_overlap(optr[q], obytes, mask, mbytes))
+      return fail(BLDP_EINVAL, "masked reduce: %s overlaps the mask", name[q]);
+  }
+  if (out && kept && spans_overlap(out, obytes, kept, obytes))
+    return fail(BLDP_EINVAL, "masked reduce: out and kept overlap");
+  return BLDP_OK;
+}
+
+static int masked_run(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                      int64_t ntime, const int64_t *win, int64_t fqavby, int64_t tavby, int op,
+                      const uint8_t *mask, const int64_t *mask_ld, float *out, uint32_t *kept,
+                      int64_t out_bank, int64_t out_ld_i, int64_t out_ld_t, void *stream) {
+  MaskedArgs a;
+  Plan p;
+  bool empty = false;
+  int rc = masked_prepare(nbank, in, nchan, nif, ntime, win, fqavby, tavby, op, mask, mask_ld, out,
+                          kept, out_bank, out_ld_i, out_ld_t, false, &a, &p, &empty);
+  if (rc || empty) return rc;
+  hipError_t e = launch_masked(a, p, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(BLDP_EHIP, "masked reduce launch: %s", hipGetErrorString(e));
+  return BLDP_OK;
+}
+
+int bldp_masked_reduce_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                                const int64_t *win, int64_t fqavby, int64_t tavby,
+                                const uint8_t *mask, const int64_t *mask_ld, int64_t info[10]) {
+  if (!info) return fail(BLDP_EINVAL, "null info");
+  MaskedArgs a;
+  Plan p;
+  bool empty = false;
+  const float *ins[1] = {in};
+  int rc = masked_prepare(1, ins, nchan, nif, ntime, win, fqavby, tavby, BLDP_OP_SUM, mask,
+                          mask_ld, nullptr, nullptr, 0, 0, 0, true, &a, &p, &empty);
+  if (rc) return rc;
+  info[0] = p.path;
+  info[1] = p.lpg;
+  info[2] = a.r.ts;
+  info[3] = a.r.k4;
+  info[4] = p.grid;
+  info[5] = (int64_t)p.ws_bytes;
+  info[6] = p.nout;
+  info[7] = a.r.k4 != 0;
+  info[8] = a.mform;
+  info[9] = 0;
+  return BLDP_OK;
+}
+
+int bldp_masked_reduce_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                           const int64_t *win, int64_t fqavby, int64_t tavby, int op,
+                           const uint8_t *mask, const int64_t *mask_ld, float *out,
+                           uint32_t *kept, int64_t out_ld_i, int64_t out_ld_t, void *stream) {
+  const float *ins[1] = {in};
+  return masked_run(1, ins, nchan, nif, ntime, win, fqavby, tavby, op, mask, mask_ld, out, kept,
+                    0, out_ld_i, out_ld_t, stream);
+}
+
+int bldp_band_masked_reduce_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                                int64_t ntime, const int64_t *win, int64_t fqavby,
+                                int64_t tavby, int op, const uint8_t *mask,
+                                const int64_t *mask_ld, float *out, uint32_t *kept,
+                                void *stream) {
+  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
+    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
+  int64_t d[3];
+  int rc = bldp_reduce_shape(nchan, nif, ntime, win, fqavby, tavby, d);
+  if (rc) return rc;
+  // the vcat of the banks: bank k's channels at k*nco of every (IF, time) row
+  return masked_run(nbank, in, nchan, nif, ntime, win, fqavby, tavby, op, mask, mask_ld, out,
+                    kept, d[0], nbank * d[0], nbank * d[0] * d[1], stream);
+}
+
 int bldp_reduce_out_dtype(int dtype, int op) {
   const int d = typed_out_dtype(dtype, op);
   if (d < 0) return fail(BLDP_EINVAL, "unknown element type %d or op %d", dtype, op);

@@ -311,6 +311,29 @@ enum ArgExtPath { ARGEXT_LANES = 0, ARGEXT_LANES_TSPLIT = 1, ARGEXT_BLOCK = 2 };
 int plan_argext(ArgArgs &a, bool words, int num_cus, int xcd_lg, Plan *p);
 hipError_t launch_argext(const ArgArgs &a, const Plan &p, hipStream_t s);
 
+// Masked reduce of every F x T block (masked.hip): the sum or mean of the
+// samples whose flag is 0 and their count.  r is the reduce's geometry (r.out:
+// the sum / mean output or null), filled by plan_argext: the walk is argext's.
+// Flag (c, i, t) of bank b's selected window at
+//   mask[b*m_bank + c*m_cs + i*m_ld_i + t*m_ld_t]  (bytes; a stride of 0 broadcasts).
+// A by-value kernel argument of the masked kernels alone (RedArgs and ArgArgs
+// stay as they are).
+struct MaskedArgs {
+  RedArgs r;
+  uint32_t *kept;  // output (c', i, t') of bank b at kept[b*out_bank + c' + i*out_ld_i + t'*out_ld_t], or null
+  const uint8_t *mask;
+  int64_t m_cs, m_ld_i, m_ld_t, m_bank;
+  int32_t mform;   // MaskForm (plan_masked)
+  int32_t mean;    // 1: the sum divided once by Float32(kept)
+};
+// How the flags are loaded: a byte per element at the strided address, one
+// aligned dword for the four flags of a float4, one byte per row (m_cs == 0).
+enum MaskForm { MASK_BYTE = 0, MASK_DWORD = 1, MASK_ROW = 2 };
+// plan_argext's plan (paths ArgExtPath) plus the mask form; `mask_words`: the
+// mask pointer is 4-byte aligned.  Filled without a GPU.
+int plan_masked(MaskedArgs &a, bool words, bool mask_words, int num_cus, int xcd_lg, Plan *p);
+hipError_t launch_masked(const MaskedArgs &a, const Plan &p, hipStream_t s);
+
 // median / var / std of every block of T selected spectra of every (channel,
 // IF) column (tstats.hip): tavfunc, fqav's rule on the time axis.  Window
 // element (c, i, t) of bank k at in[k][in_off + c*in_cs + i*in_ld_i +

@@ -516,6 +516,62 @@ extern "C" int bldp_argext_host_f32(int dev, const float *in, int64_t nchan, int
   });
 }
 
+// The same staging for the masked reduce: the window's rows and the mask's span
+// (the bytes its strides reach, from the pointer on) go to the device once; the
+// dense (nco, ni, nto) outputs that the caller asked for come back.
+extern "C" int bldp_masked_reduce_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                           int64_t ntime, const int64_t *win, int64_t fqavby,
+                                           int64_t tavby, int op, const uint8_t *mask,
+                                           const int64_t *mask_ld, float *out, uint32_t *kept) {
+  // (every argument check, before any staging)
+  int64_t info[10];
+  int rc = bldp_masked_reduce_plan_f32(nullptr, nchan, nif, ntime, win, fqavby, tavby, nullptr,
+                                       mask_ld, info);
+  if (rc) return rc;
+  if (op != BLDP_OP_SUM && op != BLDP_OP_MEAN)
+    return bldp::set_error(BLDP_EINVAL, "masked reduce: op %d is not sum (%d) or mean (%d)", op,
+                           BLDP_OP_SUM, BLDP_OP_MEAN);
+  int64_t sh[3];
+  rc = bldp_reduce_shape(nchan, nif, ntime, win, fqavby, tavby, sh);
+  if (rc) return rc;
+  const int64_t nco = sh[0], ni = sh[1], nto = sh[2], nout = nco * ni * nto;
+  if (nout == 0) return BLDP_OK;
+  if (!in) return bldp::set_error(BLDP_EINVAL, "masked reduce: null input pointer");
+  if (!out && !kept)
+    return bldp::set_error(BLDP_EINVAL, "masked reduce: out and kept are both null");
+  if (!mask) return bldp::set_error(BLDP_EINVAL, "masked reduce: null mask pointer");
+  const int64_t F = fqavby <= 1 ? 1 : fqavby, T = tavby <= 1 ? 1 : tavby;
+  const int64_t nc = nco * F, nt = nto * T;
+  const int64_t ld[3] = {mask_ld ? mask_ld[0] : 1, mask_ld ? mask_ld[1] : nc,
+                         mask_ld ? mask_ld[2] : nc * ni};
+  const size_t mb = (size_t)((nc - 1) * ld[0] + (ni - 1) * ld[1] + (nt - 1) * ld[2] + 1);
+  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
+  return with_stager(dev, [&](bldp::Stager *sg) -> int {
+    float *dbuf, *dout = nullptr;
+    uint8_t *dmask;
+    uint32_t *dkept = nullptr;
+    int r = bldp::stager_buffer(sg, 0, (size_t)(h.span * ni * nt) * 4, (void **)&dbuf);
+    if (!r) r = bldp::stager_buffer(sg, 1, mb, (void **)&dmask);
+    if (!r && out) r = bldp::stager_buffer(sg, 2, (size_t)nout * sizeof(float), (void **)&dout);
+    if (!r && kept)
+      r = bldp::stager_buffer(sg, 3, (size_t)nout * sizeof(uint32_t), (void **)&dkept);
+    if (!r) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
+    if (r) return r;
+    HCHK(hipMemcpyAsync(dmask, mask, mb, hipMemcpyHostToDevice, sg->st[0]));
+    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
+    r = bldp_masked_reduce_f32(dbuf, h.span, ni, nt, dwin, fqavby, tavby, op, dmask, ld, dout,
+                               dkept, nco, nco * ni, sg->st[0]);
+    if (r) return r;
+    if (out)
+      HCHK(hipMemcpyAsync(out, dout, (size_t)nout * sizeof(float), hipMemcpyDeviceToHost,
+                          sg->st[0]));
+    if (kept)
+      HCHK(hipMemcpyAsync(kept, dkept, (size_t)nout * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                          sg->st[0]));
+    return BLDP_OK;
+  });
+}
+
 // ---------------------------------------------------------------------------
 // Host forms of the typed entry points (include/bldp.h), staged like the
 // Float32 forms above: only the window's rows (its channel span of every

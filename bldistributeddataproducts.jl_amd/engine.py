@@ -1297,6 +1297,167 @@ def argext_host(a: np.ndarray, fqavby, tavby, op, win=None, values=False, device
     return (idx, val) if values else idx
 
 
+MASKED_OPS = ("sum", "mean")
+
+
+def _masked_op(op) -> int:
+    if op not in MASKED_OPS:
+        raise _lib.ArgumentError(_lib.BLDP_EINVAL,
+                                 f"masked reduce takes {MASKED_OPS}, not {op!r}")
+    return _lib.OPS[op]
+
+
+def _mask_strides(shape, strides, wshape, what):
+    """mask_ld of a 3-D mask over a ``wshape`` window: an axis of length 1 is a
+    broadcast (stride 0); any other length must be the window's (ValueError)."""
+    if len(shape) != 3:
+        raise ValueError(f"{what}: the mask is {len(shape)}-D, expected the 3-D window "
+                         f"{tuple(wshape)} (an axis may be 1: a broadcast)")
+    ld = []
+    for ax in range(3):
+        if shape[ax] == 1:
+            ld.append(0)
+        elif shape[ax] == wshape[ax]:
+            ld.append(int(strides[ax]))
+        else:
+            raise ValueError(f"{what}: mask shape {tuple(shape)} does not broadcast to the window "
+                             f"{tuple(wshape)}")
+    return ld
+
+
+def _mask_arg(mask, wshape, device, what):
+    """(pointer, mask_ld array) of a device mask, checked before any GPU work:
+    a uint8 or bool tensor (TypeError) that broadcasts to ``wshape`` (ValueError).
+    A strided view passes its strides."""
+    torch = _torch()
+    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.bool):
+        raise TypeError(f"{what}: the mask must be a uint8 or bool device tensor, not "
+                        f"{getattr(mask, 'dtype', type(mask).__name__)}")
+    ld = _mask_strides(tuple(mask.shape), mask.stride(), wshape, what)
+    if not mask.is_cuda:
+        raise TypeError(f"{what}: the mask must be a device tensor (masked_reduce_host takes "
+                        f"host arrays)")
+    if mask.device != torch.device(device):
+        raise ValueError(f"{what}: the mask is on {mask.device}, the data on {device}")
+    return (mask.data_ptr() if mask.numel() else None), (ctypes.c_int64 * 3)(*ld)
+
+
+def masked_reduce(x, mask, fqavby=1, tavby=1, op="sum", win=None, stream=None):
+    """``"sum"`` or ``"mean"`` of the unflagged samples of every fqavby x tavby
+    block of the window, and how many there were, from one read of the window and
+    one of the mask (bldp_masked_reduce_f32; the rule of include/bldp.h).  x: a
+    Float32 device filterbank tensor; ``mask``: a uint8 or bool device tensor of
+    the window's shape (nc, ni, nt), any axis of which may be 1 (a broadcast: a
+    bad-channel list is (nc, 1, 1)); a byte of 0 keeps the sample, any other
+    value drops it.  ``engine.outliers(..., mask=True)["mask"]`` goes in as it
+    is; a strided view passes its strides.  Returns a dict of Julia-order
+    (nc/F, ni, nt/T) device tensors: ``"data"`` (Float32; 0.0 for the sum and NaN
+    for the mean of a block with nothing kept) and ``"kept"`` (int32), the weight
+    of each product."""
+    torch = _torch()
+    code = _masked_op(op)
+    if x.dtype != torch.float32:
+        _need_f32("masked_reduce", x.dtype, "masked_reduce")
+    shape = tuple(x.shape)
+    _check_bounds(win, shape)
+    wshape = window_shape(win, shape)
+    mptr, ld = _mask_arg(mask, wshape, x.device, "masked_reduce")
+    dims = out_shape(shape, win, fqavby, tavby)
+    ptr, nchan, nif, ntime = _abi_dims(x)
+    data = fb_empty(*dims, device=x.device)
+    kept = fb_empty(*dims, device=x.device, dtype=torch.int32)
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    rc = _lib.lib().bldp_masked_reduce_f32(ptr, nchan, nif, ntime, wp, int(fqavby), int(tavby),
+                                           code, mptr, ld, _ptr(data), _ptr(kept), dims[0],
+                                           dims[0] * dims[1], _lib.stream_ptr(stream))
+    _lib.check(rc, "bldp_masked_reduce_f32")
+    return {"data": data, "kept": kept}
+
+
+def masked_reduce_plan(x, mask, fqavby=1, tavby=1, win=None) -> dict:
+    """Launch plan of ``masked_reduce(x, mask, fqavby, tavby, win=win)``
+    (bldp_masked_reduce_plan_f32): the keys of ``argext_plan`` (the walk is
+    argext's) and ``mask_loads``, how the flags are read (_lib.MASK_LOADS:
+    "byte" per element, one "dword" per float4, one byte per "row")."""
+    shape = tuple(x.shape)
+    _check_bounds(win, shape)
+    wshape = window_shape(win, shape)
+    mptr, ld = _mask_arg(mask, wshape, x.device, "masked_reduce_plan")
+    ptr, nchan, nif, ntime = _abi_dims(x)
+    info = (ctypes.c_int64 * 10)()
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    _lib.check(_lib.lib().bldp_masked_reduce_plan_f32(ptr, nchan, nif, ntime, wp, int(fqavby),
+                                                      int(tavby), mptr, ld, info),
+               "bldp_masked_reduce_plan_f32")
+    keys = ["path", "lanes_per_block", "time_slices", "float4_per_lane", "workgroups",
+            "workspace_bytes", "outputs", "vector_loads", "mask_loads"]
+    d = dict(zip(keys, [int(v) for v in info]))
+    d["path"] = _lib.ARGEXT_PATHS[d["path"]]
+    d["mask_loads"] = _lib.MASK_LOADS[d["mask_loads"]]
+    return d
+
+
+def band_masked_reduce(banks, mask, fqavby=1, tavby=1, op="sum", win=None, stream=None):
+    """``masked_reduce`` of every bank of a band resident on ONE GPU in one
+    launch (bldp_band_masked_reduce_f32): the dict of ``masked_reduce`` with dense
+    (nbank*nco, ni, nto) tensors, the vcat of the per-bank results.  ``mask``
+    covers the stitched window, (nbank*nc, ni, nt) with any axis allowed to be 1:
+    bank b's channel c is its channel b*nc + c (``band_outliers``' mask as it
+    is)."""
+    torch = _torch()
+    code = _masked_op(op)
+    banks = list(banks)
+    if not banks:
+        raise ValueError("no banks")
+    for b in banks:
+        if b.dtype != torch.float32:
+            _need_f32("band_masked_reduce", b.dtype, "masked_reduce")
+    shape = tuple(banks[0].shape)
+    _check_bounds(win, shape)
+    nc, ni, nt = window_shape(win, shape)
+    nb = len(banks)
+    mptr, ld = _mask_arg(mask, (nb * nc, ni, nt), banks[0].device, "band_masked_reduce")
+    banks, geo, data, ptrs, (keep, wp) = _band_args(banks, fqavby, tavby, win, None)
+    kept = fb_empty(*data.shape, device=data.device, dtype=torch.int32)
+    rc = _lib.lib().bldp_band_masked_reduce_f32(nb, ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp,
+                                                int(fqavby), int(tavby), code, mptr, ld,
+                                                _ptr(data), _ptr(kept), _lib.stream_ptr(stream))
+    _lib.check(rc, "bldp_band_masked_reduce_f32")
+    return {"data": data, "kept": kept}
+
+
+def masked_reduce_host(a: np.ndarray, mask: np.ndarray, fqavby=1, tavby=1, op="sum", win=None,
+                       device=0) -> dict:
+    """Host Fortran-ordered Float32 array and host uint8 / bool mask in (the
+    window's shape, any axis allowed to be 1), the dict of ``masked_reduce`` as
+    Fortran-ordered host arrays out (bldp_masked_reduce_host_f32: the window's
+    rows and the mask staged on ``device`` once)."""
+    code = _masked_op(op)
+    a = np.asarray(a)
+    if a.dtype != np.float32:
+        _need_f32("masked_reduce_host", a.dtype, "masked_reduce")
+    if not a.flags.f_contiguous or a.ndim != 3:
+        raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
+    m = np.asarray(mask)
+    if m.dtype not in (np.dtype(np.uint8), np.dtype(np.bool_)):
+        raise TypeError(f"masked_reduce_host: the mask must be a uint8 or bool array, not {m.dtype}")
+    _check_bounds(win, a.shape)
+    wshape = window_shape(win, a.shape)
+    if m.ndim == 3 and any(s < 0 for s in m.strides):
+        m = np.asfortranarray(m)
+    ld = (ctypes.c_int64 * 3)(*_mask_strides(m.shape, m.strides, wshape, "masked_reduce_host"))
+    dims = out_shape(a.shape, win, fqavby, tavby)
+    data = np.empty(dims, dtype=np.float32, order="F")
+    kept = np.empty(dims, dtype=np.uint32, order="F")
+    keep, wp = _lib.win_arg(_full_win(win, a.shape))
+    rc = _lib.lib().bldp_masked_reduce_host_f32(
+        int(device), a.ctypes.data if a.size else None, a.shape[0], a.shape[1], a.shape[2], wp,
+        int(fqavby), int(tavby), code, m.ctypes.data if m.size else None, ld,
+        data.ctypes.data if data.size else None, kept.ctypes.data if kept.size else None)
+    _lib.check(rc, "bldp_masked_reduce_host_f32")
+    return {"data": data, "kept": kept.view(np.int32)}  # counts are < 2^31
+
+
 def stitch(gathered, nbank, out=None, stream=None):
     """gathered: nbank dense (nc, ni, nt) blocks back to back (1-D or a
     [nbank, nt, ni, nc] contiguous tensor); returns vcat (nbank*nc, ni, nt)."""

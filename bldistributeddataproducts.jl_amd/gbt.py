@@ -122,6 +122,17 @@ def getoutliers(workers, fnames, idxs=(COLON, COLON, COLON), *, n=None, axis=2, 
                                               device=int(w)))
 
 
+def getclean(workers, fnames, idxs=(COLON, COLON, COLON), *, fqavby=1, tavby=1, n=None, axis=2,
+             nsigma=5.0, func="sum"):
+    """getkurtosis' fan-out (src/gbt.jl:81-88) with the flag-and-integrate of
+    WorkerFunctions.getclean: per-bank dicts of the product over the unflagged
+    samples (``"data"``), its weights (``"kept"``) and the per-block flag counts
+    (``"count"``) from one read of every file."""
+    return _fanout(workers, fnames,
+                   lambda w, f: W.getclean(f, idxs, fqavby=fqavby, tavby=tavby, n=n, axis=axis,
+                                           nsigma=nsigma, func=func, device=int(w)))
+
+
 def _chan_window(idxs, nchans):
     """(start0, count, step) of the channel index (idxs[0]) over nchans."""
     from .idxs import JRange, is_colon, sanitizeidxs

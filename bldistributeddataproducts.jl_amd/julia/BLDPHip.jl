@@ -15,7 +15,8 @@ export gpu_init, gpu_finalize, gpu_pin, gpu_unpin, gpu_fqav, gpu_reduce, gpu_kur
        gpu_tstat, gpu_argext, gpu_skewness, gpu_moments, gpu_comm_id, gpu_comm_init, gpu_comm_destroy, gpu_band_gather,
        mad, quantile, gpu_quantile, gpu_quantile_plan, gpu_band_quantile,
        gpu_quantiles, gpu_quantiles_plan, gpu_band_quantiles,
-       gpu_outliers, gpu_outliers_plan, gpu_band_outliers
+       gpu_outliers, gpu_outliers_plan, gpu_band_outliers,
+       gpu_masked_reduce, gpu_band_masked_reduce
 
 const libbldp = get(ENV, "BLDP_LIB", joinpath(@__DIR__, "..", "libbldp_hip.so"))
 
@@ -706,6 +707,95 @@ function gpu_band_outliers(banks::Vector{Ptr{Float32}}, dims::NTuple{3,Integer},
          Ptr{Float32}, Ptr{Float32}, Ptr{UInt32}, Ptr{UInt8}, Ptr{Cvoid}),
         length(banks), banks, dims[1], dims[2], dims[3], win, axis, n, ns, med, mad, count, mask,
         stream))
+    nothing
+end
+
+# ---- masked reduce: bldp_*masked_reduce_* (a window over its unflagged samples) ----
+_maskedop(f) = f === sum ? Cint(0) : f === mean ? Cint(1) :
+               throw(ArgumentError("masked reduce takes sum or mean, not $f"))
+# mask_ld of a UInt8 array over a window of size wsz: an axis of length 1 is a
+# broadcast (stride 0)
+function _mask_ld(msk::Array{UInt8,3}, wsz)
+    all(size(msk, a) == 1 || size(msk, a) == wsz[a] for a in 1:3) ||
+        throw(DimensionMismatch("mask $(size(msk)) does not broadcast to the window $wsz"))
+    Int64[size(msk, a) == 1 ? 0 : stride(msk, a) for a in 1:3]
+end
+
+"""
+    gpu_masked_reduce(A::Array{Float32,3}, msk::Array{UInt8,3}, fqavby=1, tavby=1; f=sum,
+                      idxs=(:,:,:), dev=0) -> (data, kept)
+
+`f` (`sum` or `mean`) of the samples of every `fqavby` x `tavby` block of
+`A[idxs...]` whose byte of `msk` is 0, and how many there were, on GPU `dev`
+(bldp_masked_reduce_host_f32).  `msk` has the window's size, any axis of which
+may be 1 (a broadcast: a bad-channel list is `(nc, 1, 1)`); `gpu_outliers`' mask
+goes in as it is.  A flagged `NaN` or `Inf` leaves the result finite; a block
+with nothing kept gives `0.0f0` (`sum`) or `NaN32` (`mean`).  `data` is `Float32`,
+`kept` `Int32`: the weight of each product."""
+function gpu_masked_reduce(A::Array{Float32,3}, msk::Array{UInt8,3}, fqavby::Integer=1,
+                           tavby::Integer=1; f=sum, idxs::Tuple=(:, :, :), dev::Integer=0)
+    op = _maskedop(f)
+    win = window(idxs, size(A))
+    shp = zeros(Int64, 3)
+    GC.@preserve win check(ccall((:bldp_reduce_shape, libbldp), Cint,
+        (Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Ptr{Int64}),
+        size(A, 1), size(A, 2), size(A, 3), win, fqavby, tavby, shp))
+    ld = _mask_ld(msk, (shp[1] * max(fqavby, 1), shp[2], shp[3] * max(tavby, 1)))
+    data = Array{Float32,3}(undef, shp...)
+    kept = Array{UInt32,3}(undef, shp...)
+    GC.@preserve A msk win ld data kept check(ccall((:bldp_masked_reduce_host_f32, libbldp), Cint,
+        (Cint, Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Cint, Ptr{UInt8},
+         Ptr{Int64}, Ptr{Float32}, Ptr{UInt32}),
+        dev, A, size(A, 1), size(A, 2), size(A, 3), win, fqavby, tavby, op, msk, ld, data, kept))
+    data, Int32.(kept)   # counts are < 2^31
+end
+
+"""
+    gpu_masked_reduce(in::Ptr{Float32}, dims, mask::Ptr{UInt8}, out, kept, fqavby=1, tavby=1;
+                      f=sum, win=C_NULL, mask_ld=C_NULL, out_ld=nothing, stream=C_NULL)
+
+The same on DEVICE memory (bldp_masked_reduce_f32; asynchronous on `stream`, one
+launch): flag (c, i, t) of the window at `mask[c*mask_ld[1] + i*mask_ld[2] +
+t*mask_ld[3]]` (0-based c, i, t; `C_NULL`: dense), element (c, i, t) of `out` and
+`kept` at `[c + i*out_ld[1] + t*out_ld[2]]` (dense by default).  `out` or `kept`
+may be `C_NULL`, not both.  Returns the dims of the outputs."""
+function gpu_masked_reduce(in::Ptr{Float32}, dims::NTuple{3,Integer}, mask::Ptr{UInt8},
+                           out::Ptr{Float32}, kept::Ptr{UInt32}, fqavby::Integer=1,
+                           tavby::Integer=1; f=sum, win=Ptr{Int64}(C_NULL),
+                           mask_ld=Ptr{Int64}(C_NULL), out_ld=nothing, stream::Ptr{Cvoid}=C_NULL)
+    op = _maskedop(f)
+    shp = zeros(Int64, 3)
+    GC.@preserve win check(ccall((:bldp_reduce_shape, libbldp), Cint,
+        (Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Ptr{Int64}),
+        dims[1], dims[2], dims[3], win, fqavby, tavby, shp))
+    ld = out_ld === nothing ? (shp[1], shp[1] * shp[2]) : out_ld
+    GC.@preserve win mask_ld check(ccall((:bldp_masked_reduce_f32, libbldp), Cint,
+        (Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Cint, Ptr{UInt8},
+         Ptr{Int64}, Ptr{Float32}, Ptr{UInt32}, Int64, Int64, Ptr{Cvoid}),
+        in, dims[1], dims[2], dims[3], win, fqavby, tavby, op, mask, mask_ld, out, kept, ld[1],
+        ld[2], stream))
+    (shp[1], shp[2], shp[3])
+end
+
+"""
+    gpu_band_masked_reduce(banks::Vector{Ptr{Float32}}, dims, mask, out, kept, fqavby=1,
+                           tavby=1; f=sum, win=C_NULL, mask_ld=C_NULL, stream=C_NULL)
+
+The masked reduce of every bank of a band resident on one GPU in one launch
+(bldp_band_masked_reduce_f32): `out` and `kept` hold the dense vcat of the banks'
+results; bank b's channel c is channel `b*nc + c` of the mask (`C_NULL` strides:
+the dense vcat of the banks' windows, `gpu_band_outliers`' mask)."""
+function gpu_band_masked_reduce(banks::Vector{Ptr{Float32}}, dims::NTuple{3,Integer},
+                                mask::Ptr{UInt8}, out::Ptr{Float32}, kept::Ptr{UInt32},
+                                fqavby::Integer=1, tavby::Integer=1; f=sum,
+                                win=Ptr{Int64}(C_NULL), mask_ld=Ptr{Int64}(C_NULL),
+                                stream::Ptr{Cvoid}=C_NULL)
+    op = _maskedop(f)
+    GC.@preserve banks win mask_ld check(ccall((:bldp_band_masked_reduce_f32, libbldp), Cint,
+        (Cint, Ptr{Ptr{Float32}}, Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Cint,
+         Ptr{UInt8}, Ptr{Int64}, Ptr{Float32}, Ptr{UInt32}, Ptr{Cvoid}),
+        length(banks), banks, dims[1], dims[2], dims[3], win, fqavby, tavby, op, mask, mask_ld,
+        out, kept, stream))
     nothing
 end
 

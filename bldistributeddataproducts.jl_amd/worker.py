@@ -862,6 +862,77 @@ def getoutliers(src, idxs=(COLON, COLON, COLON), *, n=None, axis=2, nsigma=5.0, 
         lambda r: {k: engine.fb_to_numpy(t) for k, t in r.items()})
 
 
+def getmasked(src, idxs=(COLON, COLON, COLON), *, mask, fqavby=1, tavby=1, func="sum", device=0):
+    """The window integrated over its unflagged samples: a dict with ``"data"``,
+    the ``func`` (``"sum"`` or ``"mean"``) of the samples of every fqavby x tavby
+    block whose byte of ``mask`` is 0, and ``"kept"`` (int32), how many there
+    were: the weight of each product (engine.masked_reduce; the rule of
+    include/bldp.h).  ``mask`` has the window's shape (nc, ni, nt), any axis of
+    which may be 1 (a bad-channel list is (nc, 1, 1)); uint8 or bool, a host array
+    or a device tensor (it goes to where the data is).  Files reach the GPU as
+    getdata reads them (window_on_device) and a host array is staged there, both
+    returning host arrays; a device tensor stays on the device.  Float32 data
+    only: any other element type (host array, device tensor, 8/16-bit SIGPROC
+    file) is a TypeError."""
+    engine._masked_op(func)  # (the ValueError before any file is touched)
+    if _is_tensor(mask):
+        mdt, host_mask = str(mask.dtype).replace("torch.", ""), None
+    else:
+        host_mask = np.asarray(mask)
+        mdt = str(host_mask.dtype)
+    if mdt not in ("uint8", "bool"):
+        raise TypeError(f"getmasked: the mask must be uint8 or bool, not {mdt}")
+    kw = dict(fqavby=fqavby, tavby=tavby, op=func)
+
+    def on_device(x, win):
+        m = mask
+        if host_mask is not None:
+            import torch
+
+            m = torch.from_numpy(np.ascontiguousarray(host_mask.view(np.uint8)))
+        return engine.masked_reduce(x, m.to(x.device), win=win, **kw)
+
+    def on_host(a, win):
+        m = host_mask if host_mask is not None else mask.cpu().numpy()
+        return engine.masked_reduce_host(a, m, win=win, device=device, **kw)
+
+    return _read_moment("getmasked", "masked_reduce", src, sanitizeidxs(idxs), device, on_device,
+                        on_host, lambda r: {k: engine.fb_to_numpy(t) for k, t in r.items()})
+
+
+def getclean(src, idxs=(COLON, COLON, COLON), *, fqavby=1, tavby=1, n=None, axis=2, nsigma=5.0,
+             func="sum", device=0):
+    """Flag and integrate on the device, with no host trip between the two:
+    engine.outliers flags every block of ``n`` selected channels (``axis=0``) or
+    spectra (``axis=2``; ``n=None``: the whole selected time range) at ``nsigma``
+    scaled mads from its median, and engine.masked_reduce takes the ``func``
+    (``"sum"`` or ``"mean"``) of every fqavby x tavby block over the samples left.
+    A dict with ``"data"``, ``"kept"`` (int32, the weight of each product) and
+    ``"count"`` (int32), the flags of every block of ``outliers``.  The mask never
+    leaves the device.  Files, host arrays and device tensors as getmasked takes
+    them; Float32 data only."""
+    engine._outliers_args(axis, nsigma, ("count",))  # (ValueErrors before any file is touched)
+    engine._masked_op(func)
+
+    def on_device(x, win):
+        o = engine.outliers(x, n=n, axis=axis, nsigma=nsigma, win=win, mask=True,
+                            which=("count",))
+        r = engine.masked_reduce(x, o["mask"], fqavby=fqavby, tavby=tavby, op=func, win=win)
+        r["count"] = o["count"]
+        return r
+
+    def on_host(a, win):  # staged whole, so that both halves read one device tensor
+        import torch
+
+        dev = f"cuda:{device}"
+        with torch.cuda.device(dev):
+            return {k: engine.fb_to_numpy(t)
+                    for k, t in on_device(engine.fb_from_numpy(a, device=dev), win).items()}
+
+    return _read_moment("getclean", "getclean", src, sanitizeidxs(idxs), device, on_device, on_host,
+                        lambda r: {k: engine.fb_to_numpy(t) for k, t in r.items()})
+
+
 getinventory = readers.getinventory
 getfbheader = readers.getfbheader
 getfbh5header = readers.getfbh5header

@@ -92,7 +92,8 @@ extern "C" {
  *    wherever BLDP_OP_MEDIAN is taken (7 stays unassigned and invalid);
  *    (additive, same version) the bldp_quantile_* entry points;
  *    (additive, same version) the bldp_quantiles_* entry points;
- *    (additive, same version) the bldp_outliers_* entry points */
+ *    (additive, same version) the bldp_outliers_* entry points;
+ *    (additive, same version) the bldp_*masked_reduce_* entry points */
 #define BLDP_ABI_VERSION 5
 
 #if defined(BLDP_BUILD)
@@ -778,6 +779,89 @@ BLDP_API int bldp_band_argext_f32(int nbank, const float *const *in, int64_t nch
 BLDP_API int bldp_argext_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
                                   int64_t ntime, const int64_t *win, int64_t fqavby,
                                   int64_t tavby, int argop, uint32_t *idx, float *val);
+
+/* Masked reduce: integrate a window over its unflagged samples.  One read of the
+ * window and one read of a byte mask give, for every fqavby x tavby block of the
+ * reduce, the sum (or mean) of the unflagged samples and how many there were;
+ * the kept count is the weight that any later averaging of the products needs.
+ * Float32 input; additive in ABI 5.
+ *
+ * The block of output (c', i, t') is the reduce's.  It is the F = fqavby selected
+ * channels by T = tavby selected spectra that bldp_reduce_f32 takes, after the
+ * window's offsets, steps and direction.
+ *
+ * The mask is addressed in window coordinates, like the one bldp_outliers_f32
+ * writes.  Flag (c, i, t) of the selected (nc, ni, nt) window is the byte
+ * mask[c*mask_ld[0] + i*mask_ld[1] + t*mask_ld[2]].
+ *  - mask_ld == NULL means dense: {1, nc, nc*ni}.  The "mask" of outliers goes
+ *    in as it is.
+ *  - A stride of 0 broadcasts along that axis.  A bad-channel list is {1, 0, 0};
+ *    a bad-spectrum list is {0, 0, 1}.
+ *  - Negative strides are BLDP_EINVAL.
+ *
+ * The steps are:
+ *  1. A sample is kept when its byte is 0 and flagged for any other value: 1, 2,
+ *     255.
+ *  2. kept (uint32) is the number of kept samples of the block.
+ *  3. sum (BLDP_OP_SUM) is the Float32 sum of the kept samples, in any order, as
+ *     the plain reduce leaves its order open.  A flagged sample is excluded by
+ *     selection, never multiplied by 0: a flagged NaN or +-Inf leaves the result
+ *     finite, and a kept NaN propagates.  A block with nothing kept gives 0.0,
+ *     Julia's sum(Float32[]).
+ *  4. mean (BLDP_OP_MEAN) is that sum divided once by Float32(kept).  It is a
+ *     correctly rounded IEEE division (the kernels use __fdiv_rn).  Nothing kept
+ *     gives NaN (0/0), Julia's mean(Float32[]).
+ *  5. Every other op is BLDP_EINVAL.
+ *  6. Before any launch, each of the following is refused with the codes the
+ *     sibling entry points use: F*T > 2^31 - 1 (Python and the shim read Int32);
+ *     both outputs null on a non-empty result; a null mask; outputs that overlap
+ *     each other, the input window or the mask's span; output strides that
+ *     overlap (all BLDP_EINVAL); factors that do not divide the window
+ *     (BLDP_EDIM); a window outside the array (BLDP_EBOUNDS).
+ *  7. F = T = 1 is legal: data = kept ? x : 0.
+ *
+ * The walk of a block is bldp_argext_*'s, with the same three paths ("lanes",
+ * "lanes_tsplit", "block") chosen by the same plan.  The flags are loaded as one
+ * aligned dword for the four flags of a float4 (float4 data loads, mask_ld[0] ==
+ * 1, the mask pointer a multiple of 4 and every non-zero mask pitch a multiple
+ * of 4), as one byte per row when mask_ld[0] == 0, else as one byte per element.
+ * One launch, no workspace, no atomics.  The output shape is bldp_reduce_shape's.
+ *
+ * bldp_masked_reduce_plan_f32: info[0..7] as bldp_argext_plan_f32 reports them
+ * {path, lanes per block, time slices, float4 loads per lane per row, workgroups
+ * per bank, workspace bytes (0), outputs per bank, vector loads 1 / 0}, info[8]
+ * the mask load form (0 byte, 1 dword, 2 row-uniform), info[9] reserved (0).
+ * Launches nothing and needs no GPU; both pointers may be null (their alignment
+ * only chooses the load width, and a null pointer counts as aligned).
+ * bldp_masked_reduce_f32: device pointers, asynchronous on `stream`, one launch;
+ * element (c', i, t') of out and kept at [c' + out_ld_i * i + out_ld_t * t'].
+ * out or kept may be NULL (not both) and is then neither formed nor stored.
+ * bldp_band_masked_reduce_f32: in[] is a HOST array of device pointers of banks
+ * with one geometry; one launch; out / kept are dense (nbank*nco, ni, nto), the
+ * vcat product of bldp_band_argext_f32.  Bank b's channel c is channel b*nc + c
+ * of the mask; mask_ld == NULL is the dense (nbank*nc, ni, nt) mask that
+ * bldp_band_outliers_f32 writes.
+ * bldp_masked_reduce_host_f32: host in, host mask (mask_ld in bytes of the host
+ * mask), host dense (nco, ni, nto) outs; the window's rows and the mask's span
+ * are staged on device `dev` once.  Synchronous. */
+BLDP_API int bldp_masked_reduce_plan_f32(const float *in, int64_t nchan, int64_t nif,
+                                         int64_t ntime, const int64_t *win, int64_t fqavby,
+                                         int64_t tavby, const uint8_t *mask,
+                                         const int64_t *mask_ld, int64_t info[10]);
+BLDP_API int bldp_masked_reduce_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                                    const int64_t *win, int64_t fqavby, int64_t tavby, int op,
+                                    const uint8_t *mask, const int64_t *mask_ld, float *out,
+                                    uint32_t *kept, int64_t out_ld_i, int64_t out_ld_t,
+                                    void *stream);
+BLDP_API int bldp_band_masked_reduce_f32(int nbank, const float *const *in, int64_t nchan,
+                                         int64_t nif, int64_t ntime, const int64_t *win,
+                                         int64_t fqavby, int64_t tavby, int op,
+                                         const uint8_t *mask, const int64_t *mask_ld, float *out,
+                                         uint32_t *kept, void *stream);
+BLDP_API int bldp_masked_reduce_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                         int64_t ntime, const int64_t *win, int64_t fqavby,
+                                         int64_t tavby, int op, const uint8_t *mask,
+                                         const int64_t *mask_ld, float *out, uint32_t *kept);
 
 /* Element types other than Float32 (what Blio maps SIGPROC nbits 8 / 16 to, and
  * what HDF5.jl returns for an integer or Float64 dataset: the reference's
