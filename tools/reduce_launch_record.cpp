@@ -17,6 +17,23 @@
 //          under each plan option value (1 1: the full cross product)
 //        reduce_launch_record --loop N   the host cost of N dispatches of the
 //          prepared cfg4 band reduce (bench.py), in ns per launch_reduce
+//        reduce_launch_record --reach SHAPE_STRIDE OPTION_STRIDE   the same sweep,
+//          with all four ops per case, printing only, per symbol started, the
+//          smallest input (elements per bank) that started it
+//        reduce_launch_record --list   every registered k_reduce_* entry point
+//        reduce_launch_record --cases   what each case read from stdin runs, one
+//          case per line:
+//            NCHAN NIF NTIME WINDOW F T OP NBANK STITCHED [OPTION:VALUE ...]
+//          WINDOW is - or nine comma-separated integers (start, count, step of
+//          the channel, IF and time axes, 0-based, as bldp_reduce_f32 takes
+//          them).  RedArgs and the alignment classes are formed as
+//          prepare_reduce (api.hip) forms them, for 16-byte aligned banks and
+//          output, on 256 CUs at XCD order lg 3.  Printed per case: plan=, the
+//          fields bldp_reduce_plan_f32 reports of that launch (path, lanes per
+//          group, time-split waves, float4 per lane, time chunks, workgroups,
+//          vec_out); query=, the same of one bank of the case reduced alone
+//          into a dense array (what bldp_reduce_plan_f32, which takes one
+//          bank, answers); and the symbols launched.
 #include <cxxabi.h>
 
 #include <chrono>
@@ -156,10 +173,18 @@ struct Banks {
   bool stitched;
 };
 const Banks kBanks[] = {{1, true}, {1, false}, {8, true}, {8, false}};
-const int64_t kF[] = {1, 2, 3, 4, 5, 6, 7, 8, 12, 16, 64, 256, 512, 1024, 4096, 65536};
+// (every value of kRowG4, kIlK4, kLaneF, kLanetF and every (kVecLpg, VecK4c)
+// pair occurs: 32, 128 for G4 = 8, 32; 2048 for K4 = 8; 24 .. 768 for K4C = 3
+// and 20 .. 640 for the generic K4C = 0 at each LPG)
+const int64_t kF[] = {1,   2,   3,   4,   5,   6,   7,   8,   12,   16,   20,
+                      24,  32,  40,  48,  64,  80,  96,  128, 160,  192,  256,
+                      320, 384, 512, 640, 768, 1024, 2048, 4096, 65536};
 const int64_t kT[] = {1, 2, 3, 4, 8, 16, 272, 1024};
-// (504 and 65520: rows that groups of 5 and of 12 channels divide)
-const int64_t kRows[] = {16, 42, 504, 512, 4096, 65520, 65536, (int64_t)1 << 26};
+// (256 and 2048: banks of 1 .. 16 groups, which k_reduce_rowt and k_reduce_wavet
+// pack; 840 and 65520: rows that groups of 5 and of 12 channels divide, 840 in
+// fewer than 241 groups of 5, k_reduce_lanes' limit; 15 * 2^20: those of
+// 3 * 2^k and 5 * 2^k channels)
+const int64_t kRows[] = {16, 42, 256, 512, 840, 2048, 4096, 65520, 65536, (int64_t)15 << 20, (int64_t)1 << 26};
 const int64_t kNto[] = {1, 2, 17, 100000};
 const int64_t kNi[] = {1, 2};
 const int kXcd[] = {0, 3};
@@ -231,6 +256,16 @@ void print_args(const RedArgs &a) {
          a.st_plain, a.xcd_lg, (double)a.div);
 }
 
+struct Reach {
+  int64_t elems = -1;
+  std::string at;
+};
+bool g_reach = false;
+std::map<std::string, Reach> &reach() {
+  static std::map<std::string, Reach> m;
+  return m;
+}
+
 // One case: plan, launch, print.  Returns whether launch_reduce succeeded.
 bool run_case(uint64_t idx, int64_t F, int64_t T, int64_t rows, int64_t nto, int64_t ni, Banks bk,
               Align al, int xcd_lg, const char *optname, int64_t optval) {
@@ -240,6 +275,26 @@ bool run_case(uint64_t idx, int64_t F, int64_t T, int64_t rows, int64_t nto, int
   const int op = (int)(idx % 4);  // sum, mean, max, min
   g_launches.clear();
   const hipError_t e = bldp::launch_reduce(a, p, op, nullptr);
+  if (g_reach) {  // --reach: the smallest input (elements per bank) that started each symbol
+    bool ok = e == hipSuccess;  // (of all four ops: g_launches collects them)
+    for (int o = 1; o < 4; ++o) ok = bldp::launch_reduce(a, p, (op + o) % 4, nullptr) == hipSuccess && ok;
+    const int64_t elems = (rows * al.cs + (al.rows16 ? 0 : 1)) * ni * nto * T;
+    for (const Launch &l : g_launches) {
+      const auto it = names().find(l.fn);
+      Reach &r = reach()[it == names().end() ? "?" : it->second];
+      if (r.elems >= 0 && r.elems <= elems) continue;
+      char buf[256];
+      snprintf(buf, sizeof buf,
+               "F=%lld T=%lld rows=%lld nto=%lld ni=%lld nbank=%d stitched=%d aligned=%d "
+               "rows16=%d words=%d cs=%d xcd=%d opt=%s:%lld",
+               (long long)F, (long long)T, (long long)rows, (long long)nto, (long long)ni,
+               bk.nbank, (int)bk.stitched, (int)al.aligned, (int)al.rows16, (int)al.words, al.cs,
+               xcd_lg, optname, (long long)optval);
+      r.elems = elems;
+      r.at = buf;
+    }
+    return ok;
+  }
   printf("case F=%lld T=%lld rows=%lld nto=%lld ni=%lld nbank=%d stitched=%d aligned=%d rows16=%d "
          "words=%d cs=%d xcd=%d opt=%s:%lld op=%d | rc=%d path=%d kernel=%s lpg=%d grid=%lld "
          "nout=%lld ws_bytes=%llu nlaunch=%zu",
@@ -299,12 +354,179 @@ int loop(long n) {
   return 0;
 }
 
+// --cases: api.hip's resolve_window, resolve_factors and prepare_reduce, restated.
+struct Geo {
+  int64_t nc, ni, nt;
+  int64_t off, cs, ld_i, ld_t;
+};
+bool resolve_window(int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win, Geo *g) {
+  if (nchan < 0 || nif < 0 || ntime < 0) return false;
+  const int64_t dims[3] = {nchan, nif, ntime};
+  int64_t start[3], count[3], step[3];
+  for (int ax = 0; ax < 3; ++ax) {
+    start[ax] = win ? win[3 * ax] : 0;
+    count[ax] = win ? win[3 * ax + 1] : dims[ax];
+    step[ax] = win ? win[3 * ax + 2] : 1;
+    if (count[ax] < 0) return false;
+    if (count[ax] > 0) {
+      if (step[ax] == 0) return false;
+      const int64_t last = start[ax] + (count[ax] - 1) * step[ax];
+      if (start[ax] < 0 || start[ax] >= dims[ax] || last < 0 || last >= dims[ax]) return false;
+    }
+  }
+  g->nc = count[0], g->ni = count[1], g->nt = count[2];
+  const bool empty = g->nc == 0 || g->ni == 0 || g->nt == 0;
+  g->off = empty ? 0 : start[0] + nchan * (start[1] + nif * start[2]);
+  g->cs = step[0];
+  g->ld_i = nchan * step[1];
+  g->ld_t = nchan * nif * step[2];
+  return true;
+}
+bool pitch_ok(const Geo &g) {
+  return (g.ni <= 1 || g.ld_i % 4 == 0) && (g.nt <= 1 || g.ld_t % 4 == 0);
+}
+bool vec_ok(const Geo &g) { return g.cs == 1 && g.off % 4 == 0 && pitch_ok(g); }
+bool unaligned_vec_pays(int64_t F, bool rows16) {
+  if (!rows16) return true;
+  return F == 1 || (F % 4 == 0 && F <= 256);
+}
+
+struct Public {  // bldp_reduce_plan_f32's info[0..5], info[7]
+  int64_t v[7];
+};
+Public public_plan(const RedArgs &a, const Plan &p) {
+  return Public{{p.path, p.lpg, p.path == bldp::PATH_VEC_ROW ? a.rsplit : a.ts, a.k4, a.nchunk,
+                 p.grid, a.vec_out}};
+}
+void print_public(const char *key, const Public &q) {
+  printf(" %s=%lld,%lld,%lld,%lld,%lld,%lld,%lld", key, (long long)q.v[0], (long long)q.v[1],
+         (long long)q.v[2], (long long)q.v[3], (long long)q.v[4], (long long)q.v[5],
+         (long long)q.v[6]);
+}
+
+// The RedArgs and plan of prepare_reduce for nbank 16-byte aligned banks and a
+// 16-byte aligned output: stitched, or dense per bank (bldp_reduce_f32).
+bool prepare_case(int nbank, bool stitched, int64_t nchan, int64_t nif, int64_t ntime,
+                  const int64_t *win, int64_t fqavby, int64_t tavby, RedArgs *ap, Plan *pp) {
+  if (nbank < 1 || nbank > BLDP_MAX_BANKS) return false;
+  Geo g;
+  if (!resolve_window(nchan, nif, ntime, win, &g)) return false;
+  const int64_t F = fqavby <= 1 ? 1 : fqavby, T = tavby <= 1 ? 1 : tavby;
+  if (g.nc % F != 0 || g.nt % T != 0) return false;
+  RedArgs &a = *ap;
+  a = RedArgs{};
+  a.nco = g.nc / F;
+  a.ni = g.ni;
+  a.nto = g.nt / T;
+  a.F = F;
+  a.T = T;
+  a.nbank = nbank;
+  if (stitched) {
+    a.out_bank = a.nco;
+    a.out_ld_i = nbank * a.nco;
+    a.out_ld_t = nbank * a.nco * a.ni;
+  } else {
+    a.out_bank = a.nco * a.ni * a.nto;
+    a.out_ld_i = a.nco;
+    a.out_ld_t = a.nco * a.ni;
+  }
+  a.in_off = g.off;
+  a.in_cs = g.cs;
+  a.in_ld_i = g.ld_i;
+  a.in_ld_t = g.ld_t;
+  a.out = (float *)(uintptr_t)0x7000000000ull;
+  if (a.nco == 0 || a.ni == 0 || a.nto == 0) return false;  // (nothing is launched)
+  const bool rows16 = pitch_ok(g), words = true;  // (the banks: 16-byte aligned)
+  for (int b = 0; b < nbank; ++b) a.in[b] = fake_in(b);
+  const bool aligned = (rows16 && vec_ok(g)) ||
+                       (bldp::opt(bldp::OPT_UNALIGNED_VEC) >= 1 && words && g.cs == 1 &&
+                        unaligned_vec_pays(F, rows16));
+  *pp = bldp::plan_reduce(a, aligned, rows16, words && g.cs == 1, kNumCus, 3);
+  return true;
+}
+
+int list_symbols() {
+  for (const auto &kv : names())
+    if (kv.second.rfind("k_reduce_", 0) == 0) printf("%s\n", kv.second.c_str());
+  return 0;
+}
+
+int run_cases() {
+  char line[4096];
+  uint64_t n = 0, errors = 0;
+  while (fgets(line, sizeof line, stdin)) {
+    std::vector<std::string> tok;
+    for (char *t = strtok(line, " \t\r\n"); t; t = strtok(nullptr, " \t\r\n")) tok.push_back(t);
+    if (tok.empty() || tok[0][0] == '#') continue;
+    ++n;
+    printf("case");
+    for (const std::string &t : tok) printf(" %s", t.c_str());
+    bool ok = tok.size() >= 9;
+    int64_t win[9];
+    bool has_win = false;
+    if (ok && tok[3] != "-") {
+      has_win = sscanf(tok[3].c_str(), "%ld,%ld,%ld,%ld,%ld,%ld,%ld,%ld,%ld", &win[0], &win[1],
+                       &win[2], &win[3], &win[4], &win[5], &win[6], &win[7], &win[8]) == 9;
+      ok = has_win;
+    }
+    std::vector<int> set;
+    for (size_t k = 9; ok && k < tok.size(); ++k) {
+      const size_t c = tok[k].find(':');
+      const int o = c == std::string::npos ? -1 : bldp::plan_opt_index(tok[k].substr(0, c).c_str());
+      const int64_t v = c == std::string::npos ? -1 : atoll(tok[k].c_str() + c + 1);
+      if (o < 0 || v < 0 || !bldp::plan_opt_valid(o, v)) {
+        ok = false;
+        break;
+      }
+      bldp::plan_opt_set(o, v);
+      set.push_back(o);
+    }
+    if (ok) {
+      const int64_t nchan = atoll(tok[0].c_str()), nif = atoll(tok[1].c_str()),
+                    ntime = atoll(tok[2].c_str()), F = atoll(tok[4].c_str()),
+                    T = atoll(tok[5].c_str());
+      const int op = atoi(tok[6].c_str()), nbank = atoi(tok[7].c_str());
+      const bool stitched = atoi(tok[8].c_str()) != 0;
+      RedArgs a, a1;
+      Plan p, p1;
+      ok = op >= 0 && op <= 3 &&
+           prepare_case(nbank, stitched, nchan, nif, ntime, has_win ? win : nullptr, F, T, &a, &p) &&
+           prepare_case(1, false, nchan, nif, ntime, has_win ? win : nullptr, F, T, &a1, &p1);
+      if (ok) {
+        if (p.ws_bytes) a.ws = (float *)(uintptr_t)0x6000000000ull;
+        g_launches.clear();
+        ok = bldp::launch_reduce(a, p, op, nullptr) == hipSuccess && !g_launches.empty();
+      }
+      if (ok) {
+        printf(" | rc=0 kernel=%s", plan_kernel(p));
+        print_public("plan", public_plan(a, p));
+        print_public("query", public_plan(a1, p1));
+        for (const Launch &l : g_launches) {
+          const auto it = names().find(l.fn);
+          printf(" | launch sym=%s", it == names().end() ? "?" : it->second.c_str());
+        }
+      }
+    }
+    for (int o : set) bldp::plan_opt_set(o, -1);
+    if (!ok) {
+      ++errors;
+      printf(" | rc=1");
+    }
+    printf("\n");
+  }
+  printf("total cases=%llu errors=%llu\n", (unsigned long long)n, (unsigned long long)errors);
+  return errors ? 1 : 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
+  if (argc == 2 && !strcmp(argv[1], "--list")) return list_symbols();
+  if (argc == 2 && !strcmp(argv[1], "--cases")) return run_cases();
   if (argc == 3 && !strcmp(argv[1], "--loop")) return loop(atol(argv[2]));
+  if (argc == 4 && !strcmp(argv[1], "--reach")) g_reach = true, ++argv, --argc;
   if (argc != 3 || atol(argv[1]) < 1 || atol(argv[2]) < 1) {
-    fprintf(stderr, "usage: %s SHAPE_STRIDE OPTION_STRIDE | --loop N\n", argv[0]);
+    fprintf(stderr, "usage: %s [--reach] SHAPE_STRIDE OPTION_STRIDE | --loop N | --list | --cases\n", argv[0]);
     return 2;
   }
   uint64_t cases = 0, errors = 0;
@@ -319,6 +541,9 @@ int main(int argc, char **argv) {
     sweep((uint64_t)atol(argv[2]), o.name, o.v, &cases, &errors);
     bldp::plan_opt_set(k, -1);
   }
+  for (const auto &kv : reach())
+    printf("reach sym=%s elems=%lld %s\n", kv.first.c_str(), (long long)kv.second.elems,
+           kv.second.at.c_str());
   printf("total cases=%llu errors=%llu\n", (unsigned long long)cases, (unsigned long long)errors);
   return errors ? 1 : 0;
 }
