@@ -111,6 +111,11 @@ ARGEXT_PATHS = {0: "lanes", 1: "lanes_tsplit", 2: "block"}
 # a byte per element, one aligned dword per float4, one byte per row (stride 0
 # along the channels)
 MASK_LOADS = {0: "byte", 1: "dword", 2: "row"}
+# histogram (csrc/hist.hip): a block in one workgroup, a block's rows and columns
+# chunked over workgroups (merged by atomic adds), several neighbouring blocks in
+# a workgroup with its lanes along the channels, the same with the time chunked
+HIST_PATHS = {0: "block", 1: "block_split", 2: "lanes", 3: "lanes_tsplit"}
+MAX_HIST_BINS = 4096
 
 BLDP_OK, BLDP_EINVAL, BLDP_EDIM, BLDP_EHIP, BLDP_ENOMEM, BLDP_EBOUNDS = 0, -1, -2, -3, -5, -6
 BLDP_ECOMM, BLDP_EIO = -7, -8
@@ -222,6 +227,10 @@ SIGNATURES = {
     "bldp_masked_reduce_f32": ([P, I64, I64, I64, P, I64, I64, I, P, P, P, P, I64, I64, P], I),
     "bldp_band_masked_reduce_f32": ([I, P, I64, I64, I64, P, I64, I64, I, P, P, P, P, P], I),
     "bldp_masked_reduce_host_f32": ([I, P, I64, I64, I64, P, I64, I64, I, P, P, P, P], I),
+    "bldp_histogram_plan_f32": ([P, I64, I64, I64, P, I64, I64, I, D, D, P], I),
+    "bldp_histogram_f32": ([P, I64, I64, I64, P, I64, I64, I, D, D, P, I64, I64, I64, P], I),
+    "bldp_band_histogram_f32": ([I, P, I64, I64, I64, P, I64, I64, I, D, D, P, P], I),
+    "bldp_histogram_host_f32": ([I, P, I64, I64, I64, P, I64, I64, I, D, D, P], I),
     "bldp_fqav_range": ([D, D, I64, I64, P, P, P], I),
     "bldp_synth_f32": ([P, I64, I64, I64, I64, U64, I, P], I),
     "bldp_reduce_out_dtype": ([I, I], I),

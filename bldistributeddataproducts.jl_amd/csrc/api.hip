@@ -2075,6 +2075,154 @@ int bldp_band_masked_reduce_f32(int nbank, const float *const *in, int64_t nchan
                     kept, d[0], nbank * d[0], nbank * d[0] * d[1], stream);
 }
 
+// ---- histogram: the counts per bin of every block, with below / above / nan ----
+// Checks, window and plan of a histogram (every entry point).  Plane q of block
+// (c', i, t') of bank b sits at [b*out_bank + c' + i*out_ld_i + t'*out_ld_t +
+// q*out_ld_q].  query: the plan call (null pointers count as aligned).
+static int hist_prepare(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                        int64_t ntime, const int64_t *win, int64_t fqavby, int64_t tavby,
+                        int nbins, double lo, double hi, uint32_t *out, int64_t out_bank,
+                        int64_t out_ld_i, int64_t out_ld_t, int64_t out_ld_q, bool query,
+                        HistArgs *ap, Plan *pp, bool *empty) {
+  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
+    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
+  if (nbins < 1 || nbins > BLDP_MAX_HIST_BINS)
+    return fail(BLDP_EINVAL, "histogram: nbins=%d outside 1..%d", nbins, BLDP_MAX_HIST_BINS);
+  const float lo32 = (float)lo, hi32 = (float)hi;
+  if (!std::isfinite(lo32) || !std::isfinite(hi32) || !(lo32 < hi32))
+    return fail(BLDP_EINVAL, "histogram: Float32(lo)=%g and Float32(hi)=%g must be finite with "
+                "lo < hi", (double)lo32, (double)hi32);
+  const volatile float w = hi32 - lo32;  // (one Float32 operation each, as written)
+  if (!std::isfinite(w))
+    return fail(BLDP_EINVAL, "histogram: hi - lo overflows Float32 (lo=%g, hi=%g)", (double)lo32,
+                (double)hi32);
+  const volatile float sc = (float)nbins / w;
+  if (!std::isfinite(sc) || !(sc > 0.0f))
+    return fail(BLDP_EINVAL, "histogram: the bin scale nbins / (hi - lo) = %g is not a finite "
+                "positive Float32 (nbins=%d, lo=%g, hi=%g)", (double)sc, nbins, (double)lo32,
+                (double)hi32);
+  Geo g;
+  int rc = resolve_window(nchan, nif, ntime, win, &g);
+  if (rc) return rc;
+  int64_t F, T;
+  rc = resolve_factors(g, fqavby, tavby, &F, &T);
+  if (rc) return rc;
+  // counts are 31-bit (Python and the shim read Int32)
+  if (F > INT32_MAX / T)
+    return fail(BLDP_EINVAL, "histogram: blocks of fqavby x tavby = %lld x %lld elements are "
+                "beyond 2^31 - 1", (long long)F, (long long)T);
+  HistArgs &a = *ap;
+  a = HistArgs{};
+  a.nco = g.nc / F;
+  a.ni = g.ni;
+  a.nto = g.nt / T;
+  a.F = F;
+  a.T = T;
+  a.nbank = nbank;
+  a.B = nbins;
+  a.lo = lo32, a.hi = hi32, a.s = sc;
+  a.out = out;
+  a.out_bank = out_bank;
+  a.out_ld_i = out_ld_i;
+  a.out_ld_t = out_ld_t;
+  a.out_ld_q = out_ld_q;
+  a.in_off = g.off;
+  a.in_cs = g.cs;
+  a.in_ld_i = g.ld_i;
+  a.in_ld_t = g.ld_t;
+  *empty = a.nco == 0 || a.ni == 0 || a.nto == 0;
+  if (!in) return fail(BLDP_EINVAL, "histogram: null input pointer array");
+  bool words = true;
+  for (int b = 0; b < nbank; ++b) {
+    a.in[b] = in[b];
+    words = words && aligned4(in[b]);
+  }
+  rc = plan_hist(a, words && g.cs == 1, num_cus_current(), pp);
+  if (rc) return rc;
+  if (query || *empty) return BLDP_OK;
+  for (int b = 0; b < nbank; ++b)
+    if (!in[b]) return fail(BLDP_EINVAL, "histogram: null input pointer (bank %d)", b);
+  if (!out) return fail(BLDP_EINVAL, "histogram: null output pointer");
+  const int64_t plane = (nbank - 1) * out_bank + (a.nco - 1) + (a.ni - 1) * out_ld_i +
+                        (a.nto - 1) * out_ld_t + 1;  // the extent of a plane
+  if (out_ld_i < a.nco || out_ld_t < (a.ni - 1) * out_ld_i + a.nco ||
+      (nbank > 1 && out_bank < a.nco) || out_ld_q < plane)
+    return fail(BLDP_EINVAL, "histogram: out strides (%lld, %lld, %lld) overlap for a (%lld, %lld, "
+                "%lld, %d) result", (long long)out_ld_i, (long long)out_ld_t, (long long)out_ld_q,
+                (long long)a.nco, (long long)a.ni, (long long)a.nto, nbins + 3);
+  // the output may not overlap the window's elements
+  int64_t wlo = g.off, whi = g.off;  // lowest and highest element offset of the window
+  const int64_t span[3] = {(g.nc - 1) * g.cs, (g.ni - 1) * g.ld_i, (g.nt - 1) * g.ld_t};
+  for (int ax = 0; ax < 3; ++ax) (span[ax] < 0 ? wlo : whi) += span[ax];
+  const size_t obytes = 4 * (size_t)((int64_t)(nbins + 2) * out_ld_q + plane);
+  const size_t wbytes = 4 * (size_t)(whi - wlo + 1);
+  for (int b = 0; b < nbank; ++b)
+    if (spans_overlap(out, obytes, in[b] + wlo, wbytes))
+      return fail(BLDP_EINVAL, "histogram: out overlaps the input window (bank %d)", b);
+  return BLDP_OK;
+}
+
+static int hist_run(int nbank, const float *const *in, int64_t nchan, int64_t nif, int64_t ntime,
+                    const int64_t *win, int64_t fqavby, int64_t tavby, int nbins, double lo,
+                    double hi, uint32_t *out, int64_t out_bank, int64_t out_ld_i,
+                    int64_t out_ld_t, int64_t out_ld_q, void *stream) {
+  HistArgs a;
+  Plan p;
+  bool empty = false;
+  int rc = hist_prepare(nbank, in, nchan, nif, ntime, win, fqavby, tavby, nbins, lo, hi, out,
+                        out_bank, out_ld_i, out_ld_t, out_ld_q, false, &a, &p, &empty);
+  if (rc || empty) return rc;
+  hipError_t e = launch_hist(a, p, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(BLDP_EHIP, "histogram launch: %s", hipGetErrorString(e));
+  return BLDP_OK;
+}
+
+int bldp_histogram_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                            const int64_t *win, int64_t fqavby, int64_t tavby, int nbins,
+                            double lo, double hi, int64_t info[10]) {
+  if (!info) return fail(BLDP_EINVAL, "null info");
+  HistArgs a;
+  Plan p;
+  bool empty = false;
+  const float *ins[1] = {in};
+  int rc = hist_prepare(1, ins, nchan, nif, ntime, win, fqavby, tavby, nbins, lo, hi, nullptr, 0,
+                        0, 0, 0, true, &a, &p, &empty);
+  if (rc) return rc;
+  info[0] = p.path;
+  info[1] = p.grid;
+  info[2] = (int64_t)a.nchunk * a.ctiles;
+  info[3] = a.G;
+  info[4] = p.shm;
+  info[5] = a.R;
+  info[6] = (int64_t)p.ws_bytes;
+  info[7] = a.vec != 0;
+  info[8] = p.lpg;
+  info[9] = a.rows_per_chunk;
+  return BLDP_OK;
+}
+
+int bldp_histogram_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                       const int64_t *win, int64_t fqavby, int64_t tavby, int nbins, double lo,
+                       double hi, uint32_t *out, int64_t out_ld_i, int64_t out_ld_t,
+                       int64_t out_ld_q, void *stream) {
+  const float *ins[1] = {in};
+  return hist_run(1, ins, nchan, nif, ntime, win, fqavby, tavby, nbins, lo, hi, out, 0, out_ld_i,
+                  out_ld_t, out_ld_q, stream);
+}
+
+int bldp_band_histogram_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                            int64_t ntime, const int64_t *win, int64_t fqavby, int64_t tavby,
+                            int nbins, double lo, double hi, uint32_t *out, void *stream) {
+  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
+    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
+  int64_t d[3];
+  int rc = bldp_reduce_shape(nchan, nif, ntime, win, fqavby, tavby, d);
+  if (rc) return rc;
+  // the vcat of the banks: bank k's channels at k*nco of every (IF, time) row of every plane
+  return hist_run(nbank, in, nchan, nif, ntime, win, fqavby, tavby, nbins, lo, hi, out, d[0],
+                  nbank * d[0], nbank * d[0] * d[1], nbank * d[0] * d[1] * d[2], stream);
+}
+
 int bldp_reduce_out_dtype(int dtype, int op) {
   const int d = typed_out_dtype(dtype, op);
   if (d < 0) return fail(BLDP_EINVAL, "unknown element type %d or op %d", dtype, op);

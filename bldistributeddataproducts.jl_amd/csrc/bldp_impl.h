@@ -334,6 +334,42 @@ enum MaskForm { MASK_BYTE = 0, MASK_DWORD = 1, MASK_ROW = 2 };
 int plan_masked(MaskedArgs &a, bool words, bool mask_words, int num_cus, int xcd_lg, Plan *p);
 hipError_t launch_masked(const MaskedArgs &a, const Plan &p, hipStream_t s);
 
+// Histogram of every F x T block (hist.hip): B bins of [lo, hi) and the below,
+// above and nan counts, B + 3 planes of uint32.  Window element (c, i, t) of bank
+// b at in[b][in_off + c*in_cs + i*in_ld_i + t*in_ld_t]; plane q of block
+// (c', i, t') of bank b at out[b*out_bank + c' + i*out_ld_i + t'*out_ld_t +
+// q*out_ld_q].  A by-value kernel argument of the histogram kernels alone.
+struct HistArgs {
+  const float *in[BLDP_MAX_BANKS];  // banks with identical geometry
+  uint32_t *out;
+  int64_t out_bank, out_ld_i, out_ld_t, out_ld_q;
+  int64_t in_off, in_cs, in_ld_i, in_ld_t;
+  int64_t nco, ni, nto, F, T;
+  int32_t nbank;
+  int32_t B;        // bins: 1 .. BLDP_MAX_HIST_BINS
+  float lo, hi, s;  // Float32(lo), Float32(hi), Float32(B) / (hi - lo)
+  // the plan (plan_hist)
+  int32_t vec;     // float4 loads, else one dword per element
+  int32_t G;       // blocks of a workgroup, neighbours along the channels
+  int32_t R;       // replicas of a block's counters in LDS (a power of two)
+  int32_t wlog2;   // log2 of a workgroup's lanes along the channels
+  int32_t atomic;  // a block is shared by workgroups: atomicAdd into the zeroed out
+  int32_t nchunk;  // chunks of a block's T rows
+  int64_t rows_per_chunk;
+  int64_t ctiles;      // G == 1: column tiles of a block's F channels
+  int64_t tile_items;  // items (float4s or dwords) of a workgroup's row
+  int64_t ncg;         // channel groups: ceil(nco / G), or nco * ctiles
+};
+enum HistPath { HIST_BLOCK = 0, HIST_BLOCK_SPLIT = 1, HIST_LANES = 2, HIST_LANES_TSPLIT = 3 };
+// Fills the plan of an args struct whose shape, stride and B fields are set
+// (`words`: the channel step is 1 and every bank pointer is dword-aligned), without
+// a GPU.  p: path (HistPath), lpg = the lanes along the channels, grid = workgroups
+// per bank, shm = LDS bytes.  BLDP_OK or, with the message recorded, BLDP_EINVAL for
+// a launch too large for one grid.
+int plan_hist(HistArgs &a, bool words, int num_cus, Plan *p);
+// Zeroes the output first when a.atomic, on the same stream.
+hipError_t launch_hist(const HistArgs &a, const Plan &p, hipStream_t s);
+
 // median / var / std of every block of T selected spectra of every (channel,
 // IF) column (tstats.hip): tavfunc, fqav's rule on the time axis.  Window
 // element (c, i, t) of bank k at in[k][in_off + c*in_cs + i*in_ld_i +

@@ -572,6 +572,44 @@ extern "C" int bldp_masked_reduce_host_f32(int dev, const float *in, int64_t nch
   });
 }
 
+// The same staging for the histogram: the window's rows go to the device once;
+// the dense (nco, ni, nto, nbins + 3) counts come back.
+extern "C" int bldp_histogram_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                       int64_t ntime, const int64_t *win, int64_t fqavby,
+                                       int64_t tavby, int nbins, double lo, double hi,
+                                       uint32_t *out) {
+  // (every argument check, before any staging)
+  int64_t info[10];
+  int rc = bldp_histogram_plan_f32(nullptr, nchan, nif, ntime, win, fqavby, tavby, nbins, lo, hi,
+                                   info);
+  if (rc) return rc;
+  int64_t sh[3];
+  rc = bldp_reduce_shape(nchan, nif, ntime, win, fqavby, tavby, sh);
+  if (rc) return rc;
+  const int64_t nco = sh[0], ni = sh[1], nto = sh[2], plane = nco * ni * nto;
+  if (plane == 0) return BLDP_OK;
+  if (!in) return bldp::set_error(BLDP_EINVAL, "histogram: null input pointer");
+  if (!out) return bldp::set_error(BLDP_EINVAL, "histogram: null output pointer");
+  const int64_t F = fqavby <= 1 ? 1 : fqavby, T = tavby <= 1 ? 1 : tavby;
+  const int64_t nc = nco * F, nt = nto * T;
+  const size_t obytes = (size_t)plane * (size_t)(nbins + 3) * sizeof(uint32_t);
+  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
+  return with_stager(dev, [&](bldp::Stager *sg) -> int {
+    float *dbuf;
+    uint32_t *dout;
+    int r = bldp::stager_buffer(sg, 0, (size_t)(h.span * ni * nt) * 4, (void **)&dbuf);
+    if (!r) r = bldp::stager_buffer(sg, 2, obytes, (void **)&dout);
+    if (!r) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
+    if (r) return r;
+    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
+    r = bldp_histogram_f32(dbuf, h.span, ni, nt, dwin, fqavby, tavby, nbins, lo, hi, dout, nco,
+                           nco * ni, plane, sg->st[0]);
+    if (r) return r;
+    HCHK(hipMemcpyAsync(out, dout, obytes, hipMemcpyDeviceToHost, sg->st[0]));
+    return BLDP_OK;
+  });
+}
+
 // ---------------------------------------------------------------------------
 // Host forms of the typed entry points (include/bldp.h), staged like the
 // Float32 forms above: only the window's rows (its channel span of every

@@ -1458,6 +1458,197 @@ def masked_reduce_host(a: np.ndarray, mask: np.ndarray, fqavby=1, tavby=1, op="s
     return {"data": data, "kept": kept.view(np.int32)}  # counts are < 2^31
 
 
+def _hist_args(nbins, lo, hi):
+    """(nbins, lo, hi) of a histogram call, checked before any GPU work: the
+    parameter conditions of include/bldp.h, each an ArgumentError (BLDP_EINVAL,
+    as the library itself answers)."""
+    try:
+        B = int(nbins)
+        ok = B == nbins
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise TypeError(f"histogram: nbins must be an integer, not {nbins!r}")
+    if not 1 <= B <= _lib.MAX_HIST_BINS:
+        raise _lib.ArgumentError(_lib.BLDP_EINVAL,
+                                 f"histogram: nbins={B} outside 1..{_lib.MAX_HIST_BINS}")
+    lo, hi = float(lo), float(hi)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        lo32, hi32 = np.float32(lo), np.float32(hi)
+        if not (np.isfinite(lo32) and np.isfinite(hi32) and lo32 < hi32):
+            raise _lib.ArgumentError(_lib.BLDP_EINVAL,
+                                     f"histogram: Float32(lo)={lo32} and Float32(hi)={hi32} must be "
+                                     f"finite with lo < hi")
+        w = np.float32(hi32 - lo32)
+        s = np.float32(np.float32(B) / w)
+    if not np.isfinite(w) or not np.isfinite(s) or not s > 0:
+        raise _lib.ArgumentError(_lib.BLDP_EINVAL,
+                                 f"histogram: hi - lo = {w} or the bin scale nbins / (hi - lo) = {s} "
+                                 f"is not a finite positive Float32")
+    return B, lo, hi
+
+
+def hist_edges(nbins, lo, hi) -> np.ndarray:
+    """The nbins + 1 Float64 bin edges ``lo32 + k * (hi32 - lo32) / nbins`` of a
+    histogram: a reading aid only, the rule of include/bldp.h decides where a
+    sample goes."""
+    B, lo, hi = _hist_args(nbins, lo, hi)
+    lo32, hi32 = float(np.float32(lo)), float(np.float32(hi))
+    return lo32 + np.arange(B + 1, dtype=np.float64) * (hi32 - lo32) / B
+
+
+def _hist_factors(shape, win, fqavby, tavby):
+    """fqavby / tavby with None meaning the whole selected range of that axis."""
+    nc, _, nt = window_shape(win, shape)
+    return (max(nc, 1) if fqavby is None else fqavby), (max(nt, 1) if tavby is None else tavby)
+
+
+def _hist_out(out, dims, K, device):
+    """A caller's 4-D ``out`` of a histogram, checked before any launch: an int32
+    (\\*dims, K) tensor on ``device`` whose planes are laid out as ``planes_empty``
+    lays them (channels fastest) and do not overlap; returns (pointer, out_ld_i,
+    out_ld_t, out_ld_q) (``_planes_out`` for counts)."""
+    torch = _torch()
+    if not isinstance(out, torch.Tensor):
+        raise TypeError("out must be a device tensor")
+    if out.dtype != torch.int32:
+        raise TypeError(f"out must be int32, not {out.dtype}")
+    if out.dim() != 4 or tuple(out.shape) != (*dims, K):
+        raise ValueError(f"out is {tuple(out.shape)}, expected {(*dims, K)}")
+    if out.device != torch.device(device):
+        raise ValueError(f"out is on {out.device}, the data on {device}")
+    nc, ni, nt = dims
+    s0, s1, s2, s3 = out.stride()
+    ld_i = s1 if ni > 1 else nc
+    ld_t = s2 if nt > 1 else max(ni - 1, 0) * ld_i + nc
+    if (nc > 1 and s0 != 1) or ld_i < nc or ld_t < (ni - 1) * ld_i + nc:
+        raise ValueError(f"out strides {out.stride()} are not a Julia-order (channel-fastest) "
+                         f"layout of {(nc, ni, nt)} planes")
+    extent = max(nt - 1, 0) * ld_t + max(ni - 1, 0) * ld_i + nc
+    if s3 < extent:
+        raise ValueError(f"out strides {out.stride()}: the planes overlap")
+    return (out.data_ptr() if out.numel() else None), ld_i, ld_t, s3
+
+
+def hist_empty(nchan, nif, ntime, nplanes, device=None):
+    """``planes_empty`` for counts: an uninitialised int32 (nchan, nif, ntime,
+    nplanes) device tensor, plane after plane."""
+    torch = _torch()
+    return torch.empty((int(nplanes), int(ntime), int(nif), int(nchan)), dtype=torch.int32,
+                       device=device or "cuda").permute(3, 2, 1, 0)
+
+
+def histogram(x, nbins, lo, hi, fqavby=1, tavby=None, win=None, out=None, stream=None):
+    """Sample counts per bin of every fqavby x tavby block of the window
+    (bldp_histogram_f32; the rule of include/bldp.h).  x: a Float32 device
+    filterbank tensor; ``tavby=None``: the whole selected time range,
+    ``fqavby=None``: the whole selected channel range.  Returns an int32
+    (nc/F, ni, nt/T, nbins + 3) device tensor laid out plane after plane
+    (``hist_empty``; ``out`` when given, whatever it held): planes 0 .. nbins-1
+    are the bins of [lo, hi), plane nbins counts the samples below lo, nbins + 1
+    those at or above hi, nbins + 2 the NaNs.  The planes of a block add up to
+    F * T; counts are exact, so two calls give identical bits."""
+    torch = _torch()
+    B, lo, hi = _hist_args(nbins, lo, hi)
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
+        _need_f32("histogram", getattr(x, "dtype", type(x).__name__), "histogram")
+    shape = tuple(x.shape)
+    _check_bounds(win, shape)
+    fqavby, tavby = _hist_factors(shape, win, fqavby, tavby)
+    dims = out_shape(shape, win, fqavby, tavby)
+    ptr, nchan, nif, ntime = _abi_dims(x)
+    if out is None:
+        out = hist_empty(*dims, B + 3, device=x.device)
+    optr, ld_i, ld_t, ld_q = _hist_out(out, dims, B + 3, x.device)
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    rc = _lib.lib().bldp_histogram_f32(ptr, nchan, nif, ntime, wp, int(fqavby), int(tavby), B, lo,
+                                       hi, optr, ld_i, ld_t, ld_q, _lib.stream_ptr(stream))
+    _lib.check(rc, "bldp_histogram_f32")
+    return out
+
+
+HIST_PLAN_KEYS = ("path", "workgroups", "chunks_per_block", "blocks_per_workgroup", "lds_bytes",
+                  "replicas", "workspace_bytes", "vector_loads", "channel_lanes",
+                  "rows_per_chunk")
+
+
+def histogram_plan(x, nbins, lo, hi, fqavby=1, tavby=None, win=None) -> dict:
+    """Launch plan of ``histogram(x, nbins, lo, hi, fqavby, tavby, win=win)``
+    (bldp_histogram_plan_f32; launches nothing): ``path`` (_lib.HIST_PATHS),
+    ``workgroups`` per bank, ``chunks_per_block`` (the workgroups that share a
+    block), ``blocks_per_workgroup``, ``lds_bytes``, ``replicas`` of a block's
+    counters in LDS, ``workspace_bytes`` (0), ``vector_loads`` (1: float4),
+    ``channel_lanes`` and ``rows_per_chunk``."""
+    B, lo, hi = _hist_args(nbins, lo, hi)
+    shape = tuple(x.shape)
+    _check_bounds(win, shape)
+    fqavby, tavby = _hist_factors(shape, win, fqavby, tavby)
+    out_shape(shape, win, fqavby, tavby)
+    ptr, nchan, nif, ntime = _abi_dims(x)
+    info = (ctypes.c_int64 * 10)()
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    _lib.check(_lib.lib().bldp_histogram_plan_f32(ptr, nchan, nif, ntime, wp, int(fqavby),
+                                                  int(tavby), B, lo, hi, info),
+               "bldp_histogram_plan_f32")
+    d = dict(zip(HIST_PLAN_KEYS, [int(v) for v in info]))
+    d["path"] = _lib.HIST_PATHS[d["path"]]
+    return d
+
+
+def band_histogram(banks, nbins, lo, hi, fqavby=1, tavby=None, win=None, out=None, stream=None):
+    """``histogram`` of every bank of a band resident on ONE GPU in one launch
+    (bldp_band_histogram_f32): a dense int32 (nbank*nco, ni, nto, nbins + 3)
+    tensor, the vcat of the per-bank results."""
+    torch = _torch()
+    B, lo, hi = _hist_args(nbins, lo, hi)
+    banks = list(banks)
+    if not banks:
+        raise ValueError("no banks")
+    for b in banks:
+        if b.dtype != torch.float32:
+            _need_f32("band_histogram", b.dtype, "histogram")
+    shape = tuple(banks[0].shape)
+    _check_bounds(win, shape)
+    fqavby, tavby = _hist_factors(shape, win, fqavby, tavby)
+    nb = len(banks)
+    banks, geo, first, ptrs, (keep, wp) = _band_args(banks, fqavby, tavby, win, None)
+    dims = tuple(first.shape)
+    if out is None:
+        out = hist_empty(*dims, B + 3, device=banks[0].device)
+    optr, ld_i, ld_t, ld_q = _hist_out(out, dims, B + 3, banks[0].device)
+    plane = dims[0] * dims[1] * dims[2]
+    if plane and (ld_i, ld_t, ld_q) != (dims[0], dims[0] * dims[1], plane):
+        raise ValueError("out must be dense: plane q at q * nbank*nco*ni*nto elements")
+    rc = _lib.lib().bldp_band_histogram_f32(nb, ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp,
+                                            int(fqavby), int(tavby), B, lo, hi, optr,
+                                            _lib.stream_ptr(stream))
+    _lib.check(rc, "bldp_band_histogram_f32")
+    return out
+
+
+def histogram_host(a: np.ndarray, nbins, lo, hi, fqavby=1, tavby=None, win=None,
+                   device=0) -> np.ndarray:
+    """Host Fortran-ordered Float32 array in, Fortran-ordered int32 (nc/F, ni,
+    nt/T, nbins + 3) host array out (bldp_histogram_host_f32: the window's rows
+    staged on ``device`` once)."""
+    B, lo, hi = _hist_args(nbins, lo, hi)
+    a = np.asarray(a)
+    if a.dtype != np.float32:
+        _need_f32("histogram_host", a.dtype, "histogram")
+    if not a.flags.f_contiguous or a.ndim != 3:
+        raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
+    _check_bounds(win, a.shape)
+    fqavby, tavby = _hist_factors(a.shape, win, fqavby, tavby)
+    dims = out_shape(a.shape, win, fqavby, tavby)
+    out = np.empty((*dims, B + 3), dtype=np.uint32, order="F")
+    keep, wp = _lib.win_arg(_full_win(win, a.shape))
+    rc = _lib.lib().bldp_histogram_host_f32(
+        int(device), a.ctypes.data if a.size else None, a.shape[0], a.shape[1], a.shape[2], wp,
+        int(fqavby), int(tavby), B, lo, hi, out.ctypes.data if out.size else None)
+    _lib.check(rc, "bldp_histogram_host_f32")
+    return out.view(np.int32)  # counts are < 2^31
+
+
 def stitch(gathered, nbank, out=None, stream=None):
     """gathered: nbank dense (nc, ni, nt) blocks back to back (1-D or a
     [nbank, nt, ni, nc] contiguous tensor); returns vcat (nbank*nc, ni, nt)."""

@@ -122,6 +122,16 @@ def getoutliers(workers, fnames, idxs=(COLON, COLON, COLON), *, n=None, axis=2, 
                                               device=int(w)))
 
 
+def gethistogram(workers, fnames, idxs=(COLON, COLON, COLON), *, nbins, lo, hi, fqavby=1,
+                 tavby=None):
+    """getkurtosis' fan-out (src/gbt.jl:81-88) with the per-block histograms of
+    WorkerFunctions.gethistogram: per-bank dicts of the bin counts, the below,
+    above and nan counts and the bin edges from one read of every file."""
+    return _fanout(workers, fnames,
+                   lambda w, f: W.gethistogram(f, idxs, nbins=nbins, lo=lo, hi=hi, fqavby=fqavby,
+                                               tavby=tavby, device=int(w)))
+
+
 def getclean(workers, fnames, idxs=(COLON, COLON, COLON), *, fqavby=1, tavby=1, n=None, axis=2,
              nsigma=5.0, func="sum"):
     """getkurtosis' fan-out (src/gbt.jl:81-88) with the flag-and-integrate of

@@ -16,7 +16,8 @@ export gpu_init, gpu_finalize, gpu_pin, gpu_unpin, gpu_fqav, gpu_reduce, gpu_kur
        mad, quantile, gpu_quantile, gpu_quantile_plan, gpu_band_quantile,
        gpu_quantiles, gpu_quantiles_plan, gpu_band_quantiles,
        gpu_outliers, gpu_outliers_plan, gpu_band_outliers,
-       gpu_masked_reduce, gpu_band_masked_reduce
+       gpu_masked_reduce, gpu_band_masked_reduce,
+       gpu_histogram, gpu_histogram_plan, gpu_band_histogram
 
 const libbldp = get(ENV, "BLDP_LIB", joinpath(@__DIR__, "..", "libbldp_hip.so"))
 
@@ -796,6 +797,100 @@ function gpu_band_masked_reduce(banks::Vector{Ptr{Float32}}, dims::NTuple{3,Inte
          Ptr{UInt8}, Ptr{Int64}, Ptr{Float32}, Ptr{UInt32}, Ptr{Cvoid}),
         length(banks), banks, dims[1], dims[2], dims[3], win, fqavby, tavby, op, mask, mask_ld,
         out, kept, stream))
+    nothing
+end
+
+# ---- histogram: bldp_*histogram_* (sample counts per bin of every block) ----
+"""
+    gpu_histogram(A::Array{Float32,3}, nbins, lo, hi; fqavby=1, tavby=nothing,
+                  idxs=(:,:,:), dev=0) -> (counts, below, above, nan, edges)
+
+The sample counts of every `fqavby` x `tavby` block of `A[idxs...]` (`tavby` or
+`fqavby` `nothing`: the whole selected range of that axis) in `nbins` equal bins
+of `[lo, hi)`, on GPU `dev` (bldp_histogram_host_f32; the rule of include/bldp.h).
+`counts` is `Int32` `(nc/F, ni, nt/T, nbins)`; `below`, `above` and `nan`
+`(nc/F, ni, nt/T)` count the samples under `lo`, at or over `hi` and the NaNs.
+The counts of a block add up to `F*T` and are exact.  `edges`: the `nbins + 1`
+`Float64` bin edges, a reading aid only."""
+function gpu_histogram(A::Array{Float32,3}, nbins::Integer, lo::Real, hi::Real; fqavby=1,
+                       tavby=nothing, idxs::Tuple=(:, :, :), dev::Integer=0)
+    win = window(idxs, size(A))
+    nc, nt = win isa Ptr ? (size(A, 1), size(A, 3)) : (win[2], win[8])   # (all colons: no window)
+    F = fqavby === nothing ? max(nc, 1) : fqavby
+    T = tavby === nothing ? max(nt, 1) : tavby
+    shp = zeros(Int64, 3)
+    GC.@preserve win check(ccall((:bldp_reduce_shape, libbldp), Cint,
+        (Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Ptr{Int64}),
+        size(A, 1), size(A, 2), size(A, 3), win, F, T, shp))
+    out = Array{UInt32,4}(undef, shp[1], shp[2], shp[3], max(nbins, 0) + 3)
+    GC.@preserve A win out check(ccall((:bldp_histogram_host_f32, libbldp), Cint,
+        (Cint, Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Cint, Float64,
+         Float64, Ptr{UInt32}),
+        dev, A, size(A, 1), size(A, 2), size(A, 3), win, F, T, nbins, lo, hi, out))
+    c = Int32.(out)   # counts are < 2^31
+    lo32, hi32 = Float64(Float32(lo)), Float64(Float32(hi))
+    edges = [lo32 + k * (hi32 - lo32) / nbins for k in 0:nbins]
+    (c[:, :, :, 1:nbins], c[:, :, :, nbins + 1], c[:, :, :, nbins + 2], c[:, :, :, nbins + 3],
+     edges)
+end
+
+"""
+    gpu_histogram(in::Ptr{Float32}, dims, nbins, lo, hi, out::Ptr{UInt32}, fqavby=1, tavby=1;
+                  win=C_NULL, out_ld=nothing, stream=C_NULL)
+
+The same on DEVICE memory (bldp_histogram_f32; asynchronous on `stream`): plane q
+(`0:nbins-1` the bins, `nbins` below, `nbins+1` above, `nbins+2` nan) of block
+(c, i, t) at `out[c + i*out_ld[1] + t*out_ld[2] + q*out_ld[3]]` (0-based; dense by
+default).  `out` may hold anything beforehand.  Returns the output's dims."""
+function gpu_histogram(in::Ptr{Float32}, dims::NTuple{3,Integer}, nbins::Integer, lo::Real,
+                       hi::Real, out::Ptr{UInt32}, fqavby::Integer=1, tavby::Integer=1;
+                       win=Ptr{Int64}(C_NULL), out_ld=nothing, stream::Ptr{Cvoid}=C_NULL)
+    shp = zeros(Int64, 3)
+    GC.@preserve win check(ccall((:bldp_reduce_shape, libbldp), Cint,
+        (Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Ptr{Int64}),
+        dims[1], dims[2], dims[3], win, fqavby, tavby, shp))
+    ld = out_ld === nothing ? (shp[1], shp[1] * shp[2], shp[1] * shp[2] * shp[3]) : out_ld
+    GC.@preserve win check(ccall((:bldp_histogram_f32, libbldp), Cint,
+        (Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Cint, Float64, Float64,
+         Ptr{UInt32}, Int64, Int64, Int64, Ptr{Cvoid}),
+        in, dims[1], dims[2], dims[3], win, fqavby, tavby, nbins, lo, hi, out, ld[1], ld[2],
+        ld[3], stream))
+    (shp[1], shp[2], shp[3], nbins + 3)
+end
+
+"""
+    gpu_histogram_plan(dims, nbins, lo, hi, fqavby=1, tavby=1; win=C_NULL) -> Vector{Int64}
+
+The launch plan of that call (bldp_histogram_plan_f32; launches nothing): {path
+(0 block, 1 block_split, 2 lanes, 3 lanes_tsplit), workgroups per bank, chunks per
+block, blocks per workgroup, LDS bytes, replicas, workspace bytes, vector loads,
+lanes along the channels, rows per chunk}."""
+function gpu_histogram_plan(dims::NTuple{3,Integer}, nbins::Integer, lo::Real, hi::Real,
+                            fqavby::Integer=1, tavby::Integer=1; win=Ptr{Int64}(C_NULL))
+    info = zeros(Int64, 10)
+    GC.@preserve win info check(ccall((:bldp_histogram_plan_f32, libbldp), Cint,
+        (Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Cint, Float64, Float64,
+         Ptr{Int64}),
+        C_NULL, dims[1], dims[2], dims[3], win, fqavby, tavby, nbins, lo, hi, info))
+    info
+end
+
+"""
+    gpu_band_histogram(banks::Vector{Ptr{Float32}}, dims, nbins, lo, hi, out::Ptr{UInt32},
+                       fqavby=1, tavby=1; win=C_NULL, stream=C_NULL)
+
+The histogram of every bank of a band resident on one GPU in one launch
+(bldp_band_histogram_f32): `out` holds the dense `(nbank*nco, ni, nto, nbins + 3)`
+vcat of the banks' results."""
+function gpu_band_histogram(banks::Vector{Ptr{Float32}}, dims::NTuple{3,Integer},
+                            nbins::Integer, lo::Real, hi::Real, out::Ptr{UInt32},
+                            fqavby::Integer=1, tavby::Integer=1; win=Ptr{Int64}(C_NULL),
+                            stream::Ptr{Cvoid}=C_NULL)
+    GC.@preserve banks win check(ccall((:bldp_band_histogram_f32, libbldp), Cint,
+        (Cint, Ptr{Ptr{Float32}}, Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Cint, Float64,
+         Float64, Ptr{UInt32}, Ptr{Cvoid}),
+        length(banks), banks, dims[1], dims[2], dims[3], win, fqavby, tavby, nbins, lo, hi, out,
+        stream))
     nothing
 end
 

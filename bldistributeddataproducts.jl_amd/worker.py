@@ -933,6 +933,38 @@ def getclean(src, idxs=(COLON, COLON, COLON), *, fqavby=1, tavby=1, n=None, axis
                         lambda r: {k: engine.fb_to_numpy(t) for k, t in r.items()})
 
 
+def _hist_dict(r, nbins, edges):
+    """The dict of gethistogram from the (nco, ni, nto, nbins + 3) counts: views
+    of the one array."""
+    return {"counts": r[..., :nbins], "below": r[..., nbins], "above": r[..., nbins + 1],
+            "nan": r[..., nbins + 2], "edges": edges}
+
+
+def gethistogram(src, idxs=(COLON, COLON, COLON), *, nbins, lo, hi, fqavby=1, tavby=None,
+                 device=0):
+    """The distribution of every fqavby x tavby block of the window
+    (``tavby=None``: the whole selected time range, ``fqavby=None``: the whole
+    selected channel range) from ONE streaming read of the data: a dict with
+    ``"counts"`` (int32, (nc/F, ni, nt/T, nbins)), how many samples of the block
+    fall into each of ``nbins`` equal bins of [lo, hi), ``"below"``, ``"above"``
+    and ``"nan"`` (int32, (nc/F, ni, nt/T)), the samples under lo, at or over hi
+    and the NaNs, all views of one array whose planes add up to F * T, and
+    ``"edges"``, the nbins + 1 Float64 bin edges (a reading aid: the rule of
+    include/bldp.h decides; engine.histogram).  Counts are exact.  Files reach
+    the GPU as getdata reads them (window_on_device) and a host array is staged
+    there, both returning host arrays; a device tensor stays on the device.
+    Float32 data only: any other element type (host array, device tensor, 8/16-bit
+    SIGPROC file) is a TypeError."""
+    B, lo, hi = engine._hist_args(nbins, lo, hi)  # (the ValueError before any file is touched)
+    edges = engine.hist_edges(B, lo, hi)
+    kw = dict(fqavby=fqavby, tavby=tavby)
+    return _hist_dict(_read_moment(
+        "gethistogram", "histogram", src, sanitizeidxs(idxs), device,
+        lambda x, win: engine.histogram(x, B, lo, hi, win=win, **kw),
+        lambda a, win: engine.histogram_host(a, B, lo, hi, win=win, device=device, **kw),
+        engine.planes_to_numpy), B, edges)
+
+
 getinventory = readers.getinventory
 getfbheader = readers.getfbheader
 getfbh5header = readers.getfbh5header

@@ -93,7 +93,8 @@ extern "C" {
  *    (additive, same version) the bldp_quantile_* entry points;
  *    (additive, same version) the bldp_quantiles_* entry points;
  *    (additive, same version) the bldp_outliers_* entry points;
- *    (additive, same version) the bldp_*masked_reduce_* entry points */
+ *    (additive, same version) the bldp_*masked_reduce_* entry points;
+ *    (additive, same version) the bldp_*histogram_* entry points */
 #define BLDP_ABI_VERSION 5
 
 #if defined(BLDP_BUILD)
@@ -862,6 +863,79 @@ BLDP_API int bldp_masked_reduce_host_f32(int dev, const float *in, int64_t nchan
                                          int64_t ntime, const int64_t *win, int64_t fqavby,
                                          int64_t tavby, int op, const uint8_t *mask,
                                          const int64_t *mask_ld, float *out, uint32_t *kept);
+
+/* Histogram: the sample counts per bin of every block.  One streaming read of
+ * the window gives, for every fqavby x tavby block of the reduce, how many of its
+ * samples fall into each of nbins = B equal bins of [lo, hi), how many lie below
+ * and above, and how many are NaN.  Float32 input; additive in ABI 5.
+ *
+ * The block of output (c', i, t') is the reduce's: F = fqavby selected channels by
+ * T = tavby selected spectra, after the window's offsets, steps and direction.
+ *
+ * Parameters.  Each breach is BLDP_EINVAL with a message and launches nothing:
+ *  - 1 <= B <= BLDP_MAX_HIST_BINS;
+ *  - lo32 = Float32(lo) and hi32 = Float32(hi) are finite, and lo32 < hi32;
+ *  - w = hi32 - lo32 (Float32) is finite;
+ *  - s = Float32(B) / w (Float32 division) is finite and above 0;
+ *  - F * T <= 2^31 - 1 (Python and the shim read Int32).
+ * s is computed on the host, once, and handed to the kernel as a Float32.
+ *
+ * The rule.  A sample x is classed in this order:
+ *  1. x != x: it goes to nan.
+ *  2. x < lo32: it goes to below.
+ *  3. x >= hi32: it goes to above.
+ *  4. Otherwise k = floor((x - lo32) * s) goes to bin min(k, B - 1).
+ * The subtraction and the multiplication are two Float32 operations, each rounded
+ * once; the rule is not x*s - lo*s.  -Inf is below, +Inf above, and -0.0 with
+ * lo = 0 is in bin 0.  A sample is classed before any conversion to an integer,
+ * and the index is clamped before it addresses anything.  The clamp is needed:
+ * the largest Float32 below hi32 gives k == B for (lo, hi, B) = (-1, 1, 7),
+ * (-5, 5, 100) and (-3, 3, 6).  The rule is monotone in x, so every bin is an
+ * interval.  Bin k is roughly [lo32 + k*w/B, lo32 + (k+1)*w/B); those edges are
+ * a reading aid only, the rule above decides.
+ *
+ * Output: B + 3 planes of uint32 counts.  Planes 0 .. B-1 are the bins, plane B
+ * is below, B + 1 above, B + 2 nan.  Plane q of block (c', i, t') is
+ * out[c' + out_ld_i * i + out_ld_t * t' + out_ld_q * q] (the layout of
+ * bldp_quantiles_f32).  In every block the planes add up to F * T.  The entry
+ * points zero what they need themselves, on the caller's stream: out may hold
+ * anything.  Counts are integers, so the result does not depend on how lanes,
+ * waves and workgroups share a block, and two calls give identical bits.
+ *
+ * The paths (info[0]): 0 "block", one workgroup per block; 1 "block_split", a
+ * block's rows and columns chunked over several workgroups whose counts are
+ * merged by atomic adds into the zeroed output; 2 "lanes", several blocks that are
+ * neighbours along the channels share a workgroup, its lanes along the channels;
+ * 3 "lanes_tsplit", the same with the time range chunked over workgroups (atomic
+ * adds).  Every workgroup counts into LDS and flushes once.  No workspace.
+ *
+ * bldp_histogram_plan_f32: info = {path, workgroups per bank, chunks per block,
+ * blocks per workgroup, LDS bytes, replicas of a block's counters in LDS,
+ * workspace bytes (0), vector loads 1 / 0, lanes along the channels, rows per
+ * chunk}.  Launches nothing and needs no GPU; the pointer may be null (its
+ * alignment only chooses the load width, and a null pointer counts as aligned).
+ * bldp_histogram_f32: device pointers, asynchronous on `stream`.
+ * bldp_band_histogram_f32: in[] is a HOST array of device pointers of banks with
+ * one geometry on one GPU; out is the dense (nbank*nco, ni, nto, B + 3) vcat of
+ * the per-bank results.
+ * bldp_histogram_host_f32: host in, host dense (nco, ni, nto, B + 3) out; the
+ * window's rows are staged on device `dev` once.  Synchronous. */
+#define BLDP_MAX_HIST_BINS 4096
+BLDP_API int bldp_histogram_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                                     const int64_t *win, int64_t fqavby, int64_t tavby,
+                                     int nbins, double lo, double hi, int64_t info[10]);
+BLDP_API int bldp_histogram_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                                const int64_t *win, int64_t fqavby, int64_t tavby, int nbins,
+                                double lo, double hi, uint32_t *out, int64_t out_ld_i,
+                                int64_t out_ld_t, int64_t out_ld_q, void *stream);
+BLDP_API int bldp_band_histogram_f32(int nbank, const float *const *in, int64_t nchan,
+                                     int64_t nif, int64_t ntime, const int64_t *win,
+                                     int64_t fqavby, int64_t tavby, int nbins, double lo,
+                                     double hi, uint32_t *out, void *stream);
+BLDP_API int bldp_histogram_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                     int64_t ntime, const int64_t *win, int64_t fqavby,
+                                     int64_t tavby, int nbins, double lo, double hi,
+                                     uint32_t *out);
 
 /* Element types other than Float32 (what Blio maps SIGPROC nbits 8 / 16 to, and
  * what HDF5.jl returns for an integer or Float64 dataset: the reference's
