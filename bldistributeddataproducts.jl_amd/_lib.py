@@ -115,6 +115,9 @@ MASK_LOADS = {0: "byte", 1: "dword", 2: "row"}
 # chunked over workgroups (merged by atomic adds), several neighbouring blocks in
 # a workgroup with its lanes along the channels, the same with the time chunked
 HIST_PATHS = {0: "block", 1: "block_split", 2: "lanes", 3: "lanes_tsplit"}
+# hits (csrc/hits.hip): how the flags are loaded: a byte per element, one aligned
+# load of 4 or 16 flags a lane, one byte per row (stride 0 along the channels)
+HITS_LOADS = {0: "byte", 1: "wide", 2: "row"}
 MAX_HIST_BINS = 4096
 
 BLDP_OK, BLDP_EINVAL, BLDP_EDIM, BLDP_EHIP, BLDP_ENOMEM, BLDP_EBOUNDS = 0, -1, -2, -3, -5, -6
@@ -231,6 +234,10 @@ SIGNATURES = {
     "bldp_histogram_f32": ([P, I64, I64, I64, P, I64, I64, I, D, D, P, I64, I64, I64, P], I),
     "bldp_band_histogram_f32": ([I, P, I64, I64, I64, P, I64, I64, I, D, D, P, P], I),
     "bldp_histogram_host_f32": ([I, P, I64, I64, I64, P, I64, I64, I, D, D, P], I),
+    "bldp_hits_plan_f32": ([P, I64, I64, I64, P, P, P, I64, P], I),
+    "bldp_hits_f32": ([P, I64, I64, I64, P, P, P, I64, P, P, P, P], I),
+    "bldp_band_hits_f32": ([I, P, I64, I64, I64, P, P, P, I64, P, P, P, P], I),
+    "bldp_hits_host_f32": ([I, P, I64, I64, I64, P, P, P, I64, P, P, P], I),
     "bldp_fqav_range": ([D, D, I64, I64, P, P, P], I),
     "bldp_synth_f32": ([P, I64, I64, I64, I64, U64, I, P], I),
     "bldp_reduce_out_dtype": ([I, I], I),

@@ -2223,6 +2223,139 @@ int bldp_band_histogram_f32(int nbank, const float *const *in, int64_t nchan, in
                   nbank * d[0], nbank * d[0] * d[1], nbank * d[0] * d[1] * d[2], stream);
 }
 
+// ---- hits: the flagged samples of a window as an ordered list ----
+// Checks, window and plan of a hits call (every entry point).  The window is
+// the vcat (nbank*nc, ni, nt) of the banks; mask_ld NULL: the dense mask of that
+// shape.  query: the plan call (null pointers count as aligned).
+static int hits_prepare(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                        int64_t ntime, const int64_t *win, const uint8_t *mask,
+                        const int64_t *mask_ld, int64_t cap, int64_t *idx, float *val,
+                        uint64_t *total, bool query, HitsArgs *ap, Plan *pp, bool *empty) {
+  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
+    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
+  if (cap < 0) return fail(BLDP_EINVAL, "hits: cap=%lld is negative", (long long)cap);
+  if (!query && !total) return fail(BLDP_EINVAL, "hits: null total pointer");
+  Geo g;
+  int rc = resolve_window(nchan, nif, ntime, win, &g);
+  if (rc) return rc;
+  const int64_t NC = nbank * g.nc;
+  int64_t ld[3] = {1, NC, NC * g.ni};
+  if (mask_ld)
+    for (int ax = 0; ax < 3; ++ax) {
+      ld[ax] = mask_ld[ax];
+      if (ld[ax] < 0)
+        return fail(BLDP_EINVAL, "hits: mask stride %d is negative (%lld)", ax, (long long)ld[ax]);
+    }
+  HitsArgs &a = *ap;
+  a = HitsArgs{};
+  a.nbank = nbank;
+  a.nc = g.nc, a.NC = NC, a.ni = g.ni, a.nt = g.nt;
+  a.N = NC * g.ni * g.nt;
+  a.in_off = g.off;
+  a.in_cs = g.cs;
+  a.in_ld_i = g.ld_i;
+  a.in_ld_t = g.ld_t;
+  a.mask = mask;
+  a.m_cs = ld[0], a.m_ld_i = ld[1], a.m_ld_t = ld[2];
+  a.cap = cap;
+  a.idx = idx;
+  a.val = reinterpret_cast<uint32_t *>(val);
+  a.total = total;
+  *empty = a.N == 0;
+  *pp = Plan{};
+  if (*empty) return BLDP_OK;
+  if (!in) return fail(BLDP_EINVAL, "hits: null input pointer array");
+  for (int b = 0; b < nbank; ++b) a.in[b] = in[b];
+  rc = plan_hits(a, (uintptr_t)mask, pp);
+  if (rc || query) return rc;
+  for (int b = 0; b < nbank; ++b)
+    if (!in[b]) return fail(BLDP_EINVAL, "hits: null input pointer (bank %d)", b);
+  if (!mask) return fail(BLDP_EINVAL, "hits: null mask pointer");
+  // the outputs may not overlap the window's elements, the mask's span, nor each other
+  int64_t lo = g.off, hi = g.off;  // lowest and highest element offset of the window
+  const int64_t span[3] = {(g.nc - 1) * g.cs, (g.ni - 1) * g.ld_i, (g.nt - 1) * g.ld_t};
+  for (int ax = 0; ax < 3; ++ax) (span[ax] < 0 ? lo : hi) += span[ax];
+  const size_t wbytes = 4 * (size_t)(hi - lo + 1);
+  const size_t mbytes = (size_t)((NC - 1) * ld[0] + (g.ni - 1) * ld[1] + (g.nt - 1) * ld[2] + 1);
+  const size_t n = (size_t)std::min(cap, a.N);  // entries a list can get
+  const void *optr[3] = {idx, val, total};
+  const size_t olen[3] = {8 * n, 4 * n, 8};
+  static const char *const name[3] = {"idx", "val", "total"};
+  for (int q = 0; q < 3; ++q) {
+    if (!optr[q]) continue;
+    for (int b = 0; b < nbank; ++b)
+      if (spans_overlap(optr[q], olen[q], in[b] + lo, wbytes))
+        return fail(BLDP_EINVAL, "hits: %s overlaps the input window (bank %d)", name[q], b);
+    if (spans_overlap(optr[q], olen[q], mask, mbytes))
+      return fail(BLDP_EINVAL, "hits: %s overlaps the mask", name[q]);
+    for (int r = q + 1; r < 3; ++r)
+      if (optr[r] && spans_overlap(optr[q], olen[q], optr[r], olen[r]))
+        return fail(BLDP_EINVAL, "hits: %s and %s overlap", name[q], name[r]);
+  }
+  return BLDP_OK;
+}
+
+static int hits_run(int nbank, const float *const *in, int64_t nchan, int64_t nif, int64_t ntime,
+                    const int64_t *win, const uint8_t *mask, const int64_t *mask_ld, int64_t cap,
+                    int64_t *idx, float *val, uint64_t *total, void *stream) {
+  HitsArgs a;
+  Plan p;
+  bool empty = false;
+  int rc = hits_prepare(nbank, in, nchan, nif, ntime, win, mask, mask_ld, cap, idx, val, total,
+                        false, &a, &p, &empty);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (empty) {  // no launch: total = 0
+    HIPCHK(hipMemsetAsync(total, 0, sizeof(uint64_t), s));
+    return BLDP_OK;
+  }
+  ScratchLease lease;  // held until the last launch is queued
+  rc = scratch_lease(s, p.ws_bytes, &lease);
+  if (rc) return rc;
+  a.woff = static_cast<uint64_t *>(lease.ptr);
+  a.wcount = reinterpret_cast<uint32_t *>(a.woff + a.tiles);
+  hipError_t e = launch_hits(a, p, cap > 0 && (idx || val), s);
+  if (e != hipSuccess) return fail(BLDP_EHIP, "hits launch: %s", hipGetErrorString(e));
+  return BLDP_OK;
+}
+
+int bldp_hits_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                       const int64_t *win, const uint8_t *mask, const int64_t *mask_ld,
+                       int64_t cap, int64_t info[10]) {
+  if (!info) return fail(BLDP_EINVAL, "null info");
+  HitsArgs a;
+  Plan p;
+  bool empty = false;
+  const float *ins[1] = {in};
+  int rc = hits_prepare(1, ins, nchan, nif, ntime, win, mask, mask_ld, cap, nullptr, nullptr,
+                        nullptr, true, &a, &p, &empty);
+  if (rc) return rc;
+  for (int q = 0; q < 10; ++q) info[q] = 0;
+  if (empty) return BLDP_OK;  // (nothing is launched)
+  info[0] = p.path;
+  info[1] = a.E;
+  info[2] = a.tiles;
+  info[3] = (int64_t)p.ws_bytes;
+  info[4] = p.nout;
+  info[5] = a.W;
+  info[6] = cap == 0 ? 2 : 3;
+  return BLDP_OK;
+}
+
+int bldp_hits_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win,
+                  const uint8_t *mask, const int64_t *mask_ld, int64_t cap, int64_t *idx,
+                  float *val, uint64_t *total, void *stream) {
+  const float *ins[1] = {in};
+  return hits_run(1, ins, nchan, nif, ntime, win, mask, mask_ld, cap, idx, val, total, stream);
+}
+
+int bldp_band_hits_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                       int64_t ntime, const int64_t *win, const uint8_t *mask,
+                       const int64_t *mask_ld, int64_t cap, int64_t *idx, float *val,
+                       uint64_t *total, void *stream) {
+  return hits_run(nbank, in, nchan, nif, ntime, win, mask, mask_ld, cap, idx, val, total, stream);
+}
+
 int bldp_reduce_out_dtype(int dtype, int op) {
   const int d = typed_out_dtype(dtype, op);
   if (d < 0) return fail(BLDP_EINVAL, "unknown element type %d or op %d", dtype, op);

@@ -370,6 +370,45 @@ int plan_hist(HistArgs &a, bool words, int num_cus, Plan *p);
 // Zeroes the output first when a.atomic, on the same stream.
 hipError_t launch_hist(const HistArgs &a, const Plan &p, hipStream_t s);
 
+// The flagged samples of a window as an ordered list (hits.hip).  The window is
+// the vcat (NC = nbank*nc, ni, nt) of the banks, N elements in the linear order
+// k = c + NC*(i + ni*t); element k of bank b = c / nc at in[b][in_off + (c % nc)*in_cs
+// + i*in_ld_i + t*in_ld_t], its flag at mask[c*m_cs + i*m_ld_i + t*m_ld_t] (bytes).
+// idx[j] / val[j], j < min(total, cap): the j-th flagged k and that sample's bits;
+// a null list is not written.  A by-value kernel argument of the hits kernels alone.
+struct HitsArgs {
+  const float *in[BLDP_MAX_BANKS];  // banks with identical geometry
+  const uint8_t *mask;
+  int64_t *idx;
+  uint32_t *val;
+  uint64_t *total;
+  uint64_t *woff;    // workspace: the tiles' list offsets [tiles]
+  uint32_t *wcount;  // workspace: the tiles' flag counts [tiles]
+  int64_t in_off, in_cs, in_ld_i, in_ld_t;
+  int64_t nc, NC, ni, nt, N;
+  int64_t m_cs, m_ld_i, m_ld_t;
+  int64_t cap;
+  // the plan (plan_hits)
+  int64_t E;       // elements of a tile, a multiple of 256 * W
+  int64_t tiles;   // ceil(N / E), one workgroup each
+  int32_t nbank;
+  int32_t mform;   // MaskForm (MASK_DWORD: one aligned load of W flags)
+  int32_t W;       // flags per lane per load: 1, 4 or 16
+  int32_t mdense;  // the flag of element k is mask[k]
+};
+// The kernels of a plan: k_hits_count / k_hits_write over bytes, dwords of 4
+// flags, 16-byte loads of 16 flags, or (the count alone) one byte per row.
+enum HitsKernel { HITS_BYTE = 0, HITS_WIDE4 = 1, HITS_WIDE16 = 2, HITS_ROW = 3 };
+// Fills the plan of an args struct whose shape, stride and mask fields are set,
+// without a GPU; mask_addr: the mask pointer (its alignment chooses the load; 0
+// counts as aligned).  p: path = the MaskForm, lpg = W, grid = gx = the tiles,
+// nout = the chunks the scan loops over, ws_bytes, kernel = the HitsKernel.
+// BLDP_OK or, with the message recorded, BLDP_EINVAL for more tiles than one
+// launch takes.
+int plan_hits(HitsArgs &a, uintptr_t mask_addr, Plan *p);
+// count, scan and (write) the list kernel, on one stream
+hipError_t launch_hits(const HitsArgs &a, const Plan &p, bool write, hipStream_t s);
+
 // median / var / std of every block of T selected spectra of every (channel,
 // IF) column (tstats.hip): tavfunc, fqav's rule on the time axis.  Window
 // element (c, i, t) of bank k at in[k][in_off + c*in_cs + i*in_ld_i +

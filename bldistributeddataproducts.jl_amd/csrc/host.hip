@@ -610,6 +610,63 @@ extern "C" int bldp_histogram_host_f32(int dev, const float *in, int64_t nchan, 
   });
 }
 
+// The same staging for the hits list: the window's rows and the mask's span go to
+// the device once.  A count-only call gives total; the lists are then sized
+// min(total, cap), so the mask is counted twice on the device and the staging
+// never holds more than the entries that come back.
+extern "C" int bldp_hits_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                  int64_t ntime, const int64_t *win, const uint8_t *mask,
+                                  const int64_t *mask_ld, int64_t cap, int64_t *idx, float *val,
+                                  uint64_t *total) {
+  // (every argument check, before any staging)
+  int64_t info[10];
+  int rc = bldp_hits_plan_f32(nullptr, nchan, nif, ntime, win, nullptr, mask_ld, cap, info);
+  if (rc) return rc;
+  if (!total) return bldp::set_error(BLDP_EINVAL, "hits: null total pointer");
+  int64_t sh[3];
+  rc = bldp_reduce_shape(nchan, nif, ntime, win, 1, 1, sh);
+  if (rc) return rc;
+  const int64_t nc = sh[0], ni = sh[1], nt = sh[2];
+  *total = 0;
+  if (nc * ni * nt == 0) return BLDP_OK;
+  if (!in) return bldp::set_error(BLDP_EINVAL, "hits: null input pointer");
+  if (!mask) return bldp::set_error(BLDP_EINVAL, "hits: null mask pointer");
+  const int64_t ld[3] = {mask_ld ? mask_ld[0] : 1, mask_ld ? mask_ld[1] : nc,
+                         mask_ld ? mask_ld[2] : nc * ni};
+  const size_t mb = (size_t)((nc - 1) * ld[0] + (ni - 1) * ld[1] + (nt - 1) * ld[2] + 1);
+  const size_t tot_off = (mb + 7) & ~(size_t)7;  // total sits behind the staged mask
+  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
+  return with_stager(dev, [&](bldp::Stager *sg) -> int {
+    float *dbuf, *dval = nullptr;
+    uint8_t *dmask;
+    int64_t *didx = nullptr;
+    int r = bldp::stager_buffer(sg, 0, (size_t)(h.span * ni * nt) * 4, (void **)&dbuf);
+    if (!r) r = bldp::stager_buffer(sg, 1, tot_off + sizeof(uint64_t), (void **)&dmask);
+    if (!r) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
+    if (r) return r;
+    uint64_t *dtotal = reinterpret_cast<uint64_t *>(dmask + tot_off);
+    HCHK(hipMemcpyAsync(dmask, mask, mb, hipMemcpyHostToDevice, sg->st[0]));
+    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
+    r = bldp_hits_f32(dbuf, h.span, ni, nt, dwin, dmask, ld, 0, nullptr, nullptr, dtotal,
+                      sg->st[0]);
+    if (r) return r;
+    HCHK(hipMemcpyAsync(total, dtotal, sizeof(uint64_t), hipMemcpyDeviceToHost, sg->st[0]));
+    HCHK(hipStreamSynchronize(sg->st[0]));
+    const size_t n = (size_t)std::min<uint64_t>(*total, (uint64_t)cap);
+    if (n == 0 || (!idx && !val)) return BLDP_OK;
+    if (idx) r = bldp::stager_buffer(sg, 2, n * sizeof(int64_t), (void **)&didx);
+    if (!r && val) r = bldp::stager_buffer(sg, 3, n * sizeof(float), (void **)&dval);
+    if (!r)
+      r = bldp_hits_f32(dbuf, h.span, ni, nt, dwin, dmask, ld, (int64_t)n, didx, dval, dtotal,
+                        sg->st[0]);
+    if (r) return r;
+    if (idx)
+      HCHK(hipMemcpyAsync(idx, didx, n * sizeof(int64_t), hipMemcpyDeviceToHost, sg->st[0]));
+    if (val) HCHK(hipMemcpyAsync(val, dval, n * sizeof(float), hipMemcpyDeviceToHost, sg->st[0]));
+    return BLDP_OK;
+  });
+}
+
 // ---------------------------------------------------------------------------
 // Host forms of the typed entry points (include/bldp.h), staged like the
 // Float32 forms above: only the window's rows (its channel span of every

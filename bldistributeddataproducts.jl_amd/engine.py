@@ -1458,6 +1458,216 @@ def masked_reduce_host(a: np.ndarray, mask: np.ndarray, fqavby=1, tavby=1, op="s
     return {"data": data, "kept": kept.view(np.int32)}  # counts are < 2^31
 
 
+def _hits_cap(maxhits):
+    """``maxhits`` as the ABI's cap: None stays None (all), else an int >= 0
+    (TypeError for anything that is no integer, ValueError below 0)."""
+    if maxhits is None:
+        return None
+    if isinstance(maxhits, bool) or not isinstance(maxhits, (int, np.integer)):
+        raise TypeError(f"hits: maxhits must be an integer or None, not {type(maxhits).__name__}")
+    if maxhits < 0:
+        raise ValueError(f"hits: maxhits={maxhits} is negative")
+    return int(maxhits)
+
+
+def _hits_stream(stream, device):
+    """The torch stream a hits call queues its launches on: ``stream`` (a raw
+    hipStream_t is wrapped), or torch's current stream."""
+    torch = _torch()
+    if stream is None:
+        return torch.cuda.current_stream()
+    if isinstance(stream, int):
+        return torch.cuda.ExternalStream(stream, device=device)
+    return stream
+
+
+def _hits_lists(call, cap, device, stream):
+    """The dict of ``hits`` from ``call(cap, idx, val, total)``, which makes the
+    library call with those device tensors (None: a null pointer) on ``stream``.
+    ``total`` and the lists are made under that stream, and the stream is
+    synchronised before every read of ``total``: torch streams do not wait for
+    one another, so a read on any other stream could come before the scan's
+    store."""
+    torch = _torch()
+    s = _hits_stream(stream, device)
+    outer = torch.cuda.current_stream()
+    with torch.cuda.stream(s):
+        total = torch.empty(1, dtype=torch.int64, device=device)
+        if cap is None:  # count, then list exactly
+            call(0, None, None, total)
+            s.synchronize()
+            cap = int(total.item())
+        idx = torch.empty(cap, dtype=torch.int64, device=device)
+        val = torch.empty(cap, dtype=torch.float32, device=device)
+        call(cap, idx, val, total)
+        s.synchronize()
+        n = int(total.item())
+    if outer != s:  # the caller goes on using the lists on its own stream
+        idx.record_stream(outer)
+        val.record_stream(outer)
+    return {"total": n, "index": idx[:min(n, cap)], "value": val[:min(n, cap)]}
+
+
+def hits(x, mask, maxhits=None, win=None, stream=None):
+    """The flagged samples of the window as an ordered list, Julia's
+    ``findall(!iszero, mask)`` and ``A[mask]`` on the device (bldp_hits_f32; the
+    rule of include/bldp.h).  x: a Float32 device filterbank tensor; ``mask``: a
+    uint8 or bool device tensor of the window's shape (nc, ni, nt), any axis of
+    which may be 1 (a broadcast), as ``masked_reduce`` takes it; a byte that is
+    not 0 flags the sample.  Returns a dict: ``"total"`` (a Python int), the
+    number of flagged samples, always exact; ``"index"`` (int64, 0-based), their
+    linear window indices k = c + nc*(i + ni*t) in ascending order
+    (``hits_unravel`` gives channel, IF and time); ``"value"`` (float32), those
+    samples, bits untouched.  With a number, ``maxhits`` needs one call: the
+    lists are allocated at ``maxhits`` and returned cut to min(total, maxhits),
+    the first in that order.  ``maxhits=None`` means all: a count-only call, a
+    read of ``total``, an exact allocation and a second call, so the mask is
+    counted twice.  Either way ``total`` is read back: the call synchronises
+    ``stream`` (default: torch's current stream), on which the launches are
+    queued and under which the lists are allocated."""
+    torch = _torch()
+    cap = _hits_cap(maxhits)
+    if x.dtype != torch.float32:
+        _need_f32("hits", x.dtype, "hits")
+    shape = tuple(x.shape)
+    _check_bounds(win, shape)
+    wshape = window_shape(win, shape)
+    mptr, ld = _mask_arg(mask, wshape, x.device, "hits")
+    ptr, nchan, nif, ntime = _abi_dims(x)
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+
+    def call(c, idx, val, total):
+        rc = _lib.lib().bldp_hits_f32(ptr, nchan, nif, ntime, wp, mptr, ld, c, _ptr(idx),
+                                      _ptr(val), total.data_ptr(), _lib.stream_ptr(stream))
+        _lib.check(rc, "bldp_hits_f32")
+
+    return _hits_lists(call, cap, x.device, stream)
+
+
+HITS_PLAN_KEYS = ("mask_loads", "tile_elems", "tiles", "workspace_bytes", "scan_chunks",
+                  "flags_per_load", "launches")
+
+
+def hits_plan(x, mask, maxhits=None, win=None) -> dict:
+    """Launch plan of ``hits(x, mask, maxhits, win=win)`` (bldp_hits_plan_f32):
+    ``mask_loads`` (_lib.HITS_LOADS: "byte" per element, "wide" loads of
+    ``flags_per_load`` = 4 or 16 flags a lane, one byte per "row"), ``tile_elems``
+    and ``tiles`` (one workgroup each), ``workspace_bytes``, ``scan_chunks`` (the
+    passes of the one scan workgroup) and ``launches`` (2 for ``maxhits=0``, the
+    count-only call, else 3)."""
+    cap = _hits_cap(maxhits)
+    shape = tuple(x.shape)
+    _check_bounds(win, shape)
+    wshape = window_shape(win, shape)
+    mptr, ld = _mask_arg(mask, wshape, x.device, "hits_plan")
+    ptr, nchan, nif, ntime = _abi_dims(x)
+    info = (ctypes.c_int64 * 10)()
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    _lib.check(_lib.lib().bldp_hits_plan_f32(ptr, nchan, nif, ntime, wp, mptr, ld,
+                                             1 if cap is None else cap, info),
+               "bldp_hits_plan_f32")
+    d = dict(zip(HITS_PLAN_KEYS, [int(v) for v in info]))
+    d["mask_loads"] = _lib.HITS_LOADS[d["mask_loads"]]
+    return d
+
+
+def band_hits(banks, mask, maxhits=None, win=None, stream=None):
+    """``hits`` of a band resident on ONE GPU (bldp_band_hits_f32): the window is
+    the vcat (nbank*nc, ni, nt) of the banks' windows and ``mask`` covers it, any
+    axis allowed to be 1: bank b's channel c is channel b*nc + c of the mask and
+    of the linear index (``band_outliers``' mask as it is), so within one (IF,
+    time) row all of bank 0 comes before bank 1."""
+    torch = _torch()
+    cap = _hits_cap(maxhits)
+    banks = list(banks)
+    if not banks:
+        raise ValueError("no banks")
+    for b in banks:
+        if b.dtype != torch.float32:
+            _need_f32("band_hits", b.dtype, "hits")
+    shape = tuple(banks[0].shape)
+    _check_bounds(win, shape)
+    nc, ni, nt = window_shape(win, shape)
+    nb = len(banks)
+    mptr, ld = _mask_arg(mask, (nb * nc, ni, nt), banks[0].device, "band_hits")
+    geo = _abi_dims(banks[0])[1:]
+    for b in banks:
+        if tuple(b.shape) != shape:
+            raise ValueError("all banks of a band must have the same shape")
+        if _abi_dims(b)[1:] != geo:
+            raise ValueError("all banks of a band must have the same layout")
+    ptrs = (ctypes.c_void_p * nb)(*[b.data_ptr() for b in banks])
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+
+    def call(c, idx, val, total):
+        rc = _lib.lib().bldp_band_hits_f32(nb, ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp, mptr,
+                                           ld, c, _ptr(idx), _ptr(val), total.data_ptr(),
+                                           _lib.stream_ptr(stream))
+        _lib.check(rc, "bldp_band_hits_f32")
+
+    return _hits_lists(call, cap, banks[0].device, stream)
+
+
+def hits_host(a: np.ndarray, mask: np.ndarray, maxhits=None, win=None, device=0) -> dict:
+    """Host Fortran-ordered Float32 array and host uint8 / bool mask in (the
+    window's shape, any axis allowed to be 1), the dict of ``hits`` with host
+    arrays out (bldp_hits_host_f32: the window's rows and the mask staged on
+    ``device`` once; the mask is counted twice there)."""
+    cap = _hits_cap(maxhits)
+    a = np.asarray(a)
+    if a.dtype != np.float32:
+        _need_f32("hits_host", a.dtype, "hits")
+    if not a.flags.f_contiguous or a.ndim != 3:
+        raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
+    m = np.asarray(mask)
+    if m.dtype not in (np.dtype(np.uint8), np.dtype(np.bool_)):
+        raise TypeError(f"hits_host: the mask must be a uint8 or bool array, not {m.dtype}")
+    _check_bounds(win, a.shape)
+    wshape = window_shape(win, a.shape)
+    if m.ndim == 3 and any(s < 0 for s in m.strides):
+        m = np.asfortranarray(m)
+    ld = (ctypes.c_int64 * 3)(*_mask_strides(m.shape, m.strides, wshape, "hits_host"))
+    keep, wp = _lib.win_arg(_full_win(win, a.shape))
+    total = ctypes.c_uint64(0)
+
+    def call(c, idx, val):
+        rc = _lib.lib().bldp_hits_host_f32(
+            int(device), a.ctypes.data if a.size else None, a.shape[0], a.shape[1], a.shape[2],
+            wp, m.ctypes.data if m.size else None, ld, c,
+            idx.ctypes.data if idx is not None and idx.size else None,
+            val.ctypes.data if val is not None and val.size else None, ctypes.byref(total))
+        _lib.check(rc, "bldp_hits_host_f32")
+
+    if cap is None:
+        call(0, None, None)
+        cap = int(total.value)
+    idx = np.empty(cap, dtype=np.int64)
+    val = np.empty(cap, dtype=np.float32)
+    call(cap, idx, val)
+    n = min(int(total.value), cap)
+    return {"total": int(total.value), "index": idx[:n], "value": val[:n]}
+
+
+def hits_unravel(index, wshape):
+    """(channel, if, time), 0-based, of the linear window indices of ``hits`` over
+    a window of shape ``wshape`` = (nc, ni, nt): k = c + nc*(i + ni*t).  Works on
+    NumPy arrays and device tensors alike."""
+    nc, ni, _ = (int(v) for v in wshape)
+    if nc <= 0 or ni <= 0:
+        raise ValueError(f"hits_unravel: empty window shape {tuple(wshape)}")
+    q = index // nc
+    return index - q * nc, q - (q // ni) * ni, q // ni
+
+
+def hits_snr(value, median, mad):
+    """The signed robust SNR of listed samples: (Float64(value) - Float64(median))
+    / Float64(mad), with ``median`` and ``mad`` those of each sample's block."""
+    if isinstance(value, np.ndarray):
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return (value.astype(np.float64) - median.astype(np.float64)) / mad.astype(np.float64)
+    return (value.double() - median.double()) / mad.double()
+
+
 def _hist_args(nbins, lo, hi):
     """(nbins, lo, hi) of a histogram call, checked before any GPU work: the
     parameter conditions of include/bldp.h, each an ArgumentError (BLDP_EINVAL,

@@ -132,6 +132,24 @@ def gethistogram(workers, fnames, idxs=(COLON, COLON, COLON), *, nbins, lo, hi, 
                                                tavby=tavby, device=int(w)))
 
 
+def gethits(workers, fnames, idxs=(COLON, COLON, COLON), *, n=None, axis=2, nsigma=5.0,
+            maxhits=None):
+    """getkurtosis' fan-out (src/gbt.jl:81-88) with the flag-and-list of
+    WorkerFunctions.gethits: per-bank dicts of the flagged samples (``"total"``,
+    ``"channel"``, ``"if"``, ``"time"``, ``"value"``, ``"snr"``) and the
+    ``"median"``, ``"mad"`` and ``"count"`` planes from one read of every file."""
+    return _fanout(workers, fnames,
+                   lambda w, f: W.gethits(f, idxs, n=n, axis=axis, nsigma=nsigma, maxhits=maxhits,
+                                          device=int(w)))
+
+
+def getflagged(workers, fnames, idxs=(COLON, COLON, COLON), *, mask, maxhits=None):
+    """The same fan-out with WorkerFunctions.getflagged: per-bank dicts of the
+    samples that ``mask`` (one mask, the window's shape, for every file) flags."""
+    return _fanout(workers, fnames,
+                   lambda w, f: W.getflagged(f, idxs, mask=mask, maxhits=maxhits, device=int(w)))
+
+
 def getclean(workers, fnames, idxs=(COLON, COLON, COLON), *, fqavby=1, tavby=1, n=None, axis=2,
              nsigma=5.0, func="sum"):
     """getkurtosis' fan-out (src/gbt.jl:81-88) with the flag-and-integrate of

@@ -16,7 +16,7 @@ export gpu_init, gpu_finalize, gpu_pin, gpu_unpin, gpu_fqav, gpu_reduce, gpu_kur
        mad, quantile, gpu_quantile, gpu_quantile_plan, gpu_band_quantile,
        gpu_quantiles, gpu_quantiles_plan, gpu_band_quantiles,
        gpu_outliers, gpu_outliers_plan, gpu_band_outliers,
-       gpu_masked_reduce, gpu_band_masked_reduce,
+       gpu_masked_reduce, gpu_band_masked_reduce, gpu_hits, gpu_band_hits,
        gpu_histogram, gpu_histogram_plan, gpu_band_histogram
 
 const libbldp = get(ENV, "BLDP_LIB", joinpath(@__DIR__, "..", "libbldp_hip.so"))
@@ -890,6 +890,102 @@ function gpu_band_histogram(banks::Vector{Ptr{Float32}}, dims::NTuple{3,Integer}
         (Cint, Ptr{Ptr{Float32}}, Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Cint, Float64,
          Float64, Ptr{UInt32}, Ptr{Cvoid}),
         length(banks), banks, dims[1], dims[2], dims[3], win, fqavby, tavby, nbins, lo, hi, out,
+        stream))
+    nothing
+end
+
+# ---- hits: bldp_*hits_* (the flagged samples of a window as an ordered list) ----
+"""
+    gpu_hits(A::Array{Float32,3}, msk::Array{UInt8,3}; maxhits=nothing, idxs=(:,:,:), dev=0)
+        -> (total, index, value)
+
+`findall(!iszero, msk)` and `A[idxs...][msk]` on GPU `dev` (bldp_hits_host_f32;
+the rule of include/bldp.h).  `msk` has the window's size, any axis of which may
+be 1 (a broadcast); `gpu_outliers`' mask goes in as it is.  `total` is the number
+of flagged samples, always exact; `index` (`Int64`, 1-based linear indices of the
+window, ascending: `CartesianIndices(size)[index]` gives channel, IF and time)
+and `value` (`Float32`, the samples' bits untouched) hold the first
+`min(total, maxhits)` of them (`maxhits=nothing`: all)."""
+function gpu_hits(A::Array{Float32,3}, msk::Array{UInt8,3}; maxhits=nothing,
+                  idxs::Tuple=(:, :, :), dev::Integer=0)
+    maxhits === nothing || maxhits >= 0 || throw(ArgumentError("maxhits=$maxhits is negative"))
+    win = window(idxs, size(A))
+    shp = zeros(Int64, 3)
+    GC.@preserve win check(ccall((:bldp_reduce_shape, libbldp), Cint,
+        (Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Ptr{Int64}),
+        size(A, 1), size(A, 2), size(A, 3), win, 1, 1, shp))
+    ld = _mask_ld(msk, (shp[1], shp[2], shp[3]))
+    total = zeros(UInt64, 1)
+    call(cap, idx, val) = GC.@preserve A msk win ld idx val total check(
+        ccall((:bldp_hits_host_f32, libbldp), Cint,
+              (Cint, Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Ptr{UInt8}, Ptr{Int64}, Int64,
+               Ptr{Int64}, Ptr{Float32}, Ptr{UInt64}),
+              dev, A, size(A, 1), size(A, 2), size(A, 3), win, msk, ld, cap, idx, val, total))
+    cap = maxhits
+    if cap === nothing   # count, then list exactly
+        call(0, Ptr{Int64}(C_NULL), Ptr{Float32}(C_NULL))
+        cap = Int64(total[1])
+    end
+    idx = Vector{Int64}(undef, cap)
+    val = Vector{Float32}(undef, cap)
+    call(cap, idx, val)
+    n = min(Int64(total[1]), cap)
+    Int64(total[1]), idx[1:n] .+ 1, val[1:n]
+end
+
+"""
+    gpu_hits(in::Ptr{Float32}, dims, mask::Ptr{UInt8}, cap, idx::Ptr{Int64}, val::Ptr{Float32},
+             total::Ptr{UInt64}; win=C_NULL, mask_ld=C_NULL, stream=C_NULL)
+
+The same on DEVICE memory (bldp_hits_f32; asynchronous on `stream`, `total` a
+device pointer too): flag (c, i, t) of the window at `mask[c*mask_ld[1] +
+i*mask_ld[2] + t*mask_ld[3]]` (0-based; `C_NULL`: dense).  Entries
+`j < min(total, cap)` of `idx` and `val` are written; either may be `C_NULL`.
+The indices in `idx` are 0-BASED as the library writes them: add 1 after the
+copy back."""
+function gpu_hits(in::Ptr{Float32}, dims::NTuple{3,Integer}, mask::Ptr{UInt8}, cap::Integer,
+                  idx::Ptr{Int64}, val::Ptr{Float32}, total::Ptr{UInt64};
+                  win=Ptr{Int64}(C_NULL), mask_ld=Ptr{Int64}(C_NULL),
+                  stream::Ptr{Cvoid}=C_NULL)
+    GC.@preserve win mask_ld check(ccall((:bldp_hits_f32, libbldp), Cint,
+        (Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Ptr{UInt8}, Ptr{Int64}, Int64,
+         Ptr{Int64}, Ptr{Float32}, Ptr{UInt64}, Ptr{Cvoid}),
+        in, dims[1], dims[2], dims[3], win, mask, mask_ld, cap, idx, val, total, stream))
+    nothing
+end
+
+"""
+    gpu_hits_plan(dims, cap=1; win=C_NULL, mask_ld=C_NULL) -> Vector{Int64}
+
+The launch plan of that call (bldp_hits_plan_f32; launches nothing): {mask load
+form (0 byte, 1 wide, 2 row-uniform), elements per tile, tiles, workspace bytes,
+scan chunks, flags per lane per load, launches, 0, 0, 0}."""
+function gpu_hits_plan(dims::NTuple{3,Integer}, cap::Integer=1; win=Ptr{Int64}(C_NULL),
+                       mask_ld=Ptr{Int64}(C_NULL))
+    info = zeros(Int64, 10)
+    GC.@preserve win mask_ld info check(ccall((:bldp_hits_plan_f32, libbldp), Cint,
+        (Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Ptr{UInt8}, Ptr{Int64}, Int64,
+         Ptr{Int64}),
+        C_NULL, dims[1], dims[2], dims[3], win, C_NULL, mask_ld, cap, info))
+    info
+end
+
+"""
+    gpu_band_hits(banks::Vector{Ptr{Float32}}, dims, mask, cap, idx, val, total;
+                  win=C_NULL, mask_ld=C_NULL, stream=C_NULL)
+
+The list of a band resident on one GPU (bldp_band_hits_f32): the window is the
+vcat `(nbank*nc, ni, nt)` of the banks' windows, bank b's channel c is channel
+`b*nc + c` of the mask and of the linear index (`C_NULL` strides: the dense vcat,
+`gpu_band_outliers`' mask).  0-BASED indices, as the device form."""
+function gpu_band_hits(banks::Vector{Ptr{Float32}}, dims::NTuple{3,Integer}, mask::Ptr{UInt8},
+                       cap::Integer, idx::Ptr{Int64}, val::Ptr{Float32}, total::Ptr{UInt64};
+                       win=Ptr{Int64}(C_NULL), mask_ld=Ptr{Int64}(C_NULL),
+                       stream::Ptr{Cvoid}=C_NULL)
+    GC.@preserve banks win mask_ld check(ccall((:bldp_band_hits_f32, libbldp), Cint,
+        (Cint, Ptr{Ptr{Float32}}, Int64, Int64, Int64, Ptr{Int64}, Ptr{UInt8}, Ptr{Int64}, Int64,
+         Ptr{Int64}, Ptr{Float32}, Ptr{UInt64}, Ptr{Cvoid}),
+        length(banks), banks, dims[1], dims[2], dims[3], win, mask, mask_ld, cap, idx, val, total,
         stream))
     nothing
 end

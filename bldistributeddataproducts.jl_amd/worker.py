@@ -965,6 +965,111 @@ def gethistogram(src, idxs=(COLON, COLON, COLON), *, nbins, lo, hi, fqavby=1, ta
         engine.planes_to_numpy), B, edges)
 
 
+def _mask_to_device(host_mask, device):
+    """A host uint8 / bool mask as a uint8 device tensor of the same shape with
+    channel-fastest strides (1, nc, nc*ni), whatever the host order was: the
+    layout of the window and of ``outliers``' mask, so a dense mask keeps the
+    aligned wide flag loads instead of strided bytes."""
+    import torch
+
+    m = np.asarray(host_mask).view(np.uint8)
+    if m.ndim != 3:  # (engine's checks word the error)
+        return torch.from_numpy(np.ascontiguousarray(m)).to(device)
+    return torch.from_numpy(np.ascontiguousarray(m.transpose(2, 1, 0))).to(device).permute(2, 1, 0)
+
+
+def _hits_to_host(r):
+    """The dict of getflagged / gethits with host arrays: 3-D planes through
+    fb_to_numpy, the lists copied as they are."""
+    return {k: v if isinstance(v, int) else engine.fb_to_numpy(v) if v.dim() == 3
+            else v.cpu().numpy() for k, v in r.items()}
+
+
+def _hits_coords(h, wshape):
+    """engine.hits' dict with the samples' 0-based (channel, if, time) beside
+    the linear index."""
+    c, i, t = engine.hits_unravel(h["index"], wshape)
+    return {"total": h["total"], "index": h["index"], "channel": c, "if": i, "time": t,
+            "value": h["value"]}
+
+
+def getflagged(src, idxs=(COLON, COLON, COLON), *, mask, maxhits=None, device=0):
+    """The samples of the window that ``mask`` flags, as an ordered list: Julia's
+    ``findall(!iszero, mask)`` and ``A[mask]`` on the GPU (engine.hits; the rule of
+    include/bldp.h).  A dict with ``"total"`` (int), the number of flagged
+    samples, always exact, and for the first min(total, maxhits) of them
+    (``maxhits=None``: all) in ascending linear window index: ``"index"`` (int64,
+    0-based, c + nc*(i + ni*t)), ``"channel"``, ``"if"``, ``"time"`` (int64,
+    0-based) and ``"value"`` (float32, the samples' bits untouched).  ``mask`` has
+    the window's shape (nc, ni, nt), any axis of which may be 1; uint8 or bool, a
+    host array or a device tensor (it goes to where the data is).  Files reach the
+    GPU as getdata reads them (window_on_device) and a host array is staged
+    there, both returning host arrays; a device tensor's lists stay on the device.
+    Float32 data only: any other element type (host array, device tensor, 8/16-bit
+    SIGPROC file) is a TypeError."""
+    cap = engine._hits_cap(maxhits)  # (the errors before any file is touched)
+    if _is_tensor(mask):
+        mdt, host_mask = str(mask.dtype).replace("torch.", ""), None
+    else:
+        host_mask = np.asarray(mask)
+        mdt = str(host_mask.dtype)
+    if mdt not in ("uint8", "bool"):
+        raise TypeError(f"getflagged: the mask must be uint8 or bool, not {mdt}")
+
+    def on_device(x, win):
+        m = mask.to(x.device) if host_mask is None else _mask_to_device(host_mask, x.device)
+        h = engine.hits(x, m, maxhits=cap, win=win)
+        return _hits_coords(h, engine.window_shape(win, tuple(x.shape)))
+
+    def on_host(a, win):
+        m = host_mask if host_mask is not None else mask.cpu().numpy()
+        h = engine.hits_host(a, m, maxhits=cap, win=win, device=device)
+        return _hits_coords(h, engine.window_shape(win, a.shape))
+
+    return _read_moment("getflagged", "hits", src, sanitizeidxs(idxs), device, on_device, on_host,
+                        _hits_to_host)
+
+
+def gethits(src, idxs=(COLON, COLON, COLON), *, n=None, axis=2, nsigma=5.0, maxhits=None,
+            device=0):
+    """Flag and list on the device: engine.outliers flags every block of ``n``
+    selected channels (``axis=0``) or spectra (``axis=2``; ``n=None``: the whole
+    selected time range) at ``nsigma`` scaled mads from its median, and
+    engine.hits lists the flagged samples of the same device tensor; the mask
+    never leaves the device.  A dict with ``"total"`` (int, always exact) and, for
+    the first min(total, maxhits) flagged samples in ascending linear window
+    index (``maxhits=None``: all), ``"channel"``, ``"if"``, ``"time"`` (int64,
+    0-based), ``"value"`` (float32) and ``"snr"`` (float64): (Float64(value) -
+    Float64(median_b)) / Float64(mad_b) for the sample's block b, signed, so a
+    caller can keep one side; and the ``"median"``, ``"mad"`` and ``"count"``
+    planes of ``outliers``.  Files, host arrays and device tensors as getflagged
+    takes them; Float32 data only."""
+    ax, _, _ = engine._outliers_args(axis, nsigma, engine.OUTLIER_PLANES)  # (errors first)
+    cap = engine._hits_cap(maxhits)
+
+    def on_device(x, win):
+        wshape = engine.window_shape(win, tuple(x.shape))
+        o = engine.outliers(x, n=n, axis=axis, nsigma=nsigma, win=win, mask=True)
+        h = _hits_coords(engine.hits(x, o["mask"], maxhits=cap, win=win), wshape)
+        nb = engine._outliers_n(n, ax, wshape[0], wshape[2])
+        c, i, t = h["channel"], h["if"], h["time"]
+        blk = (c // nb, i, t) if ax == 0 else (c, i, t // nb)
+        h["snr"] = engine.hits_snr(h["value"], o["median"][blk], o["mad"][blk])
+        del h["index"]
+        h.update(median=o["median"], mad=o["mad"], count=o["count"])
+        return h
+
+    def on_host(a, win):  # staged whole, so that both halves read one device tensor
+        import torch
+
+        dev = f"cuda:{device}"
+        with torch.cuda.device(dev):
+            return _hits_to_host(on_device(engine.fb_from_numpy(a, device=dev), win))
+
+    return _read_moment("gethits", "gethits", src, sanitizeidxs(idxs), device, on_device, on_host,
+                        _hits_to_host)
+
+
 getinventory = readers.getinventory
 getfbheader = readers.getfbheader
 getfbh5header = readers.getfbh5header

@@ -94,7 +94,8 @@ extern "C" {
  *    (additive, same version) the bldp_quantiles_* entry points;
  *    (additive, same version) the bldp_outliers_* entry points;
  *    (additive, same version) the bldp_*masked_reduce_* entry points;
- *    (additive, same version) the bldp_*histogram_* entry points */
+ *    (additive, same version) the bldp_*histogram_* entry points;
+ *    (additive, same version) the bldp_*hits_* entry points */
 #define BLDP_ABI_VERSION 5
 
 #if defined(BLDP_BUILD)
@@ -936,6 +937,80 @@ BLDP_API int bldp_histogram_host_f32(int dev, const float *in, int64_t nchan, in
                                      int64_t ntime, const int64_t *win, int64_t fqavby,
                                      int64_t tavby, int nbins, double lo, double hi,
                                      uint32_t *out);
+
+/* Hits: the flagged samples of a window as an ordered list, Julia's
+ * findall(!iszero, mask) and A[mask] done on the device.  The mask never leaves
+ * the device and the result is a short list.  Float32 input; additive in ABI 5.
+ *
+ * The window is the reduce's: `win` with offsets, steps and direction selects
+ * (nc, ni, nt).  The mask is addressed exactly as bldp_masked_reduce_f32
+ * addresses it: window coordinates, mask_ld in bytes, NULL = dense {1, nc,
+ * nc*ni}, a stride of 0 broadcasts, negative strides are BLDP_EINVAL.  The mask
+ * of bldp_outliers_f32 goes in as it is; a bad-channel list is {1, 0, 0}.
+ *
+ *  1. Sample (c, i, t) is flagged when its byte is not 0 (1, 2, 255): the
+ *     complement of the masked reduce's "kept".
+ *  2. total (uint64) is the number of flagged samples of the window, always
+ *     exact, whatever cap is.
+ *  3. The flagged samples are listed in ascending linear window index
+ *     k = c + nc*(i + ni*t), Julia's column-major findall order.  idx[j] (int64,
+ *     0-based) is the j-th such k, val[j] that sample's Float32 bits, untouched:
+ *     a NaN keeps its payload and -0.0 stays -0.0.
+ *  4. Only entries j < min(total, cap) are written, the first cap in that order.
+ *     Nothing beyond them is touched.
+ *  5. idx or val may be NULL and is then not written.  cap = 0 is legal.  With
+ *     cap = 0 or both lists NULL the call only counts: the third launch is not
+ *     issued.
+ *  6. Two calls give identical bytes.  A list position is a function of k and of
+ *     integer sums of flag counts alone; no atomic and no arrival order takes
+ *     part.
+ *  7. Refused before any launch: a null total, a null mask (non-empty window),
+ *     cap < 0, outputs that overlap each other, the input window or the mask's
+ *     span, more tiles than one launch takes (all BLDP_EINVAL); a window outside
+ *     the array (BLDP_EBOUNDS).
+ *  8. An empty window gives total = 0 and launches nothing.
+ *
+ * Band form: the window is the vcat (nbank*nc, ni, nt); bank b's channel c is
+ * channel b*nc + c of the mask and of k, as in bldp_band_masked_reduce_f32, so
+ * within one (i, t) row all of bank 0 comes before bank 1.
+ *
+ * The window's linear order is cut into tiles, a contiguous run of k each, one
+ * workgroup per tile; three launches on `stream` (count the flags of every
+ * tile, one workgroup's exclusive prefix of the counts, write the lists) with
+ * 12 bytes of library scratch per tile.  The smallest tile is 4 steps of 256
+ * lanes; it doubles until at most 8192 tiles cover the window, up to 2^31
+ * elements a tile.  The flags are loaded as one aligned load of 16 or 4 flags a
+ * lane (mask_ld[0] == 1, nc a multiple of that width, the mask pointer and
+ * every pitch in use a multiple of it), as one byte per row when mask_ld[0] == 0
+ * (the count; the list kernel reads that byte per element), else as one byte
+ * per element.
+ *
+ * bldp_hits_plan_f32: info = {mask load form (0 byte, 1 wide, 2 row-uniform),
+ * elements per tile, tiles, workspace bytes, chunks the scan workgroup loops
+ * over, flags per lane per load, launches (2 for cap = 0, else 3), 0, 0, 0}; all
+ * 0 for an empty window.  Launches nothing and needs no GPU; both pointers may
+ * be null (a null pointer counts as aligned).
+ * bldp_hits_f32: device pointers (total too), asynchronous on `stream`.
+ * bldp_band_hits_f32: in[] is a HOST array of device pointers of banks with one
+ * geometry; mask_ld == NULL is the dense (nbank*nc, ni, nt) mask.
+ * bldp_hits_host_f32: host in, host mask (mask_ld in bytes of the host mask),
+ * host lists and total; the window's rows and the mask's span are staged on
+ * device `dev` once, the mask is counted twice there (the lists are sized from
+ * the first count).  Synchronous. */
+BLDP_API int bldp_hits_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                                const int64_t *win, const uint8_t *mask, const int64_t *mask_ld,
+                                int64_t cap, int64_t info[10]);
+BLDP_API int bldp_hits_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                           const int64_t *win, const uint8_t *mask, const int64_t *mask_ld,
+                           int64_t cap, int64_t *idx, float *val, uint64_t *total, void *stream);
+BLDP_API int bldp_band_hits_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                                int64_t ntime, const int64_t *win, const uint8_t *mask,
+                                const int64_t *mask_ld, int64_t cap, int64_t *idx, float *val,
+                                uint64_t *total, void *stream);
+BLDP_API int bldp_hits_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                int64_t ntime, const int64_t *win, const uint8_t *mask,
+                                const int64_t *mask_ld, int64_t cap, int64_t *idx, float *val,
+                                uint64_t *total);
 
 /* Element types other than Float32 (what Blio maps SIGPROC nbits 8 / 16 to, and
  * what HDF5.jl returns for an integer or Float64 dataset: the reference's
