@@ -12,12 +12,12 @@ from . import _lib, band, engine, fbh5, filestream, gbt, h5chunks, idxs, readers
 from ._lib import ArgumentError, BLDPError, BoundsError, DimensionMismatch, ReadError  # noqa: F401
 from ._lib import quantile, quantiles  # noqa: F401
 from .idxs import COLON, JRange, sanitizeidxs  # noqa: F401
-from .worker import FRange, fqav, getclean, getflagged, gethistogram, gethits, getmasked, getmoments, getoutliers, getskewness  # noqa: F401
+from .worker import FRange, fqav, getbandpass, getclean, getflagged, getflattened, gethistogram, gethits, getmasked, getmoments, getoutliers, getskewness  # noqa: F401
 
 GBT = gbt
 GBT.WorkerFunctions = worker
 WorkerFunctions = worker
 
-__all__ = ["GBT", "WorkerFunctions", "fqav", "quantile", "quantiles", "getskewness", "getmoments", "getoutliers", "getmasked", "getclean", "gethistogram", "gethits", "getflagged", "JRange", "FRange", "COLON",
+__all__ = ["GBT", "WorkerFunctions", "fqav", "quantile", "quantiles", "getskewness", "getmoments", "getoutliers", "getmasked", "getclean", "gethistogram", "gethits", "getflagged", "getbandpass", "getflattened", "JRange", "FRange", "COLON",
            "sanitizeidxs",
            "engine", "band", "DimensionMismatch", "BoundsError", "BLDPError", "ReadError"]

@@ -119,6 +119,12 @@ HIST_PATHS = {0: "block", 1: "block_split", 2: "lanes", 3: "lanes_tsplit"}
 # load of 4 or 16 flags a lane, one byte per row (stride 0 along the channels)
 HITS_LOADS = {0: "byte", 1: "wide", 2: "row"}
 MAX_HIST_BINS = 4096
+# fold (csrc/fold.hip): lanes along the fine channels, each walking the coarse
+# channels and spectra; or a workgroup's lanes along a row of several coarse
+# channels, meeting through LDS.  The flags: MASK_LOADS, or no mask at all
+FOLD_PATHS = {0: "cols", 1: "rows"}
+FOLD_MASK_LOADS = {0: "byte", 1: "dword", 2: "row", 3: "none"}
+UNFOLD_OPS = {"divide": 0, "subtract": 1}
 
 BLDP_OK, BLDP_EINVAL, BLDP_EDIM, BLDP_EHIP, BLDP_ENOMEM, BLDP_EBOUNDS = 0, -1, -2, -3, -5, -6
 BLDP_ECOMM, BLDP_EIO = -7, -8
@@ -238,6 +244,15 @@ SIGNATURES = {
     "bldp_hits_f32": ([P, I64, I64, I64, P, P, P, I64, P, P, P, P], I),
     "bldp_band_hits_f32": ([I, P, I64, I64, I64, P, P, P, I64, P, P, P, P], I),
     "bldp_hits_host_f32": ([I, P, I64, I64, I64, P, P, P, I64, P, P, P], I),
+    "bldp_fold_shape": ([I64, I64, I64, P, I64, I64, P], I),
+    "bldp_fold_plan_f32": ([P, I64, I64, I64, P, I64, I64, P, P, P], I),
+    "bldp_fold_f32": ([P, I64, I64, I64, P, I64, I64, I, P, P, P, P, I64, I64, P], I),
+    "bldp_band_fold_f32": ([I, P, I64, I64, I64, P, I64, I64, I, P, P, P, P, P], I),
+    "bldp_fold_host_f32": ([I, P, I64, I64, I64, P, I64, I64, I, P, P, P, P], I),
+    "bldp_unfold_plan_f32": ([P, I64, I64, I64, P, I64, I64, P, I64, I64, P, I64, I64, P], I),
+    "bldp_unfold_f32": ([P, I64, I64, I64, P, I64, I64, I, P, I64, I64, P, I64, I64, P], I),
+    "bldp_band_unfold_f32": ([I, P, I64, I64, I64, P, I64, I64, I, P, I64, I64, P, P], I),
+    "bldp_unfold_host_f32": ([I, P, I64, I64, I64, P, I64, I64, I, P, P], I),
     "bldp_fqav_range": ([D, D, I64, I64, P, P, P], I),
     "bldp_synth_f32": ([P, I64, I64, I64, I64, U64, I, P], I),
     "bldp_reduce_out_dtype": ([I, I], I),

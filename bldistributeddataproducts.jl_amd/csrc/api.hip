@@ -2356,6 +2356,320 @@ int bldp_band_hits_f32(int nbank, const float *const *in, int64_t nchan, int64_t
   return hits_run(nbank, in, nchan, nif, ntime, win, mask, mask_ld, cap, idx, val, total, stream);
 }
 
+// ---- fold / unfold: a window over its coarse channels, and back ----
+// The window, nfpc and T of a fold or an unfold: J = nc / nfpc coarse channels per
+// bank, nto = nt / T time blocks.
+static int fold_geometry(int nbank, int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win,
+                         int64_t nfpc, int64_t tavby, Geo *g, int64_t *J, int64_t *T) {
+  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
+    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
+  if (nfpc < 1) return fail(BLDP_EINVAL, "fold: nfpc=%lld is less than 1", (long long)nfpc);
+  int rc = resolve_window(nchan, nif, ntime, win, g);
+  if (rc) return rc;
+  *T = tavby <= 1 ? 1 : tavby;
+  if (g->nc % nfpc != 0)
+    return fail(BLDP_EDIM, "DimensionMismatch: nfpc=%lld does not divide nchan=%lld",
+                (long long)nfpc, (long long)g->nc);
+  if (g->nt % *T != 0)
+    return fail(BLDP_EDIM, "DimensionMismatch: tavby=%lld does not divide ntime=%lld",
+                (long long)*T, (long long)g->nt);
+  *J = g->nc / nfpc;
+  return BLDP_OK;
+}
+
+// lowest element offset and byte length of a window's elements
+static void window_span(const Geo &g, int64_t *lo, size_t *bytes) {
+  int64_t l = g.off, h = g.off;
+  const int64_t span[3] = {(g.nc - 1) * g.cs, (g.ni - 1) * g.ld_i, (g.nt - 1) * g.ld_t};
+  for (int ax = 0; ax < 3; ++ax) (span[ax] < 0 ? l : h) += span[ax];
+  *lo = l;
+  *bytes = 4 * (size_t)(h - l + 1);
+}
+
+// 16-byte loads of every float4 of a unit-step window's rows are legal
+static bool fold_vec_ok(int nbank, const float *const *in, const Geo &g) {
+  if (g.cs != 1 || g.off % 4 != 0) return false;
+  if ((g.ni > 1 && g.ld_i % 4 != 0) || (g.nt > 1 && g.ld_t % 4 != 0)) return false;
+  for (int b = 0; b < nbank; ++b)
+    if (!aligned16(in[b])) return false;
+  return true;
+}
+
+// Checks, window and plan of a fold (every entry point).  has_mask: the plan call
+// asks with a null mask pointer, which counts as aligned.
+static int fold_prepare(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                        int64_t ntime, const int64_t *win, int64_t nfpc, int64_t tavby, int op,
+                        const uint8_t *mask, bool has_mask, const int64_t *mask_ld, float *out,
+                        uint32_t *kept, int64_t out_ld_i, int64_t out_ld_t, bool query,
+                        FoldArgs *ap, Plan *pp, bool *empty) {
+  Geo g;
+  int64_t J, T;
+  int rc = fold_geometry(nbank, nchan, nif, ntime, win, nfpc, tavby, &g, &J, &T);
+  if (rc) return rc;
+  if (op != BLDP_OP_SUM && op != BLDP_OP_MEAN)
+    return fail(BLDP_EINVAL, "fold: op %d is not sum (%d) or mean (%d)", op, BLDP_OP_SUM,
+                BLDP_OP_MEAN);
+  // kept is 31-bit (Python and the shim read Int32)
+  if (nbank * J > INT32_MAX / T)
+    return fail(BLDP_EINVAL, "fold: blocks of J x tavby = %lld x %lld samples are beyond 2^31 - 1",
+                (long long)(nbank * J), (long long)T);
+  int64_t ld[3] = {0, 0, 0};
+  if (has_mask) {
+    ld[0] = 1, ld[1] = nbank * g.nc, ld[2] = nbank * g.nc * g.ni;
+    if (mask_ld)
+      for (int ax = 0; ax < 3; ++ax) {
+        ld[ax] = mask_ld[ax];
+        if (ld[ax] < 0)
+          return fail(BLDP_EINVAL, "fold: mask stride %d is negative (%lld)", ax,
+                      (long long)ld[ax]);
+      }
+  }
+  FoldArgs &a = *ap;
+  a = FoldArgs{};
+  a.out = out, a.kept = kept, a.mask = mask;
+  a.in_off = g.off, a.in_cs = g.cs, a.in_ld_i = g.ld_i, a.in_ld_t = g.ld_t;
+  a.m_cs = ld[0], a.m_ld_i = ld[1], a.m_ld_t = ld[2], a.m_bank = g.nc * ld[0];
+  a.out_ld_i = out_ld_i, a.out_ld_t = out_ld_t;
+  a.nfpc = nfpc, a.J = J, a.ni = g.ni, a.T = T, a.nto = g.nt / T;
+  a.nbank = nbank;
+  a.mean = op == BLDP_OP_MEAN;
+  a.mask_present = has_mask;
+  *empty = g.nc == 0 || g.ni == 0 || g.nt == 0;
+  if (!in) return fail(BLDP_EINVAL, "fold: null input pointer array");
+  for (int b = 0; b < nbank; ++b) a.in[b] = in[b];
+  rc = plan_fold(a, fold_vec_ok(nbank, in, g), aligned4(mask), num_cus_current(), pp);
+  if (rc) return rc;
+  if (query || *empty) return BLDP_OK;
+  for (int b = 0; b < nbank; ++b)
+    if (!in[b]) return fail(BLDP_EINVAL, "fold: null input pointer (bank %d)", b);
+  if (!out && !kept) return fail(BLDP_EINVAL, "fold: out and kept are both null");
+  if (out_ld_i < nfpc || out_ld_t < (g.ni - 1) * out_ld_i + nfpc)
+    return fail(BLDP_EINVAL, "fold: out strides (%lld, %lld) overlap for a (%lld, %lld, %lld) result",
+                (long long)out_ld_i, (long long)out_ld_t, (long long)nfpc, (long long)g.ni,
+                (long long)a.nto);
+  // the outputs may not overlap the window's elements, the mask's span, nor each other
+  int64_t lo;
+  size_t wbytes;
+  window_span(g, &lo, &wbytes);
+  const size_t obytes =
+      4 * (size_t)((nfpc - 1) + (g.ni - 1) * out_ld_i + (a.nto - 1) * out_ld_t + 1);
+  const size_t mbytes =
+      has_mask ? (size_t)((nbank * g.nc - 1) * ld[0] + (g.ni - 1) * ld[1] + (g.nt - 1) * ld[2] + 1)
+               : 0;
+  const void *optr[2] = {out, kept};
+  static const char *const name[2] = {"out", "kept"};
+  for (int q = 0; q < 2; ++q) {
+    if (!optr[q]) continue;
+    for (int b = 0; b < nbank; ++b)
+      if (spans_overlap(optr[q], obytes, in[b] + lo, wbytes))
+        return fail(BLDP_EINVAL, "fold: %s overlaps the input window (bank %d)", name[q], b);
+    if (spans_overlap(optr[q], obytes, mask, mbytes))
+      return fail(BLDP_EINVAL, "fold: %s overlaps the mask", name[q]);
+  }
+  if (out && kept && spans_overlap(out, obytes, kept, obytes))
+    return fail(BLDP_EINVAL, "fold: out and kept overlap");
+  return BLDP_OK;
+}
+
+static int fold_run(int nbank, const float *const *in, int64_t nchan, int64_t nif, int64_t ntime,
+                    const int64_t *win, int64_t nfpc, int64_t tavby, int op, const uint8_t *mask,
+                    const int64_t *mask_ld, float *out, uint32_t *kept, int64_t out_ld_i,
+                    int64_t out_ld_t, void *stream) {
+  FoldArgs a;
+  Plan p;
+  bool empty = false;
+  int rc = fold_prepare(nbank, in, nchan, nif, ntime, win, nfpc, tavby, op, mask, mask != nullptr,
+                        mask_ld, out, kept, out_ld_i, out_ld_t, false, &a, &p, &empty);
+  if (rc || empty) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  ScratchLease lease;  // the chunks' partials, held until the merge is queued
+  if (p.ws_bytes) {
+    rc = scratch_lease(s, p.ws_bytes, &lease);
+    if (rc) return rc;
+    a.ws_sum = static_cast<double *>(lease.ptr);
+    a.ws_kept = reinterpret_cast<uint32_t *>(a.ws_sum + (size_t)a.nchunk * (size_t)a.nout);
+  }
+  hipError_t e = launch_fold(a, p, s);
+  if (e != hipSuccess) return fail(BLDP_EHIP, "fold launch: %s", hipGetErrorString(e));
+  return BLDP_OK;
+}
+
+int bldp_fold_shape(int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win, int64_t nfpc,
+                    int64_t tavby, int64_t out_shape[3]) {
+  if (!out_shape) return fail(BLDP_EINVAL, "null out_shape");
+  Geo g;
+  int64_t J, T;
+  int rc = fold_geometry(1, nchan, nif, ntime, win, nfpc, tavby, &g, &J, &T);
+  if (rc) return rc;
+  out_shape[0] = g.nc == 0 ? 0 : nfpc;
+  out_shape[1] = g.ni;
+  out_shape[2] = g.nt / T;
+  return BLDP_OK;
+}
+
+int bldp_fold_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                       const int64_t *win, int64_t nfpc, int64_t tavby, const uint8_t *mask,
+                       const int64_t *mask_ld, int64_t info[10]) {
+  if (!info) return fail(BLDP_EINVAL, "null info");
+  FoldArgs a;
+  Plan p;
+  bool empty = false;
+  const float *ins[1] = {in};
+  int rc = fold_prepare(1, ins, nchan, nif, ntime, win, nfpc, tavby, BLDP_OP_SUM, mask,
+                        mask != nullptr || mask_ld != nullptr, mask_ld, nullptr, nullptr, 0, 0,
+                        true, &a, &p, &empty);
+  if (rc) return rc;
+  for (int q = 0; q < 10; ++q) info[q] = 0;
+  if (empty) return BLDP_OK;  // (nothing is launched)
+  info[0] = p.path;
+  info[1] = p.lpg;
+  info[2] = a.nchunk;
+  info[3] = p.grid;
+  info[4] = (int64_t)p.ws_bytes;
+  info[5] = a.nchunk > 1 ? 2 : 1;
+  info[6] = a.mform;
+  info[7] = a.vec;
+  info[8] = a.nout;
+  info[9] = a.CU;
+  return BLDP_OK;
+}
+
+int bldp_fold_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win,
+                  int64_t nfpc, int64_t tavby, int op, const uint8_t *mask,
+                  const int64_t *mask_ld, float *out, uint32_t *kept, int64_t out_ld_i,
+                  int64_t out_ld_t, void *stream) {
+  const float *ins[1] = {in};
+  return fold_run(1, ins, nchan, nif, ntime, win, nfpc, tavby, op, mask, mask_ld, out, kept,
+                  out_ld_i, out_ld_t, stream);
+}
+
+int bldp_band_fold_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                       int64_t ntime, const int64_t *win, int64_t nfpc, int64_t tavby, int op,
+                       const uint8_t *mask, const int64_t *mask_ld, float *out, uint32_t *kept,
+                       void *stream) {
+  int64_t d[3];
+  int rc = bldp_fold_shape(nchan, nif, ntime, win, nfpc, tavby, d);
+  if (rc) return rc;
+  // ONE dense (nfpc, ni, nto) profile over the coarse channels of every bank
+  return fold_run(nbank, in, nchan, nif, ntime, win, nfpc, tavby, op, mask, mask_ld, out, kept,
+                  nfpc, nfpc * d[1], stream);
+}
+
+// Checks and args of an unfold (every entry point); out: bank b's channel c at
+// out[b*nc + c + i*out_ld_i + t*out_ld_t].
+static int unfold_prepare(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                          int64_t ntime, const int64_t *win, int64_t nfpc, int64_t tavby, int uop,
+                          const float *prof, int64_t prof_ld_i, int64_t prof_ld_t, float *out,
+                          int64_t out_ld_i, int64_t out_ld_t, bool query, UnfoldArgs *ap,
+                          int64_t *grid, bool *empty) {
+  Geo g;
+  int64_t J, T;
+  int rc = fold_geometry(nbank, nchan, nif, ntime, win, nfpc, tavby, &g, &J, &T);
+  if (rc) return rc;
+  if (uop != BLDP_UNFOLD_DIV && uop != BLDP_UNFOLD_SUB)
+    return fail(BLDP_EINVAL, "unfold: op %d is not divide (%d) or subtract (%d)", uop,
+                BLDP_UNFOLD_DIV, BLDP_UNFOLD_SUB);
+  UnfoldArgs &a = *ap;
+  a = UnfoldArgs{};
+  a.prof = prof, a.out = out;
+  a.in_off = g.off, a.in_cs = g.cs, a.in_ld_i = g.ld_i, a.in_ld_t = g.ld_t;
+  a.prof_ld_i = prof_ld_i, a.prof_ld_t = prof_ld_t, a.out_ld_i = out_ld_i, a.out_ld_t = out_ld_t;
+  a.nc = g.nc, a.ni = g.ni, a.nt = g.nt, a.nfpc = nfpc, a.T = T;
+  a.nbank = nbank;
+  a.sub = uop == BLDP_UNFOLD_SUB;
+  *empty = g.nc == 0 || g.ni == 0 || g.nt == 0;
+  if (!in) return fail(BLDP_EINVAL, "unfold: null input pointer array");
+  for (int b = 0; b < nbank; ++b) a.in[b] = in[b];
+  const int64_t nto = g.nt / T;
+  const bool pitch4 = (g.ni <= 1 || (prof_ld_i % 4 == 0 && out_ld_i % 4 == 0)) &&
+                      (nto <= 1 || prof_ld_t % 4 == 0) && (g.nt <= 1 || out_ld_t % 4 == 0);
+  *grid = plan_unfold(a, fold_vec_ok(nbank, in, g) && aligned16(prof) && aligned16(out) && pitch4);
+  if (query || *empty) return BLDP_OK;
+  for (int b = 0; b < nbank; ++b)
+    if (!in[b]) return fail(BLDP_EINVAL, "unfold: null input pointer (bank %d)", b);
+  if (!prof) return fail(BLDP_EINVAL, "unfold: null profile pointer");
+  if (!out) return fail(BLDP_EINVAL, "unfold: null output pointer");
+  if (prof_ld_i < 0 || prof_ld_t < 0)
+    return fail(BLDP_EINVAL, "unfold: profile strides (%lld, %lld) are negative",
+                (long long)prof_ld_i, (long long)prof_ld_t);
+  const int64_t NC = nbank * g.nc;
+  if (out_ld_i < NC || out_ld_t < (g.ni - 1) * out_ld_i + NC)
+    return fail(BLDP_EINVAL, "unfold: out strides (%lld, %lld) overlap for a (%lld, %lld, %lld) result",
+                (long long)out_ld_i, (long long)out_ld_t, (long long)NC, (long long)g.ni,
+                (long long)g.nt);
+  int64_t lo;
+  size_t wbytes;
+  window_span(g, &lo, &wbytes);
+  const size_t obytes = 4 * (size_t)((NC - 1) + (g.ni - 1) * out_ld_i + (g.nt - 1) * out_ld_t + 1);
+  const size_t pbytes =
+      4 * (size_t)((nfpc - 1) + (g.ni - 1) * prof_ld_i + (nto - 1) * prof_ld_t + 1);
+  for (int b = 0; b < nbank; ++b)
+    if (spans_overlap(out, obytes, in[b] + lo, wbytes))
+      return fail(BLDP_EINVAL, "unfold: out overlaps the input window (bank %d); the unfold is "
+                  "not in place", b);
+  if (spans_overlap(out, obytes, prof, pbytes))
+    return fail(BLDP_EINVAL, "unfold: out overlaps the profile");
+  return BLDP_OK;
+}
+
+static int unfold_run(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                      int64_t ntime, const int64_t *win, int64_t nfpc, int64_t tavby, int uop,
+                      const float *prof, int64_t prof_ld_i, int64_t prof_ld_t, float *out,
+                      int64_t out_ld_i, int64_t out_ld_t, void *stream) {
+  UnfoldArgs a;
+  int64_t grid = 0;
+  bool empty = false;
+  int rc = unfold_prepare(nbank, in, nchan, nif, ntime, win, nfpc, tavby, uop, prof, prof_ld_i,
+                          prof_ld_t, out, out_ld_i, out_ld_t, false, &a, &grid, &empty);
+  if (rc || empty) return rc;
+  hipError_t e = launch_unfold(a, grid, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(BLDP_EHIP, "unfold launch: %s", hipGetErrorString(e));
+  return BLDP_OK;
+}
+
+int bldp_unfold_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                         const int64_t *win, int64_t nfpc, int64_t tavby, const float *prof,
+                         int64_t prof_ld_i, int64_t prof_ld_t, const float *out, int64_t out_ld_i,
+                         int64_t out_ld_t, int64_t info[4]) {
+  if (!info) return fail(BLDP_EINVAL, "null info");
+  UnfoldArgs a;
+  int64_t grid = 0;
+  bool empty = false;
+  const float *ins[1] = {in};
+  int rc = unfold_prepare(1, ins, nchan, nif, ntime, win, nfpc, tavby, BLDP_UNFOLD_DIV, prof,
+                          prof_ld_i, prof_ld_t, const_cast<float *>(out), out_ld_i, out_ld_t, true,
+                          &a, &grid, &empty);
+  if (rc) return rc;
+  info[0] = empty ? 0 : a.vec;
+  info[1] = empty ? 0 : grid;
+  info[2] = empty ? 0 : (a.vec ? 4 : 1);
+  info[3] = 0;
+  return BLDP_OK;
+}
+
+int bldp_unfold_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                    const int64_t *win, int64_t nfpc, int64_t tavby, int uop, const float *prof,
+                    int64_t prof_ld_i, int64_t prof_ld_t, float *out, int64_t out_ld_i,
+                    int64_t out_ld_t, void *stream) {
+  const float *ins[1] = {in};
+  return unfold_run(1, ins, nchan, nif, ntime, win, nfpc, tavby, uop, prof, prof_ld_i, prof_ld_t,
+                    out, out_ld_i, out_ld_t, stream);
+}
+
+int bldp_band_unfold_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                         int64_t ntime, const int64_t *win, int64_t nfpc, int64_t tavby, int uop,
+                         const float *prof, int64_t prof_ld_i, int64_t prof_ld_t, float *out,
+                         void *stream) {
+  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
+    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
+  int64_t d[3];
+  int rc = bldp_reduce_shape(nchan, nif, ntime, win, 1, 1, d);
+  if (rc) return rc;
+  // the dense vcat of the banks: bank b's channels at b*nc of every (IF, time) row
+  return unfold_run(nbank, in, nchan, nif, ntime, win, nfpc, tavby, uop, prof, prof_ld_i, prof_ld_t,
+                    out, nbank * d[0], nbank * d[0] * d[1], stream);
+}
+
 int bldp_reduce_out_dtype(int dtype, int op) {
   const int d = typed_out_dtype(dtype, op);
   if (d < 0) return fail(BLDP_EINVAL, "unknown element type %d or op %d", dtype, op);

@@ -409,6 +409,70 @@ int plan_hits(HitsArgs &a, uintptr_t mask_addr, Plan *p);
 // count, scan and (write) the list kernel, on one stream
 hipError_t launch_hits(const HitsArgs &a, const Plan &p, bool write, hipStream_t s);
 
+// Fold of a window over its coarse channels (fold.hip): output (k, i, t') is the
+// Float64 sum (or mean) of the unflagged samples A[k + nfpc*j, i, t'*T + tt] of
+// every bank, rounded once to Float32, and their count.  Window element (c, i, t)
+// of bank b at in[b][in_off + c*in_cs + i*in_ld_i + t*in_ld_t], its flag at
+// mask[b*m_bank + c*m_cs + i*m_ld_i + t*m_ld_t] (bytes), output (k, i, t') at
+// [k + i*out_ld_i + t'*out_ld_t] of out and kept (a null one is not written).
+// A by-value kernel argument of the fold kernels alone.
+struct FoldArgs {
+  const float *in[BLDP_MAX_BANKS];  // banks with identical geometry
+  float *out;
+  uint32_t *kept;
+  const uint8_t *mask;
+  double *ws_sum;     // workspace (nchunk > 1): the chunks' sums [nchunk][nto][ni][nfpc]
+  uint32_t *ws_kept;  // ... and their counts, behind the sums
+  int64_t in_off, in_cs, in_ld_i, in_ld_t;
+  int64_t m_cs, m_ld_i, m_ld_t, m_bank;
+  int64_t out_ld_i, out_ld_t;
+  int64_t nfpc, J, ni, T, nto;
+  int32_t nbank;
+  int32_t mean;          // 1: the sum divided once in Float64 by Float64(kept)
+  int32_t mask_present;  // 0: everything is kept, no flag is loaded
+  // the plan (plan_fold)
+  int32_t vec;     // float4 loads, else one dword per element
+  int32_t mform;   // MaskForm, or FOLD_MASK_NONE
+  int32_t rows;    // FoldPath
+  int32_t nchunk;  // chunks of a block's units, a workgroup each
+  int32_t mew;     // the merge: outputs of a workgroup (a power of two <= 64)
+  int64_t P;       // items (float4s or values) of a coarse channel
+  int64_t G;       // coarse channels a workgroup's lanes cover (cols: 1)
+  int64_t xwg;     // cols: workgroups along k
+  int64_t JG;      // ceil(J / G)
+  int64_t U, CU;   // units (bank, coarse group, spectrum) of a block; units per chunk
+  int64_t nout;    // nfpc * ni * nto
+};
+enum FoldPath { FOLD_COLS = 0, FOLD_ROWS = 1 };
+constexpr int FOLD_MASK_NONE = 3;  // beside MaskForm's 0 .. 2
+// Fills the plan of an args struct whose shape, stride and mask fields are set,
+// without a GPU (`vec`: 16-byte loads of every item are legal when nfpc % 4 == 0;
+// `mask_words`: the mask pointer is 4-byte aligned).  p: path (FoldPath), lpg = the
+// lanes along the channels, grid = the fold's workgroups, nout, ws_bytes.  BLDP_OK
+// or, with the message recorded, BLDP_EINVAL for a launch too large for one grid.
+int plan_fold(FoldArgs &a, bool vec, bool mask_words, int num_cus, Plan *p);
+// the fold and, when a.nchunk > 1, the merge, on one stream
+hipError_t launch_fold(const FoldArgs &a, const Plan &p, hipStream_t s);
+
+// Unfold (fold.hip): out[b*nc + c + i*out_ld_i + t*out_ld_t] = A_b[c, i, t] / or -
+// prof[c mod nfpc + i*prof_ld_i + (t div T)*prof_ld_t], one rounded Float32
+// operation.  A by-value kernel argument of k_unfold alone.
+struct UnfoldArgs {
+  const float *in[BLDP_MAX_BANKS];  // banks with identical geometry
+  const float *prof;
+  float *out;
+  int64_t in_off, in_cs, in_ld_i, in_ld_t;
+  int64_t prof_ld_i, prof_ld_t, out_ld_i, out_ld_t;
+  int64_t nc, ni, nt, nfpc, T;
+  int32_t nbank;
+  int32_t sub;  // 0 divide, 1 subtract
+  int32_t vec;  // float4 loads and stores (plan_unfold)
+};
+// Sets a.vec (`vec`: 16-byte accesses of the window, the profile and the output are
+// legal when nfpc % 4 == 0) and returns the workgroups per bank.
+int64_t plan_unfold(UnfoldArgs &a, bool vec);
+hipError_t launch_unfold(const UnfoldArgs &a, int64_t grid, hipStream_t s);
+
 // median / var / std of every block of T selected spectra of every (channel,
 // IF) column (tstats.hip): tavfunc, fqav's rule on the time axis.  Window
 // element (c, i, t) of bank k at in[k][in_off + c*in_cs + i*in_ld_i +

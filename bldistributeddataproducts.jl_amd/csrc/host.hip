@@ -667,6 +667,97 @@ extern "C" int bldp_hits_host_f32(int dev, const float *in, int64_t nchan, int64
   });
 }
 
+// The same staging for the fold: the window's rows and (where there is one) the
+// mask's span go to the device once; the dense (nfpc, ni, nto) outputs that the
+// caller asked for come back.
+extern "C" int bldp_fold_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                  int64_t ntime, const int64_t *win, int64_t nfpc, int64_t tavby,
+                                  int op, const uint8_t *mask, const int64_t *mask_ld, float *out,
+                                  uint32_t *kept) {
+  // (every argument check, before any staging)
+  int64_t info[10];
+  int rc = bldp_fold_plan_f32(nullptr, nchan, nif, ntime, win, nfpc, tavby, nullptr,
+                              mask ? mask_ld : nullptr, info);
+  if (rc) return rc;
+  if (op != BLDP_OP_SUM && op != BLDP_OP_MEAN)
+    return bldp::set_error(BLDP_EINVAL, "fold: op %d is not sum (%d) or mean (%d)", op,
+                           BLDP_OP_SUM, BLDP_OP_MEAN);
+  int64_t sh[3], wsh[3];
+  rc = bldp_fold_shape(nchan, nif, ntime, win, nfpc, tavby, sh);
+  if (!rc) rc = bldp_reduce_shape(nchan, nif, ntime, win, 1, 1, wsh);
+  if (rc) return rc;
+  const int64_t nc = wsh[0], ni = wsh[1], nt = wsh[2], nto = sh[2], nout = sh[0] * ni * nto;
+  if (nout == 0) return BLDP_OK;
+  if (!in) return bldp::set_error(BLDP_EINVAL, "fold: null input pointer");
+  if (!out && !kept) return bldp::set_error(BLDP_EINVAL, "fold: out and kept are both null");
+  const int64_t ld[3] = {mask_ld ? mask_ld[0] : 1, mask_ld ? mask_ld[1] : nc,
+                         mask_ld ? mask_ld[2] : nc * ni};
+  const size_t mb =
+      mask ? (size_t)((nc - 1) * ld[0] + (ni - 1) * ld[1] + (nt - 1) * ld[2] + 1) : 0;
+  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
+  return with_stager(dev, [&](bldp::Stager *sg) -> int {
+    float *dbuf, *dout = nullptr;
+    uint8_t *dmask = nullptr;
+    uint32_t *dkept = nullptr;
+    int r = bldp::stager_buffer(sg, 0, (size_t)(h.span * ni * nt) * 4, (void **)&dbuf);
+    if (!r && mask) r = bldp::stager_buffer(sg, 1, mb, (void **)&dmask);
+    if (!r && out) r = bldp::stager_buffer(sg, 2, (size_t)nout * sizeof(float), (void **)&dout);
+    if (!r && kept)
+      r = bldp::stager_buffer(sg, 3, (size_t)nout * sizeof(uint32_t), (void **)&dkept);
+    if (!r) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
+    if (r) return r;
+    if (mask) HCHK(hipMemcpyAsync(dmask, mask, mb, hipMemcpyHostToDevice, sg->st[0]));
+    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
+    r = bldp_fold_f32(dbuf, h.span, ni, nt, dwin, nfpc, tavby, op, dmask, ld, dout, dkept, nfpc,
+                      nfpc * ni, sg->st[0]);
+    if (r) return r;
+    if (out)
+      HCHK(hipMemcpyAsync(out, dout, (size_t)nout * sizeof(float), hipMemcpyDeviceToHost,
+                          sg->st[0]));
+    if (kept)
+      HCHK(hipMemcpyAsync(kept, dkept, (size_t)nout * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                          sg->st[0]));
+    return BLDP_OK;
+  });
+}
+
+// ... and for the unfold: the window's rows and the dense (nfpc, ni, nto) profile
+// go to the device once; the dense (nc, ni, nt) result comes back.
+extern "C" int bldp_unfold_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                    int64_t ntime, const int64_t *win, int64_t nfpc,
+                                    int64_t tavby, int uop, const float *prof, float *out) {
+  // (every argument check, before any staging)
+  int64_t sh[3], wsh[3];
+  int rc = bldp_fold_shape(nchan, nif, ntime, win, nfpc, tavby, sh);
+  if (!rc) rc = bldp_reduce_shape(nchan, nif, ntime, win, 1, 1, wsh);
+  if (rc) return rc;
+  if (uop != BLDP_UNFOLD_DIV && uop != BLDP_UNFOLD_SUB)
+    return bldp::set_error(BLDP_EINVAL, "unfold: op %d is not divide (%d) or subtract (%d)", uop,
+                           BLDP_UNFOLD_DIV, BLDP_UNFOLD_SUB);
+  const int64_t nc = wsh[0], ni = wsh[1], nt = wsh[2], nto = sh[2];
+  if (nc * ni * nt == 0) return BLDP_OK;
+  if (!in) return bldp::set_error(BLDP_EINVAL, "unfold: null input pointer");
+  if (!prof) return bldp::set_error(BLDP_EINVAL, "unfold: null profile pointer");
+  if (!out) return bldp::set_error(BLDP_EINVAL, "unfold: null output pointer");
+  const size_t pbytes = (size_t)(nfpc * ni * nto) * 4, obytes = (size_t)(nc * ni * nt) * 4;
+  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
+  return with_stager(dev, [&](bldp::Stager *sg) -> int {
+    float *dbuf, *dprof, *dout;
+    int r = bldp::stager_buffer(sg, 0, (size_t)(h.span * ni * nt) * 4, (void **)&dbuf);
+    if (!r) r = bldp::stager_buffer(sg, 1, pbytes, (void **)&dprof);
+    if (!r) r = bldp::stager_buffer(sg, 2, obytes, (void **)&dout);
+    if (!r) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
+    if (r) return r;
+    HCHK(hipMemcpyAsync(dprof, prof, pbytes, hipMemcpyHostToDevice, sg->st[0]));
+    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
+    r = bldp_unfold_f32(dbuf, h.span, ni, nt, dwin, nfpc, tavby, uop, dprof, nfpc, nfpc * ni, dout,
+                        nc, nc * ni, sg->st[0]);
+    if (r) return r;
+    HCHK(hipMemcpyAsync(out, dout, obytes, hipMemcpyDeviceToHost, sg->st[0]));
+    return BLDP_OK;
+  });
+}
+
 // ---------------------------------------------------------------------------
 // Host forms of the typed entry points (include/bldp.h), staged like the
 // Float32 forms above: only the window's rows (its channel span of every

@@ -1859,6 +1859,303 @@ def histogram_host(a: np.ndarray, nbins, lo, hi, fqavby=1, tavby=None, win=None,
     return out.view(np.int32)  # counts are < 2^31
 
 
+FOLD_PLAN_KEYS = ("path", "channel_lanes", "chunks_per_block", "workgroups", "workspace_bytes",
+                  "launches", "mask_loads", "vector_loads", "outputs", "units_per_chunk")
+UNFOLD_PLAN_KEYS = ("vector_loads", "workgroups", "elements_per_lane")
+
+
+def _fold_factors(shape, win, nfpc, tavby):
+    """(nfpc, T, (nfpc, ni, nto)) of a fold; ``tavby=None``: the whole selected time
+    range.  nfpc < 1 is an ArgumentError, a factor that does not divide the window
+    a DimensionMismatch, both before any GPU work."""
+    nc, ni, nt = window_shape(win, shape)
+    if nfpc is None or int(nfpc) < 1:
+        raise _lib.ArgumentError(_lib.BLDP_EINVAL, f"fold: nfpc={nfpc!r} is less than 1")
+    nfpc = int(nfpc)
+    T = max(nt, 1) if tavby is None else max(int(tavby), 1)
+    if nc % nfpc:
+        raise _lib.DimensionMismatch(_lib.BLDP_EDIM,
+                                     f"DimensionMismatch: nfpc={nfpc} does not divide nchan={nc}")
+    if nt % T:
+        raise _lib.DimensionMismatch(_lib.BLDP_EDIM,
+                                     f"DimensionMismatch: tavby={T} does not divide ntime={nt}")
+    return nfpc, T, ((nfpc if nc else 0), ni, nt // T)
+
+
+def _unfold_op(how) -> int:
+    if how not in _lib.UNFOLD_OPS:
+        raise _lib.ArgumentError(_lib.BLDP_EINVAL,
+                                 f"unfold takes {tuple(_lib.UNFOLD_OPS)}, not {how!r}")
+    return _lib.UNFOLD_OPS[how]
+
+
+def _fold_mask(mask, wshape, device, what):
+    """_mask_arg, with None for no mask: (None, None)."""
+    if mask is None:
+        return None, None
+    return _mask_arg(mask, wshape, device, what)
+
+
+def fold(x, nfpc, tavby=None, op="mean", mask=None, win=None, stream=None):
+    """The profile of the window over its coarse channels (bldp_fold_f32; the rule
+    of include/bldp.h): selected channel c has fine index c mod nfpc, and output
+    (k, i, t') is the ``"sum"`` or ``"mean"`` of the samples of fine index k of
+    every coarse channel and of the ``tavby`` spectra of time block t'
+    (``tavby=None``: the whole selected time range), summed in Float64 and rounded
+    once.  x: a Float32 device filterbank tensor.  ``mask``: None, or a uint8 / bool
+    device tensor as ``masked_reduce`` takes it (the window's shape, any axis may be
+    1; a byte of 0 keeps the sample).  Returns a dict of Julia-order (nfpc, ni, nto)
+    device tensors: ``"data"`` (Float32; 0.0 for the sum and NaN for the mean where
+    nothing is kept) and ``"kept"`` (int32).  Two calls give identical bits."""
+    torch = _torch()
+    code = _masked_op(op)
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
+        _need_f32("fold", getattr(x, "dtype", type(x).__name__), "fold")
+    shape = tuple(x.shape)
+    _check_bounds(win, shape)
+    nfpc, T, dims = _fold_factors(shape, win, nfpc, tavby)
+    mptr, ld = _fold_mask(mask, window_shape(win, shape), x.device, "fold")
+    ptr, nchan, nif, ntime = _abi_dims(x)
+    data = fb_empty(*dims, device=x.device)
+    kept = fb_empty(*dims, device=x.device, dtype=torch.int32)
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    rc = _lib.lib().bldp_fold_f32(ptr, nchan, nif, ntime, wp, nfpc, T, code, mptr, ld, _ptr(data),
+                                  _ptr(kept), dims[0], dims[0] * dims[1], _lib.stream_ptr(stream))
+    _lib.check(rc, "bldp_fold_f32")
+    return {"data": data, "kept": kept}
+
+
+def fold_plan(x, nfpc, tavby=None, mask=None, win=None) -> dict:
+    """Launch plan of ``fold(x, nfpc, tavby, mask=mask, win=win)``
+    (bldp_fold_plan_f32; launches nothing): ``path`` (_lib.FOLD_PATHS),
+    ``channel_lanes`` of a workgroup, ``chunks_per_block`` (the workgroups that
+    share a block), ``workgroups``, ``workspace_bytes``, ``launches`` (2 with the
+    merge), ``mask_loads`` (_lib.FOLD_MASK_LOADS), ``vector_loads`` (1: float4),
+    ``outputs`` and ``units_per_chunk``."""
+    shape = tuple(x.shape)
+    _check_bounds(win, shape)
+    nfpc, T, dims = _fold_factors(shape, win, nfpc, tavby)
+    mptr, ld = _fold_mask(mask, window_shape(win, shape), x.device, "fold_plan")
+    ptr, nchan, nif, ntime = _abi_dims(x)
+    info = (ctypes.c_int64 * 10)()
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    _lib.check(_lib.lib().bldp_fold_plan_f32(ptr, nchan, nif, ntime, wp, nfpc, T, mptr, ld, info),
+               "bldp_fold_plan_f32")
+    d = dict(zip(FOLD_PLAN_KEYS, [int(v) for v in info]))
+    d["path"] = _lib.FOLD_PATHS[d["path"]]
+    d["mask_loads"] = _lib.FOLD_MASK_LOADS[d["mask_loads"]]
+    return d
+
+
+def band_fold(banks, nfpc, tavby=None, op="mean", mask=None, win=None, stream=None):
+    """``fold`` of a band resident on ONE GPU (bldp_band_fold_f32): ONE (nfpc, ni,
+    nto) profile over the coarse channels of every bank, not a vcat.  ``mask``
+    covers the stitched window, (nbank*nc, ni, nt) with any axis allowed to be 1:
+    bank b's channel c is its channel b*nc + c."""
+    torch = _torch()
+    code = _masked_op(op)
+    banks = list(banks)
+    if not banks:
+        raise ValueError("no banks")
+    for b in banks:
+        if b.dtype != torch.float32:
+            _need_f32("band_fold", b.dtype, "fold")
+    shape = tuple(banks[0].shape)
+    _check_bounds(win, shape)
+    nfpc, T, dims = _fold_factors(shape, win, nfpc, tavby)
+    nc, ni, nt = window_shape(win, shape)
+    nb = len(banks)
+    mptr, ld = _fold_mask(mask, (nb * nc, ni, nt), banks[0].device, "band_fold")
+    geo = _band_geo(banks)
+    ptrs = (ctypes.c_void_p * nb)(*[b.data_ptr() for b in banks])
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    data = fb_empty(*dims, device=banks[0].device)
+    kept = fb_empty(*dims, device=banks[0].device, dtype=torch.int32)
+    rc = _lib.lib().bldp_band_fold_f32(nb, ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp, nfpc, T,
+                                       code, mptr, ld, _ptr(data), _ptr(kept),
+                                       _lib.stream_ptr(stream))
+    _lib.check(rc, "bldp_band_fold_f32")
+    return {"data": data, "kept": kept}
+
+
+def _host_fb(a, what, fn):
+    a = np.asarray(a)
+    if a.dtype != np.float32:
+        _need_f32(what, a.dtype, fn)
+    if not a.flags.f_contiguous or a.ndim != 3:
+        raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
+    return a
+
+
+def fold_host(a: np.ndarray, nfpc, tavby=None, op="mean", mask=None, win=None, device=0) -> dict:
+    """Host Fortran-ordered Float32 array and (or None) host uint8 / bool mask in,
+    the dict of ``fold`` as Fortran-ordered host arrays out (bldp_fold_host_f32:
+    the window's rows and the mask staged on ``device`` once)."""
+    code = _masked_op(op)
+    a = _host_fb(a, "fold_host", "fold")
+    _check_bounds(win, a.shape)
+    nfpc, T, dims = _fold_factors(a.shape, win, nfpc, tavby)
+    mptr = ld = None
+    if mask is not None:
+        m = np.asarray(mask)
+        if m.dtype not in (np.dtype(np.uint8), np.dtype(np.bool_)):
+            raise TypeError(f"fold_host: the mask must be a uint8 or bool array, not {m.dtype}")
+        if m.ndim == 3 and any(s < 0 for s in m.strides):
+            m = np.asfortranarray(m)
+        ld = (ctypes.c_int64 * 3)(*_mask_strides(m.shape, m.strides, window_shape(win, a.shape),
+                                                 "fold_host"))
+        mptr = m.ctypes.data if m.size else None
+    data = np.empty(dims, dtype=np.float32, order="F")
+    kept = np.empty(dims, dtype=np.uint32, order="F")
+    keep, wp = _lib.win_arg(_full_win(win, a.shape))
+    rc = _lib.lib().bldp_fold_host_f32(
+        int(device), a.ctypes.data if a.size else None, a.shape[0], a.shape[1], a.shape[2], wp,
+        nfpc, T, code, mptr, ld, data.ctypes.data if data.size else None,
+        kept.ctypes.data if kept.size else None)
+    _lib.check(rc, "bldp_fold_host_f32")
+    return {"data": data, "kept": kept.view(np.int32)}  # counts are < 2^31
+
+
+def _unfold_prof(prof, dims, device, what):
+    """(pointer, prof_ld_i, prof_ld_t) of a Float32 device profile of shape ``dims``
+    with the fine channels fastest; a strided view passes its strides."""
+    torch = _torch()
+    if not isinstance(prof, torch.Tensor) or prof.dtype != torch.float32:
+        raise TypeError(f"{what}: the profile must be a Float32 device tensor, not "
+                        f"{getattr(prof, 'dtype', type(prof).__name__)}")
+    if tuple(prof.shape) != tuple(dims):
+        raise ValueError(f"{what}: the profile is {tuple(prof.shape)}, expected {tuple(dims)}")
+    if not prof.is_cuda:
+        raise TypeError(f"{what}: the profile must be a device tensor (unfold_host takes host "
+                        f"arrays)")
+    if prof.device != torch.device(device):
+        raise ValueError(f"{what}: the profile is on {prof.device}, the data on {device}")
+    s0, s1, s2 = prof.stride()
+    if (dims[0] > 1 and s0 != 1) or min(s1, s2) < 0:
+        raise ValueError(f"{what}: profile strides {prof.stride()}: the fine channels must be "
+                         f"the fastest axis")
+    return (prof.data_ptr() if prof.numel() else None), (s1 if dims[1] > 1 else 0), \
+        (s2 if dims[2] > 1 else 0)
+
+
+def _unfold_out(out, dims, device):
+    """(pointer, out_ld_i, out_ld_t) of a caller's Float32 ``out`` of shape ``dims``,
+    channels fastest; a strided view (a bank's slot of a stitched band) passes its
+    strides."""
+    torch = _torch()
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.float32:
+        raise TypeError(f"out must be a Float32 device tensor, not "
+                        f"{getattr(out, 'dtype', type(out).__name__)}")
+    if tuple(out.shape) != tuple(dims):
+        raise ValueError(f"out is {tuple(out.shape)}, expected {tuple(dims)}")
+    if out.device != torch.device(device):
+        raise ValueError(f"out is on {out.device}, the data on {device}")
+    nc, ni, nt = dims
+    s0, s1, s2 = out.stride()
+    ld_i = s1 if ni > 1 else nc
+    ld_t = s2 if nt > 1 else max(ni - 1, 0) * ld_i + nc
+    if nc > 1 and s0 != 1:
+        raise ValueError(f"out strides {out.stride()}: the channels must be the fastest axis")
+    return (out.data_ptr() if out.numel() else None), ld_i, ld_t
+
+
+def unfold(x, prof, nfpc, tavby=None, how="divide", win=None, out=None, stream=None):
+    """The window with a profile taken out (bldp_unfold_f32): element (c, i, t) is
+    ``x[c, i, t] / prof[c mod nfpc, i, t div tavby]`` (``how="divide"``, one correctly
+    rounded Float32 division) or the difference (``"subtract"``); bit for bit
+    NumPy's Float32 ``/`` and ``-``.  ``prof``: a Float32 (nfpc, ni, nto) device
+    tensor, ``fold``'s ``"data"`` as it is.  Returns a Float32 (nc, ni, nt) device
+    tensor (``out`` when given: any channel-fastest view, such as a bank's slot of a
+    stitched band; it may not overlap ``x``)."""
+    torch = _torch()
+    code = _unfold_op(how)
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
+        _need_f32("unfold", getattr(x, "dtype", type(x).__name__), "unfold")
+    shape = tuple(x.shape)
+    _check_bounds(win, shape)
+    nfpc, T, dims = _fold_factors(shape, win, nfpc, tavby)
+    wshape = window_shape(win, shape)
+    pptr, pld_i, pld_t = _unfold_prof(prof, dims, x.device, "unfold")
+    ptr, nchan, nif, ntime = _abi_dims(x)
+    if out is None:
+        out = fb_empty(*wshape, device=x.device)
+    optr, ld_i, ld_t = _unfold_out(out, wshape, x.device)
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    rc = _lib.lib().bldp_unfold_f32(ptr, nchan, nif, ntime, wp, nfpc, T, code, pptr, pld_i, pld_t,
+                                    optr, ld_i, ld_t, _lib.stream_ptr(stream))
+    _lib.check(rc, "bldp_unfold_f32")
+    return out
+
+
+def unfold_plan(x, nfpc, tavby=None, win=None, prof=None, out=None) -> dict:
+    """Launch plan of ``unfold`` (bldp_unfold_plan_f32; launches nothing):
+    ``vector_loads`` (1: float4), ``workgroups`` per bank, ``elements_per_lane``.
+    Without ``prof`` / ``out`` dense, aligned ones are assumed."""
+    shape = tuple(x.shape)
+    _check_bounds(win, shape)
+    nfpc, T, dims = _fold_factors(shape, win, nfpc, tavby)
+    wshape = window_shape(win, shape)
+    pptr, pld_i, pld_t = (None, dims[0], dims[0] * dims[1]) if prof is None else \
+        _unfold_prof(prof, dims, x.device, "unfold_plan")
+    optr, ld_i, ld_t = (None, wshape[0], wshape[0] * wshape[1]) if out is None else \
+        _unfold_out(out, wshape, x.device)
+    ptr, nchan, nif, ntime = _abi_dims(x)
+    info = (ctypes.c_int64 * 4)()
+    keep, wp = _lib.win_arg(_full_win(win, shape))
+    _lib.check(_lib.lib().bldp_unfold_plan_f32(ptr, nchan, nif, ntime, wp, nfpc, T, pptr, pld_i,
+                                               pld_t, optr, ld_i, ld_t, info),
+               "bldp_unfold_plan_f32")
+    return dict(zip(UNFOLD_PLAN_KEYS, [int(v) for v in info]))
+
+
+def band_unfold(banks, prof, nfpc, tavby=None, how="divide", win=None, stream=None):
+    """``unfold`` of every bank of a band resident on ONE GPU in one launch
+    (bldp_band_unfold_f32) with ONE profile (``band_fold``'s): the dense vcat
+    (nbank*nc, ni, nt)."""
+    torch = _torch()
+    code = _unfold_op(how)
+    banks = list(banks)
+    if not banks:
+        raise ValueError("no banks")
+    for b in banks:
+        if b.dtype != torch.float32:
+            _need_f32("band_unfold", b.dtype, "unfold")
+    shape = tuple(banks[0].shape)
+    _check_bounds(win, shape)
+    nfpc, T, dims = _fold_factors(shape, win, nfpc, tavby)
+    pptr, pld_i, pld_t = _unfold_prof(prof, dims, banks[0].device, "band_unfold")
+    banks, geo, out, ptrs, (keep, wp) = _band_args(banks, 1, 1, win, None)
+    rc = _lib.lib().bldp_band_unfold_f32(len(banks), ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp,
+                                         nfpc, T, code, pptr, pld_i, pld_t, _ptr(out),
+                                         _lib.stream_ptr(stream))
+    _lib.check(rc, "bldp_band_unfold_f32")
+    return out
+
+
+def unfold_host(a: np.ndarray, prof: np.ndarray, nfpc, tavby=None, how="divide", win=None,
+                device=0) -> np.ndarray:
+    """Host Fortran-ordered Float32 array and host Float32 (nfpc, ni, nto) profile
+    in, the Fortran-ordered (nc, ni, nt) result out (bldp_unfold_host_f32: the
+    window's rows and the profile staged on ``device`` once)."""
+    code = _unfold_op(how)
+    a = _host_fb(a, "unfold_host", "unfold")
+    _check_bounds(win, a.shape)
+    nfpc, T, dims = _fold_factors(a.shape, win, nfpc, tavby)
+    p = np.asarray(prof)
+    if p.dtype != np.float32:
+        raise TypeError(f"unfold_host: the profile must be float32, not {p.dtype}")
+    if p.shape != tuple(dims):
+        raise ValueError(f"unfold_host: the profile is {p.shape}, expected {tuple(dims)}")
+    p = np.asfortranarray(p)
+    out = np.empty(window_shape(win, a.shape), dtype=np.float32, order="F")
+    keep, wp = _lib.win_arg(_full_win(win, a.shape))
+    rc = _lib.lib().bldp_unfold_host_f32(
+        int(device), a.ctypes.data if a.size else None, a.shape[0], a.shape[1], a.shape[2], wp,
+        nfpc, T, code, p.ctypes.data if p.size else None, out.ctypes.data if out.size else None)
+    _lib.check(rc, "bldp_unfold_host_f32")
+    return out
+
+
 def stitch(gathered, nbank, out=None, stream=None):
     """gathered: nbank dense (nc, ni, nt) blocks back to back (1-D or a
     [nbank, nt, ni, nc] contiguous tensor); returns vcat (nbank*nc, ni, nt)."""

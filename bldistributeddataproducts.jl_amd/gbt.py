@@ -161,6 +161,49 @@ def getclean(workers, fnames, idxs=(COLON, COLON, COLON), *, fqavby=1, tavby=1, 
                                            nsigma=nsigma, func=func, device=int(w)))
 
 
+def _combine_bandpass(parts, func):
+    """One profile from the banks' ``sum`` and ``kept`` planes: both added in Float64
+    / int64 on the host before any division, the result rounded once to Float32."""
+    s = np.zeros(parts[0]["data"].shape, dtype=np.float64, order="F")
+    k = np.zeros(parts[0]["kept"].shape, dtype=np.int64, order="F")
+    for p in parts:
+        s += p["data"].astype(np.float64)
+        k += p["kept"]
+    if func == "mean":
+        with np.errstate(invalid="ignore", divide="ignore"):
+            s = s / k.astype(np.float64)
+    return {"data": s.astype(np.float32), "kept": k}
+
+
+def getbandpass(workers, fnames, idxs=(COLON, COLON, COLON), *, nfpc=None, tavby=None,
+                func="mean", mask=None):
+    """getkurtosis' fan-out (src/gbt.jl:81-88) with the fold of
+    WorkerFunctions.getbandpass: every worker folds its bank with ``"sum"``, and the
+    banks' ``sum`` and ``kept`` planes are combined in Float64 on the host before any
+    division, so the (nfpc, ni, nto) profile is the band's (the banks of a column
+    when ``workers`` is 2-D: a list with one dict per column).  ``kept`` is int64.
+    ``mask``: one mask, the window's shape, for every file."""
+    from . import engine
+
+    engine._masked_op(func)
+    res = _fanout(workers, fnames,
+                  lambda w, f: W.getbandpass(f, idxs, nfpc=nfpc, tavby=tavby, func="sum", mask=mask,
+                                             device=int(w)))
+    if res.ndim <= 1:
+        return _combine_bandpass(list(res), func)
+    return [_combine_bandpass(list(res[:, j]), func) for j in range(res.shape[1])]
+
+
+def getflattened(workers, fnames, idxs=(COLON, COLON, COLON), *, nfpc=None, tavby=None,
+                 how="divide", n=None, axis=2, nsigma=None):
+    """The same fan-out with WorkerFunctions.getflattened, bank by bank: per-bank
+    dicts of the flattened window (``"data"``), the bank's own profile
+    (``"profile"``) and ``"kept"``."""
+    return _fanout(workers, fnames,
+                   lambda w, f: W.getflattened(f, idxs, nfpc=nfpc, tavby=tavby, how=how, n=n,
+                                               axis=axis, nsigma=nsigma, device=int(w)))
+
+
 def _chan_window(idxs, nchans):
     """(start0, count, step) of the channel index (idxs[0]) over nchans."""
     from .idxs import JRange, is_colon, sanitizeidxs

@@ -17,7 +17,8 @@ export gpu_init, gpu_finalize, gpu_pin, gpu_unpin, gpu_fqav, gpu_reduce, gpu_kur
        gpu_quantiles, gpu_quantiles_plan, gpu_band_quantiles,
        gpu_outliers, gpu_outliers_plan, gpu_band_outliers,
        gpu_masked_reduce, gpu_band_masked_reduce, gpu_hits, gpu_band_hits,
-       gpu_histogram, gpu_histogram_plan, gpu_band_histogram
+       gpu_histogram, gpu_histogram_plan, gpu_band_histogram,
+       gpu_fold, gpu_fold_plan, gpu_band_fold, gpu_unfold, gpu_band_unfold
 
 const libbldp = get(ENV, "BLDP_LIB", joinpath(@__DIR__, "..", "libbldp_hip.so"))
 
@@ -987,6 +988,174 @@ function gpu_band_hits(banks::Vector{Ptr{Float32}}, dims::NTuple{3,Integer}, mas
          Ptr{Int64}, Ptr{Float32}, Ptr{UInt64}, Ptr{Cvoid}),
         length(banks), banks, dims[1], dims[2], dims[3], win, mask, mask_ld, cap, idx, val, total,
         stream))
+    nothing
+end
+
+# ---- fold / unfold: bldp_*fold_* and bldp_*unfold_* (a window over its coarse channels) ----
+_unfoldop(how) = how === :divide ? Cint(0) : how === :subtract ? Cint(1) :
+                 throw(ArgumentError("unfold takes :divide or :subtract, not $how"))
+# (nfpc, ni, nto) of a fold; tavby = nothing: the whole selected time range
+function _fold_shape(sz, win, nfpc, tavby)
+    shp = zeros(Int64, 3)
+    T = tavby === nothing ? max(win[8], 1) : tavby
+    GC.@preserve win check(ccall((:bldp_fold_shape, libbldp), Cint,
+        (Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Ptr{Int64}),
+        sz[1], sz[2], sz[3], win, nfpc, T, shp))
+    shp, T
+end
+
+"""
+    gpu_fold(A::Array{Float32,3}, nfpc; tavby=nothing, f=mean, mask=nothing, idxs=(:,:,:),
+             dev=0) -> (data, kept)
+
+The profile of `A[idxs...]` over its coarse channels on GPU `dev`
+(bldp_fold_host_f32): selected channel c has fine index `c mod nfpc`, and element
+`(k, i, t')` of `data` is `f` (`sum` or `mean`) of the samples of fine index k of
+every coarse channel and of the `tavby` spectra of time block t' (`nothing`: the
+whole selected time range), summed in Float64 and rounded once.  `mask`: `nothing`
+or a `UInt8` array of the window's size, any axis of which may be 1; a byte of 0
+keeps the sample.  `data` is `Float32` `(nfpc, ni, nto)`, `kept` `Int32`."""
+function gpu_fold(A::Array{Float32,3}, nfpc::Integer; tavby=nothing, f=mean, mask=nothing,
+                  idxs::Tuple=(:, :, :), dev::Integer=0)
+    op = _maskedop(f)
+    win = window(idxs, size(A))
+    shp, T = _fold_shape(size(A), win, nfpc, tavby)
+    ld = mask === nothing ? Int64[] : _mask_ld(mask, (win[2], win[5], win[8]))
+    mptr = mask === nothing ? Ptr{UInt8}(C_NULL) : pointer(mask)
+    ldp = mask === nothing ? Ptr{Int64}(C_NULL) : pointer(ld)
+    data = Array{Float32,3}(undef, shp...)
+    kept = Array{UInt32,3}(undef, shp...)
+    GC.@preserve A mask win ld data kept check(ccall((:bldp_fold_host_f32, libbldp), Cint,
+        (Cint, Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Cint, Ptr{UInt8},
+         Ptr{Int64}, Ptr{Float32}, Ptr{UInt32}),
+        dev, A, size(A, 1), size(A, 2), size(A, 3), win, nfpc, T, op, mptr, ldp, data, kept))
+    data, Int32.(kept)   # counts are < 2^31
+end
+
+"""
+    gpu_fold(in::Ptr{Float32}, dims, nfpc, tavby, mask::Ptr{UInt8}, out, kept; f=mean,
+             win=C_NULL, mask_ld=C_NULL, out_ld=nothing, stream=C_NULL)
+
+The same on DEVICE memory (bldp_fold_f32; asynchronous on `stream`): `mask` may be
+`C_NULL` (everything is kept); element (k, i, t') of `out` and `kept` at
+`[k + i*out_ld[1] + t'*out_ld[2]]` (dense by default).  `out` or `kept` may be
+`C_NULL`, not both.  Returns the dims of the outputs."""
+function gpu_fold(in::Ptr{Float32}, dims::NTuple{3,Integer}, nfpc::Integer, tavby::Integer,
+                  mask::Ptr{UInt8}, out::Ptr{Float32}, kept::Ptr{UInt32}; f=mean,
+                  win=Ptr{Int64}(C_NULL), mask_ld=Ptr{Int64}(C_NULL), out_ld=nothing,
+                  stream::Ptr{Cvoid}=C_NULL)
+    op = _maskedop(f)
+    shp = zeros(Int64, 3)
+    GC.@preserve win check(ccall((:bldp_fold_shape, libbldp), Cint,
+        (Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Ptr{Int64}),
+        dims[1], dims[2], dims[3], win, nfpc, tavby, shp))
+    ld = out_ld === nothing ? (shp[1], shp[1] * shp[2]) : out_ld
+    GC.@preserve win mask_ld check(ccall((:bldp_fold_f32, libbldp), Cint,
+        (Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Cint, Ptr{UInt8},
+         Ptr{Int64}, Ptr{Float32}, Ptr{UInt32}, Int64, Int64, Ptr{Cvoid}),
+        in, dims[1], dims[2], dims[3], win, nfpc, tavby, op, mask, mask_ld, out, kept, ld[1],
+        ld[2], stream))
+    (shp[1], shp[2], shp[3])
+end
+
+"""
+    gpu_fold_plan(dims, nfpc, tavby; win=C_NULL, mask_ld=C_NULL) -> NamedTuple
+
+The launch plan of `gpu_fold` on aligned device memory (bldp_fold_plan_f32;
+launches nothing and needs no GPU).  `mask_ld = C_NULL`: no mask."""
+function gpu_fold_plan(dims::NTuple{3,Integer}, nfpc::Integer, tavby::Integer;
+                       win=Ptr{Int64}(C_NULL), mask_ld=Ptr{Int64}(C_NULL))
+    info = zeros(Int64, 10)
+    GC.@preserve win mask_ld info check(ccall((:bldp_fold_plan_f32, libbldp), Cint,
+        (Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Ptr{UInt8}, Ptr{Int64},
+         Ptr{Int64}),
+        C_NULL, dims[1], dims[2], dims[3], win, nfpc, tavby, C_NULL, mask_ld, info))
+    (path = (:cols, :rows)[info[1] + 1], channel_lanes = info[2], chunks_per_block = info[3],
+     workgroups = info[4], workspace_bytes = info[5], launches = info[6],
+     mask_loads = (:byte, :dword, :row, :none)[info[7] + 1], vector_loads = info[8] != 0,
+     outputs = info[9], units_per_chunk = info[10])
+end
+
+"""
+    gpu_band_fold(banks::Vector{Ptr{Float32}}, dims, nfpc, tavby, mask, out, kept; f=mean,
+                  win=C_NULL, mask_ld=C_NULL, stream=C_NULL)
+
+The fold of a band resident on one GPU (bldp_band_fold_f32): ONE dense
+`(nfpc, ni, nto)` profile over the coarse channels of every bank, not a vcat; bank
+b's channel c is channel `b*nc + c` of the mask."""
+function gpu_band_fold(banks::Vector{Ptr{Float32}}, dims::NTuple{3,Integer}, nfpc::Integer,
+                       tavby::Integer, mask::Ptr{UInt8}, out::Ptr{Float32}, kept::Ptr{UInt32};
+                       f=mean, win=Ptr{Int64}(C_NULL), mask_ld=Ptr{Int64}(C_NULL),
+                       stream::Ptr{Cvoid}=C_NULL)
+    op = _maskedop(f)
+    GC.@preserve banks win mask_ld check(ccall((:bldp_band_fold_f32, libbldp), Cint,
+        (Cint, Ptr{Ptr{Float32}}, Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Cint,
+         Ptr{UInt8}, Ptr{Int64}, Ptr{Float32}, Ptr{UInt32}, Ptr{Cvoid}),
+        length(banks), banks, dims[1], dims[2], dims[3], win, nfpc, tavby, op, mask, mask_ld,
+        out, kept, stream))
+    nothing
+end
+
+"""
+    gpu_unfold(A::Array{Float32,3}, prof::Array{Float32,3}, nfpc; tavby=nothing,
+               how=:divide, idxs=(:,:,:), dev=0) -> Array{Float32,3}
+
+`A[idxs...]` with the profile taken out on GPU `dev` (bldp_unfold_host_f32):
+element (c, i, t) divided by (`:divide`) or less (`:subtract`)
+`prof[c mod nfpc, i, t div tavby]` (1-based: `prof[mod(c-1, nfpc)+1, i, div(t-1, tavby)+1]`),
+one rounded Float32 operation.  `prof` is `gpu_fold`'s `data`."""
+function gpu_unfold(A::Array{Float32,3}, prof::Array{Float32,3}, nfpc::Integer; tavby=nothing,
+                    how::Symbol=:divide, idxs::Tuple=(:, :, :), dev::Integer=0)
+    uop = _unfoldop(how)
+    win = window(idxs, size(A))
+    shp, T = _fold_shape(size(A), win, nfpc, tavby)
+    size(prof) == (shp[1], shp[2], shp[3]) ||
+        throw(DimensionMismatch("profile $(size(prof)) is not $((shp[1], shp[2], shp[3]))"))
+    out = Array{Float32,3}(undef, win[2], win[5], win[8])
+    GC.@preserve A prof win out check(ccall((:bldp_unfold_host_f32, libbldp), Cint,
+        (Cint, Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Cint, Ptr{Float32},
+         Ptr{Float32}),
+        dev, A, size(A, 1), size(A, 2), size(A, 3), win, nfpc, T, uop, prof, out))
+    out
+end
+
+"""
+    gpu_unfold(in::Ptr{Float32}, dims, nfpc, tavby, prof::Ptr{Float32}, prof_ld, out, out_ld;
+               how=:divide, win=C_NULL, stream=C_NULL)
+
+The same on DEVICE memory (bldp_unfold_f32; asynchronous on `stream`, one launch):
+`prof[k + prof_ld[1]*i + prof_ld[2]*t']`, `out[c + out_ld[1]*i + out_ld[2]*t]`
+(0-based), so a bank can write its slot of a stitched band.  Not in place."""
+function gpu_unfold(in::Ptr{Float32}, dims::NTuple{3,Integer}, nfpc::Integer, tavby::Integer,
+                    prof::Ptr{Float32}, prof_ld::NTuple{2,Integer}, out::Ptr{Float32},
+                    out_ld::NTuple{2,Integer}; how::Symbol=:divide, win=Ptr{Int64}(C_NULL),
+                    stream::Ptr{Cvoid}=C_NULL)
+    uop = _unfoldop(how)
+    GC.@preserve win check(ccall((:bldp_unfold_f32, libbldp), Cint,
+        (Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Cint, Ptr{Float32}, Int64,
+         Int64, Ptr{Float32}, Int64, Int64, Ptr{Cvoid}),
+        in, dims[1], dims[2], dims[3], win, nfpc, tavby, uop, prof, prof_ld[1], prof_ld[2], out,
+        out_ld[1], out_ld[2], stream))
+    nothing
+end
+
+"""
+    gpu_band_unfold(banks::Vector{Ptr{Float32}}, dims, nfpc, tavby, prof, prof_ld, out;
+                    how=:divide, win=C_NULL, stream=C_NULL)
+
+The unfold of every bank of a band resident on one GPU in one launch
+(bldp_band_unfold_f32) with ONE profile: `out` holds the dense vcat
+`(nbank*nc, ni, nt)`."""
+function gpu_band_unfold(banks::Vector{Ptr{Float32}}, dims::NTuple{3,Integer}, nfpc::Integer,
+                         tavby::Integer, prof::Ptr{Float32}, prof_ld::NTuple{2,Integer},
+                         out::Ptr{Float32}; how::Symbol=:divide, win=Ptr{Int64}(C_NULL),
+                         stream::Ptr{Cvoid}=C_NULL)
+    uop = _unfoldop(how)
+    GC.@preserve banks win check(ccall((:bldp_band_unfold_f32, libbldp), Cint,
+        (Cint, Ptr{Ptr{Float32}}, Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Cint,
+         Ptr{Float32}, Int64, Int64, Ptr{Float32}, Ptr{Cvoid}),
+        length(banks), banks, dims[1], dims[2], dims[3], win, nfpc, tavby, uop, prof, prof_ld[1],
+        prof_ld[2], out, stream))
     nothing
 end
 

@@ -1070,6 +1070,94 @@ def gethits(src, idxs=(COLON, COLON, COLON), *, n=None, axis=2, nsigma=5.0, maxh
                         _hits_to_host)
 
 
+def _source_nfpc(src, nfpc, what):
+    """``nfpc`` as given, or the file header's; an array source must name it."""
+    if nfpc is not None:
+        if int(nfpc) < 1:
+            raise ValueError(f"{what}: nfpc={nfpc!r} is less than 1")
+        return int(nfpc)
+    if isinstance(src, (str, bytes)) or hasattr(src, "__fspath__"):
+        return int(readers.getheader(src)["nfpc"])
+    raise ValueError(f"{what}: an array source has no header; name nfpc")
+
+
+def getbandpass(src, idxs=(COLON, COLON, COLON), *, nfpc=None, tavby=None, func="mean", mask=None,
+                device=0):
+    """The window folded over its coarse channels: a dict with ``"data"``, the
+    (nfpc, ni, nto) ``func`` (``"sum"`` or ``"mean"``) over every coarse channel and
+    every block of ``tavby`` selected spectra (``None``: the whole selected time
+    range) at each fine-channel index, and ``"kept"`` (int32), the samples that went
+    into it (engine.fold; the rule of include/bldp.h).  ``nfpc=None`` takes the file
+    header's ``nfpc``; an array source must name it.  ``mask``: None, or flags of the
+    window's shape as getmasked takes them.  Files reach the GPU as getdata reads
+    them and a host array is staged there, both returning host arrays; a device
+    tensor stays on the device.  Float32 data only."""
+    engine._masked_op(func)  # (the ValueErrors before any file is touched)
+    host_mask = None
+    if mask is not None:
+        if _is_tensor(mask):
+            mdt = str(mask.dtype).replace("torch.", "")
+        else:
+            host_mask = np.asarray(mask)
+            mdt = str(host_mask.dtype)
+        if mdt not in ("uint8", "bool"):
+            raise TypeError(f"getbandpass: the mask must be uint8 or bool, not {mdt}")
+    nfpc = _source_nfpc(src, nfpc, "getbandpass")
+    kw = dict(nfpc=nfpc, tavby=tavby, op=func)
+
+    def on_device(x, win):
+        m = mask
+        if host_mask is not None:
+            import torch
+
+            m = torch.from_numpy(np.ascontiguousarray(host_mask.view(np.uint8)))
+        return engine.fold(x, mask=None if m is None else m.to(x.device), win=win, **kw)
+
+    def on_host(a, win):
+        m = host_mask if host_mask is not None or mask is None else mask.cpu().numpy()
+        return engine.fold_host(a, mask=m, win=win, device=device, **kw)
+
+    return _read_moment("getbandpass", "fold", src, sanitizeidxs(idxs), device, on_device, on_host,
+                        lambda r: {k: engine.fb_to_numpy(t) for k, t in r.items()})
+
+
+def getflattened(src, idxs=(COLON, COLON, COLON), *, nfpc=None, tavby=None, how="divide", n=None,
+                 axis=2, nsigma=None, device=0):
+    """Fold and unfold on one device tensor: the window divided by
+    (``how="divide"``) or less (``"subtract"``) its own mean profile over the coarse
+    channels.  A dict with ``"data"``, the flattened (nc, ni, nt) window,
+    ``"profile"``, the (nfpc, ni, nto) mean of engine.fold, and ``"kept"`` (int32).
+    With ``nsigma``, engine.outliers first flags every block of ``n`` selected
+    channels (``axis=0``) or spectra (``axis=2``; ``n=None``: the whole selected time
+    range) and the profile is folded over the unflagged samples alone; the mask
+    never leaves the device.  Sources and ``nfpc`` as getbandpass takes them;
+    Float32 data only."""
+    engine._unfold_op(how)  # (the ValueErrors before any file is touched)
+    if nsigma is not None:
+        engine._outliers_args(axis, nsigma, ("count",))
+    nfpc = _source_nfpc(src, nfpc, "getflattened")
+
+    def on_device(x, win):
+        m = None
+        if nsigma is not None:
+            m = engine.outliers(x, n=n, axis=axis, nsigma=nsigma, win=win, mask=True,
+                                which=("count",))["mask"]
+        p = engine.fold(x, nfpc, tavby, "mean", mask=m, win=win)
+        return {"data": engine.unfold(x, p["data"], nfpc, tavby, how, win=win),
+                "profile": p["data"], "kept": p["kept"]}
+
+    def on_host(a, win):  # staged whole, so that every step reads one device tensor
+        import torch
+
+        dev = f"cuda:{device}"
+        with torch.cuda.device(dev):
+            return {k: engine.fb_to_numpy(t)
+                    for k, t in on_device(engine.fb_from_numpy(a, device=dev), win).items()}
+
+    return _read_moment("getflattened", "getflattened", src, sanitizeidxs(idxs), device, on_device,
+                        on_host, lambda r: {k: engine.fb_to_numpy(t) for k, t in r.items()})
+
+
 getinventory = readers.getinventory
 getfbheader = readers.getfbheader
 getfbh5header = readers.getfbh5header

@@ -95,7 +95,8 @@ extern "C" {
  *    (additive, same version) the bldp_outliers_* entry points;
  *    (additive, same version) the bldp_*masked_reduce_* entry points;
  *    (additive, same version) the bldp_*histogram_* entry points;
- *    (additive, same version) the bldp_*hits_* entry points */
+ *    (additive, same version) the bldp_*hits_* entry points;
+ *    (additive, same version) the bldp_*fold_* and bldp_*unfold_* entry points */
 #define BLDP_ABI_VERSION 5
 
 #if defined(BLDP_BUILD)
@@ -1011,6 +1012,135 @@ BLDP_API int bldp_hits_host_f32(int dev, const float *in, int64_t nchan, int64_t
                                 int64_t ntime, const int64_t *win, const uint8_t *mask,
                                 const int64_t *mask_ld, int64_t cap, int64_t *idx, float *val,
                                 uint64_t *total);
+
+/* Fold and unfold: a window over its coarse channels.  Every coarse channel of a
+ * filterbank product carries the polyphase filterbank's passband; the fold gives
+ * that shape as a profile over the fine-channel index, and the unfold takes it out
+ * of the window.  Float32 input; additive in ABI 5.
+ *
+ * The window and its blocks
+ *  - win selects (nc, ni, nt) with offsets, steps and direction, as for
+ *    bldp_reduce_f32.
+ *  - Selected channel c (0-based, in window order) has fine index k = c mod nfpc
+ *    and coarse index j = c div nfpc; J = nc / nfpc.
+ *  - tavby = T cuts the selected spectra into nto = nt / T blocks; tavby <= 1
+ *    means T = 1.
+ *  - In Julia terms the fold is
+ *    dropdims(sum(reshape(A, nfpc, J, ni, T, nto); dims=(2,4)); dims=(2,4)).
+ *
+ * Fold, for output (k, i, t').  The block is the J*T samples
+ * A[k + nfpc*j, i, t'*T + tt].
+ *  1. The mask is optional: mask == NULL keeps everything.
+ *  2. The mask is addressed exactly as bldp_masked_reduce_f32 addresses it: in
+ *     window coordinates, flag (c, i, t) the byte mask[c*mask_ld[0] + i*mask_ld[1]
+ *     + t*mask_ld[2]]; mask_ld == NULL means dense {1, nc, nc*ni}; a stride of 0
+ *     broadcasts; a byte of 0 keeps the sample and any other value flags it;
+ *     negative strides are BLDP_EINVAL.
+ *  3. The mask of bldp_outliers_f32 and a bad-channel list {1, 0, 0} go in as they
+ *     are.
+ *  4. kept (uint32) is the number of kept samples of the block.
+ *  5. BLDP_OP_SUM is the Float64 sum of the kept Float32 samples, in any order,
+ *     rounded once to Float32.
+ *  6. Blocks reach 64 x 879616 samples on a 0001 bank, so no partial sum is ever
+ *     held in Float32: lanes, workgroups and the merge all add Float64.
+ *  7. A flagged sample is excluded by selection, never multiplied by 0: a flagged
+ *     NaN or +-Inf leaves the result finite, a kept NaN propagates, and a block
+ *     with nothing kept gives +0.0.
+ *  8. BLDP_OP_MEAN is that Float64 sum divided once in Float64 by Float64(kept),
+ *     then rounded once to Float32.  Nothing kept gives NaN.
+ *  9. Every other op is BLDP_EINVAL.
+ * 10. Two calls give identical bits.  Where a block is shared between workgroups
+ *     the Float64 partial sums and the integer counts go to leased library scratch
+ *     and a merge launch adds them in an order the plan fixes.  No floating-point atomics.
+ *
+ * Unfold.  out[c, i, t] = A[c, i, t] o prof[c mod nfpc, i, t div T].
+ *  - BLDP_UNFOLD_DIV = 0: one correctly rounded Float32 division; IEEE results
+ *    stand for a zero, infinite or NaN profile value.
+ *  - BLDP_UNFOLD_SUB = 1: one Float32 subtraction.
+ *  - prof is addressed as prof[k + prof_ld_i*i + prof_ld_t*t'], out as
+ *    out[c + out_ld_i*i + out_ld_t*t], so a bank can write its slot of a stitched
+ *    band.
+ *
+ * Refusals, all before any launch
+ *  - BLDP_EINVAL: nfpc < 1; an op outside the family; J*T > 2^31 - 1 (over all
+ *    banks of a band: Python and the shim read Int32 counts); both fold outputs
+ *    NULL on a non-empty result; a null in, prof or out; negative mask or profile
+ *    strides; negative or overlapping output strides; outputs that overlap each
+ *    other, the input window, the mask's span or the profile.  The unfold is
+ *    therefore not in place.
+ *  - BLDP_EDIM: nfpc not dividing nc, or T not dividing nt.
+ *  - BLDP_EBOUNDS: a window outside the array.
+ *  - An empty window launches nothing; its shape is (0, ni, nto).
+ *
+ * Band form, one GPU.  The window is the vcat (nbank*nc, ni, nt); nfpc must divide
+ * the per-bank nc, so every bank starts at k = 0.  bldp_band_fold_f32 returns ONE
+ * dense (nfpc, ni, nto) profile over all nbank*J coarse channels, not a vcat; bank
+ * b's channel c is channel b*nc + c of the mask (mask_ld == NULL: the dense
+ * (nbank*nc, ni, nt) mask).  bldp_band_unfold_f32 writes the dense vcat
+ * (nbank*nc, ni, nt).
+ *
+ * The kernels (csrc/fold.hip).  An item is the float4 a lane loads when the channel
+ * step is 1, nfpc % 4 == 0 and every row of the window starts on a 16-byte
+ * boundary, else one value.  "cols" (more than 128 items per coarse channel): lanes
+ * along k, each walking j and tt.  "rows" (up to 128): the lanes of a workgroup lie
+ * along c over up to 256 items of a row, several coarse channels, and lanes with
+ * equal k meet through LDS.  Where the (k, i, t') tiles alone do not fill the device a block's
+ * (bank, j, tt) walk is cut into chunks, a workgroup each, and merged.  The flags
+ * are loaded as for the masked reduce: one aligned dword per float4, one byte per
+ * row when mask_ld[0] == 0, else a byte per element.
+ *
+ * bldp_fold_shape: out_shape = (nfpc, ni, nto).
+ * bldp_fold_plan_f32: info = {path (0 cols, 1 rows), lanes along the channels,
+ * chunks per block, workgroups of the fold launch, workspace bytes, launches (1,
+ * or 2 with the merge), mask load form (0 byte, 1 dword, 2 row-uniform, 3 no
+ * mask), vector loads 1 / 0, outputs, (bank, coarse group, spectrum) units per
+ * chunk}.  Launches nothing and needs no GPU; the pointers may be null (a null
+ * pointer counts as aligned).  mask and mask_ld both NULL: no mask; mask NULL and
+ * mask_ld given: an aligned mask of those strides.
+ * bldp_fold_f32: device pointers, asynchronous on `stream`; out or kept may be
+ * NULL (not both) and is then neither formed nor stored.
+ * bldp_fold_host_f32: host in, host mask (or NULL), host dense (nfpc, ni, nto)
+ * outs; the window's rows and the mask's span are staged on device `dev` once.
+ * Synchronous.
+ * bldp_unfold_plan_f32: info = {vector loads 1 / 0, workgroups per bank, elements
+ * per lane per pass, reserved (0)}.
+ * bldp_unfold_f32: device pointers, asynchronous on `stream`, one launch.
+ * bldp_unfold_host_f32: host in, host dense (nfpc, ni, nto) prof, host dense
+ * (nc, ni, nt) out.  Synchronous. */
+enum bldp_unfold_op { BLDP_UNFOLD_DIV = 0, BLDP_UNFOLD_SUB = 1 };
+BLDP_API int bldp_fold_shape(int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win,
+                             int64_t nfpc, int64_t tavby, int64_t out_shape[3]);
+BLDP_API int bldp_fold_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                                const int64_t *win, int64_t nfpc, int64_t tavby,
+                                const uint8_t *mask, const int64_t *mask_ld, int64_t info[10]);
+BLDP_API int bldp_fold_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                           const int64_t *win, int64_t nfpc, int64_t tavby, int op,
+                           const uint8_t *mask, const int64_t *mask_ld, float *out,
+                           uint32_t *kept, int64_t out_ld_i, int64_t out_ld_t, void *stream);
+BLDP_API int bldp_band_fold_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                                int64_t ntime, const int64_t *win, int64_t nfpc, int64_t tavby,
+                                int op, const uint8_t *mask, const int64_t *mask_ld, float *out,
+                                uint32_t *kept, void *stream);
+BLDP_API int bldp_fold_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                int64_t ntime, const int64_t *win, int64_t nfpc, int64_t tavby,
+                                int op, const uint8_t *mask, const int64_t *mask_ld, float *out,
+                                uint32_t *kept);
+BLDP_API int bldp_unfold_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                                  const int64_t *win, int64_t nfpc, int64_t tavby,
+                                  const float *prof, int64_t prof_ld_i, int64_t prof_ld_t,
+                                  const float *out, int64_t out_ld_i, int64_t out_ld_t,
+                                  int64_t info[4]);
+BLDP_API int bldp_unfold_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                             const int64_t *win, int64_t nfpc, int64_t tavby, int uop,
+                             const float *prof, int64_t prof_ld_i, int64_t prof_ld_t, float *out,
+                             int64_t out_ld_i, int64_t out_ld_t, void *stream);
+BLDP_API int bldp_band_unfold_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                                  int64_t ntime, const int64_t *win, int64_t nfpc, int64_t tavby,
+                                  int uop, const float *prof, int64_t prof_ld_i,
+                                  int64_t prof_ld_t, float *out, void *stream);
+BLDP_API int bldp_unfold_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                  int64_t ntime, const int64_t *win, int64_t nfpc, int64_t tavby,
+                                  int uop, const float *prof, float *out);
 
 /* Element types other than Float32 (what Blio maps SIGPROC nbits 8 / 16 to, and
  * what HDF5.jl returns for an integer or Float64 dataset: the reference's
