@@ -106,6 +106,155 @@ int resolve_factors(const Geo &g, int64_t fqavby, int64_t tavby, int64_t *F, int
   return BLDP_OK;
 }
 
+// ---- the front end the block operations share --------------------------------
+// An operation's prepare is its own checks and fields, its planner call and a
+// list of these; `what` is the prefix of the family's messages ("" the reduce's).
+int check_nbank(int nbank) {
+  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
+    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
+  return BLDP_OK;
+}
+
+// The window and the factors of its blocks.
+int resolve_blocks(int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win, int64_t fqavby,
+                   int64_t tavby, Geo *g, int64_t *F, int64_t *T) {
+  const int rc = resolve_window(nchan, nif, ntime, win, g);
+  return rc ? rc : resolve_factors(*g, fqavby, tavby, F, T);
+}
+
+// counts, sums and offsets within a block are 31-bit (Python and the shim read
+// Int32).  F <= nc and T <= nt: the product cannot overflow int64 for arrays
+// that exist, and is checked by division anyway.
+int check_block31(const char *what, int64_t F, int64_t T) {
+  if (F > INT32_MAX / T)
+    return fail(BLDP_EINVAL, "%sblocks of fqavby x tavby = %lld x %lld elements are beyond "
+                "2^31 - 1", what, (long long)F, (long long)T);
+  return BLDP_OK;
+}
+
+bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+bool aligned4(const void *p) { return ((uintptr_t)p & 3) == 0; }
+
+// The banks and the window's strides of any args struct; *words / *rows16: every
+// bank pointer is 4 / 16-byte aligned (a null one counts as aligned).
+template <class A>
+int set_window(const char *what, A &a, const Geo &g, int nbank, const float *const *in,
+               bool *words = nullptr, bool *rows16 = nullptr) {
+  if (!in) return fail(BLDP_EINVAL, "%snull input pointer array", what);
+  a.nbank = nbank;
+  a.in_off = g.off, a.in_cs = g.cs, a.in_ld_i = g.ld_i, a.in_ld_t = g.ld_t;
+  bool w = true, r = true;
+  for (int b = 0; b < nbank; ++b) {
+    a.in[b] = in[b];
+    w = w && aligned4(in[b]);
+    r = r && aligned16(in[b]);
+  }
+  if (words) *words = w;
+  if (rows16) *rows16 = r;
+  return BLDP_OK;
+}
+
+int check_banks(const char *what, int nbank, const float *const *in) {
+  for (int b = 0; b < nbank; ++b)
+    if (!in[b]) return fail(BLDP_EINVAL, "%snull input pointer (bank %d)", what, b);
+  return BLDP_OK;
+}
+
+// The F x T blocks of a window and where their results go: output (c', i, t') of
+// bank b at [b*out_bank + c' + i*out_ld_i + t'*out_ld_t].  True when there is none.
+template <class A>
+bool set_blocks(A &a, const Geo &g, int64_t F, int64_t T, int64_t out_bank, int64_t out_ld_i,
+                int64_t out_ld_t) {
+  a.nco = g.nc / F, a.ni = g.ni, a.nto = g.nt / T, a.F = F, a.T = T;
+  a.out_bank = out_bank, a.out_ld_i = out_ld_i, a.out_ld_t = out_ld_t;
+  return a.nco == 0 || a.ni == 0 || a.nto == 0;
+}
+
+// The dense vcat of nbank (d[0], d[1], d[2]) products: bank k's channels at k*d[0]
+// of every (IF, time) row.
+void vcat_layout(int nbank, const int64_t d[3], int64_t *bank, int64_t *ld_i, int64_t *ld_t) {
+  *bank = d[0];
+  *ld_i = nbank * d[0];
+  *ld_t = nbank * d[0] * d[1];
+}
+
+// What a band entry point checks before its run, and where its dense product
+// goes: l = {out_bank, out_ld_i, out_ld_t, out_ld_q} of the vcat of the banks.
+int band_layout(int nbank, int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win,
+                int64_t fqavby, int64_t tavby, int64_t l[4]) {
+  int rc = check_nbank(nbank);
+  if (rc) return rc;
+  Geo g;
+  int64_t F, T;
+  rc = resolve_blocks(nchan, nif, ntime, win, fqavby, tavby, &g, &F, &T);
+  if (rc) return rc;
+  const int64_t d[3] = {g.nc / F, g.ni, g.nt / T};
+  vcat_layout(nbank, d, &l[0], &l[1], &l[2]);
+  l[3] = l[2] * d[2];
+  return BLDP_OK;
+}
+
+int check_out_strides(const char *what, int nbank, int64_t out_bank, int64_t ld_i, int64_t ld_t,
+                      int64_t d0, int64_t d1, int64_t d2) {
+  if (ld_i < d0 || ld_t < (d1 - 1) * ld_i + d0 || (nbank > 1 && out_bank < d0))
+    return fail(BLDP_EINVAL, "%sout strides (%lld, %lld) overlap for a (%lld, %lld, %lld) result",
+                what, (long long)ld_i, (long long)ld_t, (long long)d0, (long long)d1,
+                (long long)d2);
+  return BLDP_OK;
+}
+
+// The strides of a mask of an (NC, ni, .) window: the dense ones, or the caller's.
+int mask_strides(const char *what, const int64_t *mask_ld, int64_t NC, int64_t ni, int64_t ld[3]) {
+  ld[0] = 1, ld[1] = NC, ld[2] = NC * ni;
+  for (int ax = 0; mask_ld && ax < 3; ++ax) {
+    ld[ax] = mask_ld[ax];
+    if (ld[ax] < 0)
+      return fail(BLDP_EINVAL, "%smask stride %d is negative (%lld)", what, ax, (long long)ld[ax]);
+  }
+  return BLDP_OK;
+}
+
+// lowest element offset and byte length of a window's elements
+void window_span(const Geo &g, int64_t *lo, size_t *bytes) {
+  int64_t l = g.off, h = g.off;
+  const int64_t span[3] = {(g.nc - 1) * g.cs, (g.ni - 1) * g.ld_i, (g.nt - 1) * g.ld_t};
+  for (int ax = 0; ax < 3; ++ax) (span[ax] < 0 ? l : h) += span[ax];
+  *lo = l;
+  *bytes = 4 * (size_t)(h - l + 1);
+}
+
+bool spans_overlap(const void *a, size_t na, const void *b, size_t nb) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return na > 0 && nb > 0 && x < y + nb && y < x + na;
+}
+
+// The outputs (null ones skipped) may not overlap the window's elements of any
+// bank, the mask's or profile's span `aux`, nor each other.
+struct Span {
+  const void *p;
+  size_t bytes;
+  const char *name;
+};
+int check_disjoint(const char *what, const Span *out, int nout, const Geo &g, int nbank,
+                   const float *const *in, const Span &aux) {
+  int64_t lo;
+  size_t wbytes;
+  window_span(g, &lo, &wbytes);
+  for (int q = 0; q < nout; ++q) {
+    if (!out[q].p) continue;
+    for (int b = 0; b < nbank; ++b)
+      if (spans_overlap(out[q].p, out[q].bytes, in[b] + lo, wbytes))
+        return fail(BLDP_EINVAL, "%s%s overlaps the input window (bank %d)", what, out[q].name, b);
+    if (spans_overlap(out[q].p, out[q].bytes, aux.p, aux.bytes))
+      return fail(BLDP_EINVAL, "%s%s overlaps %s", what, out[q].name, aux.name);
+  }
+  for (int q = 0; q < nout; ++q)
+    for (int r = q + 1; r < nout; ++r)
+      if (out[q].p && out[r].p && spans_overlap(out[q].p, out[q].bytes, out[r].p, out[r].bytes))
+        return fail(BLDP_EINVAL, "%s%s and %s overlap", what, out[q].name, out[r].name);
+  return BLDP_OK;
+}
+
 int num_cus_current() {
   static std::mutex mu;
   static std::map<int, int> cache;
@@ -257,9 +406,30 @@ void bldp::scratch_release_all() {
 
 namespace {
 
+// Queue a planned operation on s: lease `ws_bytes` of scratch (held until
+// `launch(workspace)` has queued every kernel) and record a failed launch.
+template <class Launch>
+int run_planned(const char *what, size_t ws_bytes, hipStream_t s, Launch launch) {
+  ScratchLease lease;
+  if (ws_bytes) {
+    const int rc = scratch_lease(s, ws_bytes, &lease);
+    if (rc) return rc;
+  }
+  const hipError_t e = launch(lease.ptr);
+  if (e != hipSuccess) return fail(BLDP_EHIP, "%s launch: %s", what, hipGetErrorString(e));
+  return BLDP_OK;
+}
 
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-bool aligned4(const void *p) { return ((uintptr_t)p & 3) == 0; }
+// The first eight words of a plan query over the reduce's plan and the tstat's.
+void fill_reduce_info(int64_t *info, const Plan &p, const RedArgs &a) {
+  info[0] = p.path, info[1] = p.lpg, info[2] = a.ts, info[3] = a.k4, info[4] = a.nchunk;
+  info[5] = p.grid, info[6] = (int64_t)p.ws_bytes, info[7] = a.vec_out;
+}
+void fill_tstat_info(int64_t *info, const TStatPlan &p, const TStatArgs &a) {
+  info[0] = p.path, info[1] = p.cpl, info[2] = p.tsplit, info[3] = p.passes;
+  info[4] = p.grid, info[5] = (int64_t)p.ws_bytes, info[6] = a.nb;
+  info[7] = p.tsplit > 1 ? ((int64_t)1 << a.lx_log2) : 0;
+}
 
 bool pitch_ok(const Geo &g) {
   return (g.ni <= 1 || g.ld_i % 4 == 0) && (g.nt <= 1 || g.ld_t % 4 == 0);
@@ -300,8 +470,8 @@ int prepare_reduce(int nbank, const float *const *in, int64_t nchan, int64_t nif
                    int64_t out_bank, int64_t out_ld_i, int64_t out_ld_t, bool stitched,
                    bool query, RedArgs *ap, Plan *pp, bool *empty, const double *qp = nullptr,
                    bool qset = false) {
-  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
-    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
+  int rc = check_nbank(nbank);
+  if (rc) return rc;
   if (qset)  // (the bldp_quantiles_* entry points: the ranks travel in a QSet)
     op = kOpQuantiles;
   else if (qp)
@@ -316,46 +486,26 @@ int prepare_reduce(int nbank, const float *const *in, int64_t nchan, int64_t nif
                 "tavby=%lld: var/std/median/mad have no time integration (tavby <= 1)",
                 (long long)tavby);
   Geo g;
-  int rc = resolve_window(nchan, nif, ntime, win, &g);
-  if (rc) return rc;
   int64_t F, T;
-  rc = resolve_factors(g, fqavby, tavby, &F, &T);
+  rc = resolve_blocks(nchan, nif, ntime, win, fqavby, tavby, &g, &F, &T);
   if (rc) return rc;
   RedArgs &a = *ap;
   a = RedArgs{};
-  a.nco = g.nc / F;
-  a.ni = g.ni;
-  a.nto = g.nt / T;
-  a.F = F;
-  a.T = T;
-  a.nbank = nbank;
   if (qp && F > 1) {
     int64_t q;
     quantile_rank(F, *qp, &q, &a.qg);
     a.qrank = (int32_t)q;
   }
   if (stitched) {
-    a.out_bank = a.nco;
-    a.out_ld_i = nbank * a.nco;
-    a.out_ld_t = nbank * a.nco * a.ni;
-  } else {
-    a.out_bank = out_bank;
-    a.out_ld_i = out_ld_i;
-    a.out_ld_t = out_ld_t;
+    const int64_t d[3] = {g.nc / F, g.ni, g.nt / T};
+    vcat_layout(nbank, d, &out_bank, &out_ld_i, &out_ld_t);
   }
-  a.in_off = g.off;
-  a.in_cs = g.cs;
-  a.in_ld_i = g.ld_i;
-  a.in_ld_t = g.ld_t;
+  *empty = set_blocks(a, g, F, T, out_bank, out_ld_i, out_ld_t);
   a.out = out;
-  *empty = a.nco == 0 || a.ni == 0 || a.nto == 0;
-  bool rows16 = pitch_ok(g), words = true;
-  if (!in) return fail(BLDP_EINVAL, "null input pointer array");
-  for (int b = 0; b < nbank; ++b) {
-    a.in[b] = in[b];
-    rows16 = rows16 && aligned16(a.in[b]);
-    words = words && aligned4(a.in[b]);
-  }
+  bool rows16, words;
+  rc = set_window("", a, g, nbank, in, &words, &rows16);
+  if (rc) return rc;
+  rows16 = rows16 && pitch_ok(g);
   const bool aligned = (rows16 && vec_ok(g)) ||
                        (opt(OPT_UNALIGNED_VEC) >= 1 && words && g.cs == 1 &&
                         unaligned_vec_pays(F, rows16));
@@ -366,26 +516,20 @@ int prepare_reduce(int nbank, const float *const *in, int64_t nchan, int64_t nif
     *pp = plan_reduce(a, aligned, rows16, words && g.cs == 1, num_cus_current(),
                       xcd_log2_current());
   }
-  if (!query) {
-    for (int b = 0; b < nbank; ++b)
-      if (!in[b] && !*empty) return fail(BLDP_EINVAL, "null input pointer (bank %d)", b);
-    if (!out && !*empty) return fail(BLDP_EINVAL, "null output pointer");
-  }
+  if (query || *empty) return BLDP_OK;
+  rc = check_banks("", nbank, in);
+  if (rc) return rc;
+  if (!out) return fail(BLDP_EINVAL, "null output pointer");
   return BLDP_OK;
 }
 
 // Queue a prepared reduce on stream s (scratch leased for time-chunk partials).
 int run_reduce(RedArgs a, const Plan &p, int op, hipStream_t s) {
-  ScratchLease lease;  // held until the launches are queued
-  if (p.ws_bytes) {
-    int rc = scratch_lease(s, p.ws_bytes, &lease);
-    if (rc) return rc;
-    a.ws = (float *)lease.ptr;
-  }
-  hipError_t e = stat_op(op) || op == kOpQuantile ? launch_stats(a, p, op, s)
-                                                  : launch_reduce(a, p, op, s);
-  if (e != hipSuccess) return fail(BLDP_EHIP, "reduce launch: %s", hipGetErrorString(e));
-  return BLDP_OK;
+  return run_planned("reduce", p.ws_bytes, s, [&](void *ws) {
+    if (ws) a.ws = (float *)ws;
+    return stat_op(op) || op == kOpQuantile ? launch_stats(a, p, op, s)
+                                            : launch_reduce(a, p, op, s);
+  });
 }
 
 int reduce_impl(int nbank, const float *const *in, int64_t nchan, int64_t nif, int64_t ntime,
@@ -400,14 +544,8 @@ int reduce_impl(int nbank, const float *const *in, int64_t nchan, int64_t nif, i
   if (rc) return rc;
   if (qp) op = kOpQuantile;
   if (info) {
-    info[0] = p.path;
-    info[1] = p.lpg;
-    info[2] = p.path == PATH_VEC_ROW ? a.rsplit : a.ts;  // (k_reduce_rows: slices splitting T)
-    info[3] = a.k4;
-    info[4] = a.nchunk;
-    info[5] = p.grid;
-    info[6] = (int64_t)p.ws_bytes;
-    info[7] = a.vec_out;
+    fill_reduce_info(info, p, a);
+    if (p.path == PATH_VEC_ROW) info[2] = a.rsplit;  // (k_reduce_rows: slices splitting T)
     if (qp) info[6] = a.F > 1 ? a.qrank : -1;  // (no workspace: the slot carries the lower rank)
     return BLDP_OK;  // plan query only
   }
@@ -453,10 +591,8 @@ int bldp_reduce_shape(int64_t nchan, int64_t nif, int64_t ntime, const int64_t *
                       int64_t fqavby, int64_t tavby, int64_t out_shape[3]) {
   if (!out_shape) return fail(BLDP_EINVAL, "null out_shape");
   Geo g;
-  int rc = resolve_window(nchan, nif, ntime, win, &g);
-  if (rc) return rc;
   int64_t F, T;
-  rc = resolve_factors(g, fqavby, tavby, &F, &T);
+  const int rc = resolve_blocks(nchan, nif, ntime, win, fqavby, tavby, &g, &F, &T);
   if (rc) return rc;
   out_shape[0] = g.nc / F;
   out_shape[1] = g.ni;
@@ -777,8 +913,7 @@ int bldp_band_reduce_multi_f32(int nbank, const int *bank_dev, const float *cons
 
 int bldp_stitch_f32(int nbank, const float *gathered, int64_t nc, int64_t nif, int64_t ntime,
                     float *out, void *stream) {
-  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
-    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
+  if (check_nbank(nbank)) return BLDP_EINVAL;
   if (nc < 0 || nif < 0 || ntime < 0) return fail(BLDP_EINVAL, "negative dimension");
   const int64_t n = nc * nif * ntime;
   if (n > 0 && (!gathered || !out)) return fail(BLDP_EINVAL, "null pointer");
@@ -811,8 +946,7 @@ int bldp_despike_f32(float *data, int64_t nchan, int64_t nif, int64_t ntime, int
 static bool any_plane(double *const *mo) { return mo && (mo[0] || mo[1] || mo[2] || mo[3]); }
 static int kurt_setup(int nbank, const float *const *in, int64_t nchan, int64_t nif,
                       int64_t ntime, const int64_t *win, KurtArgs *k, int order) {
-  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
-    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
+  if (check_nbank(nbank)) return BLDP_EINVAL;
   Geo g;
   int rc = resolve_window(nchan, nif, ntime, win, &g);
   if (rc) return rc;
@@ -1037,11 +1171,6 @@ static int mom_plan_info(const MomKind &c, const float *in, int64_t nchan, int64
   return BLDP_OK;
 }
 
-static bool spans_overlap(const void *a, size_t na, const void *b, size_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return na > 0 && nb > 0 && x < y + nb && y < x + na;
-}
-
 // Moments only: the planes may not overlap each other or the input array.
 // `span` elements from each plane's pointer hold its result, `in_elems` floats
 // each bank's array.
@@ -1254,8 +1383,8 @@ static int tstat_prepare(int nbank, const float *const *in, int64_t nchan, int64
                          int64_t out_bank, int64_t out_ld_i, int64_t out_ld_b, bool query,
                          TStatArgs *ap, TStatPlan *pp, bool *copy, bool *empty,
                          const double *qp = nullptr) {
-  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
-    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
+  int rc = check_nbank(nbank);
+  if (rc) return rc;
   if (qp)  // (the bldp_quantile_* entry points: kOpQuantile, which no caller's op can be)
     op = kOpQuantile;
   else if (!stat_op(op))
@@ -1264,23 +1393,16 @@ static int tstat_prepare(int nbank, const float *const *in, int64_t nchan, int64
                 "bldp_reduce_* with tavby)",
                 op);
   Geo g;
-  int rc = resolve_window(nchan, nif, ntime, win, &g);
-  if (rc) return rc;
   int64_t F, T;
-  rc = resolve_factors(g, 1, tavby, &F, &T);
+  rc = resolve_blocks(nchan, nif, ntime, win, 1, tavby, &g, &F, &T);
   if (rc) return rc;
   *copy = T <= 1;
   TStatArgs &a = *ap;
   a = TStatArgs{};
-  a.nbank = nbank;
   a.nc = g.nc;
   a.ni = g.ni;
   a.T = T;
   a.nb = g.nt / T;
-  a.in_off = g.off;
-  a.in_cs = g.cs;
-  a.in_ld_i = g.ld_i;
-  a.in_ld_t = g.ld_t;
   a.out = out;
   a.out_bank = out_bank;
   a.out_ld_i = out_ld_i;
@@ -1291,29 +1413,19 @@ static int tstat_prepare(int nbank, const float *const *in, int64_t nchan, int64
     a.qrank = (int32_t)q;
   }
   *empty = a.nc == 0 || a.ni == 0 || a.nb == 0;
-  if (!in) return fail(BLDP_EINVAL, "tstat: null input pointer array");
-  bool words = true;
-  for (int b = 0; b < nbank; ++b) {
-    a.in[b] = in[b];
-    words = words && aligned4(in[b]);
-  }
+  bool words;
+  rc = set_window("tstat: ", a, g, nbank, in, &words);
+  if (rc) return rc;
   *pp = TStatPlan{};
   if (!*copy) {
     rc = plan_tstat(a, op, words, num_cus_current(), xcd_log2_current(), pp);
     if (rc) return rc;
   }
-  if (!query && !*empty) {
-    for (int b = 0; b < nbank; ++b)
-      if (!in[b]) return fail(BLDP_EINVAL, "tstat: null input pointer (bank %d)", b);
-    if (!out) return fail(BLDP_EINVAL, "tstat: null output pointer");
-    if (out_ld_i < a.nc || out_ld_b < (a.ni - 1) * out_ld_i + a.nc ||
-        (nbank > 1 && out_bank < a.nc))
-      return fail(BLDP_EINVAL,
-                  "tstat: out strides (%lld, %lld) overlap for a (%lld, %lld, %lld) result",
-                  (long long)out_ld_i, (long long)out_ld_b, (long long)a.nc, (long long)a.ni,
-                  (long long)a.nb);
-  }
-  return BLDP_OK;
+  if (query || *empty) return BLDP_OK;
+  rc = check_banks("tstat: ", nbank, in);
+  if (rc) return rc;
+  if (!out) return fail(BLDP_EINVAL, "tstat: null output pointer");
+  return check_out_strides("tstat: ", nbank, out_bank, out_ld_i, out_ld_b, a.nc, a.ni, a.nb);
 }
 
 static int tstat_run(int nbank, const float *const *in, int64_t nchan, int64_t nif, int64_t ntime,
@@ -1331,15 +1443,10 @@ static int tstat_run(int nbank, const float *const *in, int64_t nchan, int64_t n
   if (copy)  // the window itself: the reduce's F = T = 1 copy
     return reduce_impl(nbank, in, nchan, nif, ntime, win, 1, 1, BLDP_OP_SUM, out, out_bank,
                        out_ld_i, out_ld_b, false, s, nullptr);
-  ScratchLease lease;  // held until the launches are queued
-  if (p.ws_bytes) {
-    rc = scratch_lease(s, p.ws_bytes, &lease);
-    if (rc) return rc;
-    a.ws = (double *)lease.ptr;
-  }
-  hipError_t e = launch_tstat(a, p, op, s);
-  if (e != hipSuccess) return fail(BLDP_EHIP, "tstat launch: %s", hipGetErrorString(e));
-  return BLDP_OK;
+  return run_planned("tstat", p.ws_bytes, s, [&](void *ws) {
+    if (ws) a.ws = (double *)ws;
+    return launch_tstat(a, p, op, s);
+  });
 }
 
 int bldp_tstat_shape(int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win, int64_t tavby,
@@ -1368,14 +1475,7 @@ static int tstat_plan(const float *in, int64_t nchan, int64_t nif, int64_t ntime
     if (qp) info[5] = -1;  // (no rank: the window itself)
     return BLDP_OK;
   }
-  info[0] = p.path;
-  info[1] = p.cpl;
-  info[2] = p.tsplit;
-  info[3] = p.passes;
-  info[4] = p.grid;
-  info[5] = (int64_t)p.ws_bytes;
-  info[6] = a.nb;
-  info[7] = p.tsplit > 1 ? ((int64_t)1 << a.lx_log2) : 0;
+  fill_tstat_info(info, p, a);
   if (qp) info[5] = a.qrank;  // (no workspace: the slot carries the lower rank)
   return BLDP_OK;
 }
@@ -1396,14 +1496,10 @@ int bldp_tstat_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime, c
 int bldp_band_tstat_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
                         int64_t ntime, const int64_t *win, int64_t tavby, int op, float *out,
                         void *stream) {
-  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
-    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
-  int64_t d[3];
-  int rc = bldp_tstat_shape(nchan, nif, ntime, win, tavby, d);
+  int64_t l[4];
+  const int rc = band_layout(nbank, nchan, nif, ntime, win, 1, tavby, l);
   if (rc) return rc;
-  // the vcat of the banks: bank k's channels at k*nc of every (IF, block) row
-  return tstat_run(nbank, in, nchan, nif, ntime, win, tavby, op, out, d[0], nbank * d[0],
-                   nbank * d[0] * d[1], stream);
+  return tstat_run(nbank, in, nchan, nif, ntime, win, tavby, op, out, l[0], l[1], l[2], stream);
 }
 
 // ---- quantile(p): an order statistic of blocks of channels or of spectra -----
@@ -1459,14 +1555,10 @@ int bldp_band_quantile_f32(int nbank, const float *const *in, int64_t nchan, int
   if (axis == 0)
     return reduce_impl(nbank, in, nchan, nif, ntime, win, n, 1, 0, out, 0, 0, 0, true,
                        (hipStream_t)stream, nullptr, &p);
-  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
-    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
-  int64_t d[3];
-  rc = bldp_tstat_shape(nchan, nif, ntime, win, n, d);
+  int64_t l[4];  // (the vcat of the banks, as bldp_band_tstat_f32)
+  rc = band_layout(nbank, nchan, nif, ntime, win, 1, n, l);
   if (rc) return rc;
-  // the vcat of the banks, as bldp_band_tstat_f32
-  return tstat_run(nbank, in, nchan, nif, ntime, win, n, 0, out, d[0], nbank * d[0],
-                   nbank * d[0] * d[1], stream, &p);
+  return tstat_run(nbank, in, nchan, nif, ntime, win, n, 0, out, l[0], l[1], l[2], stream, &p);
 }
 
 // ---- quantiles(ps): several quantiles of every block from one selection ------
@@ -1494,16 +1586,14 @@ static int quantiles_run(int nbank, const float *const *in, int64_t nchan, int64
                          int64_t out_ld_q, bool stitched, void *stream, int64_t *info) {
   int rc = quantiles_check(axis, np, p);
   if (rc) return rc;
-  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
-    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
+  rc = check_nbank(nbank);
+  if (rc) return rc;
   int64_t d[3];
   rc = bldp_quantile_shape(nchan, nif, ntime, win, axis, n, d);
   if (rc) return rc;
   int64_t bank = 0;
   if (stitched) {  // the vcat of the banks: dense planes one after the other
-    bank = d[0];
-    out_ld_i = nbank * d[0];
-    out_ld_t = out_ld_i * d[1];
+    vcat_layout(nbank, d, &bank, &out_ld_i, &out_ld_t);
     out_ld_q = out_ld_t * d[2];
   }
   const bool empty = d[0] == 0 || d[1] == 0 || d[2] == 0;
@@ -1548,15 +1638,12 @@ static int quantiles_run(int nbank, const float *const *in, int64_t nchan, int64
                         stitched, info != nullptr, &a, &pl, &none, nullptr, true);
     if (rc) return rc;
     if (info) {
-      info[0] = pl.path, info[1] = pl.lpg, info[2] = a.ts, info[3] = a.k4, info[4] = a.nchunk;
-      info[5] = pl.grid, info[6] = (int64_t)pl.ws_bytes, info[7] = a.vec_out;
+      fill_reduce_info(info, pl, a);
       info[8] = qs.nr, info[9] = stats_q_reads(pl);
       return BLDP_OK;
     }
     if (none) return BLDP_OK;
-    const hipError_t e = launch_stats_q(a, pl, qs, s);
-    if (e != hipSuccess) return fail(BLDP_EHIP, "quantiles launch: %s", hipGetErrorString(e));
-    return BLDP_OK;
+    return run_planned("quantiles", 0, s, [&](void *) { return launch_stats_q(a, pl, qs, s); });
   }
   TStatArgs a;
   TStatPlan pl;
@@ -1569,16 +1656,12 @@ static int quantiles_run(int nbank, const float *const *in, int64_t nchan, int64
   rc = plan_tstat_q(a, qs.nlow, words, num_cus_current(), xcd_log2_current(), &pl);
   if (rc) return rc;
   if (info) {
-    info[0] = pl.path, info[1] = pl.cpl, info[2] = pl.tsplit, info[3] = pl.passes;
-    info[4] = pl.grid, info[5] = (int64_t)pl.ws_bytes, info[6] = a.nb;
-    info[7] = pl.tsplit > 1 ? ((int64_t)1 << a.lx_log2) : 0;
+    fill_tstat_info(info, pl, a);
     info[8] = qs.nr, info[9] = pl.passes;
     return BLDP_OK;
   }
   if (none) return BLDP_OK;
-  const hipError_t e = launch_tstat_q(a, pl, qs, s);
-  if (e != hipSuccess) return fail(BLDP_EHIP, "quantiles launch: %s", hipGetErrorString(e));
-  return BLDP_OK;
+  return run_planned("quantiles", 0, s, [&](void *) { return launch_tstat_q(a, pl, qs, s); });
 }
 
 int bldp_quantiles_shape(int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win, int axis,
@@ -1657,31 +1740,26 @@ static int outliers_run(int nbank, const float *const *in, int64_t nchan, int64_
                         bool want_mask) {
   int rc = outliers_check(axis, n, nsigma);
   if (rc) return rc;
-  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
-    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
+  rc = check_nbank(nbank);
+  if (rc) return rc;
   int64_t d[3], md[3];
   rc = bldp_outliers_shape(nchan, nif, ntime, win, axis, n, d, md);
   if (rc) return rc;
   int64_t bank = 0;
-  if (stitched) {
-    bank = d[0];
-    out_ld_i = nbank * d[0];
-    out_ld_t = out_ld_i * d[1];
-  }
+  if (stitched) vcat_layout(nbank, d, &bank, &out_ld_i, &out_ld_t);
   const bool empty = d[0] == 0 || d[1] == 0 || d[2] == 0;
   if (!info && !empty) {
     if (!in) return fail(BLDP_EINVAL, "outliers: null input pointer array");
-    for (int b = 0; b < nbank; ++b)
-      if (!in[b]) return fail(BLDP_EINVAL, "outliers: null input pointer (bank %d)", b);
+    rc = check_banks("outliers: ", nbank, in);
+    if (rc) return rc;
     if (!med && !mad && !count && !mask)
       return fail(BLDP_EINVAL, "outliers: every output is null");
-    if ((med || mad || count) &&
-        (out_ld_i < d[0] || out_ld_t < (d[1] - 1) * out_ld_i + d[0]))
-      return fail(BLDP_EINVAL,
-                  "outliers: out strides (%lld, %lld) overlap for a (%lld, %lld, %lld) result",
-                  (long long)out_ld_i, (long long)out_ld_t, (long long)d[0], (long long)d[1],
-                  (long long)d[2]);
-    // the outputs may not overlap each other or the input arrays
+    if (med || mad || count) {
+      rc = check_out_strides("outliers: ", 1, 0, out_ld_i, out_ld_t, d[0], d[1], d[2]);
+      if (rc) return rc;
+    }
+    // the outputs may not overlap each other or the input arrays (the whole
+    // arrays, where the later families check the window's span)
     const int64_t span =
         (nbank - 1) * bank + (d[2] - 1) * out_ld_t + (d[1] - 1) * out_ld_i + d[0];
     const void *ptr[4] = {med, mad, count, mask};
@@ -1716,15 +1794,12 @@ static int outliers_run(int nbank, const float *const *in, int64_t nchan, int64_
                         out_ld_i, out_ld_t, false, true, &a, &pl, &none);
     if (rc) return rc;
     if (info) {
-      info[0] = pl.path, info[1] = pl.lpg, info[2] = a.ts, info[3] = a.k4, info[4] = a.nchunk;
-      info[5] = pl.grid, info[6] = (int64_t)pl.ws_bytes, info[7] = a.vec_out;
+      fill_reduce_info(info, pl, a);
       info[8] = stats_outl_reads(pl, wm), info[9] = wm ? 1 : 0;
       return BLDP_OK;
     }
     if (none) return BLDP_OK;
-    const hipError_t e = launch_stats_outl(a, pl, oa, s);
-    if (e != hipSuccess) return fail(BLDP_EHIP, "outliers launch: %s", hipGetErrorString(e));
-    return BLDP_OK;
+    return run_planned("outliers", 0, s, [&](void *) { return launch_stats_outl(a, pl, oa, s); });
   }
   TStatArgs a;
   TStatPlan pl;
@@ -1733,16 +1808,12 @@ static int outliers_run(int nbank, const float *const *in, int64_t nchan, int64_
                      out_ld_t, true, &a, &pl, &copy, &none);
   if (rc) return rc;
   if (info) {
-    info[0] = pl.path, info[1] = pl.cpl, info[2] = pl.tsplit, info[3] = pl.passes;
-    info[4] = pl.grid, info[5] = (int64_t)pl.ws_bytes, info[6] = a.nb;
-    info[7] = pl.tsplit > 1 ? ((int64_t)1 << a.lx_log2) : 0;
+    fill_tstat_info(info, pl, a);
     info[8] = tstat_outl_reads(pl, wm), info[9] = wm ? 1 : 0;
     return BLDP_OK;
   }
   if (none) return BLDP_OK;
-  const hipError_t e = launch_tstat_outl(a, pl, oa, s);
-  if (e != hipSuccess) return fail(BLDP_EHIP, "outliers launch: %s", hipGetErrorString(e));
-  return BLDP_OK;
+  return run_planned("outliers", 0, s, [&](void *) { return launch_tstat_outl(a, pl, oa, s); });
 }
 
 int bldp_outliers_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
@@ -1778,77 +1849,44 @@ static int argext_prepare(int nbank, const float *const *in, int64_t nchan, int6
                           int argop, uint32_t *idx, float *val, int64_t out_bank,
                           int64_t out_ld_i, int64_t out_ld_t, bool query, ArgArgs *ap, Plan *pp,
                           bool *empty) {
-  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
-    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
+  static const char what[] = "argext: ";
+  int rc = check_nbank(nbank);
+  if (rc) return rc;
   if (argop != BLDP_ARG_MAX && argop != BLDP_ARG_MIN)
     return fail(BLDP_EINVAL, "argext: unknown argop %d (0=argmax 1=argmin)", argop);
   Geo g;
-  int rc = resolve_window(nchan, nif, ntime, win, &g);
-  if (rc) return rc;
   int64_t F, T;
-  rc = resolve_factors(g, fqavby, tavby, &F, &T);
+  rc = resolve_blocks(nchan, nif, ntime, win, fqavby, tavby, &g, &F, &T);
+  if (!rc) rc = check_block31(what, F, T);  // (the offsets)
   if (rc) return rc;
-  // offsets are 31-bit (F <= nc and T <= nt: the product cannot overflow int64
-  // for arrays that exist, and is checked by division anyway)
-  if (F > INT32_MAX / T)
-    return fail(BLDP_EINVAL, "argext: blocks of fqavby x tavby = %lld x %lld elements are beyond "
-                "2^31 - 1", (long long)F, (long long)T);
   ArgArgs &aa = *ap;
   aa = ArgArgs{};
   RedArgs &a = aa.r;
-  a.nco = g.nc / F;
-  a.ni = g.ni;
-  a.nto = g.nt / T;
-  a.F = F;
-  a.T = T;
-  a.nbank = nbank;
-  a.out_bank = out_bank;
-  a.out_ld_i = out_ld_i;
-  a.out_ld_t = out_ld_t;
-  a.in_off = g.off;
-  a.in_cs = g.cs;
-  a.in_ld_i = g.ld_i;
-  a.in_ld_t = g.ld_t;
+  *empty = set_blocks(a, g, F, T, out_bank, out_ld_i, out_ld_t);
   a.out = val;
   aa.idx = idx;
   aa.inv = argop == BLDP_ARG_MIN ? 0xffffffffu : 0u;
-  *empty = a.nco == 0 || a.ni == 0 || a.nto == 0;
-  if (!in) return fail(BLDP_EINVAL, "argext: null input pointer array");
-  bool words = true;
-  for (int b = 0; b < nbank; ++b) {
-    a.in[b] = in[b];
-    words = words && aligned4(in[b]);
-  }
-  rc = plan_argext(aa, words && g.cs == 1, num_cus_current(), xcd_log2_current(), pp);
+  bool words;
+  rc = set_window(what, a, g, nbank, in, &words);
+  if (!rc) rc = plan_argext(aa, words && g.cs == 1, num_cus_current(), xcd_log2_current(), pp);
+  if (rc || query || *empty) return rc;
+  rc = check_banks(what, nbank, in);
   if (rc) return rc;
-  if (query || *empty) return BLDP_OK;
-  for (int b = 0; b < nbank; ++b)
-    if (!in[b]) return fail(BLDP_EINVAL, "argext: null input pointer (bank %d)", b);
   if (!idx) return fail(BLDP_EINVAL, "argext: null idx pointer");
-  if (out_ld_i < a.nco || out_ld_t < (a.ni - 1) * out_ld_i + a.nco ||
-      (nbank > 1 && out_bank < a.nco))
-    return fail(BLDP_EINVAL,
-                "argext: out strides (%lld, %lld) overlap for a (%lld, %lld, %lld) result",
-                (long long)out_ld_i, (long long)out_ld_t, (long long)a.nco, (long long)a.ni,
-                (long long)a.nto);
-  // the outputs may not overlap the window's elements, nor each other
-  int64_t lo = g.off, hi = g.off;  // lowest and highest element offset of the window
-  const int64_t span[3] = {(g.nc - 1) * g.cs, (g.ni - 1) * g.ld_i, (g.nt - 1) * g.ld_t};
-  for (int ax = 0; ax < 3; ++ax) (span[ax] < 0 ? lo : hi) += span[ax];
-  const int64_t last = (nbank - 1) * out_bank + (a.nco - 1) + (a.ni - 1) * out_ld_i +
-                       (a.nto - 1) * out_ld_t;  // of an output
-  auto overlap = [](const void *p, int64_t pn, const void *q, int64_t qn) {
-    const uintptr_t a0 = (uintptr_t)p, b0 = (uintptr_t)q;
-    return a0 < b0 + (uintptr_t)qn && b0 < a0 + (uintptr_t)pn;
-  };
-  const int64_t obytes = 4 * (last + 1);
-  for (int b = 0; b < nbank; ++b) {
-    const float *w0 = in[b] + lo;
-    const int64_t wbytes = 4 * (hi - lo + 1);
-    if (overlap(idx, obytes, w0, wbytes) || (val && overlap(val, obytes, w0, wbytes)))
+  rc = check_out_strides(what, nbank, out_bank, out_ld_i, out_ld_t, a.nco, a.ni, a.nto);
+  if (rc) return rc;
+  // the outputs may not overlap the window's elements (one message for both),
+  // nor each other
+  int64_t lo;
+  size_t wbytes;
+  window_span(g, &lo, &wbytes);
+  const size_t obytes = 4 * (size_t)((nbank - 1) * out_bank + (a.nco - 1) +
+                                     (a.ni - 1) * out_ld_i + (a.nto - 1) * out_ld_t + 1);
+  for (int b = 0; b < nbank; ++b)
+    if (spans_overlap(idx, obytes, in[b] + lo, wbytes) ||
+        (val && spans_overlap(val, obytes, in[b] + lo, wbytes)))
       return fail(BLDP_EINVAL, "argext: idx / val overlap the input window (bank %d)", b);
-  }
-  if (val && overlap(idx, obytes, val, obytes))
+  if (val && spans_overlap(idx, obytes, val, obytes))
     return fail(BLDP_EINVAL, "argext: idx and val overlap");
   return BLDP_OK;
 }
@@ -1863,9 +1901,8 @@ static int argext_run(int nbank, const float *const *in, int64_t nchan, int64_t 
   int rc = argext_prepare(nbank, in, nchan, nif, ntime, win, fqavby, tavby, argop, idx, val,
                           out_bank, out_ld_i, out_ld_t, false, &a, &p, &empty);
   if (rc || empty) return rc;
-  hipError_t e = launch_argext(a, p, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(BLDP_EHIP, "argext launch: %s", hipGetErrorString(e));
-  return BLDP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  return run_planned("argext", 0, s, [&](void *) { return launch_argext(a, p, s); });
 }
 
 int bldp_argext_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
@@ -1901,14 +1938,11 @@ int bldp_argext_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
 int bldp_band_argext_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
                          int64_t ntime, const int64_t *win, int64_t fqavby, int64_t tavby,
                          int argop, uint32_t *idx, float *val, void *stream) {
-  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
-    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
-  int64_t d[3];
-  int rc = bldp_reduce_shape(nchan, nif, ntime, win, fqavby, tavby, d);
+  int64_t l[4];
+  const int rc = band_layout(nbank, nchan, nif, ntime, win, fqavby, tavby, l);
   if (rc) return rc;
-  // the vcat of the banks: bank k's channels at k*nco of every (IF, time) row
-  return argext_run(nbank, in, nchan, nif, ntime, win, fqavby, tavby, argop, idx, val, d[0],
-                    nbank * d[0], nbank * d[0] * d[1], stream);
+  return argext_run(nbank, in, nchan, nif, ntime, win, fqavby, tavby, argop, idx, val, l[0],
+                    l[1], l[2], stream);
 }
 
 // ---- masked reduce: the sum / mean of a block's unflagged samples and their count ----
@@ -1921,95 +1955,45 @@ static int masked_prepare(int nbank, const float *const *in, int64_t nchan, int6
                           int op, const uint8_t *mask, const int64_t *mask_ld, float *out,
                           uint32_t *kept, int64_t out_bank, int64_t out_ld_i, int64_t out_ld_t,
                           bool query, MaskedArgs *ap, Plan *pp, bool *empty) {
-  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
-    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
+  static const char what[] = "masked reduce: ";
+  int rc = check_nbank(nbank);
+  if (rc) return rc;
   if (op != BLDP_OP_SUM && op != BLDP_OP_MEAN)
     return fail(BLDP_EINVAL, "masked reduce: op %d is not sum (%d) or mean (%d)", op, BLDP_OP_SUM,
                 BLDP_OP_MEAN);
   Geo g;
-  int rc = resolve_window(nchan, nif, ntime, win, &g);
+  int64_t F, T, ld[3];
+  rc = resolve_blocks(nchan, nif, ntime, win, fqavby, tavby, &g, &F, &T);
+  if (!rc) rc = check_block31(what, F, T);  // (kept)
+  if (!rc) rc = mask_strides(what, mask_ld, nbank * g.nc, g.ni, ld);
   if (rc) return rc;
-  int64_t F, T;
-  rc = resolve_factors(g, fqavby, tavby, &F, &T);
-  if (rc) return rc;
-  // kept is 31-bit (Python and the shim read Int32)
-  if (F > INT32_MAX / T)
-    return fail(BLDP_EINVAL, "masked reduce: blocks of fqavby x tavby = %lld x %lld elements are "
-                "beyond 2^31 - 1", (long long)F, (long long)T);
-  int64_t ld[3] = {1, nbank * g.nc, nbank * g.nc * g.ni};
-  if (mask_ld)
-    for (int ax = 0; ax < 3; ++ax) {
-      ld[ax] = mask_ld[ax];
-      if (ld[ax] < 0)
-        return fail(BLDP_EINVAL, "masked reduce: mask stride %d is negative (%lld)", ax,
-                    (long long)ld[ax]);
-    }
   MaskedArgs &ma = *ap;
   ma = MaskedArgs{};
   RedArgs &a = ma.r;
-  a.nco = g.nc / F;
-  a.ni = g.ni;
-  a.nto = g.nt / T;
-  a.F = F;
-  a.T = T;
-  a.nbank = nbank;
-  a.out_bank = out_bank;
-  a.out_ld_i = out_ld_i;
-  a.out_ld_t = out_ld_t;
-  a.in_off = g.off;
-  a.in_cs = g.cs;
-  a.in_ld_i = g.ld_i;
-  a.in_ld_t = g.ld_t;
+  *empty = set_blocks(a, g, F, T, out_bank, out_ld_i, out_ld_t);
   a.out = out;
   ma.kept = kept;
   ma.mask = mask;
   ma.m_cs = ld[0], ma.m_ld_i = ld[1], ma.m_ld_t = ld[2];
   ma.m_bank = g.nc * ld[0];
   ma.mean = op == BLDP_OP_MEAN;
-  *empty = a.nco == 0 || a.ni == 0 || a.nto == 0;
-  if (!in) return fail(BLDP_EINVAL, "masked reduce: null input pointer array");
-  bool words = true;
-  for (int b = 0; b < nbank; ++b) {
-    a.in[b] = in[b];
-    words = words && aligned4(in[b]);
-  }
-  rc = plan_masked(ma, words && g.cs == 1, aligned4(mask), num_cus_current(), xcd_log2_current(),
-                   pp);
+  bool words;
+  rc = set_window(what, a, g, nbank, in, &words);
+  if (!rc)
+    rc = plan_masked(ma, words && g.cs == 1, aligned4(mask), num_cus_current(),
+                     xcd_log2_current(), pp);
+  if (rc || query || *empty) return rc;
+  rc = check_banks(what, nbank, in);
   if (rc) return rc;
-  if (query || *empty) return BLDP_OK;
-  for (int b = 0; b < nbank; ++b)
-    if (!in[b]) return fail(BLDP_EINVAL, "masked reduce: null input pointer (bank %d)", b);
   if (!out && !kept) return fail(BLDP_EINVAL, "masked reduce: out and kept are both null");
   if (!mask) return fail(BLDP_EINVAL, "masked reduce: null mask pointer");
-  if (out_ld_i < a.nco || out_ld_t < (a.ni - 1) * out_ld_i + a.nco ||
-      (nbank > 1 && out_bank < a.nco))
-    return fail(BLDP_EINVAL,
-                "masked reduce: out strides (%lld, %lld) overlap for a (%lld, %lld, %lld) result",
-                (long long)out_ld_i, (long long)out_ld_t, (long long)a.nco, (long long)a.ni,
-                (long long)a.nto);
-  // the outputs may not overlap the window's elements, the mask's span, nor each other
-  int64_t lo = g.off, hi = g.off;  // lowest and highest element offset of the window
-  const int64_t span[3] = {(g.nc - 1) * g.cs, (g.ni - 1) * g.ld_i, (g.nt - 1) * g.ld_t};
-  for (int ax = 0; ax < 3; ++ax) (span[ax] < 0 ? lo : hi) += span[ax];
-  const int64_t last = (nbank - 1) * out_bank + (a.nco - 1) + (a.ni - 1) * out_ld_i +
-                       (a.nto - 1) * out_ld_t;  // of an output
-  const size_t obytes = 4 * (size_t)(last + 1), wbytes = 4 * (size_t)(hi - lo + 1);
-  const size_t mbytes =
-      (size_t)((nbank * g.nc - 1) * ld[0] + (g.ni - 1) * ld[1] + (g.nt - 1) * ld[2] + 1);
-  const void *optr[2] = {out, kept};
-  static const char *const name[2] = {"out", "kept"};
-  for (int q = 0; q < 2; ++q) {
-    if (!optr[q]) continue;
-    for (int b = 0; b < nbank; ++b)
-      if (spans_overlap(optr[q], obytes, in[b] + lo, wbytes))
-        return fail(BLDP_EINVAL, "masked reduce: %s overlaps the input window (bank %d)", name[q],
-                    b);
-    if (spans_overlap(optr[q], obytes, mask, mbytes))
-      return fail(BLDP_EINVAL, "masked reduce: %s overlaps the mask", name[q]);
-  }
-  if (out && kept && spans_overlap(out, obytes, kept, obytes))
-    return fail(BLDP_EINVAL, "masked reduce: out and kept overlap");
-  return BLDP_OK;
+  rc = check_out_strides(what, nbank, out_bank, out_ld_i, out_ld_t, a.nco, a.ni, a.nto);
+  if (rc) return rc;
+  const size_t obytes = 4 * (size_t)((nbank - 1) * out_bank + (a.nco - 1) +
+                                     (a.ni - 1) * out_ld_i + (a.nto - 1) * out_ld_t + 1);
+  const Span outs[2] = {{out, obytes, "out"}, {kept, obytes, "kept"}};
+  return check_disjoint(what, outs, 2, g, nbank, in,
+                        {mask, mask_span_bytes(nbank * g.nc, g.ni, g.nt, ld), "the mask"});
 }
 
 static int masked_run(int nbank, const float *const *in, int64_t nchan, int64_t nif,
@@ -2022,9 +2006,8 @@ static int masked_run(int nbank, const float *const *in, int64_t nchan, int64_t 
   int rc = masked_prepare(nbank, in, nchan, nif, ntime, win, fqavby, tavby, op, mask, mask_ld, out,
                           kept, out_bank, out_ld_i, out_ld_t, false, &a, &p, &empty);
   if (rc || empty) return rc;
-  hipError_t e = launch_masked(a, p, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(BLDP_EHIP, "masked reduce launch: %s", hipGetErrorString(e));
-  return BLDP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  return run_planned("masked reduce", 0, s, [&](void *) { return launch_masked(a, p, s); });
 }
 
 int bldp_masked_reduce_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
@@ -2065,14 +2048,11 @@ int bldp_band_masked_reduce_f32(int nbank, const float *const *in, int64_t nchan
                                 int64_t tavby, int op, const uint8_t *mask,
                                 const int64_t *mask_ld, float *out, uint32_t *kept,
                                 void *stream) {
-  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
-    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
-  int64_t d[3];
-  int rc = bldp_reduce_shape(nchan, nif, ntime, win, fqavby, tavby, d);
+  int64_t l[4];
+  const int rc = band_layout(nbank, nchan, nif, ntime, win, fqavby, tavby, l);
   if (rc) return rc;
-  // the vcat of the banks: bank k's channels at k*nco of every (IF, time) row
   return masked_run(nbank, in, nchan, nif, ntime, win, fqavby, tavby, op, mask, mask_ld, out,
-                    kept, d[0], nbank * d[0], nbank * d[0] * d[1], stream);
+                    kept, l[0], l[1], l[2], stream);
 }
 
 // ---- histogram: the counts per bin of every block, with below / above / nan ----
@@ -2084,8 +2064,9 @@ static int hist_prepare(int nbank, const float *const *in, int64_t nchan, int64_
                         int nbins, double lo, double hi, uint32_t *out, int64_t out_bank,
                         int64_t out_ld_i, int64_t out_ld_t, int64_t out_ld_q, bool query,
                         HistArgs *ap, Plan *pp, bool *empty) {
-  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
-    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
+  static const char what[] = "histogram: ";
+  int rc = check_nbank(nbank);
+  if (rc) return rc;
   if (nbins < 1 || nbins > BLDP_MAX_HIST_BINS)
     return fail(BLDP_EINVAL, "histogram: nbins=%d outside 1..%d", nbins, BLDP_MAX_HIST_BINS);
   const float lo32 = (float)lo, hi32 = (float)hi;
@@ -2102,46 +2083,23 @@ static int hist_prepare(int nbank, const float *const *in, int64_t nchan, int64_
                 "positive Float32 (nbins=%d, lo=%g, hi=%g)", (double)sc, nbins, (double)lo32,
                 (double)hi32);
   Geo g;
-  int rc = resolve_window(nchan, nif, ntime, win, &g);
-  if (rc) return rc;
   int64_t F, T;
-  rc = resolve_factors(g, fqavby, tavby, &F, &T);
+  rc = resolve_blocks(nchan, nif, ntime, win, fqavby, tavby, &g, &F, &T);
+  if (!rc) rc = check_block31(what, F, T);  // (the counts)
   if (rc) return rc;
-  // counts are 31-bit (Python and the shim read Int32)
-  if (F > INT32_MAX / T)
-    return fail(BLDP_EINVAL, "histogram: blocks of fqavby x tavby = %lld x %lld elements are "
-                "beyond 2^31 - 1", (long long)F, (long long)T);
   HistArgs &a = *ap;
   a = HistArgs{};
-  a.nco = g.nc / F;
-  a.ni = g.ni;
-  a.nto = g.nt / T;
-  a.F = F;
-  a.T = T;
-  a.nbank = nbank;
+  *empty = set_blocks(a, g, F, T, out_bank, out_ld_i, out_ld_t);
   a.B = nbins;
   a.lo = lo32, a.hi = hi32, a.s = sc;
   a.out = out;
-  a.out_bank = out_bank;
-  a.out_ld_i = out_ld_i;
-  a.out_ld_t = out_ld_t;
   a.out_ld_q = out_ld_q;
-  a.in_off = g.off;
-  a.in_cs = g.cs;
-  a.in_ld_i = g.ld_i;
-  a.in_ld_t = g.ld_t;
-  *empty = a.nco == 0 || a.ni == 0 || a.nto == 0;
-  if (!in) return fail(BLDP_EINVAL, "histogram: null input pointer array");
-  bool words = true;
-  for (int b = 0; b < nbank; ++b) {
-    a.in[b] = in[b];
-    words = words && aligned4(in[b]);
-  }
-  rc = plan_hist(a, words && g.cs == 1, num_cus_current(), pp);
+  bool words;
+  rc = set_window(what, a, g, nbank, in, &words);
+  if (!rc) rc = plan_hist(a, words && g.cs == 1, num_cus_current(), pp);
+  if (rc || query || *empty) return rc;
+  rc = check_banks(what, nbank, in);
   if (rc) return rc;
-  if (query || *empty) return BLDP_OK;
-  for (int b = 0; b < nbank; ++b)
-    if (!in[b]) return fail(BLDP_EINVAL, "histogram: null input pointer (bank %d)", b);
   if (!out) return fail(BLDP_EINVAL, "histogram: null output pointer");
   const int64_t plane = (nbank - 1) * out_bank + (a.nco - 1) + (a.ni - 1) * out_ld_i +
                         (a.nto - 1) * out_ld_t + 1;  // the extent of a plane
@@ -2150,16 +2108,8 @@ static int hist_prepare(int nbank, const float *const *in, int64_t nchan, int64_
     return fail(BLDP_EINVAL, "histogram: out strides (%lld, %lld, %lld) overlap for a (%lld, %lld, "
                 "%lld, %d) result", (long long)out_ld_i, (long long)out_ld_t, (long long)out_ld_q,
                 (long long)a.nco, (long long)a.ni, (long long)a.nto, nbins + 3);
-  // the output may not overlap the window's elements
-  int64_t wlo = g.off, whi = g.off;  // lowest and highest element offset of the window
-  const int64_t span[3] = {(g.nc - 1) * g.cs, (g.ni - 1) * g.ld_i, (g.nt - 1) * g.ld_t};
-  for (int ax = 0; ax < 3; ++ax) (span[ax] < 0 ? wlo : whi) += span[ax];
-  const size_t obytes = 4 * (size_t)((int64_t)(nbins + 2) * out_ld_q + plane);
-  const size_t wbytes = 4 * (size_t)(whi - wlo + 1);
-  for (int b = 0; b < nbank; ++b)
-    if (spans_overlap(out, obytes, in[b] + wlo, wbytes))
-      return fail(BLDP_EINVAL, "histogram: out overlaps the input window (bank %d)", b);
-  return BLDP_OK;
+  const Span outs[1] = {{out, 4 * (size_t)((int64_t)(nbins + 2) * out_ld_q + plane), "out"}};
+  return check_disjoint(what, outs, 1, g, nbank, in, {nullptr, 0, ""});
 }
 
 static int hist_run(int nbank, const float *const *in, int64_t nchan, int64_t nif, int64_t ntime,
@@ -2172,9 +2122,8 @@ static int hist_run(int nbank, const float *const *in, int64_t nchan, int64_t ni
   int rc = hist_prepare(nbank, in, nchan, nif, ntime, win, fqavby, tavby, nbins, lo, hi, out,
                         out_bank, out_ld_i, out_ld_t, out_ld_q, false, &a, &p, &empty);
   if (rc || empty) return rc;
-  hipError_t e = launch_hist(a, p, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(BLDP_EHIP, "histogram launch: %s", hipGetErrorString(e));
-  return BLDP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  return run_planned("histogram", 0, s, [&](void *) { return launch_hist(a, p, s); });
 }
 
 int bldp_histogram_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
@@ -2213,14 +2162,11 @@ int bldp_histogram_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntim
 int bldp_band_histogram_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
                             int64_t ntime, const int64_t *win, int64_t fqavby, int64_t tavby,
                             int nbins, double lo, double hi, uint32_t *out, void *stream) {
-  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
-    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
-  int64_t d[3];
-  int rc = bldp_reduce_shape(nchan, nif, ntime, win, fqavby, tavby, d);
+  int64_t l[4];  // (the vcat of every plane)
+  const int rc = band_layout(nbank, nchan, nif, ntime, win, fqavby, tavby, l);
   if (rc) return rc;
-  // the vcat of the banks: bank k's channels at k*nco of every (IF, time) row of every plane
-  return hist_run(nbank, in, nchan, nif, ntime, win, fqavby, tavby, nbins, lo, hi, out, d[0],
-                  nbank * d[0], nbank * d[0] * d[1], nbank * d[0] * d[1] * d[2], stream);
+  return hist_run(nbank, in, nchan, nif, ntime, win, fqavby, tavby, nbins, lo, hi, out, l[0],
+                  l[1], l[2], l[3], stream);
 }
 
 // ---- hits: the flagged samples of a window as an ordered list ----
@@ -2231,30 +2177,22 @@ static int hits_prepare(int nbank, const float *const *in, int64_t nchan, int64_
                         int64_t ntime, const int64_t *win, const uint8_t *mask,
                         const int64_t *mask_ld, int64_t cap, int64_t *idx, float *val,
                         uint64_t *total, bool query, HitsArgs *ap, Plan *pp, bool *empty) {
-  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
-    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
+  static const char what[] = "hits: ";
+  int rc = check_nbank(nbank);
+  if (rc) return rc;
   if (cap < 0) return fail(BLDP_EINVAL, "hits: cap=%lld is negative", (long long)cap);
   if (!query && !total) return fail(BLDP_EINVAL, "hits: null total pointer");
   Geo g;
-  int rc = resolve_window(nchan, nif, ntime, win, &g);
+  rc = resolve_window(nchan, nif, ntime, win, &g);
   if (rc) return rc;
   const int64_t NC = nbank * g.nc;
-  int64_t ld[3] = {1, NC, NC * g.ni};
-  if (mask_ld)
-    for (int ax = 0; ax < 3; ++ax) {
-      ld[ax] = mask_ld[ax];
-      if (ld[ax] < 0)
-        return fail(BLDP_EINVAL, "hits: mask stride %d is negative (%lld)", ax, (long long)ld[ax]);
-    }
+  int64_t ld[3];
+  rc = mask_strides(what, mask_ld, NC, g.ni, ld);
+  if (rc) return rc;
   HitsArgs &a = *ap;
   a = HitsArgs{};
-  a.nbank = nbank;
   a.nc = g.nc, a.NC = NC, a.ni = g.ni, a.nt = g.nt;
   a.N = NC * g.ni * g.nt;
-  a.in_off = g.off;
-  a.in_cs = g.cs;
-  a.in_ld_i = g.ld_i;
-  a.in_ld_t = g.ld_t;
   a.mask = mask;
   a.m_cs = ld[0], a.m_ld_i = ld[1], a.m_ld_t = ld[2];
   a.cap = cap;
@@ -2264,35 +2202,16 @@ static int hits_prepare(int nbank, const float *const *in, int64_t nchan, int64_
   *empty = a.N == 0;
   *pp = Plan{};
   if (*empty) return BLDP_OK;
-  if (!in) return fail(BLDP_EINVAL, "hits: null input pointer array");
-  for (int b = 0; b < nbank; ++b) a.in[b] = in[b];
-  rc = plan_hits(a, (uintptr_t)mask, pp);
+  rc = set_window(what, a, g, nbank, in);
+  if (!rc) rc = plan_hits(a, (uintptr_t)mask, pp);
   if (rc || query) return rc;
-  for (int b = 0; b < nbank; ++b)
-    if (!in[b]) return fail(BLDP_EINVAL, "hits: null input pointer (bank %d)", b);
+  rc = check_banks(what, nbank, in);
+  if (rc) return rc;
   if (!mask) return fail(BLDP_EINVAL, "hits: null mask pointer");
-  // the outputs may not overlap the window's elements, the mask's span, nor each other
-  int64_t lo = g.off, hi = g.off;  // lowest and highest element offset of the window
-  const int64_t span[3] = {(g.nc - 1) * g.cs, (g.ni - 1) * g.ld_i, (g.nt - 1) * g.ld_t};
-  for (int ax = 0; ax < 3; ++ax) (span[ax] < 0 ? lo : hi) += span[ax];
-  const size_t wbytes = 4 * (size_t)(hi - lo + 1);
-  const size_t mbytes = (size_t)((NC - 1) * ld[0] + (g.ni - 1) * ld[1] + (g.nt - 1) * ld[2] + 1);
   const size_t n = (size_t)std::min(cap, a.N);  // entries a list can get
-  const void *optr[3] = {idx, val, total};
-  const size_t olen[3] = {8 * n, 4 * n, 8};
-  static const char *const name[3] = {"idx", "val", "total"};
-  for (int q = 0; q < 3; ++q) {
-    if (!optr[q]) continue;
-    for (int b = 0; b < nbank; ++b)
-      if (spans_overlap(optr[q], olen[q], in[b] + lo, wbytes))
-        return fail(BLDP_EINVAL, "hits: %s overlaps the input window (bank %d)", name[q], b);
-    if (spans_overlap(optr[q], olen[q], mask, mbytes))
-      return fail(BLDP_EINVAL, "hits: %s overlaps the mask", name[q]);
-    for (int r = q + 1; r < 3; ++r)
-      if (optr[r] && spans_overlap(optr[q], olen[q], optr[r], olen[r]))
-        return fail(BLDP_EINVAL, "hits: %s and %s overlap", name[q], name[r]);
-  }
-  return BLDP_OK;
+  const Span outs[3] = {{idx, 8 * n, "idx"}, {val, 4 * n, "val"}, {total, 8, "total"}};
+  return check_disjoint(what, outs, 3, g, nbank, in,
+                        {mask, mask_span_bytes(NC, g.ni, g.nt, ld), "the mask"});
 }
 
 static int hits_run(int nbank, const float *const *in, int64_t nchan, int64_t nif, int64_t ntime,
@@ -2309,14 +2228,11 @@ static int hits_run(int nbank, const float *const *in, int64_t nchan, int64_t ni
     HIPCHK(hipMemsetAsync(total, 0, sizeof(uint64_t), s));
     return BLDP_OK;
   }
-  ScratchLease lease;  // held until the last launch is queued
-  rc = scratch_lease(s, p.ws_bytes, &lease);
-  if (rc) return rc;
-  a.woff = static_cast<uint64_t *>(lease.ptr);
-  a.wcount = reinterpret_cast<uint32_t *>(a.woff + a.tiles);
-  hipError_t e = launch_hits(a, p, cap > 0 && (idx || val), s);
-  if (e != hipSuccess) return fail(BLDP_EHIP, "hits launch: %s", hipGetErrorString(e));
-  return BLDP_OK;
+  return run_planned("hits", p.ws_bytes, s, [&](void *ws) {  // (never 0: 12 bytes a tile)
+    a.woff = static_cast<uint64_t *>(ws);
+    a.wcount = reinterpret_cast<uint32_t *>(a.woff + a.tiles);
+    return launch_hits(a, p, cap > 0 && (idx || val), s);
+  });
 }
 
 int bldp_hits_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
@@ -2361,10 +2277,10 @@ int bldp_band_hits_f32(int nbank, const float *const *in, int64_t nchan, int64_t
 // bank, nto = nt / T time blocks.
 static int fold_geometry(int nbank, int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win,
                          int64_t nfpc, int64_t tavby, Geo *g, int64_t *J, int64_t *T) {
-  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
-    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
+  int rc = check_nbank(nbank);
+  if (rc) return rc;
   if (nfpc < 1) return fail(BLDP_EINVAL, "fold: nfpc=%lld is less than 1", (long long)nfpc);
-  int rc = resolve_window(nchan, nif, ntime, win, g);
+  rc = resolve_window(nchan, nif, ntime, win, g);
   if (rc) return rc;
   *T = tavby <= 1 ? 1 : tavby;
   if (g->nc % nfpc != 0)
@@ -2375,15 +2291,6 @@ static int fold_geometry(int nbank, int64_t nchan, int64_t nif, int64_t ntime, c
                 (long long)*T, (long long)g->nt);
   *J = g->nc / nfpc;
   return BLDP_OK;
-}
-
-// lowest element offset and byte length of a window's elements
-static void window_span(const Geo &g, int64_t *lo, size_t *bytes) {
-  int64_t l = g.off, h = g.off;
-  const int64_t span[3] = {(g.nc - 1) * g.cs, (g.ni - 1) * g.ld_i, (g.nt - 1) * g.ld_t};
-  for (int ax = 0; ax < 3; ++ax) (span[ax] < 0 ? l : h) += span[ax];
-  *lo = l;
-  *bytes = 4 * (size_t)(h - l + 1);
 }
 
 // 16-byte loads of every float4 of a unit-step window's rows are legal
@@ -2402,6 +2309,7 @@ static int fold_prepare(int nbank, const float *const *in, int64_t nchan, int64_
                         const uint8_t *mask, bool has_mask, const int64_t *mask_ld, float *out,
                         uint32_t *kept, int64_t out_ld_i, int64_t out_ld_t, bool query,
                         FoldArgs *ap, Plan *pp, bool *empty) {
+  static const char what[] = "fold: ";
   Geo g;
   int64_t J, T;
   int rc = fold_geometry(nbank, nchan, nif, ntime, win, nfpc, tavby, &g, &J, &T);
@@ -2415,60 +2323,32 @@ static int fold_prepare(int nbank, const float *const *in, int64_t nchan, int64_
                 (long long)(nbank * J), (long long)T);
   int64_t ld[3] = {0, 0, 0};
   if (has_mask) {
-    ld[0] = 1, ld[1] = nbank * g.nc, ld[2] = nbank * g.nc * g.ni;
-    if (mask_ld)
-      for (int ax = 0; ax < 3; ++ax) {
-        ld[ax] = mask_ld[ax];
-        if (ld[ax] < 0)
-          return fail(BLDP_EINVAL, "fold: mask stride %d is negative (%lld)", ax,
-                      (long long)ld[ax]);
-      }
+    rc = mask_strides(what, mask_ld, nbank * g.nc, g.ni, ld);
+    if (rc) return rc;
   }
   FoldArgs &a = *ap;
   a = FoldArgs{};
   a.out = out, a.kept = kept, a.mask = mask;
-  a.in_off = g.off, a.in_cs = g.cs, a.in_ld_i = g.ld_i, a.in_ld_t = g.ld_t;
   a.m_cs = ld[0], a.m_ld_i = ld[1], a.m_ld_t = ld[2], a.m_bank = g.nc * ld[0];
   a.out_ld_i = out_ld_i, a.out_ld_t = out_ld_t;
   a.nfpc = nfpc, a.J = J, a.ni = g.ni, a.T = T, a.nto = g.nt / T;
-  a.nbank = nbank;
   a.mean = op == BLDP_OP_MEAN;
   a.mask_present = has_mask;
   *empty = g.nc == 0 || g.ni == 0 || g.nt == 0;
-  if (!in) return fail(BLDP_EINVAL, "fold: null input pointer array");
-  for (int b = 0; b < nbank; ++b) a.in[b] = in[b];
-  rc = plan_fold(a, fold_vec_ok(nbank, in, g), aligned4(mask), num_cus_current(), pp);
+  rc = set_window(what, a, g, nbank, in);
+  if (!rc) rc = plan_fold(a, fold_vec_ok(nbank, in, g), aligned4(mask), num_cus_current(), pp);
+  if (rc || query || *empty) return rc;
+  rc = check_banks(what, nbank, in);
   if (rc) return rc;
-  if (query || *empty) return BLDP_OK;
-  for (int b = 0; b < nbank; ++b)
-    if (!in[b]) return fail(BLDP_EINVAL, "fold: null input pointer (bank %d)", b);
   if (!out && !kept) return fail(BLDP_EINVAL, "fold: out and kept are both null");
-  if (out_ld_i < nfpc || out_ld_t < (g.ni - 1) * out_ld_i + nfpc)
-    return fail(BLDP_EINVAL, "fold: out strides (%lld, %lld) overlap for a (%lld, %lld, %lld) result",
-                (long long)out_ld_i, (long long)out_ld_t, (long long)nfpc, (long long)g.ni,
-                (long long)a.nto);
-  // the outputs may not overlap the window's elements, the mask's span, nor each other
-  int64_t lo;
-  size_t wbytes;
-  window_span(g, &lo, &wbytes);
+  rc = check_out_strides(what, 1, 0, out_ld_i, out_ld_t, nfpc, g.ni, a.nto);
+  if (rc) return rc;
   const size_t obytes =
       4 * (size_t)((nfpc - 1) + (g.ni - 1) * out_ld_i + (a.nto - 1) * out_ld_t + 1);
-  const size_t mbytes =
-      has_mask ? (size_t)((nbank * g.nc - 1) * ld[0] + (g.ni - 1) * ld[1] + (g.nt - 1) * ld[2] + 1)
-               : 0;
-  const void *optr[2] = {out, kept};
-  static const char *const name[2] = {"out", "kept"};
-  for (int q = 0; q < 2; ++q) {
-    if (!optr[q]) continue;
-    for (int b = 0; b < nbank; ++b)
-      if (spans_overlap(optr[q], obytes, in[b] + lo, wbytes))
-        return fail(BLDP_EINVAL, "fold: %s overlaps the input window (bank %d)", name[q], b);
-    if (spans_overlap(optr[q], obytes, mask, mbytes))
-      return fail(BLDP_EINVAL, "fold: %s overlaps the mask", name[q]);
-  }
-  if (out && kept && spans_overlap(out, obytes, kept, obytes))
-    return fail(BLDP_EINVAL, "fold: out and kept overlap");
-  return BLDP_OK;
+  const Span outs[2] = {{out, obytes, "out"}, {kept, obytes, "kept"}};
+  return check_disjoint(
+      what, outs, 2, g, nbank, in,
+      {mask, has_mask ? mask_span_bytes(nbank * g.nc, g.ni, g.nt, ld) : 0, "the mask"});
 }
 
 static int fold_run(int nbank, const float *const *in, int64_t nchan, int64_t nif, int64_t ntime,
@@ -2482,16 +2362,13 @@ static int fold_run(int nbank, const float *const *in, int64_t nchan, int64_t ni
                         mask_ld, out, kept, out_ld_i, out_ld_t, false, &a, &p, &empty);
   if (rc || empty) return rc;
   hipStream_t s = (hipStream_t)stream;
-  ScratchLease lease;  // the chunks' partials, held until the merge is queued
-  if (p.ws_bytes) {
-    rc = scratch_lease(s, p.ws_bytes, &lease);
-    if (rc) return rc;
-    a.ws_sum = static_cast<double *>(lease.ptr);
-    a.ws_kept = reinterpret_cast<uint32_t *>(a.ws_sum + (size_t)a.nchunk * (size_t)a.nout);
-  }
-  hipError_t e = launch_fold(a, p, s);
-  if (e != hipSuccess) return fail(BLDP_EHIP, "fold launch: %s", hipGetErrorString(e));
-  return BLDP_OK;
+  return run_planned("fold", p.ws_bytes, s, [&](void *ws) {
+    if (ws) {  // the chunks' partials, held until the merge is queued
+      a.ws_sum = static_cast<double *>(ws);
+      a.ws_kept = reinterpret_cast<uint32_t *>(a.ws_sum + (size_t)a.nchunk * (size_t)a.nout);
+    }
+    return launch_fold(a, p, s);
+  });
 }
 
 int bldp_fold_shape(int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win, int64_t nfpc,
@@ -2566,37 +2443,35 @@ static int unfold_prepare(int nbank, const float *const *in, int64_t nchan, int6
   int64_t J, T;
   int rc = fold_geometry(nbank, nchan, nif, ntime, win, nfpc, tavby, &g, &J, &T);
   if (rc) return rc;
+  static const char what[] = "unfold: ";
   if (uop != BLDP_UNFOLD_DIV && uop != BLDP_UNFOLD_SUB)
     return fail(BLDP_EINVAL, "unfold: op %d is not divide (%d) or subtract (%d)", uop,
                 BLDP_UNFOLD_DIV, BLDP_UNFOLD_SUB);
   UnfoldArgs &a = *ap;
   a = UnfoldArgs{};
   a.prof = prof, a.out = out;
-  a.in_off = g.off, a.in_cs = g.cs, a.in_ld_i = g.ld_i, a.in_ld_t = g.ld_t;
   a.prof_ld_i = prof_ld_i, a.prof_ld_t = prof_ld_t, a.out_ld_i = out_ld_i, a.out_ld_t = out_ld_t;
   a.nc = g.nc, a.ni = g.ni, a.nt = g.nt, a.nfpc = nfpc, a.T = T;
-  a.nbank = nbank;
   a.sub = uop == BLDP_UNFOLD_SUB;
   *empty = g.nc == 0 || g.ni == 0 || g.nt == 0;
-  if (!in) return fail(BLDP_EINVAL, "unfold: null input pointer array");
-  for (int b = 0; b < nbank; ++b) a.in[b] = in[b];
+  rc = set_window(what, a, g, nbank, in);
+  if (rc) return rc;
   const int64_t nto = g.nt / T;
   const bool pitch4 = (g.ni <= 1 || (prof_ld_i % 4 == 0 && out_ld_i % 4 == 0)) &&
                       (nto <= 1 || prof_ld_t % 4 == 0) && (g.nt <= 1 || out_ld_t % 4 == 0);
   *grid = plan_unfold(a, fold_vec_ok(nbank, in, g) && aligned16(prof) && aligned16(out) && pitch4);
   if (query || *empty) return BLDP_OK;
-  for (int b = 0; b < nbank; ++b)
-    if (!in[b]) return fail(BLDP_EINVAL, "unfold: null input pointer (bank %d)", b);
+  rc = check_banks(what, nbank, in);
+  if (rc) return rc;
   if (!prof) return fail(BLDP_EINVAL, "unfold: null profile pointer");
   if (!out) return fail(BLDP_EINVAL, "unfold: null output pointer");
   if (prof_ld_i < 0 || prof_ld_t < 0)
     return fail(BLDP_EINVAL, "unfold: profile strides (%lld, %lld) are negative",
                 (long long)prof_ld_i, (long long)prof_ld_t);
   const int64_t NC = nbank * g.nc;
-  if (out_ld_i < NC || out_ld_t < (g.ni - 1) * out_ld_i + NC)
-    return fail(BLDP_EINVAL, "unfold: out strides (%lld, %lld) overlap for a (%lld, %lld, %lld) result",
-                (long long)out_ld_i, (long long)out_ld_t, (long long)NC, (long long)g.ni,
-                (long long)g.nt);
+  rc = check_out_strides(what, 1, 0, out_ld_i, out_ld_t, NC, g.ni, g.nt);
+  if (rc) return rc;
+  // (the wording of the overlap with the window is the unfold's own)
   int64_t lo;
   size_t wbytes;
   window_span(g, &lo, &wbytes);
@@ -2622,9 +2497,8 @@ static int unfold_run(int nbank, const float *const *in, int64_t nchan, int64_t 
   int rc = unfold_prepare(nbank, in, nchan, nif, ntime, win, nfpc, tavby, uop, prof, prof_ld_i,
                           prof_ld_t, out, out_ld_i, out_ld_t, false, &a, &grid, &empty);
   if (rc || empty) return rc;
-  hipError_t e = launch_unfold(a, grid, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(BLDP_EHIP, "unfold launch: %s", hipGetErrorString(e));
-  return BLDP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  return run_planned("unfold", 0, s, [&](void *) { return launch_unfold(a, grid, s); });
 }
 
 int bldp_unfold_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
@@ -2660,14 +2534,11 @@ int bldp_band_unfold_f32(int nbank, const float *const *in, int64_t nchan, int64
                          int64_t ntime, const int64_t *win, int64_t nfpc, int64_t tavby, int uop,
                          const float *prof, int64_t prof_ld_i, int64_t prof_ld_t, float *out,
                          void *stream) {
-  if (nbank < 1 || nbank > BLDP_MAX_BANKS)
-    return fail(BLDP_EINVAL, "nbank=%d outside 1..%d", nbank, BLDP_MAX_BANKS);
-  int64_t d[3];
-  int rc = bldp_reduce_shape(nchan, nif, ntime, win, 1, 1, d);
+  int64_t l[4];  // (the dense vcat of the banks' windows)
+  const int rc = band_layout(nbank, nchan, nif, ntime, win, 1, 1, l);
   if (rc) return rc;
-  // the dense vcat of the banks: bank b's channels at b*nc of every (IF, time) row
   return unfold_run(nbank, in, nchan, nif, ntime, win, nfpc, tavby, uop, prof, prof_ld_i, prof_ld_t,
-                    out, nbank * d[0], nbank * d[0] * d[1], stream);
+                    out, l[1], l[2], stream);
 }
 
 int bldp_reduce_out_dtype(int dtype, int op) {

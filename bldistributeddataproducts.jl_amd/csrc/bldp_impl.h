@@ -329,6 +329,11 @@ struct MaskedArgs {
 // How the flags are loaded: a byte per element at the strided address, one
 // aligned dword for the four flags of a float4, one byte per row (m_cs == 0).
 enum MaskForm { MASK_BYTE = 0, MASK_DWORD = 1, MASK_ROW = 2 };
+// The bytes that the mask of an (NC, ni, nt) window reaches from its pointer on,
+// with the (non-negative) strides ld; a stride of 0 adds nothing.
+inline size_t mask_span_bytes(int64_t NC, int64_t ni, int64_t nt, const int64_t ld[3]) {
+  return (size_t)((NC - 1) * ld[0] + (ni - 1) * ld[1] + (nt - 1) * ld[2] + 1);
+}
 // plan_argext's plan (paths ArgExtPath) plus the mask form; `mask_words`: the
 // mask pointer is 4-byte aligned.  Filled without a GPU.
 int plan_masked(MaskedArgs &a, bool words, bool mask_words, int num_cus, int xcd_lg, Plan *p);

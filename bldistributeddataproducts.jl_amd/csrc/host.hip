@@ -123,6 +123,76 @@ int stage_rows(const HostWin &h, int64_t r0, int64_t rows, void *dstv, hipStream
   return BLDP_OK;
 }
 
+// ---- what the host forms of the block operations share -----------------------
+// Each makes its plan call first (every argument check, before any staging),
+// takes the counts of the window and of its blocks, refuses its null pointers and
+// runs its device entry on the staged window.
+// The window's (nc, ni, nt) and its blocks' (nco, ni, nto).
+int block_counts(int64_t nchan, int64_t nif, int64_t ntime, const int64_t *win, int64_t fqavby,
+                 int64_t tavby, int64_t w[3], int64_t o[3]) {
+  const int rc = bldp_reduce_shape(nchan, nif, ntime, win, fqavby, tavby, o);
+  if (rc) return rc;
+  w[0] = o[0] * (fqavby <= 1 ? 1 : fqavby);
+  w[1] = o[1];
+  w[2] = o[2] * (tavby <= 1 ? 1 : tavby);
+  return BLDP_OK;
+}
+
+// The strides of a host mask (dense over the window unless given) and its span.
+size_t host_mask(const int64_t *mask_ld, const int64_t w[3], int64_t ld[3]) {
+  ld[0] = mask_ld ? mask_ld[0] : 1;
+  ld[1] = mask_ld ? mask_ld[1] : w[0];
+  ld[2] = mask_ld ? mask_ld[2] : w[0] * w[1];
+  return bldp::mask_span_bytes(w[0], w[1], w[2], ld);
+}
+
+// A device buffer of a staged call: `bytes` in `slot` of the pipeline (0: not
+// asked for, p stays null), the first `up_bytes` of it copied from `up`.
+struct DevBuf {
+  int slot;
+  size_t bytes;
+  const void *up;
+  size_t up_bytes;
+  void *p;
+};
+
+// The staged copy of a window: its rows dense [t][i][span] at dbuf, i.e. the
+// window dwin of a (span, ni, nt) array, on stream st.
+struct StagedWin {
+  float *dbuf;
+  int64_t span;
+  int64_t dwin[9];
+  bldp::Stager *sg;
+  hipStream_t st;
+  // a result back into the caller's memory (a null dst was not asked for)
+  int fetch(void *dst, const void *src, size_t bytes) const {
+    if (dst) HCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
+    return BLDP_OK;
+  }
+};
+
+// Stage the (nc, ni, nt) window w of `in` and the buffers of `bufs` on `dev`, then
+// run body(staged window) on the pipeline's first stream.
+template <class Body>
+int with_staged_window(int dev, const float *in, int64_t nchan, int64_t nif, const int64_t *win,
+                       const int64_t w[3], DevBuf *bufs, int nbufs, Body body) {
+  const int64_t nc = w[0], ni = w[1], nt = w[2];
+  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
+  return with_stager(dev, [&](bldp::Stager *sg) -> int {
+    StagedWin s{nullptr, h.span, {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1},
+                sg, sg->st[0]};
+    int r = bldp::stager_buffer(sg, 0, (size_t)(h.span * ni * nt) * 4, (void **)&s.dbuf);
+    for (int k = 0; k < nbufs && !r; ++k)
+      if (bufs[k].bytes) r = bldp::stager_buffer(sg, bufs[k].slot, bufs[k].bytes, &bufs[k].p);
+    if (!r) r = stage_rows(h, 0, nt, s.dbuf, s.st);
+    if (r) return r;
+    for (int k = 0; k < nbufs; ++k)
+      if (bufs[k].up_bytes)
+        HCHK(hipMemcpyAsync(bufs[k].p, bufs[k].up, bufs[k].up_bytes, hipMemcpyHostToDevice, s.st));
+    return body(s);
+  });
+}
+
 }  // namespace
 
 extern "C" int bldp_reduce_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
@@ -301,22 +371,14 @@ extern "C" int bldp_tstat_host_f32(int dev, const float *in, int64_t nchan, int6
   rc = bldp_tstat_plan_f32(nullptr, nchan, nif, ntime, win, tavby, op, nullptr, info);
   if (rc) return rc;
   const int64_t T = tavby <= 1 ? 1 : tavby;
-  const int64_t nc = sh[0], ni = sh[1], nb = sh[2], nt = nb * T;
+  const int64_t nc = sh[0], ni = sh[1], nb = sh[2], w[3] = {nc, ni, nb * T};
   if (nc * ni * nb == 0) return BLDP_OK;
   if (!out || !in) return bldp::set_error(BLDP_EINVAL, "tstat: null pointer");
-  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
-  return with_stager(dev, [&](bldp::Stager *sg) -> int {
-    float *dbuf, *dout;
-    int r = bldp::stager_buffer(sg, 0, (size_t)(h.span * ni * nt) * 4, (void **)&dbuf);
-    if (!r) r = bldp::stager_buffer(sg, 2, (size_t)(nc * ni * nb) * sizeof(float), (void **)&dout);
-    if (!r) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
-    if (r) return r;
-    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
-    r = bldp_tstat_f32(dbuf, h.span, ni, nt, dwin, tavby, op, dout, nc, nc * ni, sg->st[0]);
-    if (r) return r;
-    HCHK(hipMemcpyAsync(out, dout, (size_t)(nc * ni * nb) * sizeof(float), hipMemcpyDeviceToHost,
-                        sg->st[0]));
-    return BLDP_OK;
+  DevBuf b[1] = {{2, (size_t)(nc * ni * nb) * sizeof(float)}};
+  return with_staged_window(dev, in, nchan, nif, win, w, b, 1, [&](const StagedWin &s) {
+    const int r = bldp_tstat_f32(s.dbuf, s.span, ni, w[2], s.dwin, tavby, op, (float *)b[0].p, nc,
+                                 nc * ni, s.st);
+    return r ? r : s.fetch(out, b[0].p, b[0].bytes);
   });
 }
 
@@ -351,20 +413,12 @@ extern "C" int bldp_quantile_host_f32(int dev, const float *in, int64_t nchan, i
   const int64_t nt = axis == 2 ? sh[2] * nn : sh[2], nout = sh[0] * sh[1] * sh[2];
   if (nout == 0) return BLDP_OK;
   if (!out || !in) return bldp::set_error(BLDP_EINVAL, "quantile: null pointer");
-  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
-  return with_stager(dev, [&](bldp::Stager *sg) -> int {
-    float *dbuf, *dout;
-    int r = bldp::stager_buffer(sg, 0, (size_t)(h.span * ni * nt) * 4, (void **)&dbuf);
-    if (!r) r = bldp::stager_buffer(sg, 2, (size_t)nout * sizeof(float), (void **)&dout);
-    if (!r) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
-    if (r) return r;
-    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
-    r = bldp_quantile_f32(dbuf, h.span, ni, nt, dwin, axis, n, p, dout, sh[0], sh[0] * ni,
-                          sg->st[0]);
-    if (r) return r;
-    HCHK(hipMemcpyAsync(out, dout, (size_t)nout * sizeof(float), hipMemcpyDeviceToHost,
-                        sg->st[0]));
-    return BLDP_OK;
+  const int64_t w[3] = {nc, ni, nt};
+  DevBuf b[1] = {{2, (size_t)nout * sizeof(float)}};
+  return with_staged_window(dev, in, nchan, nif, win, w, b, 1, [&](const StagedWin &s) {
+    const int r = bldp_quantile_f32(s.dbuf, s.span, ni, nt, s.dwin, axis, n, p, (float *)b[0].p,
+                                    sh[0], sh[0] * ni, s.st);
+    return r ? r : s.fetch(out, b[0].p, b[0].bytes);
   });
 }
 
@@ -414,20 +468,12 @@ extern "C" int bldp_quantiles_host_f32(int dev, const float *in, int64_t nchan, 
   const int64_t nt = axis == 2 ? sh[2] * nn : sh[2], plane = sh[0] * sh[1] * sh[2];
   if (plane == 0) return BLDP_OK;
   if (!out || !in) return bldp::set_error(BLDP_EINVAL, "quantiles: null pointer");
-  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
-  return with_stager(dev, [&](bldp::Stager *sg) -> int {
-    float *dbuf, *dout;
-    int r = bldp::stager_buffer(sg, 0, (size_t)(h.span * ni * nt) * 4, (void **)&dbuf);
-    if (!r) r = bldp::stager_buffer(sg, 2, (size_t)(plane * np) * sizeof(float), (void **)&dout);
-    if (!r) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
-    if (r) return r;
-    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
-    r = bldp_quantiles_f32(dbuf, h.span, ni, nt, dwin, axis, n, np, p, dout, sh[0], sh[0] * ni,
-                           plane, sg->st[0]);
-    if (r) return r;
-    HCHK(hipMemcpyAsync(out, dout, (size_t)(plane * np) * sizeof(float), hipMemcpyDeviceToHost,
-                        sg->st[0]));
-    return BLDP_OK;
+  const int64_t w[3] = {nc, ni, nt};
+  DevBuf b[1] = {{2, (size_t)(plane * np) * sizeof(float)}};
+  return with_staged_window(dev, in, nchan, nif, win, w, b, 1, [&](const StagedWin &s) {
+    const int r = bldp_quantiles_f32(s.dbuf, s.span, ni, nt, s.dwin, axis, n, np, p,
+                                     (float *)b[0].p, sh[0], sh[0] * ni, plane, s.st);
+    return r ? r : s.fetch(out, b[0].p, b[0].bytes);
   });
 }
 
@@ -450,28 +496,21 @@ extern "C" int bldp_outliers_host_f32(int dev, const float *in, int64_t nchan, i
   if (!in) return bldp::set_error(BLDP_EINVAL, "outliers: null input pointer");
   if (!med && !mad && !count && !mask)
     return bldp::set_error(BLDP_EINVAL, "outliers: every output is null");
-  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
-  return with_stager(dev, [&](bldp::Stager *sg) -> int {
-    // the staged outputs: three planes of 4-byte elements, then the mask
-    const size_t pb = (size_t)plane * 4, mb = mask ? (size_t)(nc * ni * nt) : 0;
-    float *dbuf;
-    char *dout;
-    int r = bldp::stager_buffer(sg, 0, (size_t)(h.span * ni * nt) * 4, (void **)&dbuf);
-    if (!r) r = bldp::stager_buffer(sg, 2, 3 * pb + mb, (void **)&dout);
-    if (!r) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
-    if (r) return r;
+  // the staged outputs: three planes of 4-byte elements, then the mask
+  const size_t pb = (size_t)plane * 4, mb = mask ? (size_t)(nc * ni * nt) : 0;
+  DevBuf b[1] = {{2, 3 * pb + mb}};
+  return with_staged_window(dev, in, nchan, nif, win, ms, b, 1, [&](const StagedWin &s) {
+    char *dout = (char *)b[0].p;
     float *dmed = med ? (float *)dout : nullptr, *dmad = mad ? (float *)(dout + pb) : nullptr;
     uint32_t *dcount = count ? (uint32_t *)(dout + 2 * pb) : nullptr;
     uint8_t *dmask = mask ? (uint8_t *)(dout + 3 * pb) : nullptr;
-    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
-    r = bldp_outliers_f32(dbuf, h.span, ni, nt, dwin, axis, n, nsigma, dmed, dmad, dcount, dmask,
-                          sh[0], sh[0] * ni, sg->st[0]);
-    if (r) return r;
-    if (med) HCHK(hipMemcpyAsync(med, dmed, pb, hipMemcpyDeviceToHost, sg->st[0]));
-    if (mad) HCHK(hipMemcpyAsync(mad, dmad, pb, hipMemcpyDeviceToHost, sg->st[0]));
-    if (count) HCHK(hipMemcpyAsync(count, dcount, pb, hipMemcpyDeviceToHost, sg->st[0]));
-    if (mask) HCHK(hipMemcpyAsync(mask, dmask, mb, hipMemcpyDeviceToHost, sg->st[0]));
-    return BLDP_OK;
+    int r = bldp_outliers_f32(s.dbuf, s.span, ni, nt, s.dwin, axis, n, nsigma, dmed, dmad, dcount,
+                              dmask, sh[0], sh[0] * ni, s.st);
+    if (!r) r = s.fetch(med, dmed, pb);
+    if (!r) r = s.fetch(mad, dmad, pb);
+    if (!r) r = s.fetch(count, dcount, pb);
+    if (!r) r = s.fetch(mask, dmask, mb);
+    return r;
   });
 }
 
@@ -486,33 +525,19 @@ extern "C" int bldp_argext_host_f32(int dev, const float *in, int64_t nchan, int
   int rc = bldp_argext_plan_f32(nullptr, nchan, nif, ntime, win, fqavby, tavby, argop, nullptr,
                                 info);
   if (rc) return rc;
-  int64_t sh[3];
-  rc = bldp_reduce_shape(nchan, nif, ntime, win, fqavby, tavby, sh);
+  int64_t w[3], o[3];
+  rc = block_counts(nchan, nif, ntime, win, fqavby, tavby, w, o);
   if (rc) return rc;
-  const int64_t nco = sh[0], ni = sh[1], nto = sh[2], nout = nco * ni * nto;
+  const size_t nout = (size_t)(o[0] * o[1] * o[2]);
   if (nout == 0) return BLDP_OK;
   if (!in || !idx) return bldp::set_error(BLDP_EINVAL, "argext: null pointer");
-  const int64_t F = fqavby <= 1 ? 1 : fqavby, T = tavby <= 1 ? 1 : tavby;
-  const int64_t nc = nco * F, nt = nto * T;
-  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
-  return with_stager(dev, [&](bldp::Stager *sg) -> int {
-    float *dbuf, *dval = nullptr;
-    uint32_t *didx;
-    int r = bldp::stager_buffer(sg, 0, (size_t)(h.span * ni * nt) * 4, (void **)&dbuf);
-    if (!r) r = bldp::stager_buffer(sg, 2, (size_t)nout * sizeof(uint32_t), (void **)&didx);
-    if (!r && val) r = bldp::stager_buffer(sg, 3, (size_t)nout * sizeof(float), (void **)&dval);
-    if (!r) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
-    if (r) return r;
-    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
-    r = bldp_argext_f32(dbuf, h.span, ni, nt, dwin, fqavby, tavby, argop, didx, dval, nco,
-                        nco * ni, sg->st[0]);
-    if (r) return r;
-    HCHK(hipMemcpyAsync(idx, didx, (size_t)nout * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                        sg->st[0]));
-    if (val)
-      HCHK(hipMemcpyAsync(val, dval, (size_t)nout * sizeof(float), hipMemcpyDeviceToHost,
-                          sg->st[0]));
-    return BLDP_OK;
+  DevBuf b[2] = {{2, nout * sizeof(uint32_t)}, {3, val ? nout * sizeof(float) : 0}};
+  return with_staged_window(dev, in, nchan, nif, win, w, b, 2, [&](const StagedWin &s) {
+    int r = bldp_argext_f32(s.dbuf, s.span, w[1], w[2], s.dwin, fqavby, tavby, argop,
+                            (uint32_t *)b[0].p, (float *)b[1].p, o[0], o[0] * o[1], s.st);
+    if (!r) r = s.fetch(idx, b[0].p, b[0].bytes);
+    if (!r) r = s.fetch(val, b[1].p, b[1].bytes);
+    return r;
   });
 }
 
@@ -531,44 +556,24 @@ extern "C" int bldp_masked_reduce_host_f32(int dev, const float *in, int64_t nch
   if (op != BLDP_OP_SUM && op != BLDP_OP_MEAN)
     return bldp::set_error(BLDP_EINVAL, "masked reduce: op %d is not sum (%d) or mean (%d)", op,
                            BLDP_OP_SUM, BLDP_OP_MEAN);
-  int64_t sh[3];
-  rc = bldp_reduce_shape(nchan, nif, ntime, win, fqavby, tavby, sh);
+  int64_t w[3], o[3], ld[3];
+  rc = block_counts(nchan, nif, ntime, win, fqavby, tavby, w, o);
   if (rc) return rc;
-  const int64_t nco = sh[0], ni = sh[1], nto = sh[2], nout = nco * ni * nto;
+  const size_t nout = (size_t)(o[0] * o[1] * o[2]);
   if (nout == 0) return BLDP_OK;
   if (!in) return bldp::set_error(BLDP_EINVAL, "masked reduce: null input pointer");
   if (!out && !kept)
     return bldp::set_error(BLDP_EINVAL, "masked reduce: out and kept are both null");
   if (!mask) return bldp::set_error(BLDP_EINVAL, "masked reduce: null mask pointer");
-  const int64_t F = fqavby <= 1 ? 1 : fqavby, T = tavby <= 1 ? 1 : tavby;
-  const int64_t nc = nco * F, nt = nto * T;
-  const int64_t ld[3] = {mask_ld ? mask_ld[0] : 1, mask_ld ? mask_ld[1] : nc,
-                         mask_ld ? mask_ld[2] : nc * ni};
-  const size_t mb = (size_t)((nc - 1) * ld[0] + (ni - 1) * ld[1] + (nt - 1) * ld[2] + 1);
-  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
-  return with_stager(dev, [&](bldp::Stager *sg) -> int {
-    float *dbuf, *dout = nullptr;
-    uint8_t *dmask;
-    uint32_t *dkept = nullptr;
-    int r = bldp::stager_buffer(sg, 0, (size_t)(h.span * ni * nt) * 4, (void **)&dbuf);
-    if (!r) r = bldp::stager_buffer(sg, 1, mb, (void **)&dmask);
-    if (!r && out) r = bldp::stager_buffer(sg, 2, (size_t)nout * sizeof(float), (void **)&dout);
-    if (!r && kept)
-      r = bldp::stager_buffer(sg, 3, (size_t)nout * sizeof(uint32_t), (void **)&dkept);
-    if (!r) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
-    if (r) return r;
-    HCHK(hipMemcpyAsync(dmask, mask, mb, hipMemcpyHostToDevice, sg->st[0]));
-    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
-    r = bldp_masked_reduce_f32(dbuf, h.span, ni, nt, dwin, fqavby, tavby, op, dmask, ld, dout,
-                               dkept, nco, nco * ni, sg->st[0]);
-    if (r) return r;
-    if (out)
-      HCHK(hipMemcpyAsync(out, dout, (size_t)nout * sizeof(float), hipMemcpyDeviceToHost,
-                          sg->st[0]));
-    if (kept)
-      HCHK(hipMemcpyAsync(kept, dkept, (size_t)nout * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                          sg->st[0]));
-    return BLDP_OK;
+  const size_t mb = host_mask(mask_ld, w, ld);
+  DevBuf b[3] = {{1, mb, mask, mb}, {2, out ? nout * 4 : 0}, {3, kept ? nout * 4 : 0}};
+  return with_staged_window(dev, in, nchan, nif, win, w, b, 3, [&](const StagedWin &s) {
+    int r = bldp_masked_reduce_f32(s.dbuf, s.span, w[1], w[2], s.dwin, fqavby, tavby, op,
+                                   (uint8_t *)b[0].p, ld, (float *)b[1].p, (uint32_t *)b[2].p,
+                                   o[0], o[0] * o[1], s.st);
+    if (!r) r = s.fetch(out, b[1].p, b[1].bytes);
+    if (!r) r = s.fetch(kept, b[2].p, b[2].bytes);
+    return r;
   });
 }
 
@@ -583,30 +588,18 @@ extern "C" int bldp_histogram_host_f32(int dev, const float *in, int64_t nchan, 
   int rc = bldp_histogram_plan_f32(nullptr, nchan, nif, ntime, win, fqavby, tavby, nbins, lo, hi,
                                    info);
   if (rc) return rc;
-  int64_t sh[3];
-  rc = bldp_reduce_shape(nchan, nif, ntime, win, fqavby, tavby, sh);
+  int64_t w[3], o[3];
+  rc = block_counts(nchan, nif, ntime, win, fqavby, tavby, w, o);
   if (rc) return rc;
-  const int64_t nco = sh[0], ni = sh[1], nto = sh[2], plane = nco * ni * nto;
+  const int64_t plane = o[0] * o[1] * o[2];
   if (plane == 0) return BLDP_OK;
   if (!in) return bldp::set_error(BLDP_EINVAL, "histogram: null input pointer");
   if (!out) return bldp::set_error(BLDP_EINVAL, "histogram: null output pointer");
-  const int64_t F = fqavby <= 1 ? 1 : fqavby, T = tavby <= 1 ? 1 : tavby;
-  const int64_t nc = nco * F, nt = nto * T;
-  const size_t obytes = (size_t)plane * (size_t)(nbins + 3) * sizeof(uint32_t);
-  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
-  return with_stager(dev, [&](bldp::Stager *sg) -> int {
-    float *dbuf;
-    uint32_t *dout;
-    int r = bldp::stager_buffer(sg, 0, (size_t)(h.span * ni * nt) * 4, (void **)&dbuf);
-    if (!r) r = bldp::stager_buffer(sg, 2, obytes, (void **)&dout);
-    if (!r) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
-    if (r) return r;
-    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
-    r = bldp_histogram_f32(dbuf, h.span, ni, nt, dwin, fqavby, tavby, nbins, lo, hi, dout, nco,
-                           nco * ni, plane, sg->st[0]);
-    if (r) return r;
-    HCHK(hipMemcpyAsync(out, dout, obytes, hipMemcpyDeviceToHost, sg->st[0]));
-    return BLDP_OK;
+  DevBuf b[1] = {{2, (size_t)plane * (size_t)(nbins + 3) * sizeof(uint32_t)}};
+  return with_staged_window(dev, in, nchan, nif, win, w, b, 1, [&](const StagedWin &s) {
+    const int r = bldp_histogram_f32(s.dbuf, s.span, w[1], w[2], s.dwin, fqavby, tavby, nbins, lo,
+                                     hi, (uint32_t *)b[0].p, o[0], o[0] * o[1], plane, s.st);
+    return r ? r : s.fetch(out, b[0].p, b[0].bytes);
   });
 }
 
@@ -623,47 +616,36 @@ extern "C" int bldp_hits_host_f32(int dev, const float *in, int64_t nchan, int64
   int rc = bldp_hits_plan_f32(nullptr, nchan, nif, ntime, win, nullptr, mask_ld, cap, info);
   if (rc) return rc;
   if (!total) return bldp::set_error(BLDP_EINVAL, "hits: null total pointer");
-  int64_t sh[3];
-  rc = bldp_reduce_shape(nchan, nif, ntime, win, 1, 1, sh);
+  int64_t w[3], o[3], ld[3];
+  rc = block_counts(nchan, nif, ntime, win, 1, 1, w, o);
   if (rc) return rc;
-  const int64_t nc = sh[0], ni = sh[1], nt = sh[2];
   *total = 0;
-  if (nc * ni * nt == 0) return BLDP_OK;
+  if (w[0] * w[1] * w[2] == 0) return BLDP_OK;
   if (!in) return bldp::set_error(BLDP_EINVAL, "hits: null input pointer");
   if (!mask) return bldp::set_error(BLDP_EINVAL, "hits: null mask pointer");
-  const int64_t ld[3] = {mask_ld ? mask_ld[0] : 1, mask_ld ? mask_ld[1] : nc,
-                         mask_ld ? mask_ld[2] : nc * ni};
-  const size_t mb = (size_t)((nc - 1) * ld[0] + (ni - 1) * ld[1] + (nt - 1) * ld[2] + 1);
+  const size_t mb = host_mask(mask_ld, w, ld);
   const size_t tot_off = (mb + 7) & ~(size_t)7;  // total sits behind the staged mask
-  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
-  return with_stager(dev, [&](bldp::Stager *sg) -> int {
-    float *dbuf, *dval = nullptr;
-    uint8_t *dmask;
-    int64_t *didx = nullptr;
-    int r = bldp::stager_buffer(sg, 0, (size_t)(h.span * ni * nt) * 4, (void **)&dbuf);
-    if (!r) r = bldp::stager_buffer(sg, 1, tot_off + sizeof(uint64_t), (void **)&dmask);
-    if (!r) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
-    if (r) return r;
+  DevBuf b[1] = {{1, tot_off + sizeof(uint64_t), mask, mb}};
+  return with_staged_window(dev, in, nchan, nif, win, w, b, 1, [&](const StagedWin &s) -> int {
+    uint8_t *dmask = (uint8_t *)b[0].p;
     uint64_t *dtotal = reinterpret_cast<uint64_t *>(dmask + tot_off);
-    HCHK(hipMemcpyAsync(dmask, mask, mb, hipMemcpyHostToDevice, sg->st[0]));
-    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
-    r = bldp_hits_f32(dbuf, h.span, ni, nt, dwin, dmask, ld, 0, nullptr, nullptr, dtotal,
-                      sg->st[0]);
+    int r = bldp_hits_f32(s.dbuf, s.span, w[1], w[2], s.dwin, dmask, ld, 0, nullptr, nullptr,
+                          dtotal, s.st);
+    if (!r) r = s.fetch(total, dtotal, sizeof(uint64_t));
     if (r) return r;
-    HCHK(hipMemcpyAsync(total, dtotal, sizeof(uint64_t), hipMemcpyDeviceToHost, sg->st[0]));
-    HCHK(hipStreamSynchronize(sg->st[0]));
+    HCHK(hipStreamSynchronize(s.st));
     const size_t n = (size_t)std::min<uint64_t>(*total, (uint64_t)cap);
     if (n == 0 || (!idx && !val)) return BLDP_OK;
-    if (idx) r = bldp::stager_buffer(sg, 2, n * sizeof(int64_t), (void **)&didx);
-    if (!r && val) r = bldp::stager_buffer(sg, 3, n * sizeof(float), (void **)&dval);
+    int64_t *didx = nullptr;
+    float *dval = nullptr;
+    if (idx) r = bldp::stager_buffer(s.sg, 2, n * sizeof(int64_t), (void **)&didx);
+    if (!r && val) r = bldp::stager_buffer(s.sg, 3, n * sizeof(float), (void **)&dval);
     if (!r)
-      r = bldp_hits_f32(dbuf, h.span, ni, nt, dwin, dmask, ld, (int64_t)n, didx, dval, dtotal,
-                        sg->st[0]);
-    if (r) return r;
-    if (idx)
-      HCHK(hipMemcpyAsync(idx, didx, n * sizeof(int64_t), hipMemcpyDeviceToHost, sg->st[0]));
-    if (val) HCHK(hipMemcpyAsync(val, dval, n * sizeof(float), hipMemcpyDeviceToHost, sg->st[0]));
-    return BLDP_OK;
+      r = bldp_hits_f32(s.dbuf, s.span, w[1], w[2], s.dwin, dmask, ld, (int64_t)n, didx, dval,
+                        dtotal, s.st);
+    if (!r) r = s.fetch(idx, didx, n * sizeof(int64_t));
+    if (!r) r = s.fetch(val, dval, n * sizeof(float));
+    return r;
   });
 }
 
@@ -682,42 +664,23 @@ extern "C" int bldp_fold_host_f32(int dev, const float *in, int64_t nchan, int64
   if (op != BLDP_OP_SUM && op != BLDP_OP_MEAN)
     return bldp::set_error(BLDP_EINVAL, "fold: op %d is not sum (%d) or mean (%d)", op,
                            BLDP_OP_SUM, BLDP_OP_MEAN);
-  int64_t sh[3], wsh[3];
+  int64_t sh[3], w[3], o[3], ld[3];
   rc = bldp_fold_shape(nchan, nif, ntime, win, nfpc, tavby, sh);
-  if (!rc) rc = bldp_reduce_shape(nchan, nif, ntime, win, 1, 1, wsh);
+  if (!rc) rc = block_counts(nchan, nif, ntime, win, 1, 1, w, o);
   if (rc) return rc;
-  const int64_t nc = wsh[0], ni = wsh[1], nt = wsh[2], nto = sh[2], nout = sh[0] * ni * nto;
+  const int64_t ni = w[1];
+  const size_t nout = (size_t)(sh[0] * ni * sh[2]);
   if (nout == 0) return BLDP_OK;
   if (!in) return bldp::set_error(BLDP_EINVAL, "fold: null input pointer");
   if (!out && !kept) return bldp::set_error(BLDP_EINVAL, "fold: out and kept are both null");
-  const int64_t ld[3] = {mask_ld ? mask_ld[0] : 1, mask_ld ? mask_ld[1] : nc,
-                         mask_ld ? mask_ld[2] : nc * ni};
-  const size_t mb =
-      mask ? (size_t)((nc - 1) * ld[0] + (ni - 1) * ld[1] + (nt - 1) * ld[2] + 1) : 0;
-  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
-  return with_stager(dev, [&](bldp::Stager *sg) -> int {
-    float *dbuf, *dout = nullptr;
-    uint8_t *dmask = nullptr;
-    uint32_t *dkept = nullptr;
-    int r = bldp::stager_buffer(sg, 0, (size_t)(h.span * ni * nt) * 4, (void **)&dbuf);
-    if (!r && mask) r = bldp::stager_buffer(sg, 1, mb, (void **)&dmask);
-    if (!r && out) r = bldp::stager_buffer(sg, 2, (size_t)nout * sizeof(float), (void **)&dout);
-    if (!r && kept)
-      r = bldp::stager_buffer(sg, 3, (size_t)nout * sizeof(uint32_t), (void **)&dkept);
-    if (!r) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
-    if (r) return r;
-    if (mask) HCHK(hipMemcpyAsync(dmask, mask, mb, hipMemcpyHostToDevice, sg->st[0]));
-    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
-    r = bldp_fold_f32(dbuf, h.span, ni, nt, dwin, nfpc, tavby, op, dmask, ld, dout, dkept, nfpc,
-                      nfpc * ni, sg->st[0]);
-    if (r) return r;
-    if (out)
-      HCHK(hipMemcpyAsync(out, dout, (size_t)nout * sizeof(float), hipMemcpyDeviceToHost,
-                          sg->st[0]));
-    if (kept)
-      HCHK(hipMemcpyAsync(kept, dkept, (size_t)nout * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                          sg->st[0]));
-    return BLDP_OK;
+  const size_t span = host_mask(mask_ld, w, ld), mb = mask ? span : 0;
+  DevBuf b[3] = {{1, mb, mask, mb}, {2, out ? nout * 4 : 0}, {3, kept ? nout * 4 : 0}};
+  return with_staged_window(dev, in, nchan, nif, win, w, b, 3, [&](const StagedWin &s) {
+    int r = bldp_fold_f32(s.dbuf, s.span, ni, w[2], s.dwin, nfpc, tavby, op, (uint8_t *)b[0].p, ld,
+                          (float *)b[1].p, (uint32_t *)b[2].p, nfpc, nfpc * ni, s.st);
+    if (!r) r = s.fetch(out, b[1].p, b[1].bytes);
+    if (!r) r = s.fetch(kept, b[2].p, b[2].bytes);
+    return r;
   });
 }
 
@@ -727,34 +690,25 @@ extern "C" int bldp_unfold_host_f32(int dev, const float *in, int64_t nchan, int
                                     int64_t ntime, const int64_t *win, int64_t nfpc,
                                     int64_t tavby, int uop, const float *prof, float *out) {
   // (every argument check, before any staging)
-  int64_t sh[3], wsh[3];
+  int64_t sh[3], w[3], o[3];
   int rc = bldp_fold_shape(nchan, nif, ntime, win, nfpc, tavby, sh);
-  if (!rc) rc = bldp_reduce_shape(nchan, nif, ntime, win, 1, 1, wsh);
+  if (!rc) rc = block_counts(nchan, nif, ntime, win, 1, 1, w, o);
   if (rc) return rc;
   if (uop != BLDP_UNFOLD_DIV && uop != BLDP_UNFOLD_SUB)
     return bldp::set_error(BLDP_EINVAL, "unfold: op %d is not divide (%d) or subtract (%d)", uop,
                            BLDP_UNFOLD_DIV, BLDP_UNFOLD_SUB);
-  const int64_t nc = wsh[0], ni = wsh[1], nt = wsh[2], nto = sh[2];
+  const int64_t nc = w[0], ni = w[1], nt = w[2];
   if (nc * ni * nt == 0) return BLDP_OK;
   if (!in) return bldp::set_error(BLDP_EINVAL, "unfold: null input pointer");
   if (!prof) return bldp::set_error(BLDP_EINVAL, "unfold: null profile pointer");
   if (!out) return bldp::set_error(BLDP_EINVAL, "unfold: null output pointer");
-  const size_t pbytes = (size_t)(nfpc * ni * nto) * 4, obytes = (size_t)(nc * ni * nt) * 4;
-  const HostWin h = host_window(in, 4, nchan, nif, win, nc, ni);
-  return with_stager(dev, [&](bldp::Stager *sg) -> int {
-    float *dbuf, *dprof, *dout;
-    int r = bldp::stager_buffer(sg, 0, (size_t)(h.span * ni * nt) * 4, (void **)&dbuf);
-    if (!r) r = bldp::stager_buffer(sg, 1, pbytes, (void **)&dprof);
-    if (!r) r = bldp::stager_buffer(sg, 2, obytes, (void **)&dout);
-    if (!r) r = stage_rows(h, 0, nt, dbuf, sg->st[0]);
-    if (r) return r;
-    HCHK(hipMemcpyAsync(dprof, prof, pbytes, hipMemcpyHostToDevice, sg->st[0]));
-    const int64_t dwin[9] = {h.cs < 0 ? (nc - 1) * h.acs : 0, nc, h.cs, 0, ni, 1, 0, nt, 1};
-    r = bldp_unfold_f32(dbuf, h.span, ni, nt, dwin, nfpc, tavby, uop, dprof, nfpc, nfpc * ni, dout,
-                        nc, nc * ni, sg->st[0]);
-    if (r) return r;
-    HCHK(hipMemcpyAsync(out, dout, obytes, hipMemcpyDeviceToHost, sg->st[0]));
-    return BLDP_OK;
+  const size_t pbytes = (size_t)(nfpc * ni * sh[2]) * 4;
+  DevBuf b[2] = {{1, pbytes, prof, pbytes}, {2, (size_t)(nc * ni * nt) * 4}};
+  return with_staged_window(dev, in, nchan, nif, win, w, b, 2, [&](const StagedWin &s) {
+    const int r = bldp_unfold_f32(s.dbuf, s.span, ni, nt, s.dwin, nfpc, tavby, uop,
+                                  (float *)b[0].p, nfpc, nfpc * ni, (float *)b[1].p, nc, nc * ni,
+                                  s.st);
+    return r ? r : s.fetch(out, b[1].p, b[1].bytes);
   });
 }
 
