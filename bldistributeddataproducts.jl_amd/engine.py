@@ -211,20 +211,54 @@ DTYPE_CODES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.uin
 DTYPE_OF_CODE = {v: k for k, v in DTYPE_CODES.items()}
 
 
+_dtype_codes: dict = {}  # _dtype_code's answers by dtype object: every call asks, for the same few
+
+
 def _dtype_code(dt):
     """bldp_dtype of a numpy dtype or torch dtype (None if unsupported)."""
+    try:
+        return _dtype_codes[dt]
+    except (KeyError, TypeError):  # (TypeError: not hashable, so not remembered either)
+        pass
+    key = dt
     if not isinstance(dt, np.dtype):
         try:
             dt = np.dtype(str(dt).replace("torch.", ""))
         except TypeError:
             return None
-    return DTYPE_CODES.get(np.dtype(dt))
+    code = DTYPE_CODES.get(np.dtype(dt))
+    try:
+        _dtype_codes[key] = code
+    except TypeError:
+        pass
+    return code
+
+
+def _quantile_kind(op):
+    """"quantile" / "quantiles" for those function tuples (their p's checked:
+    ValueError), else None."""
+    if isinstance(op, str):  # (the common case, and never a tuple)
+        return None
+    if _lib.quantile_of(op) is not None:
+        return "quantile"
+    return "quantiles" if _lib.quantiles_of(op) is not None else None
 
 
 def _no_quantile(op, what) -> None:
-    if _lib.quantile_of(op) is not None or _lib.quantiles_of(op) is not None:
+    if _quantile_kind(op):
         raise TypeError(f"{what} takes the ops of enum bldp_op; a quantile goes through "
                         f"engine.quantile / band_quantile")
+
+
+def _route_quantile(op, form, data, n, axis, *rest):
+    """An ``op`` that is ``("quantile", p)`` or ``("quantiles", ps)`` goes to that
+    family's ``form`` ("", "_plan", "band_", "_host") with blocks of ``n`` on
+    ``axis``; None for every other op."""
+    kind = _quantile_kind(op)
+    if kind is None:
+        return None
+    name = "band_" + kind if form == "band_" else kind + form
+    return globals()[name](data, n, op[1], axis, *rest)
 
 
 def _check_stat(op: str, tavby, dtype=None) -> None:
@@ -246,7 +280,7 @@ def out_dtype(dtype, op: str) -> np.dtype:
     code = _dtype_code(dtype)
     if code is None:
         raise TypeError(f"unsupported element type {dtype}")
-    if _lib.quantile_of(op) is not None or _lib.quantiles_of(op) is not None:
+    if _quantile_kind(op):
         op = "median"  # (no op of the ABI: the median's types)
     rc = _lib.lib().bldp_reduce_out_dtype(code, _lib.OPS[op])
     _lib.check(min(rc, 0), "bldp_reduce_out_dtype")
@@ -288,19 +322,190 @@ def out_shape(shape, win, fqavby, tavby):
     return nc // F, ni, nt // T
 
 
+# The block operations (reduce, tstat, quantile(s), outliers, argext, masked
+# reduce, histogram, hits, fold, unfold) come in four forms: the device call, its
+# plan, the band and the host call.  The helpers below state once what the forms
+# share; each public function applies its family's own checks between them, in
+# its own order (tests/test_engine_front_errors.py pins that order).
+def _window(x, win):
+    """(shape, window shape) of a tensor or host array, the window inside it
+    (BoundsError)."""
+    shape = tuple(x.shape)
+    if win is None:
+        return shape, shape
+    _check_bounds(win, shape)
+    return shape, window_shape(win, shape)
+
+
+def _win_ptr(win, shape):
+    """(keep-alive, window pointer) of the ABI's nine int64 (a band passes it after
+    its banks' pointers)."""
+    return _lib.win_arg(_full_win(win, shape))
+
+
+def _win_args(x, win, allow_typed=False):
+    """What the ABI takes for a window of a device tensor: ((pointer, nchan, nif,
+    ntime, window pointer), keep-alive).  The window has passed ``_window``."""
+    dims = _abi_dims(x, allow_typed)
+    keep, wp = _lib.win_arg(_full_win(win, x.shape))
+    return (*dims, wp), keep
+
+
+def _host_args(device, a, win):
+    """``_win_args`` of a host array staged on ``device``: ((device, pointer,
+    nchan, nif, ntime, window pointer), keep-alive)."""
+    keep, wp = _lib.win_arg(_full_win(win, a.shape))
+    return (int(device), _np_ptr(a), *a.shape, wp), keep
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None and t.numel() else None
+
+
+def _np_ptr(a):
+    return a.ctypes.data if a is not None and a.size else None
+
+
+def _host_fb(a, what=None, fn=None):
+    """A host filterbank: a Fortran-ordered float32 (nchan, nif, ntime) array.
+    ``what``: the caller's name in the TypeError of another element type (``fn``
+    names the operation); None for the forms that only give the general one."""
+    a = np.asarray(a)
+    if what and a.dtype != np.float32:
+        _need_f32(what, a.dtype, fn)
+    if a.dtype != np.float32 or not a.flags.f_contiguous or a.ndim != 3:
+        raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
+    return a
+
+
+def _host_out(dims, dtype=np.float32):
+    """Fortran-ordered host output of ``dims``.  int32: the ABI writes uint32
+    offsets and counts, all below 2^31."""
+    return np.empty(dims, dtype=dtype, order="F")
+
+
+def _banks(banks, what=None, fn=None, agree=True, devices=False):
+    """The banks of a band on one GPU: (banks, nbank, their pointers as the ABI's
+    void*, (nchan, nif, ntime) every bank shares).  ``what`` / ``fn``: the banks
+    must be Float32, named so in the TypeError; ``agree=False`` stops there
+    (geometry None); ``devices``: the banks must share a device too."""
+    banks = list(banks)
+    if not banks:
+        raise ValueError("no banks")
+    if what:
+        f32 = _torch().float32
+        for b in banks:
+            if b.dtype != f32:
+                _need_f32(what, b.dtype, fn)
+    geo = None
+    if agree:
+        shape = tuple(banks[0].shape)
+        for b in banks:
+            g = _abi_dims(b)[1:] if tuple(b.shape) == shape else None
+            if geo is None and g is not None:
+                geo = g
+            if g != geo or (devices and b.device != banks[0].device):
+                raise ValueError("all banks of a band must have the same shape"
+                                 + (", layout and device" if devices else " and layout"))
+    ptrs = (ctypes.c_void_p * len(banks))(*[b.data_ptr() for b in banks])
+    return banks, len(banks), ctypes.cast(ptrs, ctypes.c_void_p), geo
+
+
+def _axis_factors(n, axis):
+    """(fqavby, tavby) of blocks of ``n`` along ``axis`` (0: channels, 2: spectra)."""
+    return (n, 1) if axis == 0 else (1, n)
+
+
+def _out_layout(t, dims, device, dtype, name="out", dtname=None, planes=None, loose=False):
+    """A caller's output tensor, checked before any launch: a ``dtype`` tensor of
+    shape ``dims`` (``(*dims, planes)`` with planes) on ``device`` with the
+    channels fastest and rows that do not overlap; returns (pointer, ld_i, ld_t),
+    with planes also ld_q (``_plane_ld``).  ``loose``: unfold's rule, which leaves
+    the rows to the library."""
+    torch = _torch()
+    nc, ni, nt = dims
+    full = tuple(dims) if planes is None else (*dims, planes)
+    if loose:
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            raise TypeError(f"{name} must be a {dtname} device tensor, not "
+                            f"{getattr(t, 'dtype', type(t).__name__)}")
+    else:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a device tensor")
+        if t.dtype != dtype:
+            raise TypeError(f"{name} must be {dtname or dtype}, not {t.dtype}")
+    if tuple(t.shape) != full:
+        raise ValueError(f"{name} is {tuple(t.shape)}, expected {full}")
+    if t.device != torch.device(device):
+        raise ValueError(f"{name} is on {t.device}, the data on {device}")
+    s0, s1, s2 = t.stride()[:3]
+    ld_i = s1 if ni > 1 else nc
+    ld_t = s2 if nt > 1 else max(ni - 1, 0) * ld_i + nc
+    if loose:
+        if nc > 1 and s0 != 1:
+            raise ValueError(f"{name} strides {t.stride()}: the channels must be the fastest axis")
+    elif (nc > 1 and s0 != 1) or ld_i < nc or ld_t < (ni - 1) * ld_i + nc:
+        raise ValueError(f"{name} strides {t.stride()} are not a Julia-order (channel-fastest) "
+                         f"layout of {(nc, ni, nt)}" + ("" if planes is None else " planes"))
+    if planes is None:
+        return _ptr(t), ld_i, ld_t
+    return _ptr(t), ld_i, ld_t, _plane_ld(t, dims, planes, ld_i, ld_t)
+
+
+def _plane_ld(t, dims, K, ld_i, ld_t):
+    """out_ld_q of a 4-D output of K planes: they may not overlap."""
+    nc, ni, nt = dims
+    extent = max(nt - 1, 0) * ld_t + max(ni - 1, 0) * ld_i + nc
+    ld_q = t.stride(3) if K > 1 else extent
+    if ld_q < extent:
+        raise ValueError(f"out strides {t.stride()}: the planes overlap")
+    return ld_q
+
+
+# The keys of the plans: the reduce's (blocks of channels, axis 0) and the
+# tstat's (blocks of spectra, axis 2), which the quantile, quantiles and outliers
+# plans extend, and the argext's, which the masked reduce extends.
+REDUCE_PLAN_KEYS = ("path", "lanes_per_group", "time_split_waves", "float4_per_lane",
+                    "time_chunks", "workgroups", "workspace_bytes", "vec_out")
+TSTAT_PLAN_KEYS = ("path", "channels_per_lane", "time_split_lanes", "passes", "workgroups",
+                   "workspace_bytes", "blocks", "channel_lanes")
+ARGEXT_PLAN_KEYS = ("path", "lanes_per_block", "time_slices", "float4_per_lane", "workgroups",
+                    "workspace_bytes", "outputs", "vector_loads")
+
+
+def _plan_dict(fn, args, n, keys, **enums):
+    """The dict of a plan entry point: ``fn(*args, info)`` fills ``n`` int64, named
+    by ``keys``; ``enums`` maps a key's code to its name ("copy" for a code with
+    none: the copy of a block of one)."""
+    info = (ctypes.c_int64 * n)()
+    _lib.check(getattr(_lib.lib(), fn)(*args, info), fn)
+    d = dict(zip(keys, info[:]))
+    for k, names in enums.items():
+        d[k] = names.get(d[k], "copy")
+    return d
+
+
+def _axis_plan(fn, args, n, axis, extra=(), rank=False):
+    """``_plan_dict`` with the reduce's keys (axis 0) or the tstat's (axis 2) and
+    ``extra``; ``rank``: the rank stands where the workspace bytes do."""
+    keys, paths = (REDUCE_PLAN_KEYS, _lib.PATHS) if axis == 0 else \
+        (TSTAT_PLAN_KEYS, _lib.TSTAT_PATHS)
+    if rank:
+        keys = tuple("rank" if k == "workspace_bytes" else k for k in keys)
+    return _plan_dict(fn, args, n, keys + tuple(extra), path=paths)
+
+
 def reduce(x, fqavby=1, tavby=1, op="sum", win=None, out=None, stream=None):
     """fqav on the channel axis fused with time integration, on the GPU.
 
     x: device filterbank tensor; win: 9-int window (see idxs.to_window) or
     None; returns a Julia-order (nc/F, ni, nt/T) device tensor."""
     _check_stat(op, tavby, x.dtype)
-    if _lib.quantile_of(op) is not None:
-        return quantile(x, fqavby, op[1], 0, win, out, stream)
-    if _lib.quantiles_of(op) is not None:
-        return quantiles(x, fqavby, op[1], 0, win, out, stream)
+    r = _route_quantile(op, "", x, fqavby, 0, win, out, stream)
+    if r is not None:
+        return r
     L = _lib.lib()
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
+    shape, _ = _window(x, win)
     nco, ni, nto = out_shape(shape, win, fqavby, tavby)
     torch = _torch()
     typed = x.dtype != torch.float32
@@ -310,16 +515,14 @@ def reduce(x, fqavby=1, tavby=1, op="sum", win=None, out=None, stream=None):
     elif tuple(out.shape) != (nco, ni, nto) or out.dtype != odt:
         raise ValueError(f"out is {out.dtype} {tuple(out.shape)}, expected {odt} {(nco, ni, nto)}")
     optr, onc, oni, _ = _abi_dims(out, allow_typed=True) if out.numel() else (0, nco, ni, nto)
-    ptr, nchan, nif, ntime = _abi_dims(x, allow_typed=True)
-    keep, wp = _lib.win_arg(_full_win(win, shape))
+    w, keep = _win_args(x, win, allow_typed=True)
     if typed:  # fqav's Julia result types for integer / Float64 data (bldp_reduce_strided)
-        rc = L.bldp_reduce_strided(_dtype_code(x.dtype), ptr, nchan, nif, ntime, wp, int(fqavby),
-                                   int(tavby), _lib.OPS[op], optr, onc, onc * oni,
-                                   _lib.stream_ptr(stream))
+        rc = L.bldp_reduce_strided(_dtype_code(x.dtype), *w, int(fqavby), int(tavby),
+                                   _lib.OPS[op], optr, onc, onc * oni, _lib.stream_ptr(stream))
         _lib.check(rc, "bldp_reduce_strided")
         return out
-    rc = L.bldp_reduce_strided_f32(ptr, nchan, nif, ntime, wp, int(fqavby), int(tavby),
-                                   _lib.OPS[op], optr, onc, onc * oni, _lib.stream_ptr(stream))
+    rc = L.bldp_reduce_strided_f32(*w, int(fqavby), int(tavby), _lib.OPS[op], optr, onc,
+                                   onc * oni, _lib.stream_ptr(stream))
     _lib.check(rc, "bldp_reduce_strided_f32")
     return out
 
@@ -376,7 +579,7 @@ class PreparedReduce(_Prepared):
                              f"{(nco, ni, nto)}")
         optr, onc, oni, _ = _abi_dims(out, allow_typed=True) if out.numel() else (0, nco, ni, nto)
         ptr, nchan, nif, ntime = _abi_dims(x, allow_typed=True)
-        keep, wp = _lib.win_arg(_full_win(win, shape))
+        keep, wp = _win_ptr(win, shape)
         h = ctypes.c_void_p()
         with torch.cuda.device(x.device):
             rc = L.bldp_reduce_prepare(_dtype_code(x.dtype), ptr, nchan, nif, ntime, wp,
@@ -401,7 +604,7 @@ class PreparedKurtosis(_Prepared):
         if out is None:
             out = torch.empty((ni, nc), dtype=torch.float64, device=x.device).t()
         ptr, nchan, nif, ntime = _abi_dims(x, allow_typed=True)
-        keep, wp = _lib.win_arg(_full_win(win, shape))
+        keep, wp = _win_ptr(win, shape)
         h = ctypes.c_void_p()
         with torch.cuda.device(x.device):
             rc = L.bldp_kurtosis_prepare(_dtype_code(x.dtype), ptr, nchan, nif, ntime, wp,
@@ -414,46 +617,21 @@ class PreparedKurtosis(_Prepared):
 
 def plan(x, fqavby=1, tavby=1, op="sum", win=None) -> dict:
     """Launch plan the library picks for this call (path, lanes/group, ...)."""
-    if _lib.quantile_of(op) is not None:
+    if _quantile_kind(op):
         _check_stat(op, tavby)
-        return quantile_plan(x, fqavby, op[1], 0, win)
-    if _lib.quantiles_of(op) is not None:
-        _check_stat(op, tavby)
-        return quantiles_plan(x, fqavby, op[1], 0, win)
-    L = _lib.lib()
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
-    ptr, nchan, nif, ntime = _abi_dims(x)
-    info = (ctypes.c_int64 * 8)()
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    rc = L.bldp_reduce_plan_f32(ptr, nchan, nif, ntime, wp, int(fqavby), int(tavby),
-                                _lib.OPS[op], None, info)
-    _lib.check(rc, "bldp_reduce_plan_f32")
-    keys = ["path", "lanes_per_group", "time_split_waves", "float4_per_lane", "time_chunks",
-            "workgroups", "workspace_bytes", "vec_out"]
-    d = dict(zip(keys, list(info)))
-    d["path"] = _lib.PATHS[d["path"]]
-    return d
+        return _route_quantile(op, "_plan", x, fqavby, 0, win)
+    _window(x, win)
+    w, keep = _win_args(x, win)
+    return _plan_dict("bldp_reduce_plan_f32", (*w, int(fqavby), int(tavby), _lib.OPS[op], None),
+                      8, REDUCE_PLAN_KEYS, path=_lib.PATHS)
 
 
 def _band_args(banks, fqavby, tavby, win, out):
-    """Checks of a one-GPU band reduce; (banks, geometry, out, ptr array, window keepalive)."""
-    banks = list(banks)
-    if not banks:
-        raise ValueError("no banks")
-    shape = tuple(banks[0].shape)
-    geo = None
-    for b in banks:
-        if tuple(b.shape) != shape:
-            raise ValueError("all banks of a band must have the same shape")
-        g = _abi_dims(b)[1:]
-        if geo is None:
-            geo = g
-        elif g != geo:
-            raise ValueError("all banks of a band must have the same layout")
-    _check_bounds(win, shape)
+    """Checks of a one-GPU band reduce; (banks, geometry, out, the banks' pointers
+    as the ABI's void*, window keepalive)."""
+    banks, nb, ptrs, geo = _banks(banks)
+    shape, _ = _window(banks[0], win)
     nco, ni, nto = out_shape(shape, win, fqavby, tavby)
-    nb = len(banks)
     if out is None:
         out = fb_empty(nb * nco, ni, nto, device=banks[0].device)
     if _dtype_code(out.dtype) != 0:
@@ -461,26 +639,24 @@ def _band_args(banks, fqavby, tavby, win, out):
     if tuple(out.shape) != (nb * nco, ni, nto) or (
             out.numel() and out.stride() != (1, nb * nco, nb * nco * ni) and ni * nto > 1):
         raise ValueError("out must be a dense Julia-order (nbank*nco, ni, nto) tensor")
-    ptrs = (ctypes.c_void_p * nb)(*[b.data_ptr() for b in banks])
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    return banks, geo, out, ptrs, (keep, wp)
+    return banks, geo, out, ptrs, _win_ptr(win, shape)
+
+
+def _band_out_device(out, banks):
+    if out.device != banks[0].device:
+        raise ValueError(f"out is on {out.device}, the banks on {banks[0].device}")
 
 
 def band_reduce(banks, fqavby=1, tavby=1, op="sum", win=None, out=None, stream=None):
     """Reduce every bank of a band resident on ONE GPU and stitch them in bank
     order (reduce(vcat, ...), src/gbt.jl:103) in a single launch."""
     _check_stat(op, tavby)
-    if _lib.quantile_of(op) is not None:
-        return band_quantile(banks, fqavby, op[1], 0, win, out, stream)
-    if _lib.quantiles_of(op) is not None:
-        return band_quantiles(banks, fqavby, op[1], 0, win, out, stream)
-    L = _lib.lib()
+    r = _route_quantile(op, "band_", banks, fqavby, 0, win, out, stream)
+    if r is not None:
+        return r
     banks, geo, out, ptrs, (keep, wp) = _band_args(banks, fqavby, tavby, win, out)
-    nchan, nif, ntime = geo
-    rc = L.bldp_band_reduce_f32(len(banks), ctypes.cast(ptrs, ctypes.c_void_p), nchan, nif, ntime,
-                                wp, int(fqavby), int(tavby), _lib.OPS[op],
-                                out.data_ptr() if out.numel() else None,
-                                _lib.stream_ptr(stream))
+    rc = _lib.lib().bldp_band_reduce_f32(len(banks), ptrs, *geo, wp, int(fqavby), int(tavby),
+                                         _lib.OPS[op], _ptr(out), _lib.stream_ptr(stream))
     _lib.check(rc, "bldp_band_reduce_f32")
     return out
 
@@ -499,7 +675,7 @@ class PreparedBandReduce:
         banks, geo, out, ptrs, (keep, wp) = _band_args(banks, fqavby, tavby, win, out)
         h = ctypes.c_void_p()
         with _torch().cuda.device(banks[0].device):
-            rc = L.bldp_band_reduce_prepare_f32(len(banks), ctypes.cast(ptrs, ctypes.c_void_p),
+            rc = L.bldp_band_reduce_prepare_f32(len(banks), ptrs,
                                                 *geo, wp, int(fqavby), int(tavby), _lib.OPS[op],
                                                 out.data_ptr() if out.numel() else None,
                                                 ctypes.byref(h))
@@ -571,7 +747,7 @@ def band_reduce_multi(banks, fqavby=1, tavby=1, op="sum", win=None, root=0, out=
                          "on the root device")
     devs = (ctypes.c_int * len(banks))(*[b.device.index for b in banks])
     ptrs = (ctypes.c_void_p * len(banks))(*[b.data_ptr() for b in banks])
-    keep, wp = _lib.win_arg(_full_win(win, shape))
+    keep, wp = _win_ptr(win, shape)
     for d in {b.device.index for b in banks}:
         torch.cuda.synchronize(d)  # inputs written on torch streams are complete
     rc = L.bldp_band_reduce_multi_f32(len(banks), ctypes.cast(devs, ctypes.c_void_p),
@@ -581,6 +757,22 @@ def band_reduce_multi(banks, fqavby=1, tavby=1, op="sum", win=None, root=0, out=
                                       (_lib.BLDP_BAND_STAGED if staged else 0)
                                       | (_lib.BLDP_BAND_PEER_STORE if peer_store else 0))
     _lib.check(rc, "bldp_band_reduce_multi_f32")
+    return out
+
+
+def reduce_host(a: np.ndarray, fqavby=1, tavby=1, op="sum", win=None, device=0) -> np.ndarray:
+    """Host array in, host array out (bldp_reduce_host_f32): the window is
+    streamed through the GPU and reduced there."""
+    _check_stat(op, tavby)
+    r = _route_quantile(op, "_host", a, fqavby, 0, win, device)
+    if r is not None:
+        return r
+    a = _host_fb(a)
+    shape, _ = _window(a, win)
+    out = _host_out(out_shape(shape, win, fqavby, tavby))
+    h, keep = _host_args(device, a, win)
+    rc = _lib.lib().bldp_reduce_host_f32(*h, int(fqavby), int(tavby), _lib.OPS[op], _np_ptr(out))
+    _lib.check(rc, "bldp_reduce_host_f32")
     return out
 
 
@@ -596,23 +788,7 @@ def _tstat_out(out, dims, device):
     """A caller's ``out`` of a tstat, checked before any launch: a Float32
     (nc, ni, nb) tensor on ``device`` with the channels fastest and rows that
     do not overlap; returns (pointer, out_ld_i, out_ld_b)."""
-    torch = _torch()
-    nc, ni, nb = dims
-    if not isinstance(out, torch.Tensor):
-        raise TypeError("out must be a device tensor")
-    if out.dtype != torch.float32:
-        raise TypeError(f"out must be Float32, not {out.dtype}")
-    if tuple(out.shape) != (nc, ni, nb):
-        raise ValueError(f"out is {tuple(out.shape)}, expected {(nc, ni, nb)}")
-    if out.device != torch.device(device):
-        raise ValueError(f"out is on {out.device}, the data on {device}")
-    s0, s1, s2 = out.stride()
-    ld_i = s1 if ni > 1 else nc
-    ld_b = s2 if nb > 1 else max(ni - 1, 0) * ld_i + nc
-    if (nc > 1 and s0 != 1) or ld_i < nc or ld_b < (ni - 1) * ld_i + nc:
-        raise ValueError(f"out strides {out.stride()} are not a Julia-order (channel-fastest) "
-                         f"layout of {(nc, ni, nb)}")
-    return (out.data_ptr() if out.numel() else None), ld_i, ld_b
+    return _out_layout(out, dims, device, _torch().float32, dtname="Float32")
 
 
 def tstat(x, tavby, op, win=None, out=None, stream=None):
@@ -622,22 +798,17 @@ def tstat(x, tavby, op, win=None, out=None, stream=None):
     returns a Julia-order (nc, ni, nt/tavby) Float32 device tensor (``out``
     when given: e.g. a bank's slot of a stitched product).  tavby <= 1 copies
     the window.  ``op`` may be ``("quantile", p)``: ``quantile`` on axis 2."""
-    if _lib.quantile_of(op) is not None:
-        return quantile(x, tavby, op[1], 2, win, out, stream)
-    if _lib.quantiles_of(op) is not None:
-        return quantiles(x, tavby, op[1], 2, win, out, stream)
-    L = _lib.lib()
+    r = _route_quantile(op, "", x, tavby, 2, win, out, stream)
+    if r is not None:
+        return r
     code = _tstat_op(op)
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
+    shape, _ = _window(x, win)
     dims = out_shape(shape, win, 1, tavby)
-    ptr, nchan, nif, ntime = _abi_dims(x)
+    w, keep = _win_args(x, win)
     if out is None:
         out = fb_empty(*dims, device=x.device)
-    optr, ld_i, ld_b = _tstat_out(out, dims, x.device)
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    rc = L.bldp_tstat_f32(ptr, nchan, nif, ntime, wp, int(tavby), code, optr, ld_i, ld_b,
-                          _lib.stream_ptr(stream))
+    o = _tstat_out(out, dims, x.device)
+    rc = _lib.lib().bldp_tstat_f32(*w, int(tavby), code, *o, _lib.stream_ptr(stream))
     _lib.check(rc, "bldp_tstat_f32")
     return out
 
@@ -648,42 +819,27 @@ def tstat_plan(x, tavby, op, win=None) -> dict:
     slices of a workgroup splitting a block (1: the register form), passes over
     the block, workgroups, workspace bytes, blocks and the lanes along the
     channels of a split workgroup."""
-    if _lib.quantile_of(op) is not None:
-        return quantile_plan(x, tavby, op[1], 2, win)
-    if _lib.quantiles_of(op) is not None:
-        return quantiles_plan(x, tavby, op[1], 2, win)
-    L = _lib.lib()
+    r = _route_quantile(op, "_plan", x, tavby, 2, win)
+    if r is not None:
+        return r
     code = _tstat_op(op)
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
-    ptr, nchan, nif, ntime = _abi_dims(x)
-    info = (ctypes.c_int64 * 8)()
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    _lib.check(L.bldp_tstat_plan_f32(ptr, nchan, nif, ntime, wp, int(tavby), code, None, info),
-               "bldp_tstat_plan_f32")
-    keys = ["path", "channels_per_lane", "time_split_lanes", "passes", "workgroups",
-            "workspace_bytes", "blocks", "channel_lanes"]
-    d = dict(zip(keys, [int(v) for v in info]))
-    d["path"] = _lib.TSTAT_PATHS.get(d["path"], "copy")
-    return d
+    _window(x, win)
+    w, keep = _win_args(x, win)
+    return _axis_plan("bldp_tstat_plan_f32", (*w, int(tavby), code, None), 8, 2)
 
 
 def band_tstat(banks, tavby, op, win=None, out=None, stream=None):
     """``tstat`` of every bank of a band resident on ONE GPU, stitched in bank
     order (the vcat of the per-bank results) in one launch
     (bldp_band_tstat_f32): a dense (nbank*nc, ni, nt/tavby) Float32 tensor."""
-    if _lib.quantile_of(op) is not None:
-        return band_quantile(banks, tavby, op[1], 2, win, out, stream)
-    if _lib.quantiles_of(op) is not None:
-        return band_quantiles(banks, tavby, op[1], 2, win, out, stream)
-    L = _lib.lib()
+    r = _route_quantile(op, "band_", banks, tavby, 2, win, out, stream)
+    if r is not None:
+        return r
     code = _tstat_op(op)
     banks, geo, out, ptrs, (keep, wp) = _band_args(banks, 1, tavby, win, out)
-    if out.device != banks[0].device:
-        raise ValueError(f"out is on {out.device}, the banks on {banks[0].device}")
-    rc = L.bldp_band_tstat_f32(len(banks), ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp,
-                               int(tavby), code, out.data_ptr() if out.numel() else None,
-                               _lib.stream_ptr(stream))
+    _band_out_device(out, banks)
+    rc = _lib.lib().bldp_band_tstat_f32(len(banks), ptrs, *geo, wp, int(tavby), code, _ptr(out),
+                                        _lib.stream_ptr(stream))
     _lib.check(rc, "bldp_band_tstat_f32")
     return out
 
@@ -691,22 +847,15 @@ def band_tstat(banks, tavby, op, win=None, out=None, stream=None):
 def tstat_host(a: np.ndarray, tavby, op, win=None, device=0) -> np.ndarray:
     """Host Fortran-ordered Float32 array in, (nc, ni, nt/tavby) Float32 host
     array out (bldp_tstat_host_f32: the window's rows staged on ``device``)."""
-    if _lib.quantile_of(op) is not None:
-        return quantile_host(a, tavby, op[1], 2, win, device)
-    if _lib.quantiles_of(op) is not None:
-        return quantiles_host(a, tavby, op[1], 2, win, device)
-    L = _lib.lib()
+    r = _route_quantile(op, "_host", a, tavby, 2, win, device)
+    if r is not None:
+        return r
     code = _tstat_op(op)
-    a = np.asarray(a)
-    if a.dtype != np.float32 or not a.flags.f_contiguous or a.ndim != 3:
-        raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
-    _check_bounds(win, a.shape)
-    dims = out_shape(a.shape, win, 1, tavby)
-    out = np.empty(dims, dtype=np.float32, order="F")
-    keep, wp = _lib.win_arg(_full_win(win, a.shape))
-    rc = L.bldp_tstat_host_f32(int(device), a.ctypes.data if a.size else None, a.shape[0],
-                               a.shape[1], a.shape[2], wp, int(tavby), code,
-                               out.ctypes.data if out.size else None)
+    a = _host_fb(a)
+    shape, _ = _window(a, win)
+    out = _host_out(out_shape(shape, win, 1, tavby))
+    h, keep = _host_args(device, a, win)
+    rc = _lib.lib().bldp_tstat_host_f32(*h, int(tavby), code, _np_ptr(out))
     _lib.check(rc, "bldp_tstat_host_f32")
     return out
 
@@ -729,17 +878,13 @@ def quantile(x, n, p, axis=0, win=None, out=None, stream=None):
     Julia-order (nc/n, ni, nt) or (nc, ni, nt/n) Float32 device tensor (``out``
     when given, laid out as ``tstat`` takes it)."""
     p, axis = _quantile_args(p, axis)
-    L = _lib.lib()
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
-    dims = out_shape(shape, win, n if axis == 0 else 1, n if axis == 2 else 1)
-    ptr, nchan, nif, ntime = _abi_dims(x)
+    shape, _ = _window(x, win)
+    dims = out_shape(shape, win, *_axis_factors(n, axis))
+    w, keep = _win_args(x, win)
     if out is None:
         out = fb_empty(*dims, device=x.device)
-    optr, ld_i, ld_t = _tstat_out(out, dims, x.device)
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    rc = L.bldp_quantile_f32(ptr, nchan, nif, ntime, wp, axis, int(n), p, optr, ld_i, ld_t,
-                             _lib.stream_ptr(stream))
+    o = _tstat_out(out, dims, x.device)
+    rc = _lib.lib().bldp_quantile_f32(*w, axis, int(n), p, *o, _lib.stream_ptr(stream))
     _lib.check(rc, "bldp_quantile_f32")
     return out
 
@@ -750,25 +895,9 @@ def quantile_plan(x, n, p, axis=0, win=None) -> dict:
     ``tstat_plan`` on axis 2) with ``rank``, the 0-based lower rank j - 1 (-1 for
     the copy of n <= 1), in place of the workspace bytes."""
     p, axis = _quantile_args(p, axis)
-    L = _lib.lib()
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
-    ptr, nchan, nif, ntime = _abi_dims(x)
-    info = (ctypes.c_int64 * 8)()
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    _lib.check(L.bldp_quantile_plan_f32(ptr, nchan, nif, ntime, wp, axis, int(n), p, None, info),
-               "bldp_quantile_plan_f32")
-    if axis == 0:
-        keys = ["path", "lanes_per_group", "time_split_waves", "float4_per_lane", "time_chunks",
-                "workgroups", "rank", "vec_out"]
-        paths = _lib.PATHS
-    else:
-        keys = ["path", "channels_per_lane", "time_split_lanes", "passes", "workgroups", "rank",
-                "blocks", "channel_lanes"]
-        paths = _lib.TSTAT_PATHS
-    d = dict(zip(keys, [int(v) for v in info]))
-    d["path"] = paths.get(d["path"], "copy")
-    return d
+    _window(x, win)
+    w, keep = _win_args(x, win)
+    return _axis_plan("bldp_quantile_plan_f32", (*w, axis, int(n), p, None), 8, axis, rank=True)
 
 
 def band_quantile(banks, n, p, axis=0, win=None, out=None, stream=None):
@@ -776,14 +905,10 @@ def band_quantile(banks, n, p, axis=0, win=None, out=None, stream=None):
     order in one launch (bldp_band_quantile_f32): a dense Float32 tensor laid out
     as ``band_reduce``'s (axis 0) or ``band_tstat``'s (axis 2)."""
     p, axis = _quantile_args(p, axis)
-    L = _lib.lib()
-    banks, geo, out, ptrs, (keep, wp) = _band_args(banks, n if axis == 0 else 1,
-                                                   n if axis == 2 else 1, win, out)
-    if out.device != banks[0].device:
-        raise ValueError(f"out is on {out.device}, the banks on {banks[0].device}")
-    rc = L.bldp_band_quantile_f32(len(banks), ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp, axis,
-                                  int(n), p, out.data_ptr() if out.numel() else None,
-                                  _lib.stream_ptr(stream))
+    banks, geo, out, ptrs, (keep, wp) = _band_args(banks, *_axis_factors(n, axis), win, out)
+    _band_out_device(out, banks)
+    rc = _lib.lib().bldp_band_quantile_f32(len(banks), ptrs, *geo, wp, axis, int(n), p, _ptr(out),
+                                           _lib.stream_ptr(stream))
     _lib.check(rc, "bldp_band_quantile_f32")
     return out
 
@@ -792,17 +917,11 @@ def quantile_host(a: np.ndarray, n, p, axis=0, win=None, device=0) -> np.ndarray
     """Host Fortran-ordered Float32 array in, dense Float32 host array out
     (bldp_quantile_host_f32: the window's rows staged on ``device``)."""
     p, axis = _quantile_args(p, axis)
-    L = _lib.lib()
-    a = np.asarray(a)
-    if a.dtype != np.float32 or not a.flags.f_contiguous or a.ndim != 3:
-        raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
-    _check_bounds(win, a.shape)
-    dims = out_shape(a.shape, win, n if axis == 0 else 1, n if axis == 2 else 1)
-    out = np.empty(dims, dtype=np.float32, order="F")
-    keep, wp = _lib.win_arg(_full_win(win, a.shape))
-    rc = L.bldp_quantile_host_f32(int(device), a.ctypes.data if a.size else None, a.shape[0],
-                                  a.shape[1], a.shape[2], wp, axis, int(n), p,
-                                  out.ctypes.data if out.size else None)
+    a = _host_fb(a)
+    shape, _ = _window(a, win)
+    out = _host_out(out_shape(shape, win, *_axis_factors(n, axis)))
+    h, keep = _host_args(device, a, win)
+    rc = _lib.lib().bldp_quantile_host_f32(*h, axis, int(n), p, _np_ptr(out))
     _lib.check(rc, "bldp_quantile_host_f32")
     return out
 
@@ -839,18 +958,12 @@ def _planes_out(out, dims, K, device):
     Float32 (\\*dims, K) tensor on ``device`` whose planes are laid out as
     ``_tstat_out`` takes a product and do not overlap; returns (pointer, out_ld_i,
     out_ld_t, out_ld_q)."""
-    torch = _torch()
-    if not isinstance(out, torch.Tensor):
+    if not isinstance(out, _torch().Tensor):
         raise TypeError("out must be a device tensor")
     if out.dim() != 4 or tuple(out.shape) != (*dims, K):
         raise ValueError(f"out is {tuple(out.shape)}, expected {(*dims, K)}")
     optr, ld_i, ld_t = _tstat_out(out[..., 0], dims, device)
-    nc, ni, nt = dims
-    extent = max(nt - 1, 0) * ld_t + max(ni - 1, 0) * ld_i + nc
-    ld_q = out.stride(3) if K > 1 else extent
-    if ld_q < extent:
-        raise ValueError(f"out strides {out.stride()}: the planes overlap")
-    return optr, ld_i, ld_t, ld_q
+    return optr, ld_i, ld_t, _plane_ld(out, dims, K, ld_i, ld_t)
 
 
 def quantiles(x, n, ps, axis=0, win=None, out=None, stream=None):
@@ -862,19 +975,16 @@ def quantiles(x, n, ps, axis=0, win=None, out=None, stream=None):
     ni, nt/n, K) Float32 device tensor laid out plane after plane
     (``planes_empty``; ``out`` when given)."""
     ps, axis = _quantiles_args(ps, axis)
-    L = _lib.lib()
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
-    dims = out_shape(shape, win, n if axis == 0 else 1, n if axis == 2 else 1)
-    ptr, nchan, nif, ntime = _abi_dims(x)
+    shape, _ = _window(x, win)
+    dims = out_shape(shape, win, *_axis_factors(n, axis))
+    w, keep = _win_args(x, win)
     if out is None:
         out = planes_empty(*dims, len(ps), device=x.device)
     optr, ld_i, ld_t, ld_q = _planes_out(out, dims, len(ps), x.device)
-    keep, wp = _lib.win_arg(_full_win(win, shape))
     for k0, arr in _p_batches(ps):
-        rc = L.bldp_quantiles_f32(ptr, nchan, nif, ntime, wp, axis, int(n), len(arr), arr,
-                                  optr + 4 * k0 * ld_q if optr else None, ld_i, ld_t, ld_q,
-                                  _lib.stream_ptr(stream))
+        rc = _lib.lib().bldp_quantiles_f32(*w, axis, int(n), len(arr), arr,
+                                           optr + 4 * k0 * ld_q if optr else None, ld_i, ld_t,
+                                           ld_q, _lib.stream_ptr(stream))
         _lib.check(rc, "bldp_quantiles_f32")
     return out
 
@@ -887,26 +997,11 @@ def quantiles_plan(x, n, ps, axis=0, win=None) -> dict:
     channel lanes) plus ``ranks``, the count of distinct ranks selected (0 for the
     copy of n <= 1), and ``reads``, how often the block is read."""
     ps, axis = _quantiles_args(ps, axis)
-    L = _lib.lib()
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
-    ptr, nchan, nif, ntime = _abi_dims(x)
-    info = (ctypes.c_int64 * 10)()
-    keep, wp = _lib.win_arg(_full_win(win, shape))
+    _window(x, win)
+    w, keep = _win_args(x, win)
     arr = (ctypes.c_double * len(ps))(*ps)
-    _lib.check(L.bldp_quantiles_plan_f32(ptr, nchan, nif, ntime, wp, axis, int(n), len(ps), arr,
-                                         None, info), "bldp_quantiles_plan_f32")
-    if axis == 0:
-        keys = ["path", "lanes_per_group", "time_split_waves", "float4_per_lane", "time_chunks",
-                "workgroups", "workspace_bytes", "vec_out", "ranks", "reads"]
-        paths = _lib.PATHS
-    else:
-        keys = ["path", "channels_per_lane", "time_split_lanes", "passes", "workgroups",
-                "workspace_bytes", "blocks", "channel_lanes", "ranks", "reads"]
-        paths = _lib.TSTAT_PATHS
-    d = dict(zip(keys, [int(v) for v in info]))
-    d["path"] = paths.get(d["path"], "copy")
-    return d
+    return _axis_plan("bldp_quantiles_plan_f32", (*w, axis, int(n), len(ps), arr, None), 10, axis,
+                      ("ranks", "reads"))
 
 
 def band_quantiles(banks, n, ps, axis=0, win=None, out=None, stream=None):
@@ -915,15 +1010,12 @@ def band_quantiles(banks, n, ps, axis=0, win=None, out=None, stream=None):
     probabilities): a dense (nbank*nc', ni, nt', K) Float32 tensor whose plane k
     is ``band_quantile(banks, n, ps[k], axis, win)``."""
     ps, axis = _quantiles_args(ps, axis)
-    L = _lib.lib()
     K = len(ps)
-    banks = list(banks)
-    if not banks:
-        raise ValueError("no banks")
-    fq, tv = (n, 1) if axis == 0 else (1, n)
+    banks = _banks(banks, agree=False)[0]
+    fq, tv = _axis_factors(n, axis)
     if out is None:
-        _check_bounds(win, tuple(banks[0].shape))
-        nco, ni, nto = out_shape(tuple(banks[0].shape), win, fq, tv)
+        shape, _ = _window(banks[0], win)
+        nco, ni, nto = out_shape(shape, win, fq, tv)
         out = planes_empty(len(banks) * nco, ni, nto, K, device=banks[0].device)
     elif out.dim() != 4 or out.shape[3] != K:
         raise ValueError(f"out is {tuple(out.shape)}, expected {K} planes on a fourth axis")
@@ -932,13 +1024,12 @@ def band_quantiles(banks, n, ps, axis=0, win=None, out=None, stream=None):
     plane = first.numel()
     if K > 1 and plane and out.stride(3) != plane:
         raise ValueError("out must be dense: plane k at k * nbank*nco*ni*nto elements")
-    if out.device != banks[0].device:
-        raise ValueError(f"out is on {out.device}, the banks on {banks[0].device}")
+    _band_out_device(out, banks)
     for k0, arr in _p_batches(ps):
-        rc = L.bldp_band_quantiles_f32(len(banks), ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp,
-                                       axis, int(n), len(arr), arr,
-                                       out.data_ptr() + 4 * k0 * plane if plane else None,
-                                       _lib.stream_ptr(stream))
+        rc = _lib.lib().bldp_band_quantiles_f32(len(banks), ptrs, *geo, wp, axis, int(n), len(arr),
+                                                arr,
+                                                out.data_ptr() + 4 * k0 * plane if plane else None,
+                                                _lib.stream_ptr(stream))
         _lib.check(rc, "bldp_band_quantiles_f32")
     return out
 
@@ -948,19 +1039,16 @@ def quantiles_host(a: np.ndarray, n, ps, axis=0, win=None, device=0) -> np.ndarr
     array out (bldp_quantiles_host_f32: the window's rows staged on ``device``,
     once per <= ``_lib.MAX_QUANTILES`` probabilities)."""
     ps, axis = _quantiles_args(ps, axis)
-    L = _lib.lib()
-    a = np.asarray(a)
-    if a.dtype != np.float32 or not a.flags.f_contiguous or a.ndim != 3:
-        raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
-    _check_bounds(win, a.shape)
-    dims = out_shape(a.shape, win, n if axis == 0 else 1, n if axis == 2 else 1)
-    out = np.empty((*dims, len(ps)), dtype=np.float32, order="F")
-    keep, wp = _lib.win_arg(_full_win(win, a.shape))
+    a = _host_fb(a)
+    shape, _ = _window(a, win)
+    dims = out_shape(shape, win, *_axis_factors(n, axis))
+    out = _host_out((*dims, len(ps)))
+    h, keep = _host_args(device, a, win)
     plane = dims[0] * dims[1] * dims[2]
     for k0, arr in _p_batches(ps):
-        rc = L.bldp_quantiles_host_f32(int(device), a.ctypes.data if a.size else None, a.shape[0],
-                                       a.shape[1], a.shape[2], wp, axis, int(n), len(arr), arr,
-                                       out.ctypes.data + 4 * k0 * plane if out.size else None)
+        rc = _lib.lib().bldp_quantiles_host_f32(*h, axis, int(n), len(arr), arr,
+                                                out.ctypes.data + 4 * k0 * plane if out.size
+                                                else None)
         _lib.check(rc, "bldp_quantiles_host_f32")
     return out
 
@@ -1005,8 +1093,20 @@ def _outliers_n(n, axis, nc, nt):
     return n
 
 
-def _ptr(t):
-    return t.data_ptr() if t is not None and t.numel() else None
+def _outliers_outs(want, mask, dims, mdims, empty):
+    """The outputs of an outliers call from ``empty(dims, dtype name)``: (the dict
+    to return, the four in the ABI's order with None for those not asked for)."""
+    outs = [empty(dims, dt) if w else None for w, dt in zip(want, ("float32", "float32", "int32"))]
+    outs.append(empty(mdims, "uint8") if mask else None)
+    res = {k: o for k, o in zip(OUTLIER_PLANES + ("mask",), outs) if o is not None}
+    if not res:
+        raise ValueError("outliers: no output asked for (which is empty and mask is False)")
+    return res, outs
+
+
+def _dev_empty(device):
+    torch = _torch()
+    return lambda dims, dt: fb_empty(*dims, device=device, dtype=getattr(torch, dt))
 
 
 def outliers(x, n, axis=2, nsigma=5.0, win=None, mask=False, which=OUTLIER_PLANES, stream=None):
@@ -1020,27 +1120,16 @@ def outliers(x, n, axis=2, nsigma=5.0, win=None, mask=False, which=OUTLIER_PLANE
     ``"median"`` and ``"mad"`` statistics give), ``"count"`` (int32) for the names
     in ``which``, each (nc/n, ni, nt) or (nc, ni, nt/n), and with ``mask=True``
     ``"mask"``, the uint8 (nc, ni, nt) flags of the window.  Float32 tensors only."""
-    torch = _torch()
     axis, ns, want = _outliers_args(axis, nsigma, which)
-    if x.dtype != torch.float32:
+    if x.dtype != _torch().float32:
         _need_f32("outliers", x.dtype, "outliers")
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
-    nc, ni, nt = window_shape(win, shape)
+    shape, (nc, ni, nt) = _window(x, win)
     n = _outliers_n(n, axis, nc, nt)
-    dims = out_shape(shape, win, n if axis == 0 else 1, n if axis == 2 else 1)
-    ptr, nchan, nif, ntime = _abi_dims(x)
-    dts = (torch.float32, torch.float32, torch.int32)
-    outs = [fb_empty(*dims, device=x.device, dtype=dt) if w else None for w, dt in zip(want, dts)]
-    m = fb_empty(nc, ni, nt, device=x.device, dtype=torch.uint8) if mask else None
-    res = {k: o for k, o in zip(OUTLIER_PLANES, outs) if o is not None}
-    if m is not None:
-        res["mask"] = m
-    if not res:
-        raise ValueError("outliers: no output asked for (which is empty and mask is False)")
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    rc = _lib.lib().bldp_outliers_f32(ptr, nchan, nif, ntime, wp, axis, n, ns, *map(_ptr, outs),
-                                      _ptr(m), dims[0], dims[0] * dims[1], _lib.stream_ptr(stream))
+    dims = out_shape(shape, win, *_axis_factors(n, axis))
+    w, keep = _win_args(x, win)
+    res, outs = _outliers_outs(want, mask, dims, (nc, ni, nt), _dev_empty(x.device))
+    rc = _lib.lib().bldp_outliers_f32(*w, axis, n, ns, *map(_ptr, outs), dims[0],
+                                      dims[0] * dims[1], _lib.stream_ptr(stream))
     _lib.check(rc, "bldp_outliers_f32")
     return res
 
@@ -1051,27 +1140,11 @@ def outliers_plan(x, n, axis=2, win=None, mask=False) -> dict:
     ``plan`` on axis 0, of ``tstat_plan`` on axis 2) plus ``reads``, how often the
     block is read, and ``mask`` (1 when one is written)."""
     axis, _, _ = _outliers_args(axis, 0.0, ())
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
-    nc, ni, nt = window_shape(win, shape)
+    _, (nc, ni, nt) = _window(x, win)
     n = _outliers_n(n, axis, nc, nt)
-    ptr, nchan, nif, ntime = _abi_dims(x)
-    info = (ctypes.c_int64 * 10)()
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    _lib.check(_lib.lib().bldp_outliers_plan_f32(ptr, nchan, nif, ntime, wp, axis, n,
-                                                 1 if mask else 0, info),
-               "bldp_outliers_plan_f32")
-    if axis == 0:
-        keys = ["path", "lanes_per_group", "time_split_waves", "float4_per_lane", "time_chunks",
-                "workgroups", "workspace_bytes", "vec_out", "reads", "mask"]
-        paths = _lib.PATHS
-    else:
-        keys = ["path", "channels_per_lane", "time_split_lanes", "passes", "workgroups",
-                "workspace_bytes", "blocks", "channel_lanes", "reads", "mask"]
-        paths = _lib.TSTAT_PATHS
-    d = dict(zip(keys, [int(v) for v in info]))
-    d["path"] = paths.get(d["path"], "copy")
-    return d
+    w, keep = _win_args(x, win)
+    return _axis_plan("bldp_outliers_plan_f32", (*w, axis, n, 1 if mask else 0), 10, axis,
+                      ("reads", "mask"))
 
 
 def band_outliers(banks, n, axis=2, nsigma=5.0, win=None, mask=False, which=OUTLIER_PLANES,
@@ -1080,33 +1153,15 @@ def band_outliers(banks, n, axis=2, nsigma=5.0, win=None, mask=False, which=OUTL
     order in one launch (bldp_band_outliers_f32): the dict of ``outliers`` with
     dense (nbank*nc', ni, nt') planes and a (nbank*nc, ni, nt) mask, the vcat of
     the banks' results."""
-    torch = _torch()
     axis, ns, want = _outliers_args(axis, nsigma, which)
-    banks = list(banks)
-    if not banks:
-        raise ValueError("no banks")
-    for b in banks:
-        if b.dtype != torch.float32:
-            _need_f32("band_outliers", b.dtype, "outliers")
-    shape = tuple(banks[0].shape)
-    _check_bounds(win, shape)
-    nc, ni, nt = window_shape(win, shape)
+    banks = _banks(banks, "band_outliers", "outliers", agree=False)[0]
+    _, (nc, ni, nt) = _window(banks[0], win)
     n = _outliers_n(n, axis, nc, nt)
-    fq, tv = (n, 1) if axis == 0 else (1, n)
-    banks, geo, first, ptrs, (keep, wp) = _band_args(banks, fq, tv, win, None)
+    banks, geo, first, ptrs, (keep, wp) = _band_args(banks, *_axis_factors(n, axis), win, None)
     nb = len(banks)
-    dims = tuple(first.shape)
-    dts = (torch.float32, torch.float32, torch.int32)
-    outs = [fb_empty(*dims, device=first.device, dtype=dt) if w else None
-            for w, dt in zip(want, dts)]
-    m = fb_empty(nb * nc, ni, nt, device=first.device, dtype=torch.uint8) if mask else None
-    res = {k: o for k, o in zip(OUTLIER_PLANES, outs) if o is not None}
-    if m is not None:
-        res["mask"] = m
-    if not res:
-        raise ValueError("outliers: no output asked for (which is empty and mask is False)")
-    rc = _lib.lib().bldp_band_outliers_f32(nb, ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp, axis,
-                                           n, ns, *map(_ptr, outs), _ptr(m),
+    res, outs = _outliers_outs(want, mask, tuple(first.shape), (nb * nc, ni, nt),
+                               _dev_empty(first.device))
+    rc = _lib.lib().bldp_band_outliers_f32(nb, ptrs, *geo, wp, axis, n, ns, *map(_ptr, outs),
                                            _lib.stream_ptr(stream))
     _lib.check(rc, "bldp_band_outliers_f32")
     return res
@@ -1118,27 +1173,13 @@ def outliers_host(a: np.ndarray, n, axis=2, nsigma=5.0, win=None, mask=False,
     Fortran-ordered host arrays out (bldp_outliers_host_f32: the window's rows
     staged on ``device`` once).  Float32 arrays only."""
     axis, ns, want = _outliers_args(axis, nsigma, which)
-    a = np.asarray(a)
-    if a.dtype != np.float32:
-        _need_f32("outliers_host", a.dtype, "outliers")
-    if not a.flags.f_contiguous or a.ndim != 3:
-        raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
-    _check_bounds(win, a.shape)
-    nc, ni, nt = window_shape(win, a.shape)
+    a = _host_fb(a, "outliers_host", "outliers")
+    shape, (nc, ni, nt) = _window(a, win)
     n = _outliers_n(n, axis, nc, nt)
-    dims = out_shape(a.shape, win, n if axis == 0 else 1, n if axis == 2 else 1)
-    dts = (np.float32, np.float32, np.int32)
-    outs = [np.empty(dims, dtype=dt, order="F") if w else None for w, dt in zip(want, dts)]
-    m = np.empty((nc, ni, nt), dtype=np.uint8, order="F") if mask else None
-    res = {k: o for k, o in zip(OUTLIER_PLANES, outs) if o is not None}
-    if m is not None:
-        res["mask"] = m
-    if not res:
-        raise ValueError("outliers: no output asked for (which is empty and mask is False)")
-    keep, wp = _lib.win_arg(_full_win(win, a.shape))
-    hp = [o.ctypes.data if o is not None and o.size else None for o in outs + [m]]
-    rc = _lib.lib().bldp_outliers_host_f32(int(device), a.ctypes.data if a.size else None,
-                                           a.shape[0], a.shape[1], a.shape[2], wp, axis, n, ns, *hp)
+    dims = out_shape(shape, win, *_axis_factors(n, axis))
+    res, outs = _outliers_outs(want, mask, dims, (nc, ni, nt), _host_out)
+    h, keep = _host_args(device, a, win)
+    rc = _lib.lib().bldp_outliers_host_f32(*h, axis, n, ns, *map(_np_ptr, outs))
     _lib.check(rc, "bldp_outliers_host_f32")
     return res
 
@@ -1158,7 +1199,6 @@ def _argext_out(out, dims, device, values):
     (the ABI takes one pair of strides).  Returns (idx, val or None, idx
     pointer, val pointer, out_ld_i, out_ld_t)."""
     torch = _torch()
-    nco, ni, nto = dims
     if out is None:
         idx = fb_empty(*dims, device=device, dtype=torch.int32)
         val = fb_empty(*dims, device=device) if values else None
@@ -1168,31 +1208,14 @@ def _argext_out(out, dims, device, values):
         idx, val = out
     else:
         idx, val = out, None
-    lds = []
-    for t, dt, name in ((idx, torch.int32, "idx"), (val, torch.float32, "val")):
-        if t is None:
-            continue
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name} must be a device tensor")
-        if t.dtype != dt:
-            raise TypeError(f"{name} must be {dt}, not {t.dtype}")
-        if tuple(t.shape) != (nco, ni, nto):
-            raise ValueError(f"{name} is {tuple(t.shape)}, expected {(nco, ni, nto)}")
-        if t.device != torch.device(device):
-            raise ValueError(f"{name} is on {t.device}, the data on {device}")
-        s0, s1, s2 = t.stride()
-        ld_i = s1 if ni > 1 else nco
-        ld_t = s2 if nto > 1 else max(ni - 1, 0) * ld_i + nco
-        if (nco > 1 and s0 != 1) or ld_i < nco or ld_t < (ni - 1) * ld_i + nco:
-            raise ValueError(f"{name} strides {t.stride()} are not a Julia-order "
-                             f"(channel-fastest) layout of {(nco, ni, nto)}")
-        lds.append((ld_i, ld_t))
-    if len(lds) == 2 and lds[0] != lds[1]:
-        raise ValueError(f"idx and val must share one layout, not strides {idx.stride()} and "
-                         f"{val.stride()}")
-    n = nco * ni * nto
-    return (idx, val, idx.data_ptr() if n else None,
-            val.data_ptr() if (n and val is not None) else None, lds[0][0], lds[0][1])
+    iptr, *ld = _out_layout(idx, dims, device, torch.int32, "idx")
+    vptr = None
+    if val is not None:
+        vptr, *vld = _out_layout(val, dims, device, torch.float32, "val")
+        if vld != ld:
+            raise ValueError(f"idx and val must share one layout, not strides {idx.stride()} and "
+                             f"{val.stride()}")
+    return idx, val, iptr, vptr, ld[0], ld[1]
 
 
 def argext(x, fqavby, tavby, op, win=None, values=False, out=None, stream=None):
@@ -1206,16 +1229,13 @@ def argext(x, fqavby, tavby, op, win=None, values=False, out=None, stream=None):
     (idx, val), val holding the winners' bits (Float32).  ``out``: the idx
     tensor (the pair with ``values``) to write, e.g. a bank's slot of a
     stitched product."""
-    L = _lib.lib()
     code = _argext_op(op)
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
+    shape, _ = _window(x, win)
     dims = out_shape(shape, win, fqavby, tavby)
-    ptr, nchan, nif, ntime = _abi_dims(x)
+    w, keep = _win_args(x, win)
     idx, val, iptr, vptr, ld_i, ld_t = _argext_out(out, dims, x.device, values)
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    rc = L.bldp_argext_f32(ptr, nchan, nif, ntime, wp, int(fqavby), int(tavby), code, iptr, vptr,
-                           ld_i, ld_t, _lib.stream_ptr(stream))
+    rc = _lib.lib().bldp_argext_f32(*w, int(fqavby), int(tavby), code, iptr, vptr, ld_i, ld_t,
+                                    _lib.stream_ptr(stream))
     _lib.check(rc, "bldp_argext_f32")
     return (idx, val) if values else idx
 
@@ -1226,20 +1246,11 @@ def argext_plan(x, fqavby, tavby, op, win=None) -> dict:
     block (256: a workgroup), the time slices of a workgroup splitting a
     block's rows, float4 loads per lane per row, workgroups, workspace bytes,
     outputs and whether the loads are float4."""
-    L = _lib.lib()
     code = _argext_op(op)
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
-    ptr, nchan, nif, ntime = _abi_dims(x)
-    info = (ctypes.c_int64 * 8)()
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    _lib.check(L.bldp_argext_plan_f32(ptr, nchan, nif, ntime, wp, int(fqavby), int(tavby), code,
-                                      None, info), "bldp_argext_plan_f32")
-    keys = ["path", "lanes_per_block", "time_slices", "float4_per_lane", "workgroups",
-            "workspace_bytes", "outputs", "vector_loads"]
-    d = dict(zip(keys, [int(v) for v in info]))
-    d["path"] = _lib.ARGEXT_PATHS[d["path"]]
-    return d
+    _window(x, win)
+    w, keep = _win_args(x, win)
+    return _plan_dict("bldp_argext_plan_f32", (*w, int(fqavby), int(tavby), code, None), 8,
+                      ARGEXT_PLAN_KEYS, path=_lib.ARGEXT_PATHS)
 
 
 def band_argext(banks, fqavby, tavby, op, win=None, values=False, stream=None):
@@ -1247,29 +1258,16 @@ def band_argext(banks, fqavby, tavby, op, win=None, values=False, stream=None):
     (bldp_band_argext_f32): dense (nbank*nco, ni, nto) tensors, the vcat of the
     per-bank results (offsets are relative to each block, so stitching is
     concatenation)."""
-    L = _lib.lib()
     code = _argext_op(op)
     torch = _torch()
-    banks = list(banks)
-    if not banks:
-        raise ValueError("no banks")
-    shape = tuple(banks[0].shape)
-    geo = _abi_dims(banks[0])[1:]
-    for b in banks:
-        if tuple(b.shape) != shape or _abi_dims(b)[1:] != geo or b.device != banks[0].device:
-            raise ValueError("all banks of a band must have the same shape, layout and device")
-    _check_bounds(win, shape)
+    banks, nb, ptrs, geo = _banks(banks, devices=True)
+    shape, _ = _window(banks[0], win)
     nco, ni, nto = out_shape(shape, win, fqavby, tavby)
-    nb = len(banks)
     idx = fb_empty(nb * nco, ni, nto, device=banks[0].device, dtype=torch.int32)
     val = fb_empty(nb * nco, ni, nto, device=banks[0].device) if values else None
-    ptrs = (ctypes.c_void_p * nb)(*[b.data_ptr() for b in banks])
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    n = idx.numel()
-    rc = L.bldp_band_argext_f32(nb, ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp, int(fqavby),
-                                int(tavby), code, idx.data_ptr() if n else None,
-                                val.data_ptr() if (n and values) else None,
-                                _lib.stream_ptr(stream))
+    keep, wp = _win_ptr(win, shape)
+    rc = _lib.lib().bldp_band_argext_f32(nb, ptrs, *geo, wp, int(fqavby), int(tavby), code,
+                                         _ptr(idx), _ptr(val), _lib.stream_ptr(stream))
     _lib.check(rc, "bldp_band_argext_f32")
     return (idx, val) if values else idx
 
@@ -1278,22 +1276,16 @@ def argext_host(a: np.ndarray, fqavby, tavby, op, win=None, values=False, device
     """Host Fortran-ordered Float32 array in, (nco, ni, nto) int32 host array of
     offsets out, with ``values`` the pair (idx, val)
     (bldp_argext_host_f32: the window's rows staged on ``device``)."""
-    L = _lib.lib()
     code = _argext_op(op)
-    a = np.asarray(a)
-    if a.dtype != np.float32 or not a.flags.f_contiguous or a.ndim != 3:
-        raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
-    _check_bounds(win, a.shape)
-    dims = out_shape(a.shape, win, fqavby, tavby)
-    idx = np.empty(dims, dtype=np.uint32, order="F")
-    val = np.empty(dims, dtype=np.float32, order="F") if values else None
-    keep, wp = _lib.win_arg(_full_win(win, a.shape))
-    rc = L.bldp_argext_host_f32(int(device), a.ctypes.data if a.size else None, a.shape[0],
-                                a.shape[1], a.shape[2], wp, int(fqavby), int(tavby), code,
-                                idx.ctypes.data if idx.size else None,
-                                val.ctypes.data if (values and val.size) else None)
+    a = _host_fb(a)
+    shape, _ = _window(a, win)
+    dims = out_shape(shape, win, fqavby, tavby)
+    idx = _host_out(dims, np.int32)
+    val = _host_out(dims) if values else None
+    h, keep = _host_args(device, a, win)
+    rc = _lib.lib().bldp_argext_host_f32(*h, int(fqavby), int(tavby), code, _np_ptr(idx),
+                                         _np_ptr(val))
     _lib.check(rc, "bldp_argext_host_f32")
-    idx = idx.view(np.int32)  # offsets are < 2^31
     return (idx, val) if values else idx
 
 
@@ -1339,7 +1331,30 @@ def _mask_arg(mask, wshape, device, what):
                         f"host arrays)")
     if mask.device != torch.device(device):
         raise ValueError(f"{what}: the mask is on {mask.device}, the data on {device}")
-    return (mask.data_ptr() if mask.numel() else None), (ctypes.c_int64 * 3)(*ld)
+    return _ptr(mask), (ctypes.c_int64 * 3)(*ld)
+
+
+def _host_mask(mask, what):
+    """A host mask: a uint8 or bool array (TypeError); one with a negative stride
+    is copied to Fortran order.  ``_host_mask_arg`` gives what the ABI takes."""
+    m = np.asarray(mask)
+    if m.dtype not in (np.dtype(np.uint8), np.dtype(np.bool_)):
+        raise TypeError(f"{what}: the mask must be a uint8 or bool array, not {m.dtype}")
+    if m.ndim == 3 and any(s < 0 for s in m.strides):
+        m = np.asfortranarray(m)
+    return m
+
+
+def _host_mask_arg(m, wshape, what):
+    """(pointer, mask_ld array) of a ``_host_mask`` that broadcasts to ``wshape``."""
+    return _np_ptr(m), (ctypes.c_int64 * 3)(*_mask_strides(m.shape, m.strides, wshape, what))
+
+
+def _data_kept(dims, device, data=None):
+    """The result of a masked reduce or a fold: Float32 ``"data"`` and the int32
+    weights ``"kept"``, Julia-order device tensors of ``dims``."""
+    return {"data": fb_empty(*dims, device=device) if data is None else data,
+            "kept": fb_empty(*dims, device=device, dtype=_torch().int32)}
 
 
 def masked_reduce(x, mask, fqavby=1, tavby=1, op="sum", win=None, stream=None):
@@ -1354,24 +1369,19 @@ def masked_reduce(x, mask, fqavby=1, tavby=1, op="sum", win=None, stream=None):
     (nc/F, ni, nt/T) device tensors: ``"data"`` (Float32; 0.0 for the sum and NaN
     for the mean of a block with nothing kept) and ``"kept"`` (int32), the weight
     of each product."""
-    torch = _torch()
     code = _masked_op(op)
-    if x.dtype != torch.float32:
+    if x.dtype != _torch().float32:
         _need_f32("masked_reduce", x.dtype, "masked_reduce")
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
-    wshape = window_shape(win, shape)
+    shape, wshape = _window(x, win)
     mptr, ld = _mask_arg(mask, wshape, x.device, "masked_reduce")
     dims = out_shape(shape, win, fqavby, tavby)
-    ptr, nchan, nif, ntime = _abi_dims(x)
-    data = fb_empty(*dims, device=x.device)
-    kept = fb_empty(*dims, device=x.device, dtype=torch.int32)
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    rc = _lib.lib().bldp_masked_reduce_f32(ptr, nchan, nif, ntime, wp, int(fqavby), int(tavby),
-                                           code, mptr, ld, _ptr(data), _ptr(kept), dims[0],
+    w, keep = _win_args(x, win)
+    res = _data_kept(dims, x.device)
+    rc = _lib.lib().bldp_masked_reduce_f32(*w, int(fqavby), int(tavby), code, mptr, ld,
+                                           _ptr(res["data"]), _ptr(res["kept"]), dims[0],
                                            dims[0] * dims[1], _lib.stream_ptr(stream))
     _lib.check(rc, "bldp_masked_reduce_f32")
-    return {"data": data, "kept": kept}
+    return res
 
 
 def masked_reduce_plan(x, mask, fqavby=1, tavby=1, win=None) -> dict:
@@ -1379,22 +1389,12 @@ def masked_reduce_plan(x, mask, fqavby=1, tavby=1, win=None) -> dict:
     (bldp_masked_reduce_plan_f32): the keys of ``argext_plan`` (the walk is
     argext's) and ``mask_loads``, how the flags are read (_lib.MASK_LOADS:
     "byte" per element, one "dword" per float4, one byte per "row")."""
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
-    wshape = window_shape(win, shape)
+    _, wshape = _window(x, win)
     mptr, ld = _mask_arg(mask, wshape, x.device, "masked_reduce_plan")
-    ptr, nchan, nif, ntime = _abi_dims(x)
-    info = (ctypes.c_int64 * 10)()
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    _lib.check(_lib.lib().bldp_masked_reduce_plan_f32(ptr, nchan, nif, ntime, wp, int(fqavby),
-                                                      int(tavby), mptr, ld, info),
-               "bldp_masked_reduce_plan_f32")
-    keys = ["path", "lanes_per_block", "time_slices", "float4_per_lane", "workgroups",
-            "workspace_bytes", "outputs", "vector_loads", "mask_loads"]
-    d = dict(zip(keys, [int(v) for v in info]))
-    d["path"] = _lib.ARGEXT_PATHS[d["path"]]
-    d["mask_loads"] = _lib.MASK_LOADS[d["mask_loads"]]
-    return d
+    w, keep = _win_args(x, win)
+    return _plan_dict("bldp_masked_reduce_plan_f32", (*w, int(fqavby), int(tavby), mptr, ld), 10,
+                      ARGEXT_PLAN_KEYS + ("mask_loads",), path=_lib.ARGEXT_PATHS,
+                      mask_loads=_lib.MASK_LOADS)
 
 
 def band_masked_reduce(banks, mask, fqavby=1, tavby=1, op="sum", win=None, stream=None):
@@ -1404,26 +1404,17 @@ def band_masked_reduce(banks, mask, fqavby=1, tavby=1, op="sum", win=None, strea
     covers the stitched window, (nbank*nc, ni, nt) with any axis allowed to be 1:
     bank b's channel c is its channel b*nc + c (``band_outliers``' mask as it
     is)."""
-    torch = _torch()
     code = _masked_op(op)
-    banks = list(banks)
-    if not banks:
-        raise ValueError("no banks")
-    for b in banks:
-        if b.dtype != torch.float32:
-            _need_f32("band_masked_reduce", b.dtype, "masked_reduce")
-    shape = tuple(banks[0].shape)
-    _check_bounds(win, shape)
-    nc, ni, nt = window_shape(win, shape)
-    nb = len(banks)
+    banks, nb, _, _ = _banks(banks, "band_masked_reduce", "masked_reduce", agree=False)
+    _, (nc, ni, nt) = _window(banks[0], win)
     mptr, ld = _mask_arg(mask, (nb * nc, ni, nt), banks[0].device, "band_masked_reduce")
     banks, geo, data, ptrs, (keep, wp) = _band_args(banks, fqavby, tavby, win, None)
-    kept = fb_empty(*data.shape, device=data.device, dtype=torch.int32)
-    rc = _lib.lib().bldp_band_masked_reduce_f32(nb, ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp,
-                                                int(fqavby), int(tavby), code, mptr, ld,
-                                                _ptr(data), _ptr(kept), _lib.stream_ptr(stream))
+    res = _data_kept(tuple(data.shape), data.device, data)
+    rc = _lib.lib().bldp_band_masked_reduce_f32(nb, ptrs, *geo, wp, int(fqavby), int(tavby), code,
+                                                mptr, ld, _ptr(data), _ptr(res["kept"]),
+                                                _lib.stream_ptr(stream))
     _lib.check(rc, "bldp_band_masked_reduce_f32")
-    return {"data": data, "kept": kept}
+    return res
 
 
 def masked_reduce_host(a: np.ndarray, mask: np.ndarray, fqavby=1, tavby=1, op="sum", win=None,
@@ -1433,29 +1424,17 @@ def masked_reduce_host(a: np.ndarray, mask: np.ndarray, fqavby=1, tavby=1, op="s
     Fortran-ordered host arrays out (bldp_masked_reduce_host_f32: the window's
     rows and the mask staged on ``device`` once)."""
     code = _masked_op(op)
-    a = np.asarray(a)
-    if a.dtype != np.float32:
-        _need_f32("masked_reduce_host", a.dtype, "masked_reduce")
-    if not a.flags.f_contiguous or a.ndim != 3:
-        raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
-    m = np.asarray(mask)
-    if m.dtype not in (np.dtype(np.uint8), np.dtype(np.bool_)):
-        raise TypeError(f"masked_reduce_host: the mask must be a uint8 or bool array, not {m.dtype}")
-    _check_bounds(win, a.shape)
-    wshape = window_shape(win, a.shape)
-    if m.ndim == 3 and any(s < 0 for s in m.strides):
-        m = np.asfortranarray(m)
-    ld = (ctypes.c_int64 * 3)(*_mask_strides(m.shape, m.strides, wshape, "masked_reduce_host"))
-    dims = out_shape(a.shape, win, fqavby, tavby)
-    data = np.empty(dims, dtype=np.float32, order="F")
-    kept = np.empty(dims, dtype=np.uint32, order="F")
-    keep, wp = _lib.win_arg(_full_win(win, a.shape))
-    rc = _lib.lib().bldp_masked_reduce_host_f32(
-        int(device), a.ctypes.data if a.size else None, a.shape[0], a.shape[1], a.shape[2], wp,
-        int(fqavby), int(tavby), code, m.ctypes.data if m.size else None, ld,
-        data.ctypes.data if data.size else None, kept.ctypes.data if kept.size else None)
+    a = _host_fb(a, "masked_reduce_host", "masked_reduce")
+    m = _host_mask(mask, "masked_reduce_host")
+    shape, wshape = _window(a, win)
+    mptr, ld = _host_mask_arg(m, wshape, "masked_reduce_host")
+    dims = out_shape(shape, win, fqavby, tavby)
+    res = {"data": _host_out(dims), "kept": _host_out(dims, np.int32)}
+    h, keep = _host_args(device, a, win)
+    rc = _lib.lib().bldp_masked_reduce_host_f32(*h, int(fqavby), int(tavby), code, mptr, ld,
+                                                _np_ptr(res["data"]), _np_ptr(res["kept"]))
     _lib.check(rc, "bldp_masked_reduce_host_f32")
-    return {"data": data, "kept": kept.view(np.int32)}  # counts are < 2^31
+    return res
 
 
 def _hits_cap(maxhits):
@@ -1481,16 +1460,22 @@ def _hits_stream(stream, device):
     return stream
 
 
-def _hits_lists(call, cap, device, stream):
-    """The dict of ``hits`` from ``call(cap, idx, val, total)``, which makes the
-    library call with those device tensors (None: a null pointer) on ``stream``.
-    ``total`` and the lists are made under that stream, and the stream is
-    synchronised before every read of ``total``: torch streams do not wait for
-    one another, so a read on any other stream could come before the scan's
-    store."""
+def _hits_lists(fn, head, cap, device, stream):
+    """The dict of ``hits`` from ``fn(*head, cap, idx, val, total, stream)``, the
+    library call made with those device tensors (None: a null pointer) on
+    ``stream``.  ``total`` and the lists are made under that stream, and the
+    stream is synchronised before every read of ``total``: torch streams do not
+    wait for one another, so a read on any other stream could come before the
+    scan's store."""
     torch = _torch()
     s = _hits_stream(stream, device)
     outer = torch.cuda.current_stream()
+
+    def call(c, idx, val, total):
+        rc = getattr(_lib.lib(), fn)(*head, c, _ptr(idx), _ptr(val), total.data_ptr(),
+                                     _lib.stream_ptr(stream))
+        _lib.check(rc, fn)
+
     with torch.cuda.stream(s):
         total = torch.empty(1, dtype=torch.int64, device=device)
         if cap is None:  # count, then list exactly
@@ -1525,23 +1510,13 @@ def hits(x, mask, maxhits=None, win=None, stream=None):
     counted twice.  Either way ``total`` is read back: the call synchronises
     ``stream`` (default: torch's current stream), on which the launches are
     queued and under which the lists are allocated."""
-    torch = _torch()
     cap = _hits_cap(maxhits)
-    if x.dtype != torch.float32:
+    if x.dtype != _torch().float32:
         _need_f32("hits", x.dtype, "hits")
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
-    wshape = window_shape(win, shape)
+    _, wshape = _window(x, win)
     mptr, ld = _mask_arg(mask, wshape, x.device, "hits")
-    ptr, nchan, nif, ntime = _abi_dims(x)
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-
-    def call(c, idx, val, total):
-        rc = _lib.lib().bldp_hits_f32(ptr, nchan, nif, ntime, wp, mptr, ld, c, _ptr(idx),
-                                      _ptr(val), total.data_ptr(), _lib.stream_ptr(stream))
-        _lib.check(rc, "bldp_hits_f32")
-
-    return _hits_lists(call, cap, x.device, stream)
+    w, keep = _win_args(x, win)
+    return _hits_lists("bldp_hits_f32", (*w, mptr, ld), cap, x.device, stream)
 
 
 HITS_PLAN_KEYS = ("mask_loads", "tile_elems", "tiles", "workspace_bytes", "scan_chunks",
@@ -1556,19 +1531,11 @@ def hits_plan(x, mask, maxhits=None, win=None) -> dict:
     passes of the one scan workgroup) and ``launches`` (2 for ``maxhits=0``, the
     count-only call, else 3)."""
     cap = _hits_cap(maxhits)
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
-    wshape = window_shape(win, shape)
+    _, wshape = _window(x, win)
     mptr, ld = _mask_arg(mask, wshape, x.device, "hits_plan")
-    ptr, nchan, nif, ntime = _abi_dims(x)
-    info = (ctypes.c_int64 * 10)()
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    _lib.check(_lib.lib().bldp_hits_plan_f32(ptr, nchan, nif, ntime, wp, mptr, ld,
-                                             1 if cap is None else cap, info),
-               "bldp_hits_plan_f32")
-    d = dict(zip(HITS_PLAN_KEYS, [int(v) for v in info]))
-    d["mask_loads"] = _lib.HITS_LOADS[d["mask_loads"]]
-    return d
+    w, keep = _win_args(x, win)
+    return _plan_dict("bldp_hits_plan_f32", (*w, mptr, ld, 1 if cap is None else cap), 10,
+                      HITS_PLAN_KEYS, mask_loads=_lib.HITS_LOADS)
 
 
 def band_hits(banks, mask, maxhits=None, win=None, stream=None):
@@ -1577,35 +1544,14 @@ def band_hits(banks, mask, maxhits=None, win=None, stream=None):
     axis allowed to be 1: bank b's channel c is channel b*nc + c of the mask and
     of the linear index (``band_outliers``' mask as it is), so within one (IF,
     time) row all of bank 0 comes before bank 1."""
-    torch = _torch()
     cap = _hits_cap(maxhits)
-    banks = list(banks)
-    if not banks:
-        raise ValueError("no banks")
-    for b in banks:
-        if b.dtype != torch.float32:
-            _need_f32("band_hits", b.dtype, "hits")
-    shape = tuple(banks[0].shape)
-    _check_bounds(win, shape)
-    nc, ni, nt = window_shape(win, shape)
-    nb = len(banks)
+    banks, nb, _, _ = _banks(banks, "band_hits", "hits", agree=False)
+    shape, (nc, ni, nt) = _window(banks[0], win)
     mptr, ld = _mask_arg(mask, (nb * nc, ni, nt), banks[0].device, "band_hits")
-    geo = _abi_dims(banks[0])[1:]
-    for b in banks:
-        if tuple(b.shape) != shape:
-            raise ValueError("all banks of a band must have the same shape")
-        if _abi_dims(b)[1:] != geo:
-            raise ValueError("all banks of a band must have the same layout")
-    ptrs = (ctypes.c_void_p * nb)(*[b.data_ptr() for b in banks])
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-
-    def call(c, idx, val, total):
-        rc = _lib.lib().bldp_band_hits_f32(nb, ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp, mptr,
-                                           ld, c, _ptr(idx), _ptr(val), total.data_ptr(),
-                                           _lib.stream_ptr(stream))
-        _lib.check(rc, "bldp_band_hits_f32")
-
-    return _hits_lists(call, cap, banks[0].device, stream)
+    _, _, ptrs, geo = _banks(banks)
+    keep, wp = _win_ptr(win, shape)
+    return _hits_lists("bldp_band_hits_f32", (nb, ptrs, *geo, wp, mptr, ld), cap,
+                       banks[0].device, stream)
 
 
 def hits_host(a: np.ndarray, mask: np.ndarray, maxhits=None, win=None, device=0) -> dict:
@@ -1614,28 +1560,16 @@ def hits_host(a: np.ndarray, mask: np.ndarray, maxhits=None, win=None, device=0)
     arrays out (bldp_hits_host_f32: the window's rows and the mask staged on
     ``device`` once; the mask is counted twice there)."""
     cap = _hits_cap(maxhits)
-    a = np.asarray(a)
-    if a.dtype != np.float32:
-        _need_f32("hits_host", a.dtype, "hits")
-    if not a.flags.f_contiguous or a.ndim != 3:
-        raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
-    m = np.asarray(mask)
-    if m.dtype not in (np.dtype(np.uint8), np.dtype(np.bool_)):
-        raise TypeError(f"hits_host: the mask must be a uint8 or bool array, not {m.dtype}")
-    _check_bounds(win, a.shape)
-    wshape = window_shape(win, a.shape)
-    if m.ndim == 3 and any(s < 0 for s in m.strides):
-        m = np.asfortranarray(m)
-    ld = (ctypes.c_int64 * 3)(*_mask_strides(m.shape, m.strides, wshape, "hits_host"))
-    keep, wp = _lib.win_arg(_full_win(win, a.shape))
+    a = _host_fb(a, "hits_host", "hits")
+    m = _host_mask(mask, "hits_host")
+    _, wshape = _window(a, win)
+    mptr, ld = _host_mask_arg(m, wshape, "hits_host")
+    h, keep = _host_args(device, a, win)
     total = ctypes.c_uint64(0)
 
     def call(c, idx, val):
-        rc = _lib.lib().bldp_hits_host_f32(
-            int(device), a.ctypes.data if a.size else None, a.shape[0], a.shape[1], a.shape[2],
-            wp, m.ctypes.data if m.size else None, ld, c,
-            idx.ctypes.data if idx is not None and idx.size else None,
-            val.ctypes.data if val is not None and val.size else None, ctypes.byref(total))
+        rc = _lib.lib().bldp_hits_host_f32(*h, mptr, ld, c, _np_ptr(idx), _np_ptr(val),
+                                           ctypes.byref(total))
         _lib.check(rc, "bldp_hits_host_f32")
 
     if cap is None:
@@ -1718,26 +1652,7 @@ def _hist_out(out, dims, K, device):
     (\\*dims, K) tensor on ``device`` whose planes are laid out as ``planes_empty``
     lays them (channels fastest) and do not overlap; returns (pointer, out_ld_i,
     out_ld_t, out_ld_q) (``_planes_out`` for counts)."""
-    torch = _torch()
-    if not isinstance(out, torch.Tensor):
-        raise TypeError("out must be a device tensor")
-    if out.dtype != torch.int32:
-        raise TypeError(f"out must be int32, not {out.dtype}")
-    if out.dim() != 4 or tuple(out.shape) != (*dims, K):
-        raise ValueError(f"out is {tuple(out.shape)}, expected {(*dims, K)}")
-    if out.device != torch.device(device):
-        raise ValueError(f"out is on {out.device}, the data on {device}")
-    nc, ni, nt = dims
-    s0, s1, s2, s3 = out.stride()
-    ld_i = s1 if ni > 1 else nc
-    ld_t = s2 if nt > 1 else max(ni - 1, 0) * ld_i + nc
-    if (nc > 1 and s0 != 1) or ld_i < nc or ld_t < (ni - 1) * ld_i + nc:
-        raise ValueError(f"out strides {out.stride()} are not a Julia-order (channel-fastest) "
-                         f"layout of {(nc, ni, nt)} planes")
-    extent = max(nt - 1, 0) * ld_t + max(ni - 1, 0) * ld_i + nc
-    if s3 < extent:
-        raise ValueError(f"out strides {out.stride()}: the planes overlap")
-    return (out.data_ptr() if out.numel() else None), ld_i, ld_t, s3
+    return _out_layout(out, dims, device, _torch().int32, dtname="int32", planes=K)
 
 
 def hist_empty(nchan, nif, ntime, nplanes, device=None):
@@ -1762,17 +1677,15 @@ def histogram(x, nbins, lo, hi, fqavby=1, tavby=None, win=None, out=None, stream
     B, lo, hi = _hist_args(nbins, lo, hi)
     if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
         _need_f32("histogram", getattr(x, "dtype", type(x).__name__), "histogram")
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
+    shape, _ = _window(x, win)
     fqavby, tavby = _hist_factors(shape, win, fqavby, tavby)
     dims = out_shape(shape, win, fqavby, tavby)
-    ptr, nchan, nif, ntime = _abi_dims(x)
+    w, keep = _win_args(x, win)
     if out is None:
         out = hist_empty(*dims, B + 3, device=x.device)
-    optr, ld_i, ld_t, ld_q = _hist_out(out, dims, B + 3, x.device)
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    rc = _lib.lib().bldp_histogram_f32(ptr, nchan, nif, ntime, wp, int(fqavby), int(tavby), B, lo,
-                                       hi, optr, ld_i, ld_t, ld_q, _lib.stream_ptr(stream))
+    o = _hist_out(out, dims, B + 3, x.device)
+    rc = _lib.lib().bldp_histogram_f32(*w, int(fqavby), int(tavby), B, lo, hi, *o,
+                                       _lib.stream_ptr(stream))
     _lib.check(rc, "bldp_histogram_f32")
     return out
 
@@ -1790,37 +1703,22 @@ def histogram_plan(x, nbins, lo, hi, fqavby=1, tavby=None, win=None) -> dict:
     counters in LDS, ``workspace_bytes`` (0), ``vector_loads`` (1: float4),
     ``channel_lanes`` and ``rows_per_chunk``."""
     B, lo, hi = _hist_args(nbins, lo, hi)
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
+    shape, _ = _window(x, win)
     fqavby, tavby = _hist_factors(shape, win, fqavby, tavby)
     out_shape(shape, win, fqavby, tavby)
-    ptr, nchan, nif, ntime = _abi_dims(x)
-    info = (ctypes.c_int64 * 10)()
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    _lib.check(_lib.lib().bldp_histogram_plan_f32(ptr, nchan, nif, ntime, wp, int(fqavby),
-                                                  int(tavby), B, lo, hi, info),
-               "bldp_histogram_plan_f32")
-    d = dict(zip(HIST_PLAN_KEYS, [int(v) for v in info]))
-    d["path"] = _lib.HIST_PATHS[d["path"]]
-    return d
+    w, keep = _win_args(x, win)
+    return _plan_dict("bldp_histogram_plan_f32", (*w, int(fqavby), int(tavby), B, lo, hi), 10,
+                      HIST_PLAN_KEYS, path=_lib.HIST_PATHS)
 
 
 def band_histogram(banks, nbins, lo, hi, fqavby=1, tavby=None, win=None, out=None, stream=None):
     """``histogram`` of every bank of a band resident on ONE GPU in one launch
     (bldp_band_histogram_f32): a dense int32 (nbank*nco, ni, nto, nbins + 3)
     tensor, the vcat of the per-bank results."""
-    torch = _torch()
     B, lo, hi = _hist_args(nbins, lo, hi)
-    banks = list(banks)
-    if not banks:
-        raise ValueError("no banks")
-    for b in banks:
-        if b.dtype != torch.float32:
-            _need_f32("band_histogram", b.dtype, "histogram")
-    shape = tuple(banks[0].shape)
-    _check_bounds(win, shape)
+    banks = _banks(banks, "band_histogram", "histogram", agree=False)[0]
+    shape, _ = _window(banks[0], win)
     fqavby, tavby = _hist_factors(shape, win, fqavby, tavby)
-    nb = len(banks)
     banks, geo, first, ptrs, (keep, wp) = _band_args(banks, fqavby, tavby, win, None)
     dims = tuple(first.shape)
     if out is None:
@@ -1829,9 +1727,8 @@ def band_histogram(banks, nbins, lo, hi, fqavby=1, tavby=None, win=None, out=Non
     plane = dims[0] * dims[1] * dims[2]
     if plane and (ld_i, ld_t, ld_q) != (dims[0], dims[0] * dims[1], plane):
         raise ValueError("out must be dense: plane q at q * nbank*nco*ni*nto elements")
-    rc = _lib.lib().bldp_band_histogram_f32(nb, ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp,
-                                            int(fqavby), int(tavby), B, lo, hi, optr,
-                                            _lib.stream_ptr(stream))
+    rc = _lib.lib().bldp_band_histogram_f32(len(banks), ptrs, *geo, wp, int(fqavby), int(tavby), B,
+                                            lo, hi, optr, _lib.stream_ptr(stream))
     _lib.check(rc, "bldp_band_histogram_f32")
     return out
 
@@ -1842,21 +1739,14 @@ def histogram_host(a: np.ndarray, nbins, lo, hi, fqavby=1, tavby=None, win=None,
     nt/T, nbins + 3) host array out (bldp_histogram_host_f32: the window's rows
     staged on ``device`` once)."""
     B, lo, hi = _hist_args(nbins, lo, hi)
-    a = np.asarray(a)
-    if a.dtype != np.float32:
-        _need_f32("histogram_host", a.dtype, "histogram")
-    if not a.flags.f_contiguous or a.ndim != 3:
-        raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
-    _check_bounds(win, a.shape)
-    fqavby, tavby = _hist_factors(a.shape, win, fqavby, tavby)
-    dims = out_shape(a.shape, win, fqavby, tavby)
-    out = np.empty((*dims, B + 3), dtype=np.uint32, order="F")
-    keep, wp = _lib.win_arg(_full_win(win, a.shape))
-    rc = _lib.lib().bldp_histogram_host_f32(
-        int(device), a.ctypes.data if a.size else None, a.shape[0], a.shape[1], a.shape[2], wp,
-        int(fqavby), int(tavby), B, lo, hi, out.ctypes.data if out.size else None)
+    a = _host_fb(a, "histogram_host", "histogram")
+    shape, _ = _window(a, win)
+    fqavby, tavby = _hist_factors(shape, win, fqavby, tavby)
+    out = _host_out((*out_shape(shape, win, fqavby, tavby), B + 3), np.int32)
+    h, keep = _host_args(device, a, win)
+    rc = _lib.lib().bldp_histogram_host_f32(*h, int(fqavby), int(tavby), B, lo, hi, _np_ptr(out))
     _lib.check(rc, "bldp_histogram_host_f32")
-    return out.view(np.int32)  # counts are < 2^31
+    return out
 
 
 FOLD_PLAN_KEYS = ("path", "channel_lanes", "chunks_per_block", "workgroups", "workspace_bytes",
@@ -1911,18 +1801,16 @@ def fold(x, nfpc, tavby=None, op="mean", mask=None, win=None, stream=None):
     code = _masked_op(op)
     if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
         _need_f32("fold", getattr(x, "dtype", type(x).__name__), "fold")
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
+    shape, wshape = _window(x, win)
     nfpc, T, dims = _fold_factors(shape, win, nfpc, tavby)
-    mptr, ld = _fold_mask(mask, window_shape(win, shape), x.device, "fold")
-    ptr, nchan, nif, ntime = _abi_dims(x)
-    data = fb_empty(*dims, device=x.device)
-    kept = fb_empty(*dims, device=x.device, dtype=torch.int32)
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    rc = _lib.lib().bldp_fold_f32(ptr, nchan, nif, ntime, wp, nfpc, T, code, mptr, ld, _ptr(data),
-                                  _ptr(kept), dims[0], dims[0] * dims[1], _lib.stream_ptr(stream))
+    mptr, ld = _fold_mask(mask, wshape, x.device, "fold")
+    w, keep = _win_args(x, win)
+    res = _data_kept(dims, x.device)
+    rc = _lib.lib().bldp_fold_f32(*w, nfpc, T, code, mptr, ld, _ptr(res["data"]),
+                                  _ptr(res["kept"]), dims[0], dims[0] * dims[1],
+                                  _lib.stream_ptr(stream))
     _lib.check(rc, "bldp_fold_f32")
-    return {"data": data, "kept": kept}
+    return res
 
 
 def fold_plan(x, nfpc, tavby=None, mask=None, win=None) -> dict:
@@ -1932,19 +1820,12 @@ def fold_plan(x, nfpc, tavby=None, mask=None, win=None) -> dict:
     share a block), ``workgroups``, ``workspace_bytes``, ``launches`` (2 with the
     merge), ``mask_loads`` (_lib.FOLD_MASK_LOADS), ``vector_loads`` (1: float4),
     ``outputs`` and ``units_per_chunk``."""
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
+    shape, wshape = _window(x, win)
     nfpc, T, dims = _fold_factors(shape, win, nfpc, tavby)
-    mptr, ld = _fold_mask(mask, window_shape(win, shape), x.device, "fold_plan")
-    ptr, nchan, nif, ntime = _abi_dims(x)
-    info = (ctypes.c_int64 * 10)()
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    _lib.check(_lib.lib().bldp_fold_plan_f32(ptr, nchan, nif, ntime, wp, nfpc, T, mptr, ld, info),
-               "bldp_fold_plan_f32")
-    d = dict(zip(FOLD_PLAN_KEYS, [int(v) for v in info]))
-    d["path"] = _lib.FOLD_PATHS[d["path"]]
-    d["mask_loads"] = _lib.FOLD_MASK_LOADS[d["mask_loads"]]
-    return d
+    mptr, ld = _fold_mask(mask, wshape, x.device, "fold_plan")
+    w, keep = _win_args(x, win)
+    return _plan_dict("bldp_fold_plan_f32", (*w, nfpc, T, mptr, ld), 10, FOLD_PLAN_KEYS,
+                      path=_lib.FOLD_PATHS, mask_loads=_lib.FOLD_MASK_LOADS)
 
 
 def band_fold(banks, nfpc, tavby=None, op="mean", mask=None, win=None, stream=None):
@@ -1952,39 +1833,19 @@ def band_fold(banks, nfpc, tavby=None, op="mean", mask=None, win=None, stream=No
     nto) profile over the coarse channels of every bank, not a vcat.  ``mask``
     covers the stitched window, (nbank*nc, ni, nt) with any axis allowed to be 1:
     bank b's channel c is its channel b*nc + c."""
-    torch = _torch()
     code = _masked_op(op)
-    banks = list(banks)
-    if not banks:
-        raise ValueError("no banks")
-    for b in banks:
-        if b.dtype != torch.float32:
-            _need_f32("band_fold", b.dtype, "fold")
-    shape = tuple(banks[0].shape)
-    _check_bounds(win, shape)
+    banks, nb, _, _ = _banks(banks, "band_fold", "fold", agree=False)
+    shape, (nc, ni, nt) = _window(banks[0], win)
     nfpc, T, dims = _fold_factors(shape, win, nfpc, tavby)
-    nc, ni, nt = window_shape(win, shape)
-    nb = len(banks)
     mptr, ld = _fold_mask(mask, (nb * nc, ni, nt), banks[0].device, "band_fold")
-    geo = _band_geo(banks)
-    ptrs = (ctypes.c_void_p * nb)(*[b.data_ptr() for b in banks])
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    data = fb_empty(*dims, device=banks[0].device)
-    kept = fb_empty(*dims, device=banks[0].device, dtype=torch.int32)
-    rc = _lib.lib().bldp_band_fold_f32(nb, ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp, nfpc, T,
-                                       code, mptr, ld, _ptr(data), _ptr(kept),
+    _, _, ptrs, geo = _banks(banks)
+    keep, wp = _win_ptr(win, shape)
+    res = _data_kept(dims, banks[0].device)
+    rc = _lib.lib().bldp_band_fold_f32(nb, ptrs, *geo, wp, nfpc, T, code, mptr, ld,
+                                       _ptr(res["data"]), _ptr(res["kept"]),
                                        _lib.stream_ptr(stream))
     _lib.check(rc, "bldp_band_fold_f32")
-    return {"data": data, "kept": kept}
-
-
-def _host_fb(a, what, fn):
-    a = np.asarray(a)
-    if a.dtype != np.float32:
-        _need_f32(what, a.dtype, fn)
-    if not a.flags.f_contiguous or a.ndim != 3:
-        raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
-    return a
+    return res
 
 
 def fold_host(a: np.ndarray, nfpc, tavby=None, op="mean", mask=None, win=None, device=0) -> dict:
@@ -1993,27 +1854,17 @@ def fold_host(a: np.ndarray, nfpc, tavby=None, op="mean", mask=None, win=None, d
     the window's rows and the mask staged on ``device`` once)."""
     code = _masked_op(op)
     a = _host_fb(a, "fold_host", "fold")
-    _check_bounds(win, a.shape)
-    nfpc, T, dims = _fold_factors(a.shape, win, nfpc, tavby)
+    shape, wshape = _window(a, win)
+    nfpc, T, dims = _fold_factors(shape, win, nfpc, tavby)
     mptr = ld = None
     if mask is not None:
-        m = np.asarray(mask)
-        if m.dtype not in (np.dtype(np.uint8), np.dtype(np.bool_)):
-            raise TypeError(f"fold_host: the mask must be a uint8 or bool array, not {m.dtype}")
-        if m.ndim == 3 and any(s < 0 for s in m.strides):
-            m = np.asfortranarray(m)
-        ld = (ctypes.c_int64 * 3)(*_mask_strides(m.shape, m.strides, window_shape(win, a.shape),
-                                                 "fold_host"))
-        mptr = m.ctypes.data if m.size else None
-    data = np.empty(dims, dtype=np.float32, order="F")
-    kept = np.empty(dims, dtype=np.uint32, order="F")
-    keep, wp = _lib.win_arg(_full_win(win, a.shape))
-    rc = _lib.lib().bldp_fold_host_f32(
-        int(device), a.ctypes.data if a.size else None, a.shape[0], a.shape[1], a.shape[2], wp,
-        nfpc, T, code, mptr, ld, data.ctypes.data if data.size else None,
-        kept.ctypes.data if kept.size else None)
+        mptr, ld = _host_mask_arg(_host_mask(mask, "fold_host"), wshape, "fold_host")
+    res = {"data": _host_out(dims), "kept": _host_out(dims, np.int32)}
+    h, keep = _host_args(device, a, win)
+    rc = _lib.lib().bldp_fold_host_f32(*h, nfpc, T, code, mptr, ld, _np_ptr(res["data"]),
+                                       _np_ptr(res["kept"]))
     _lib.check(rc, "bldp_fold_host_f32")
-    return {"data": data, "kept": kept.view(np.int32)}  # counts are < 2^31
+    return res
 
 
 def _unfold_prof(prof, dims, device, what):
@@ -2034,29 +1885,14 @@ def _unfold_prof(prof, dims, device, what):
     if (dims[0] > 1 and s0 != 1) or min(s1, s2) < 0:
         raise ValueError(f"{what}: profile strides {prof.stride()}: the fine channels must be "
                          f"the fastest axis")
-    return (prof.data_ptr() if prof.numel() else None), (s1 if dims[1] > 1 else 0), \
-        (s2 if dims[2] > 1 else 0)
+    return _ptr(prof), (s1 if dims[1] > 1 else 0), (s2 if dims[2] > 1 else 0)
 
 
 def _unfold_out(out, dims, device):
     """(pointer, out_ld_i, out_ld_t) of a caller's Float32 ``out`` of shape ``dims``,
     channels fastest; a strided view (a bank's slot of a stitched band) passes its
     strides."""
-    torch = _torch()
-    if not isinstance(out, torch.Tensor) or out.dtype != torch.float32:
-        raise TypeError(f"out must be a Float32 device tensor, not "
-                        f"{getattr(out, 'dtype', type(out).__name__)}")
-    if tuple(out.shape) != tuple(dims):
-        raise ValueError(f"out is {tuple(out.shape)}, expected {tuple(dims)}")
-    if out.device != torch.device(device):
-        raise ValueError(f"out is on {out.device}, the data on {device}")
-    nc, ni, nt = dims
-    s0, s1, s2 = out.stride()
-    ld_i = s1 if ni > 1 else nc
-    ld_t = s2 if nt > 1 else max(ni - 1, 0) * ld_i + nc
-    if nc > 1 and s0 != 1:
-        raise ValueError(f"out strides {out.stride()}: the channels must be the fastest axis")
-    return (out.data_ptr() if out.numel() else None), ld_i, ld_t
+    return _out_layout(out, tuple(dims), device, _torch().float32, dtname="Float32", loose=True)
 
 
 def unfold(x, prof, nfpc, tavby=None, how="divide", win=None, out=None, stream=None):
@@ -2071,18 +1907,14 @@ def unfold(x, prof, nfpc, tavby=None, how="divide", win=None, out=None, stream=N
     code = _unfold_op(how)
     if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
         _need_f32("unfold", getattr(x, "dtype", type(x).__name__), "unfold")
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
+    shape, wshape = _window(x, win)
     nfpc, T, dims = _fold_factors(shape, win, nfpc, tavby)
-    wshape = window_shape(win, shape)
-    pptr, pld_i, pld_t = _unfold_prof(prof, dims, x.device, "unfold")
-    ptr, nchan, nif, ntime = _abi_dims(x)
+    p = _unfold_prof(prof, dims, x.device, "unfold")
+    w, keep = _win_args(x, win)
     if out is None:
         out = fb_empty(*wshape, device=x.device)
-    optr, ld_i, ld_t = _unfold_out(out, wshape, x.device)
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    rc = _lib.lib().bldp_unfold_f32(ptr, nchan, nif, ntime, wp, nfpc, T, code, pptr, pld_i, pld_t,
-                                    optr, ld_i, ld_t, _lib.stream_ptr(stream))
+    o = _unfold_out(out, wshape, x.device)
+    rc = _lib.lib().bldp_unfold_f32(*w, nfpc, T, code, *p, *o, _lib.stream_ptr(stream))
     _lib.check(rc, "bldp_unfold_f32")
     return out
 
@@ -2091,42 +1923,27 @@ def unfold_plan(x, nfpc, tavby=None, win=None, prof=None, out=None) -> dict:
     """Launch plan of ``unfold`` (bldp_unfold_plan_f32; launches nothing):
     ``vector_loads`` (1: float4), ``workgroups`` per bank, ``elements_per_lane``.
     Without ``prof`` / ``out`` dense, aligned ones are assumed."""
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
+    shape, wshape = _window(x, win)
     nfpc, T, dims = _fold_factors(shape, win, nfpc, tavby)
-    wshape = window_shape(win, shape)
-    pptr, pld_i, pld_t = (None, dims[0], dims[0] * dims[1]) if prof is None else \
+    p = (None, dims[0], dims[0] * dims[1]) if prof is None else \
         _unfold_prof(prof, dims, x.device, "unfold_plan")
-    optr, ld_i, ld_t = (None, wshape[0], wshape[0] * wshape[1]) if out is None else \
+    o = (None, wshape[0], wshape[0] * wshape[1]) if out is None else \
         _unfold_out(out, wshape, x.device)
-    ptr, nchan, nif, ntime = _abi_dims(x)
-    info = (ctypes.c_int64 * 4)()
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    _lib.check(_lib.lib().bldp_unfold_plan_f32(ptr, nchan, nif, ntime, wp, nfpc, T, pptr, pld_i,
-                                               pld_t, optr, ld_i, ld_t, info),
-               "bldp_unfold_plan_f32")
-    return dict(zip(UNFOLD_PLAN_KEYS, [int(v) for v in info]))
+    w, keep = _win_args(x, win)
+    return _plan_dict("bldp_unfold_plan_f32", (*w, nfpc, T, *p, *o), 4, UNFOLD_PLAN_KEYS)
 
 
 def band_unfold(banks, prof, nfpc, tavby=None, how="divide", win=None, stream=None):
     """``unfold`` of every bank of a band resident on ONE GPU in one launch
     (bldp_band_unfold_f32) with ONE profile (``band_fold``'s): the dense vcat
     (nbank*nc, ni, nt)."""
-    torch = _torch()
     code = _unfold_op(how)
-    banks = list(banks)
-    if not banks:
-        raise ValueError("no banks")
-    for b in banks:
-        if b.dtype != torch.float32:
-            _need_f32("band_unfold", b.dtype, "unfold")
-    shape = tuple(banks[0].shape)
-    _check_bounds(win, shape)
+    banks = _banks(banks, "band_unfold", "unfold", agree=False)[0]
+    shape, _ = _window(banks[0], win)
     nfpc, T, dims = _fold_factors(shape, win, nfpc, tavby)
-    pptr, pld_i, pld_t = _unfold_prof(prof, dims, banks[0].device, "band_unfold")
+    p = _unfold_prof(prof, dims, banks[0].device, "band_unfold")
     banks, geo, out, ptrs, (keep, wp) = _band_args(banks, 1, 1, win, None)
-    rc = _lib.lib().bldp_band_unfold_f32(len(banks), ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp,
-                                         nfpc, T, code, pptr, pld_i, pld_t, _ptr(out),
+    rc = _lib.lib().bldp_band_unfold_f32(len(banks), ptrs, *geo, wp, nfpc, T, code, *p, _ptr(out),
                                          _lib.stream_ptr(stream))
     _lib.check(rc, "bldp_band_unfold_f32")
     return out
@@ -2139,19 +1956,17 @@ def unfold_host(a: np.ndarray, prof: np.ndarray, nfpc, tavby=None, how="divide",
     window's rows and the profile staged on ``device`` once)."""
     code = _unfold_op(how)
     a = _host_fb(a, "unfold_host", "unfold")
-    _check_bounds(win, a.shape)
-    nfpc, T, dims = _fold_factors(a.shape, win, nfpc, tavby)
+    shape, wshape = _window(a, win)
+    nfpc, T, dims = _fold_factors(shape, win, nfpc, tavby)
     p = np.asarray(prof)
     if p.dtype != np.float32:
         raise TypeError(f"unfold_host: the profile must be float32, not {p.dtype}")
     if p.shape != tuple(dims):
         raise ValueError(f"unfold_host: the profile is {p.shape}, expected {tuple(dims)}")
     p = np.asfortranarray(p)
-    out = np.empty(window_shape(win, a.shape), dtype=np.float32, order="F")
-    keep, wp = _lib.win_arg(_full_win(win, a.shape))
-    rc = _lib.lib().bldp_unfold_host_f32(
-        int(device), a.ctypes.data if a.size else None, a.shape[0], a.shape[1], a.shape[2], wp,
-        nfpc, T, code, p.ctypes.data if p.size else None, out.ctypes.data if out.size else None)
+    out = _host_out(wshape)
+    h, keep = _host_args(device, a, win)
+    rc = _lib.lib().bldp_unfold_host_f32(*h, nfpc, T, code, _np_ptr(p), _np_ptr(out))
     _lib.check(rc, "bldp_unfold_host_f32")
     return out
 
@@ -2233,19 +2048,13 @@ def _moment_call(fn, x, win, tblock, stream, want=(True,)):
     """Device call: (nc, ni, nt/tblock) float64 tensors, (nc, ni) ones for the
     whole window (``tblock=None``)."""
     torch = _torch()
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
-    nc, ni, nt = window_shape(win, shape)
+    _, (nc, ni, nt) = _window(x, win)
     M = _skew_tblock(tblock, nt)
     nb = nt // M if M else 1
     outs = [torch.empty((nb, ni, nc), dtype=torch.float64, device=x.device).permute(2, 1, 0)
             if w else None for w in want]
-    ptr, nchan, nif, ntime = _abi_dims(x)
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    rc = getattr(_lib.lib(), fn)(
-        ptr, nchan, nif, ntime, wp, M,
-        *[o.data_ptr() if o is not None and o.numel() else None for o in outs],
-        nc, nc * ni, _lib.stream_ptr(stream))
+    w, keep = _win_args(x, win)
+    rc = getattr(_lib.lib(), fn)(*w, M, *map(_ptr, outs), nc, nc * ni, _lib.stream_ptr(stream))
     _lib.check(rc, fn)
     return [o if o is None or M else o[:, :, 0] for o in outs]
 
@@ -2253,86 +2062,48 @@ def _moment_call(fn, x, win, tblock, stream, want=(True,)):
 def _moment_plan(fn, x, win, tblock, check=_skew_tblock) -> dict:
     """Plan call: the path ("regs", "mid", "leaf", "twopass"), fused, the block
     count and the workspace bytes."""
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
-    check(tblock, window_shape(win, shape)[2])
-    ptr, nchan, nif, ntime = _abi_dims(x)
-    info = (ctypes.c_int64 * 4)()
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    _lib.check(getattr(_lib.lib(), fn)(ptr, nchan, nif, ntime, wp, int(tblock or 0), info), fn)
-    return {"path": _lib.KURT_PATHS[info[0]], "fused": int(info[1]), "blocks": int(info[2]),
-            "workspace_bytes": int(info[3])}
+    _, wshape = _window(x, win)
+    check(tblock, wshape[2])
+    w, keep = _win_args(x, win)
+    return _plan_dict(fn, (*w, int(tblock or 0)), 4,
+                      ("path", "fused", "blocks", "workspace_bytes"), path=_lib.KURT_PATHS)
 
 
-def _band_geo(banks):
-    """The ABI geometry (nchan, nif, ntime) every bank of a band must share."""
-    shape = tuple(banks[0].shape)
-    geo = _abi_dims(banks[0])[1:]
-    for b in banks[1:]:
-        if tuple(b.shape) != shape or _abi_dims(b)[1:] != geo:
-            raise ValueError("all banks of a band must have the same shape and layout")
-    return geo
-
-
-def _band_moment_call(fn, banks, win, tblock, stream, want=(True,), geo=None):
+def _band_moment_call(fn, banks, win, tblock, stream, want=(True,)):
     """Band call: per bank the list of its planes, views of one buffer per
-    plane.  ``geo``: the banks' geometry where the caller has checked it."""
+    plane."""
     torch = _torch()
-    shape = tuple(banks[0].shape)
-    _check_bounds(win, shape)
-    nc, ni, nt = window_shape(win, shape)
+    shape, (nc, ni, nt) = _window(banks[0], win)
     M = _skew_tblock(tblock, nt)
     nb = nt // M if M else 1
-    if geo is None:
-        geo = _band_geo(banks)
-    ptrs = (ctypes.c_void_p * len(banks))(*[b.data_ptr() for b in banks])
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    bufs = [torch.empty((len(banks), nb, ni, nc), dtype=torch.float64, device=banks[0].device)
+    banks, nbank, ptrs, geo = _banks(banks)
+    keep, wp = _win_ptr(win, shape)
+    bufs = [torch.empty((nbank, nb, ni, nc), dtype=torch.float64, device=banks[0].device)
             if w else None for w in want]
-    rc = getattr(_lib.lib(), fn)(
-        len(banks), ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp, M,
-        *[b.data_ptr() if b is not None and b.numel() else None for b in bufs],
-        _lib.stream_ptr(stream))
+    rc = getattr(_lib.lib(), fn)(nbank, ptrs, *geo, wp, M, *map(_ptr, bufs),
+                                 _lib.stream_ptr(stream))
     _lib.check(rc, fn)
 
     def view(buf, k):
         if buf is None:
             return None
         return buf[k].permute(2, 1, 0) if M else buf[k, 0].t()
-    return [[view(buf, k) for buf in bufs] for k in range(len(banks))]
-
-
-def _f32_banks(banks, what, fn):
-    banks = list(banks)
-    if not banks:
-        raise ValueError("no banks")
-    f32 = _torch().float32
-    for b in banks:
-        if b.dtype != f32:
-            _need_f32(what, b.dtype, fn)
-    return banks
+    return [[view(buf, k) for buf in bufs] for k in range(nbank)]
 
 
 def _moment_host(fn, a, win, device, tblock, want=(True,), what=None, takes="skewness"):
     """Host call: Fortran-ordered (nc, ni, nt/tblock) float64 arrays, (nc, ni)
     ones for the whole window.  ``what``: the caller's name in the TypeError of
     an element type other than Float32 (``takes`` names the statistic)."""
-    a = np.asarray(a)
-    if what and a.dtype != np.float32:
-        _need_f32(what, a.dtype, takes)
-    if a.dtype != np.float32 or not a.flags.f_contiguous or a.ndim != 3:
-        raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
-    _check_bounds(win, a.shape)
-    nc, ni, nt = window_shape(win, a.shape)
+    a = _host_fb(a, what, takes)
+    _, (nc, ni, nt) = _window(a, win)
     M = _skew_tblock(tblock, nt)
     outs = [np.empty((nc, ni, nt // M) if M else (nc, ni), dtype=np.float64, order="F")
             if w else None for w in want]
-    keep, wp = _lib.win_arg(_full_win(win, a.shape))
+    h, keep = _host_args(device, a, win)
     # (bldp_kurtosis_host_f32, the whole-window kurtosis, takes no tblock)
-    rc = getattr(_lib.lib(), fn)(
-        int(device), a.ctypes.data if a.size else None, a.shape[0], a.shape[1], a.shape[2], wp,
-        *(() if fn == "bldp_kurtosis_host_f32" else (M,)),
-        *[o.ctypes.data if o is not None and o.size else None for o in outs])
+    rc = getattr(_lib.lib(), fn)(*h, *(() if fn == "bldp_kurtosis_host_f32" else (M,)),
+                                 *map(_np_ptr, outs))
     _lib.check(rc, fn)
     return outs
 
@@ -2348,9 +2119,7 @@ def kurtosis(x, win=None, tblock=None, stream=None):
     if tblock is not None and x.dtype == torch.float32:
         return _moment_call("bldp_kurtosis_blocks_f32", x, win, tblock, stream)[0]
     L = _lib.lib()
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
-    nc, ni, nt = window_shape(win, shape)
+    shape, (nc, ni, nt) = _window(x, win)
     if tblock is not None:
         nb = _check_tblock(tblock, nt)
         out = torch.empty((nb, ni, nc), dtype=torch.float64, device=x.device).permute(2, 1, 0)
@@ -2358,15 +2127,12 @@ def kurtosis(x, win=None, tblock=None, stream=None):
             out[:, :, b] = kurtosis(x, _block_win(win, shape, int(tblock), b), stream=stream)
         return out
     out = torch.empty((ni, nc), dtype=torch.float64, device=x.device).t()
-    ptr, nchan, nif, ntime = _abi_dims(x, allow_typed=True)
-    keep, wp = _lib.win_arg(_full_win(win, shape))
+    w, keep = _win_args(x, win, allow_typed=True)
     if x.dtype != torch.float32:  # StatsBase in Float64 for integer / Float64 rows
-        rc = L.bldp_kurtosis(_dtype_code(x.dtype), ptr, nchan, nif, ntime, wp,
-                             out.data_ptr() if out.numel() else None, _lib.stream_ptr(stream))
+        rc = L.bldp_kurtosis(_dtype_code(x.dtype), *w, _ptr(out), _lib.stream_ptr(stream))
         _lib.check(rc, "bldp_kurtosis")
         return out
-    rc = L.bldp_kurtosis_f32(ptr, nchan, nif, ntime, wp, out.data_ptr() if out.numel() else None,
-                             None, _lib.stream_ptr(stream))
+    rc = L.bldp_kurtosis_f32(*w, _ptr(out), None, _lib.stream_ptr(stream))
     _lib.check(rc, "bldp_kurtosis_f32")
     return out
 
@@ -2374,15 +2140,10 @@ def kurtosis(x, win=None, tblock=None, stream=None):
 def kurtosis_plan(x, win=None) -> dict:
     """Kurtosis plan for this tensor and window: path ("regs", "mid", "leaf",
     "twopass"), K (level of the pairwise-sum blocks), leaf slots, workspace."""
-    L = _lib.lib()
-    shape = tuple(x.shape)
-    _check_bounds(win, shape)
-    ptr, nchan, nif, ntime = _abi_dims(x)
-    info = (ctypes.c_int64 * 4)()
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    _lib.check(L.bldp_kurtosis_plan_f32(ptr, nchan, nif, ntime, wp, info), "bldp_kurtosis_plan_f32")
-    return {"path": _lib.KURT_PATHS[info[0]], "K": info[1], "leaf_slots": info[2],
-            "workspace_bytes": info[3]}
+    _window(x, win)
+    w, keep = _win_args(x, win)
+    return _plan_dict("bldp_kurtosis_plan_f32", w, 4, ("path", "K", "leaf_slots", "workspace_bytes"),
+                      path=_lib.KURT_PATHS)
 
 
 def kurtosis_blocks_plan(x, tblock, win=None) -> dict:
@@ -2398,25 +2159,16 @@ def band_kurtosis(banks, win=None, tblock=None, stream=None):
     returns a list of (nc, ni) float64 tensors (views of one buffer), or with
     ``tblock`` of (nc, ni, nt/tblock) ones (bldp_band_kurtosis_blocks_f32)."""
     torch = _torch()
-    L = _lib.lib()
-    banks = list(banks)
-    if not banks:
-        raise ValueError("no banks")
-    shape = tuple(banks[0].shape)
-    geo = _band_geo(banks)
-    _check_bounds(win, shape)
+    banks, nb, ptrs, geo = _banks(banks)
+    shape, (nc, ni, nt) = _window(banks[0], win)
     if tblock is not None:
         return [v[0] for v in _band_moment_call("bldp_band_kurtosis_blocks_f32", banks, win,
-                                                tblock, stream, geo=geo)]
-    nc, ni, nt = window_shape(win, shape)
-    ptrs = (ctypes.c_void_p * len(banks))(*[b.data_ptr() for b in banks])
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    buf = torch.empty((len(banks), ni, nc), dtype=torch.float64, device=banks[0].device)
-    rc = L.bldp_band_kurtosis_f32(len(banks), ctypes.cast(ptrs, ctypes.c_void_p), *geo, wp,
-                                  buf.data_ptr() if buf.numel() else None,
-                                  _lib.stream_ptr(stream))
+                                                tblock, stream)]
+    keep, wp = _win_ptr(win, shape)
+    buf = torch.empty((nb, ni, nc), dtype=torch.float64, device=banks[0].device)
+    rc = _lib.lib().bldp_band_kurtosis_f32(nb, ptrs, *geo, wp, _ptr(buf), _lib.stream_ptr(stream))
     _lib.check(rc, "bldp_band_kurtosis_f32")
-    return [buf[k].t() for k in range(len(banks))]
+    return [buf[k].t() for k in range(nb)]
 
 
 def kurtosis_host(a: np.ndarray, win=None, device=0, tblock=None) -> np.ndarray:
@@ -2448,7 +2200,7 @@ def band_skewness(banks, win=None, tblock=None, stream=None):
     """Skewness of every bank of a band on one GPU in one set of launches
     (bldp_band_skewness_f32): a list of (nc, ni) float64 tensors (views of one
     buffer), or with ``tblock`` of (nc, ni, nt/tblock) ones."""
-    banks = _f32_banks(banks, "band_skewness", "skewness")
+    banks = _banks(banks, "band_skewness", "skewness", agree=False)[0]
     return [v[0] for v in _band_moment_call("bldp_band_skewness_f32", banks, win, tblock, stream)]
 
 
@@ -2506,7 +2258,7 @@ def band_moments(banks, win=None, tblock=None, stream=None, which=MOMENTS):
     (bldp_band_moments_f32): a list of ``Moments`` (views of one buffer per
     plane), shaped as ``moments`` shapes them."""
     want = _which_planes(which)
-    banks = _f32_banks(banks, "band_moments", "moments")
+    banks = _banks(banks, "band_moments", "moments", agree=False)[0]
     return [Moments(*v) for v in _band_moment_call("bldp_band_moments_f32", banks, win, tblock,
                                                     stream, want)]
 
@@ -2535,49 +2287,21 @@ def synth(nchan, nif, ntime, nfpc=1024, seed=0, kind=0, device=None, stream=None
     return out
 
 
-def reduce_host(a: np.ndarray, fqavby=1, tavby=1, op="sum", win=None, device=0) -> np.ndarray:
-    """Host array in, host array out (bldp_reduce_host_f32): the window is
-    streamed through the GPU and reduced there."""
-    _check_stat(op, tavby)
-    if _lib.quantile_of(op) is not None:
-        return quantile_host(a, fqavby, op[1], 0, win, device)
-    if _lib.quantiles_of(op) is not None:
-        return quantiles_host(a, fqavby, op[1], 0, win, device)
-    L = _lib.lib()
-    a = np.asarray(a)
-    if a.dtype != np.float32 or not a.flags.f_contiguous or a.ndim != 3:
-        raise TypeError("host filterbank must be a Fortran-ordered float32 (nchan, nif, ntime)")
-    shape = a.shape
-    _check_bounds(win, shape)
-    nco, ni, nto = out_shape(shape, win, fqavby, tavby)
-    out = np.empty((nco, ni, nto), dtype=np.float32, order="F")
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    rc = L.bldp_reduce_host_f32(int(device), a.ctypes.data if a.size else None, shape[0],
-                                shape[1], shape[2], wp, int(fqavby), int(tavby), _lib.OPS[op],
-                                out.ctypes.data if out.size else None)
-    _lib.check(rc, "bldp_reduce_host_f32")
-    return out
-
-
 def reduce_host_typed(a: np.ndarray, fqavby=1, tavby=1, op="sum", win=None, device=0) -> np.ndarray:
     """Host array of any supported element type in, host array of fqav's
     Julia result type out (bldp_reduce_host): e.g. UInt8 SIGPROC data summed
     into UInt64, averaged into Float64, max / min kept as UInt8."""
     a = np.asarray(a)
     _check_stat(op, tavby, a.dtype)
-    L = _lib.lib()
     code = _dtype_code(a.dtype)
     if code is None or a.ndim != 3:
         raise TypeError(f"unsupported host filterbank {a.dtype} {a.shape}")
     a = np.asfortranarray(a)
-    shape = a.shape
-    _check_bounds(win, shape)
-    nco, ni, nto = out_shape(shape, win, fqavby, tavby)
-    out = np.empty((nco, ni, nto), dtype=out_dtype(a.dtype, op), order="F")
-    keep, wp = _lib.win_arg(_full_win(win, shape))
-    rc = L.bldp_reduce_host(int(device), code, a.ctypes.data if a.size else None, shape[0],
-                            shape[1], shape[2], wp, int(fqavby), int(tavby), _lib.OPS[op],
-                            out.ctypes.data if out.size else None)
+    shape, _ = _window(a, win)
+    out = _host_out(out_shape(shape, win, fqavby, tavby), out_dtype(a.dtype, op))
+    (dev, *h), keep = _host_args(device, a, win)
+    rc = _lib.lib().bldp_reduce_host(dev, code, *h, int(fqavby), int(tavby), _lib.OPS[op],
+                                     _np_ptr(out))
     _lib.check(rc, "bldp_reduce_host")
     return out
 
@@ -2587,14 +2311,12 @@ def kurtosis_host_typed(a: np.ndarray, win=None, device=0, tblock=None) -> np.nd
     (bldp_kurtosis_host; StatsBase's recipe in Float64 for non-Float32 rows,
     8- and 16-bit integer rows from exact integer power sums).  With ``tblock``:
     one such call per block of tblock selected spectra, (nc, ni, nt/tblock)."""
-    L = _lib.lib()
     a = np.asarray(a)
     code = _dtype_code(a.dtype)
     if code is None or a.ndim != 3:
         raise TypeError(f"unsupported host filterbank {a.dtype} {a.shape}")
     a = np.asfortranarray(a)
-    _check_bounds(win, a.shape)
-    nc, ni, nt = window_shape(win, a.shape)
+    _, (nc, ni, nt) = _window(a, win)
     if tblock is not None:
         nb = _check_tblock(tblock, nt)
         out = np.empty((nc, ni, nb), dtype=np.float64, order="F")
@@ -2602,9 +2324,8 @@ def kurtosis_host_typed(a: np.ndarray, win=None, device=0, tblock=None) -> np.nd
             out[:, :, b] = kurtosis_host_typed(a, _block_win(win, a.shape, int(tblock), b),
                                                device=device)
         return out
-    out = np.empty((nc, ni), dtype=np.float64, order="F")
-    keep, wp = _lib.win_arg(_full_win(win, a.shape))
-    rc = L.bldp_kurtosis_host(int(device), code, a.ctypes.data if a.size else None, a.shape[0],
-                              a.shape[1], a.shape[2], wp, out.ctypes.data if out.size else None)
+    out = _host_out((nc, ni), np.float64)
+    (dev, *h), keep = _host_args(device, a, win)
+    rc = _lib.lib().bldp_kurtosis_host(dev, code, *h, _np_ptr(out))
     _lib.check(rc, "bldp_kurtosis_host")
     return out
