@@ -12,12 +12,13 @@ from . import _lib, band, engine, fbh5, filestream, gbt, h5chunks, idxs, readers
 from ._lib import ArgumentError, BLDPError, BoundsError, DimensionMismatch, ReadError  # noqa: F401
 from ._lib import quantile, quantiles  # noqa: F401
 from .idxs import COLON, JRange, sanitizeidxs  # noqa: F401
+from .worker import getdedoppler, getdrifthits  # noqa: F401
 from .worker import FRange, fqav, getbandpass, getclean, getflagged, getflattened, gethistogram, gethits, getmasked, getmoments, getoutliers, getskewness  # noqa: F401
 
 GBT = gbt
 GBT.WorkerFunctions = worker
 WorkerFunctions = worker
 
-__all__ = ["GBT", "WorkerFunctions", "fqav", "quantile", "quantiles", "getskewness", "getmoments", "getoutliers", "getmasked", "getclean", "gethistogram", "gethits", "getflagged", "getbandpass", "getflattened", "JRange", "FRange", "COLON",
+__all__ = ["GBT", "WorkerFunctions", "fqav", "quantile", "quantiles", "getskewness", "getmoments", "getoutliers", "getmasked", "getclean", "gethistogram", "gethits", "getflagged", "getbandpass", "getflattened", "getdedoppler", "getdrifthits", "JRange", "FRange", "COLON",
            "sanitizeidxs",
            "engine", "band", "DimensionMismatch", "BoundsError", "BLDPError", "ReadError"]

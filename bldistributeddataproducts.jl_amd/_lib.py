@@ -125,6 +125,10 @@ MAX_HIST_BINS = 4096
 FOLD_PATHS = {0: "cols", 1: "rows"}
 FOLD_MASK_LOADS = {0: "byte", 1: "dword", 2: "row", 3: "none"}
 UNFOLD_OPS = {"divide": 0, "subtract": 1}
+# dedoppler (csrc/dedoppler.hip): a block's rows staged in LDS once, or a chunk of
+# rows at a time and read again for every group of drifts
+DEDOPPLER_PATHS = {0: "resident", 1: "chunked"}
+MAX_DRIFT = 1024
 
 BLDP_OK, BLDP_EINVAL, BLDP_EDIM, BLDP_EHIP, BLDP_ENOMEM, BLDP_EBOUNDS = 0, -1, -2, -3, -5, -6
 BLDP_ECOMM, BLDP_EIO = -7, -8
@@ -253,6 +257,10 @@ SIGNATURES = {
     "bldp_unfold_f32": ([P, I64, I64, I64, P, I64, I64, I, P, I64, I64, P, I64, I64, P], I),
     "bldp_band_unfold_f32": ([I, P, I64, I64, I64, P, I64, I64, I, P, I64, I64, P, P], I),
     "bldp_unfold_host_f32": ([I, P, I64, I64, I64, P, I64, I64, I, P, P], I),
+    "bldp_dedoppler_plan_f32": ([P, I64, I64, I64, P, I64, I64, I64, P], I),
+    "bldp_dedoppler_f32": ([P, I64, I64, I64, P, I64, I64, I64, P, P, P, I64, I64, I64, P], I),
+    "bldp_band_dedoppler_f32": ([I, P, I64, I64, I64, P, I64, I64, I64, P, P, P, P], I),
+    "bldp_dedoppler_host_f32": ([I, P, I64, I64, I64, P, I64, I64, I64, P, P, P], I),
     "bldp_fqav_range": ([D, D, I64, I64, P, P, P], I),
     "bldp_synth_f32": ([P, I64, I64, I64, I64, U64, I, P], I),
     "bldp_reduce_out_dtype": ([I, I], I),

@@ -2541,6 +2541,121 @@ int bldp_band_unfold_f32(int nbank, const float *const *in, int64_t nchan, int64
                     out, l[1], l[2], stream);
 }
 
+// ---- dedoppler: the drift-rate sums of every channel ---------------------------
+// Checks, window and plan of a dedoppler (every entry point).  l = {out_bank,
+// out_ld_i, out_ld_t, out_ld_q}: output (c, i, b) of bank k at [k*l[0] + c + i*l[1]
+// + b*l[2]], drift plane q of sums at + q*l[3].  query: the plan call.
+static int dedop_prepare(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                         int64_t ntime, const int64_t *win, int64_t tavby, int64_t maxdrift,
+                         int64_t seg, float *best, int *drift, float *sums, const int64_t l[4],
+                         bool query, DedopArgs *ap, Plan *pp, bool *empty) {
+  static const char what[] = "dedoppler: ";
+  int rc = check_nbank(nbank);
+  if (rc) return rc;
+  if (tavby < 2)
+    return fail(BLDP_EINVAL, "dedoppler: tavby=%lld: a block needs two spectra", (long long)tavby);
+  if (tavby > ((int64_t)1 << 20))
+    return fail(BLDP_EINVAL, "dedoppler: tavby=%lld beyond 2^20", (long long)tavby);
+  if (maxdrift < 0 || maxdrift > BLDP_MAX_DRIFT)
+    return fail(BLDP_EINVAL, "dedoppler: maxdrift=%lld outside 0..%d", (long long)maxdrift,
+                BLDP_MAX_DRIFT);
+  if (seg < 0) return fail(BLDP_EINVAL, "dedoppler: seg=%lld is negative", (long long)seg);
+  Geo g;
+  int64_t F, T;
+  rc = resolve_blocks(nchan, nif, ntime, win, 1, tavby, &g, &F, &T);
+  if (rc) return rc;
+  DedopArgs &a = *ap;
+  a = DedopArgs{};
+  a.best = best, a.drift = drift, a.sums = sums;
+  a.out_bank = l[0], a.out_ld_i = l[1], a.out_ld_t = l[2], a.out_ld_q = l[3];
+  a.nc = g.nc, a.ni = g.ni, a.nb = g.nt / T, a.T = T;
+  a.seg = seg, a.D = (int32_t)maxdrift;
+  *empty = g.nc == 0 || g.ni == 0 || g.nt == 0;
+  bool words, rows16;
+  rc = set_window(what, a, g, nbank, in, &words, &rows16);
+  if (!rc) rc = plan_dedoppler(a, rows16 && vec_ok(g), pp);
+  if (rc || query || *empty) return rc;
+  rc = check_banks(what, nbank, in);
+  if (rc) return rc;
+  if ((best == nullptr) != (drift == nullptr))
+    return fail(BLDP_EINVAL, "dedoppler: best and drift go together");
+  if (!best && !sums) return fail(BLDP_EINVAL, "dedoppler: best / drift and sums are all null");
+  rc = check_out_strides(what, nbank, l[0], l[1], l[2], a.nc, a.ni, a.nb);
+  if (rc) return rc;
+  const int64_t K = 2 * maxdrift + 1;
+  const int64_t plane = (nbank - 1) * l[0] + (a.nc - 1) + (a.ni - 1) * l[1] + (a.nb - 1) * l[2] + 1;
+  if (sums && K > 1 && l[3] < plane)
+    return fail(BLDP_EINVAL, "dedoppler: sums planes %lld elements apart overlap for a (%lld, %lld, "
+                "%lld) plane with strides (%lld, %lld)", (long long)l[3], (long long)(nbank * a.nc),
+                (long long)a.ni, (long long)a.nb, (long long)l[1], (long long)l[2]);
+  const Span outs[3] = {{best, 4 * (size_t)plane, "best"},
+                        {drift, 4 * (size_t)plane, "drift"},
+                        {sums, 4 * (size_t)((K - 1) * l[3] + plane), "sums"}};
+  return check_disjoint(what, outs, 3, g, nbank, in, {nullptr, 0, ""});
+}
+
+static int dedop_run(int nbank, const float *const *in, int64_t nchan, int64_t nif, int64_t ntime,
+                     const int64_t *win, int64_t tavby, int64_t maxdrift, int64_t seg, float *best,
+                     int *drift, float *sums, const int64_t l[4], void *stream) {
+  DedopArgs a;
+  Plan p;
+  bool empty = false;
+  int rc = dedop_prepare(nbank, in, nchan, nif, ntime, win, tavby, maxdrift, seg, best, drift,
+                         sums, l, false, &a, &p, &empty);
+  if (rc || empty) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  return run_planned("dedoppler", 0, s, [&](void *) { return launch_dedoppler(a, p, s); });
+}
+
+int bldp_dedoppler_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                            const int64_t *win, int64_t tavby, int64_t maxdrift, int64_t seg,
+                            int64_t info[10]) {
+  if (!info) return fail(BLDP_EINVAL, "null info");
+  DedopArgs a;
+  Plan p;
+  bool empty = false;
+  const float *ins[1] = {in};
+  const int64_t l[4] = {0, 0, 0, 0};
+  int rc = dedop_prepare(1, ins, nchan, nif, ntime, win, tavby, maxdrift, seg, nullptr, nullptr,
+                         nullptr, l, true, &a, &p, &empty);
+  if (rc) return rc;
+  for (int q = 0; q < 10; ++q) info[q] = 0;
+  if (empty) return BLDP_OK;  // (nothing is launched)
+  info[0] = p.path;
+  info[1] = a.C;
+  info[2] = a.H;
+  info[3] = a.R;
+  info[4] = dedoppler_group();
+  info[5] = p.nrw;
+  info[6] = p.shm;
+  info[7] = p.grid;
+  info[8] = a.vec;
+  info[9] = (int64_t)p.ws_bytes;
+  return BLDP_OK;
+}
+
+int bldp_dedoppler_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                       const int64_t *win, int64_t tavby, int64_t maxdrift, int64_t seg,
+                       float *best, int *drift, float *sums, int64_t out_ld_i,
+                       int64_t out_ld_t, int64_t out_ld_q, void *stream) {
+  const float *ins[1] = {in};
+  const int64_t l[4] = {0, out_ld_i, out_ld_t, out_ld_q};
+  return dedop_run(1, ins, nchan, nif, ntime, win, tavby, maxdrift, seg, best, drift, sums, l,
+                   stream);
+}
+
+int bldp_band_dedoppler_f32(int nbank, const float *const *in, int64_t nchan, int64_t nif,
+                            int64_t ntime, const int64_t *win, int64_t tavby, int64_t maxdrift,
+                            int64_t seg, float *best, int *drift, float *sums, void *stream) {
+  if (tavby < 2)  // (band_layout reads a tavby below 2 as no blocks at all)
+    return fail(BLDP_EINVAL, "dedoppler: tavby=%lld: a block needs two spectra", (long long)tavby);
+  int64_t l[4];
+  const int rc = band_layout(nbank, nchan, nif, ntime, win, 1, tavby, l);
+  if (rc) return rc;
+  return dedop_run(nbank, in, nchan, nif, ntime, win, tavby, maxdrift, seg, best, drift, sums, l,
+                   stream);
+}
+
 int bldp_reduce_out_dtype(int dtype, int op) {
   const int d = typed_out_dtype(dtype, op);
   if (d < 0) return fail(BLDP_EINVAL, "unknown element type %d or op %d", dtype, op);

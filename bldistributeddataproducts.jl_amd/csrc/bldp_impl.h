@@ -478,6 +478,45 @@ struct UnfoldArgs {
 int64_t plan_unfold(UnfoldArgs &a, bool vec);
 hipError_t launch_unfold(const UnfoldArgs &a, int64_t grid, hipStream_t s);
 
+// Drift-rate sums of every channel (dedoppler.hip): S[c, i, b, d] = the Float32 sum
+// over t = 0 .. T-1, in that order, of A[c + off(d, t), i, b*T + t] inside the
+// segment of c, for d = -D .. D; best / drift: the greatest sum and its d over the
+// scan 0, -1, +1, ..., -D, +D (bldp.h has the rule).  Window element (c, i, t) of
+// bank k at in[k][in_off + c*in_cs + i*in_ld_i + t*in_ld_t]; output (c, i, b) of
+// bank k at [k*out_bank + c + i*out_ld_i + b*out_ld_t] of best and drift, drift d's
+// plane of sums at + (d + D)*out_ld_q (a null output is not written).  A by-value
+// kernel argument of k_dedoppler alone.
+struct DedopArgs {
+  const float *in[BLDP_MAX_BANKS];  // banks with identical geometry
+  float *best;
+  int32_t *drift;
+  float *sums;
+  int64_t out_bank, out_ld_i, out_ld_t, out_ld_q;
+  int64_t in_off, in_cs, in_ld_i, in_ld_t;
+  int64_t nc, ni, nb, T;
+  int64_t seg;  // channels of a segment; 0: the whole window
+  int32_t nbank;
+  int32_t D;
+  // the plan (plan_dedoppler)
+  int32_t vec;  // rows staged by float4 loads, else a dword at a time
+  int32_t C;    // channels of a tile = lanes of a workgroup
+  int32_t H;    // halo channels staged on each side (>= D)
+  int32_t RW;   // words of a staged row: C + 2H
+  int32_t R;    // rows of a staging chunk (resident: T)
+  int64_t tiles;
+};
+enum DedopPath { DEDOP_RESIDENT = 0, DEDOP_CHUNKED = 1 };
+enum DedopKernel { DEDOP_K_VEC = 0, DEDOP_K_SCALAR = 1 };
+// Fills the plan of an args struct whose shape, stride, seg and D fields are set,
+// without a GPU (`vec`: 16-byte loads of every aligned float4 of the rows are
+// legal).  p: path (DedopPath), lpg = block = C, grid = workgroups per bank, gx / gy
+// / gz, shm = LDS bytes, kernel (DedopKernel), nrw = the drift groups, nout,
+// ws_bytes = 0.  BLDP_OK or, with the message recorded, BLDP_EINVAL for a launch too
+// large for one grid.
+int plan_dedoppler(DedopArgs &a, bool vec, Plan *p);
+int dedoppler_group();  // drifts of a group
+hipError_t launch_dedoppler(const DedopArgs &a, const Plan &p, hipStream_t s);
+
 // median / var / std of every block of T selected spectra of every (channel,
 // IF) column (tstats.hip): tavfunc, fqav's rule on the time axis.  Window
 // element (c, i, t) of bank k at in[k][in_off + c*in_cs + i*in_ld_i +

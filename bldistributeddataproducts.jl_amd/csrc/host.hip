@@ -712,6 +712,40 @@ extern "C" int bldp_unfold_host_f32(int dev, const float *in, int64_t nchan, int
   });
 }
 
+// ... and for the dedoppler: the window's rows go to the device once; the dense
+// (nc, ni, nb) best and drift and the dense (nc, ni, nb, 2*maxdrift + 1) sums that
+// the caller asked for come back.
+extern "C" int bldp_dedoppler_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                       int64_t ntime, const int64_t *win, int64_t tavby,
+                                       int64_t maxdrift, int64_t seg, float *best, int *drift,
+                                       float *sums) {
+  // (every argument check, before any staging)
+  int64_t info[10];
+  int rc = bldp_dedoppler_plan_f32(nullptr, nchan, nif, ntime, win, tavby, maxdrift, seg, info);
+  if (rc) return rc;
+  int64_t w[3], o[3];
+  rc = block_counts(nchan, nif, ntime, win, 1, tavby, w, o);
+  if (rc) return rc;
+  const size_t plane = (size_t)(o[0] * o[1] * o[2]);
+  if (plane == 0) return BLDP_OK;
+  if (!in) return bldp::set_error(BLDP_EINVAL, "dedoppler: null input pointer");
+  if ((best == nullptr) != (drift == nullptr))
+    return bldp::set_error(BLDP_EINVAL, "dedoppler: best and drift go together");
+  if (!best && !sums)
+    return bldp::set_error(BLDP_EINVAL, "dedoppler: best / drift and sums are all null");
+  const size_t K = (size_t)(2 * maxdrift + 1);
+  DevBuf b[3] = {{2, best ? plane * 4 : 0}, {3, drift ? plane * 4 : 0}, {1, sums ? plane * K * 4 : 0}};
+  return with_staged_window(dev, in, nchan, nif, win, w, b, 3, [&](const StagedWin &s) {
+    int r = bldp_dedoppler_f32(s.dbuf, s.span, w[1], w[2], s.dwin, tavby, maxdrift, seg,
+                               (float *)b[0].p, (int *)b[1].p, (float *)b[2].p, o[0],
+                               o[0] * o[1], (int64_t)plane, s.st);
+    if (!r) r = s.fetch(best, b[0].p, b[0].bytes);
+    if (!r) r = s.fetch(drift, b[1].p, b[1].bytes);
+    if (!r) r = s.fetch(sums, b[2].p, b[2].bytes);
+    return r;
+  });
+}
+
 // ---------------------------------------------------------------------------
 // Host forms of the typed entry points (include/bldp.h), staged like the
 // Float32 forms above: only the window's rows (its channel span of every

@@ -323,7 +323,7 @@ def out_shape(shape, win, fqavby, tavby):
 
 
 # The block operations (reduce, tstat, quantile(s), outliers, argext, masked
-# reduce, histogram, hits, fold, unfold) come in four forms: the device call, its
+# reduce, histogram, hits, fold, unfold, dedoppler) come in four forms: the device call, its
 # plan, the band and the host call.  The helpers below state once what the forms
 # share; each public function applies its family's own checks between them, in
 # its own order (tests/test_engine_front_errors.py pins that order).
@@ -1969,6 +1969,152 @@ def unfold_host(a: np.ndarray, prof: np.ndarray, nfpc, tavby=None, how="divide",
     rc = _lib.lib().bldp_unfold_host_f32(*h, nfpc, T, code, _np_ptr(p), _np_ptr(out))
     _lib.check(rc, "bldp_unfold_host_f32")
     return out
+
+
+DEDOPPLER_PLAN_KEYS = ("path", "tile_channels", "halo", "rows_per_chunk", "drifts_per_group",
+                       "groups", "lds_bytes", "workgroups", "vector_loads", "workspace_bytes")
+MAX_TAVBY_DEDOPPLER = 1 << 20
+
+
+def drift_offsets(maxdrift, T) -> np.ndarray:
+    """The paths of a dedoppler: the (2*maxdrift + 1, T) Int64 table off(d_k, t) =
+    sign(d) * floor((2|d|t + (T-1)) / (2(T-1))), d_k = k - maxdrift: the straight
+    line from 0 to d over the T spectra of a block, rounded to the nearest channel,
+    halves away from zero."""
+    D, T = int(maxdrift), int(T)
+    if D < 0 or T < 2:
+        raise _lib.ArgumentError(_lib.BLDP_EINVAL,
+                                 f"drift_offsets: maxdrift={maxdrift!r} < 0 or T={T!r} < 2")
+    d = np.arange(-D, D + 1, dtype=np.int64)[:, None]
+    t = np.arange(T, dtype=np.int64)[None, :]
+    return np.sign(d) * ((2 * np.abs(d) * t + (T - 1)) // (2 * (T - 1)))
+
+
+def drift_rates(maxdrift, T, foff, tsamp) -> np.ndarray:
+    """The drift rates, in Hz/s, of the 2*maxdrift + 1 drifts of a dedoppler over
+    blocks of T spectra: d * foff * 1e6 / ((T - 1) * tsamp), with ``foff`` the
+    channel width in MHz (its sign is the band's direction) and ``tsamp`` the
+    spectrum spacing in seconds."""
+    D, T = int(maxdrift), int(T)
+    if D < 0 or T < 2:
+        raise _lib.ArgumentError(_lib.BLDP_EINVAL,
+                                 f"drift_rates: maxdrift={maxdrift!r} < 0 or T={T!r} < 2")
+    d = np.arange(-D, D + 1, dtype=np.float64)
+    return d * (float(foff) * 1e6) / ((T - 1) * float(tsamp))
+
+
+def _dedop_args(shape, win, maxdrift, tavby, seg):
+    """(D, T, seg, (nc, ni, nb)) of a dedoppler, with the library's refusals raised
+    before any GPU work; ``tavby=None``: the whole selected time range, ``seg``
+    None or 0: the whole window is one segment."""
+    nc, ni, nt = window_shape(win, shape)
+    if isinstance(maxdrift, bool) or int(maxdrift) != maxdrift or \
+            not 0 <= int(maxdrift) <= _lib.MAX_DRIFT:
+        raise _lib.ArgumentError(_lib.BLDP_EINVAL,
+                                 f"dedoppler: maxdrift={maxdrift!r} outside 0..{_lib.MAX_DRIFT}")
+    T = nt if tavby is None else int(tavby)
+    if T < 2 or T > MAX_TAVBY_DEDOPPLER:
+        raise _lib.ArgumentError(_lib.BLDP_EINVAL,
+                                 f"dedoppler: tavby={T} outside 2..2^20 (a block needs two spectra)")
+    seg = 0 if seg is None else int(seg)
+    if seg < 0:
+        raise _lib.ArgumentError(_lib.BLDP_EINVAL, f"dedoppler: seg={seg} is negative")
+    if nt % T:
+        raise _lib.DimensionMismatch(_lib.BLDP_EDIM,
+                                     f"DimensionMismatch: tavby={T} does not divide ntime={nt}")
+    return int(maxdrift), T, seg, (nc, ni, nt // T)
+
+
+def _dedop_outs(dims, K, device, sums):
+    """The outputs of a dedoppler and what the ABI takes for them: (result dict,
+    best pointer, drift pointer, sums pointer, ld_i, ld_t, ld_q)."""
+    torch = _torch()
+    res = {"best": fb_empty(*dims, device=device),
+           "drift": fb_empty(*dims, device=device, dtype=torch.int32)}
+    _, ld_i, ld_t = _out_layout(res["best"], dims, device, torch.float32, name="best")
+    sptr, ld_q = None, max(dims[0] * dims[1] * dims[2], 1)
+    if sums:
+        res["sums"] = planes_empty(*dims, K, device=device)
+        sptr, _, _, ld_q = _out_layout(res["sums"], dims, device, torch.float32, name="sums",
+                                       planes=K)
+    return res, _ptr(res["best"]), _ptr(res["drift"]), sptr, ld_i, ld_t, ld_q
+
+
+def dedoppler(x, maxdrift, tavby=None, seg=None, win=None, sums=False, stream=None):
+    """The drift-rate sums of every channel of the window (bldp_dedoppler_f32; the
+    rule of include/bldp.h): ``tavby`` spectra make a block (None: the whole
+    selected time range), drift d in -maxdrift .. maxdrift moves ``drift_offsets``'
+    off(d, t) selected channels at spectrum t of a block, and S[c, i, b, d] is the
+    Float32 sum of the block's samples along that path, added in time order; a
+    path takes no sample outside the segment of c (``seg`` channels each: the
+    coarse channels; None: the whole window).  x: a Float32 device filterbank
+    tensor.  Returns a dict of Julia-order device tensors: ``"best"`` (Float32,
+    (nc, ni, nb)), the greatest sum of every channel, ``"drift"`` (int32), the d
+    it belongs to (ties and a flat window give the drift nearest 0, the negative
+    one first), and with ``sums`` also ``"sums"`` ((nc, ni, nb, 2*maxdrift + 1),
+    plane d + maxdrift; laid out as ``planes_empty``).  ``sums`` is for zoom
+    windows: it is (2*maxdrift + 1) / tavby times the input.  Two calls give
+    identical bits."""
+    torch = _torch()
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
+        _need_f32("dedoppler", getattr(x, "dtype", type(x).__name__), "dedoppler")
+    shape, _ = _window(x, win)
+    D, T, seg, dims = _dedop_args(shape, win, maxdrift, tavby, seg)
+    w, keep = _win_args(x, win)
+    res, bptr, dptr, sptr, ld_i, ld_t, ld_q = _dedop_outs(dims, 2 * D + 1, x.device, sums)
+    rc = _lib.lib().bldp_dedoppler_f32(*w, T, D, seg, bptr, dptr, sptr, ld_i, ld_t, ld_q,
+                                       _lib.stream_ptr(stream))
+    _lib.check(rc, "bldp_dedoppler_f32")
+    return res
+
+
+def dedoppler_plan(x, maxdrift, tavby=None, seg=None, win=None) -> dict:
+    """Launch plan of ``dedoppler(x, maxdrift, tavby, seg, win)``
+    (bldp_dedoppler_plan_f32; launches nothing): ``path`` (_lib.DEDOPPLER_PATHS),
+    ``tile_channels`` (the lanes of a workgroup), ``halo`` channels staged on each
+    side, ``rows_per_chunk`` in LDS (resident: tavby), ``drifts_per_group`` a lane
+    sums at a time, ``groups``, ``lds_bytes``, ``workgroups`` per bank,
+    ``vector_loads`` (1: float4) and ``workspace_bytes`` (0)."""
+    shape, _ = _window(x, win)
+    D, T, seg, _ = _dedop_args(shape, win, maxdrift, tavby, seg)
+    w, keep = _win_args(x, win)
+    return _plan_dict("bldp_dedoppler_plan_f32", (*w, T, D, seg), 10, DEDOPPLER_PLAN_KEYS,
+                      path=_lib.DEDOPPLER_PATHS)
+
+
+def band_dedoppler(banks, maxdrift, tavby=None, seg=None, win=None, sums=False, stream=None):
+    """``dedoppler`` of every bank of a band resident on ONE GPU in one launch
+    (bldp_band_dedoppler_f32): dense (nbank*nc, ni, nb[, K]) tensors, the vcat of
+    the per-bank results.  Segments are counted from each bank's first selected
+    channel, so no path crosses from one bank into the next."""
+    banks, nb, ptrs, geo = _banks(banks, "band_dedoppler", "dedoppler", devices=True)
+    shape, _ = _window(banks[0], win)
+    D, T, seg, (nc, ni, nblk) = _dedop_args(shape, win, maxdrift, tavby, seg)
+    keep, wp = _win_ptr(win, shape)
+    res, bptr, dptr, sptr, _, _, _ = _dedop_outs((nb * nc, ni, nblk), 2 * D + 1, banks[0].device,
+                                                 sums)
+    rc = _lib.lib().bldp_band_dedoppler_f32(nb, ptrs, *geo, wp, T, D, seg, bptr, dptr, sptr,
+                                            _lib.stream_ptr(stream))
+    _lib.check(rc, "bldp_band_dedoppler_f32")
+    return res
+
+
+def dedoppler_host(a: np.ndarray, maxdrift, tavby=None, seg=None, win=None, sums=False,
+                   device=0) -> dict:
+    """Host Fortran-ordered Float32 array in, the dict of ``dedoppler`` as
+    Fortran-ordered host arrays out (bldp_dedoppler_host_f32: the window's rows
+    staged on ``device`` once)."""
+    a = _host_fb(a, "dedoppler_host", "dedoppler")
+    shape, _ = _window(a, win)
+    D, T, seg, dims = _dedop_args(shape, win, maxdrift, tavby, seg)
+    res = {"best": _host_out(dims), "drift": _host_out(dims, np.int32)}
+    if sums:
+        res["sums"] = _host_out((*dims, 2 * D + 1))
+    h, keep = _host_args(device, a, win)
+    rc = _lib.lib().bldp_dedoppler_host_f32(*h, T, D, seg, _np_ptr(res["best"]),
+                                            _np_ptr(res["drift"]), _np_ptr(res.get("sums")))
+    _lib.check(rc, "bldp_dedoppler_host_f32")
+    return res
 
 
 def stitch(gathered, nbank, out=None, stream=None):

@@ -204,6 +204,28 @@ def getflattened(workers, fnames, idxs=(COLON, COLON, COLON), *, nfpc=None, tavb
                                                axis=axis, nsigma=nsigma, device=int(w)))
 
 
+def getdedoppler(workers, fnames, idxs=(COLON, COLON, COLON), *, maxdrift, tavby=None, nfpc=None,
+                 despike=False, sums=False):
+    """getkurtosis' fan-out (src/gbt.jl:81-88) with the drift-rate sums of
+    WorkerFunctions.getdedoppler, bank by bank: per-bank dicts of ``"best"``,
+    ``"drift"`` and, with ``sums``, ``"sums"``.  No path leaves its coarse channel,
+    so the band's planes are the vcat of the banks'."""
+    return _fanout(workers, fnames,
+                   lambda w, f: W.getdedoppler(f, idxs, maxdrift=maxdrift, tavby=tavby, nfpc=nfpc,
+                                               despike=despike, sums=sums, device=int(w)))
+
+
+def getdrifthits(workers, fnames, idxs=(COLON, COLON, COLON), *, maxdrift, tavby=None, nfpc=None,
+                 n=None, nsigma=5.0, maxhits=None):
+    """The same fan-out with the search-and-list of WorkerFunctions.getdrifthits:
+    per-bank dicts of the hits of the best plane (``"total"``, ``"channel"``,
+    ``"if"``, ``"time"``, ``"value"``, ``"snr"``, ``"drift"``, ``"drift_rate"``) and the
+    ``"median"``, ``"mad"`` and ``"count"`` planes."""
+    return _fanout(workers, fnames,
+                   lambda w, f: W.getdrifthits(f, idxs, maxdrift=maxdrift, tavby=tavby, nfpc=nfpc,
+                                               n=n, nsigma=nsigma, maxhits=maxhits, device=int(w)))
+
+
 def _chan_window(idxs, nchans):
     """(start0, count, step) of the channel index (idxs[0]) over nchans."""
     from .idxs import JRange, is_colon, sanitizeidxs

@@ -18,7 +18,8 @@ export gpu_init, gpu_finalize, gpu_pin, gpu_unpin, gpu_fqav, gpu_reduce, gpu_kur
        gpu_outliers, gpu_outliers_plan, gpu_band_outliers,
        gpu_masked_reduce, gpu_band_masked_reduce, gpu_hits, gpu_band_hits,
        gpu_histogram, gpu_histogram_plan, gpu_band_histogram,
-       gpu_fold, gpu_fold_plan, gpu_band_fold, gpu_unfold, gpu_band_unfold
+       gpu_fold, gpu_fold_plan, gpu_band_fold, gpu_unfold, gpu_band_unfold,
+       gpu_dedoppler, gpu_dedoppler_plan, gpu_band_dedoppler
 
 const libbldp = get(ENV, "BLDP_LIB", joinpath(@__DIR__, "..", "libbldp_hip.so"))
 
@@ -1156,6 +1157,95 @@ function gpu_band_unfold(banks::Vector{Ptr{Float32}}, dims::NTuple{3,Integer}, n
          Ptr{Float32}, Int64, Int64, Ptr{Float32}, Ptr{Cvoid}),
         length(banks), banks, dims[1], dims[2], dims[3], win, nfpc, tavby, uop, prof, prof_ld[1],
         prof_ld[2], out, stream))
+    nothing
+end
+
+# ---- dedoppler: bldp_*dedoppler_* (the drift-rate sums of every channel) ----
+"""
+    gpu_dedoppler(A::Array{Float32,3}, maxdrift; tavby=nothing, seg=0, idxs=(:,:,:), dev=0,
+                  sums=false) -> (best, drift[, sums])
+
+The drift-rate sums of every channel of `A[idxs...]` on GPU `dev`
+(bldp_dedoppler_host_f32; the rule of include/bldp.h): `tavby` spectra make a block
+(`nothing`: the whole selected time range), drift d in `-maxdrift:maxdrift` moves
+`sign(d) * fld(2|d|t + T-1, 2(T-1))` selected channels at spectrum t of a block, and
+a sum adds the block's samples along that path in Float32, in time order, inside
+the segment of `seg` channels that holds the channel (`0`: the whole window).
+`best` is `Float32` `(nc, ni, nb)`, the greatest sum of every channel; `drift`
+`Int32`, the d it belongs to; with `sums=true` also the `(nc, ni, nb, 2maxdrift+1)`
+sums, plane `d + maxdrift + 1`."""
+function gpu_dedoppler(A::Array{Float32,3}, maxdrift::Integer; tavby=nothing, seg::Integer=0,
+                       idxs::Tuple=(:, :, :), dev::Integer=0, sums::Bool=false)
+    win = window(idxs, size(A))
+    T = tavby === nothing ? max(win[8], 1) : Int64(tavby)
+    T >= 2 || throw(ArgumentError("dedoppler: tavby=$T: a block needs two spectra"))
+    win[8] % T == 0 ||
+        throw(DimensionMismatch("tavby=$T does not divide ntime=$(win[8])"))
+    shp = (win[2], win[5], win[8] ÷ T)
+    best = Array{Float32,3}(undef, shp...)
+    drift = Array{Cint,3}(undef, shp...)
+    S = sums ? Array{Float32,4}(undef, shp..., 2 * maxdrift + 1) : nothing
+    sptr = sums ? pointer(S) : Ptr{Float32}(C_NULL)
+    GC.@preserve A win best drift S check(ccall((:bldp_dedoppler_host_f32, libbldp), Cint,
+        (Cint, Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Int64, Ptr{Float32},
+         Ptr{Cint}, Ptr{Float32}),
+        dev, A, size(A, 1), size(A, 2), size(A, 3), win, T, maxdrift, seg, best, drift, sptr))
+    sums ? (best, Int32.(drift), S) : (best, Int32.(drift))
+end
+
+"""
+    gpu_dedoppler(in::Ptr{Float32}, dims, tavby, maxdrift, best, drift, sums; seg=0,
+                  win=C_NULL, out_ld, stream=C_NULL)
+
+The same on DEVICE memory (bldp_dedoppler_f32; asynchronous on `stream`, one
+launch): element (c, i, b) of `best` and `drift` at `[c + i*out_ld[1] + b*out_ld[2]]`,
+plane k of `sums` at `+ k*out_ld[3]`.  `best` and `drift` go together; that pair or
+`sums` may be `C_NULL`, not both."""
+function gpu_dedoppler(in::Ptr{Float32}, dims::NTuple{3,Integer}, tavby::Integer,
+                       maxdrift::Integer, best::Ptr{Float32}, drift::Ptr{Cint},
+                       sums::Ptr{Float32}; seg::Integer=0, win=Ptr{Int64}(C_NULL),
+                       out_ld::NTuple{3,Integer}, stream::Ptr{Cvoid}=C_NULL)
+    GC.@preserve win check(ccall((:bldp_dedoppler_f32, libbldp), Cint,
+        (Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Int64, Ptr{Float32},
+         Ptr{Cint}, Ptr{Float32}, Int64, Int64, Int64, Ptr{Cvoid}),
+        in, dims[1], dims[2], dims[3], win, tavby, maxdrift, seg, best, drift, sums, out_ld[1],
+        out_ld[2], out_ld[3], stream))
+    nothing
+end
+
+"""
+    gpu_dedoppler_plan(dims, tavby, maxdrift; seg=0, win=C_NULL) -> NamedTuple
+
+The launch plan of `gpu_dedoppler` on aligned device memory
+(bldp_dedoppler_plan_f32; launches nothing and needs no GPU)."""
+function gpu_dedoppler_plan(dims::NTuple{3,Integer}, tavby::Integer, maxdrift::Integer;
+                            seg::Integer=0, win=Ptr{Int64}(C_NULL))
+    info = zeros(Int64, 10)
+    GC.@preserve win info check(ccall((:bldp_dedoppler_plan_f32, libbldp), Cint,
+        (Ptr{Float32}, Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Int64, Ptr{Int64}),
+        C_NULL, dims[1], dims[2], dims[3], win, tavby, maxdrift, seg, info))
+    (path = (:resident, :chunked)[info[1] + 1], tile_channels = info[2], halo = info[3],
+     rows_per_chunk = info[4], drifts_per_group = info[5], groups = info[6],
+     lds_bytes = info[7], workgroups = info[8], vector_loads = info[9] != 0,
+     workspace_bytes = info[10])
+end
+
+"""
+    gpu_band_dedoppler(banks::Vector{Ptr{Float32}}, dims, tavby, maxdrift, best, drift, sums;
+                       seg=0, win=C_NULL, stream=C_NULL)
+
+The dedoppler of every bank of a band resident on one GPU in one launch
+(bldp_band_dedoppler_f32): dense outputs, the vcat `(nbank*nc, ni, nb[, K])` of the
+banks'.  Segments are counted from each bank's first selected channel."""
+function gpu_band_dedoppler(banks::Vector{Ptr{Float32}}, dims::NTuple{3,Integer},
+                            tavby::Integer, maxdrift::Integer, best::Ptr{Float32},
+                            drift::Ptr{Cint}, sums::Ptr{Float32}; seg::Integer=0,
+                            win=Ptr{Int64}(C_NULL), stream::Ptr{Cvoid}=C_NULL)
+    GC.@preserve banks win check(ccall((:bldp_band_dedoppler_f32, libbldp), Cint,
+        (Cint, Ptr{Ptr{Float32}}, Int64, Int64, Int64, Ptr{Int64}, Int64, Int64, Int64,
+         Ptr{Float32}, Ptr{Cint}, Ptr{Float32}, Ptr{Cvoid}),
+        length(banks), banks, dims[1], dims[2], dims[3], win, tavby, maxdrift, seg, best, drift,
+        sums, stream))
     nothing
 end
 

@@ -1158,6 +1158,123 @@ def getflattened(src, idxs=(COLON, COLON, COLON), *, nfpc=None, tavby=None, how=
                         on_host, lambda r: {k: engine.fb_to_numpy(t) for k, t in r.items()})
 
 
+def _dedop_seg(src, nfpc, what):
+    """The segment length of a dedoppler: ``nfpc`` as ``_source_nfpc`` takes it, or
+    0 for the whole window as one segment."""
+    if nfpc is not None and not isinstance(nfpc, bool) and int(nfpc) == 0:
+        return 0
+    return _source_nfpc(src, nfpc, what)
+
+
+def _dense_window(x, win):
+    """The selected window of a device tensor as a dense Julia-order copy."""
+    if win is None:
+        return engine.fb_empty(*x.shape, device=x.device).copy_(x)
+    import torch
+
+    for ax in range(3):
+        st, ct, sp = win[3 * ax: 3 * ax + 3]
+        x = x.index_select(ax, st + sp * torch.arange(ct, device=x.device))
+    return engine.fb_empty(*x.shape, device=x.device).copy_(x)
+
+
+def _on_staged(on_device, device, to_host):
+    """``on_host`` of a composition: the host window staged whole on ``device`` so
+    that every step reads one device tensor."""
+    def on_host(a, win):
+        import torch
+
+        dev = f"cuda:{device}"
+        with torch.cuda.device(dev):
+            return to_host(on_device(engine.fb_from_numpy(a, device=dev), win))
+    return on_host
+
+
+def _planes_to_host(r):
+    return {k: engine.fb_to_numpy(t) if t.dim() == 3 else engine.planes_to_numpy(t)
+            for k, t in r.items()}
+
+
+def getdedoppler(src, idxs=(COLON, COLON, COLON), *, maxdrift, tavby=None, nfpc=None,
+                 despike=False, sums=False, device=0):
+    """The drift-rate sums of every channel of the window (engine.dedoppler; the
+    rule of include/bldp.h): a dict with ``"best"`` (Float32, (nc, ni, nb)), the
+    greatest sum over the drifts -maxdrift .. maxdrift of every channel and block
+    of ``tavby`` selected spectra (``None``: the whole selected time range),
+    ``"drift"`` (int32), the channels that path moves over a block, and with
+    ``sums`` ``"sums"`` ((nc, ni, nb, 2*maxdrift + 1); for zoom windows).  No path
+    leaves its coarse channel of ``nfpc`` selected channels: ``nfpc=None`` takes the
+    file header's (an array source must name it), ``nfpc=0`` makes the whole
+    window one segment.  ``despike=True`` first gives every coarse channel's DC bin
+    its left neighbour's value (engine.despike) on a device copy of the window.
+    Files reach the GPU as getdata reads them and a host array is staged there,
+    both returning host arrays; a device tensor stays on the device.  Float32 data
+    only."""
+    seg = _dedop_seg(src, nfpc, "getdedoppler")
+    if despike and seg < 1:
+        raise ValueError("getdedoppler: despike needs the coarse channels (nfpc >= 1)")
+    kw = dict(maxdrift=maxdrift, tavby=tavby, seg=seg, sums=sums)
+
+    def on_device(x, win):
+        if despike:
+            x, win = engine.despike(_dense_window(x, win), seg), None
+        return engine.dedoppler(x, win=win, **kw)
+
+    on_host = _on_staged(on_device, device, _planes_to_host) if despike else \
+        (lambda a, win: engine.dedoppler_host(a, win=win, device=device, **kw))
+    return _read_moment("getdedoppler", "dedoppler", src, sanitizeidxs(idxs), device, on_device,
+                        on_host, _planes_to_host)
+
+
+def getdrifthits(src, idxs=(COLON, COLON, COLON), *, maxdrift, tavby=None, nfpc=None, n=None,
+                 nsigma=5.0, maxhits=None, device=0):
+    """Search and list on the device: engine.dedoppler gives every channel's best
+    drift-rate sum, engine.outliers flags the channels of that plane that lie
+    ``nsigma`` scaled mads from the median of their block of ``n`` channels
+    (``None``: ``nfpc``, or the whole plane when ``nfpc=0``), and engine.hits lists
+    them; nothing but the list leaves the device.  gethits' dict over the (nc, ni,
+    nb) best plane (``"time"`` is the block) with ``"drift"`` (int32), each hit's
+    channels per block, and, when the source is a file, ``"drift_rate"`` in Hz/s
+    (engine.drift_rates with the header's foff, times the window's channel step,
+    and tsamp).  ``maxdrift``, ``tavby`` and ``nfpc`` as getdedoppler takes them."""
+    engine._outliers_args(0, nsigma, engine.OUTLIER_PLANES)  # (errors first)
+    cap = engine._hits_cap(maxhits)
+    seg = _dedop_seg(src, nfpc, "getdrifthits")
+    idxs = sanitizeidxs(idxs)
+    hdr = None
+    if isinstance(src, (str, bytes)) or hasattr(src, "__fspath__"):
+        hdr = readers.getheader(src)
+
+    def on_device(x, win):
+        d = engine.dedoppler(x, maxdrift, tavby, seg, win=win)
+        best = d["best"]
+        nb = engine._outliers_n(n if n is not None else (seg or best.shape[0]), 0, best.shape[0],
+                                best.shape[2])
+        o = engine.outliers(best, n=nb, axis=0, nsigma=nsigma, mask=True)
+        h = _hits_coords(engine.hits(best, o["mask"], maxhits=cap), tuple(best.shape))
+        c, i, t = h["channel"], h["if"], h["time"]
+        h["snr"] = engine.hits_snr(h["value"], o["median"][c // nb, i, t], o["mad"][c // nb, i, t])
+        h["drift"] = d["drift"][c, i, t]
+        if hdr is not None:
+            T = x.shape[2] if tavby is None and win is None else \
+                (engine.window_shape(win, x.shape)[2] if tavby is None else int(tavby))
+            step = idxs[0].step if hasattr(idxs[0], "step") and idxs[0].step else 1
+            rates = engine.drift_rates(maxdrift, T, float(hdr["foff"]) * step, hdr["tsamp"])
+            h["drift_rate"] = _torch_from(rates, x.device)[h["drift"].long() + int(maxdrift)]
+        del h["index"]
+        h.update(median=o["median"], mad=o["mad"], count=o["count"])
+        return h
+
+    return _read_moment("getdrifthits", "getdrifthits", src, idxs, device, on_device,
+                        _on_staged(on_device, device, _hits_to_host), _hits_to_host)
+
+
+def _torch_from(a, device):
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(a)).to(device)
+
+
 getinventory = readers.getinventory
 getfbheader = readers.getfbheader
 getfbh5header = readers.getfbh5header

@@ -96,7 +96,8 @@ extern "C" {
  *    (additive, same version) the bldp_*masked_reduce_* entry points;
  *    (additive, same version) the bldp_*histogram_* entry points;
  *    (additive, same version) the bldp_*hits_* entry points;
- *    (additive, same version) the bldp_*fold_* and bldp_*unfold_* entry points */
+ *    (additive, same version) the bldp_*fold_* and bldp_*unfold_* entry points;
+ *    (additive, same version) the bldp_*dedoppler_* entry points */
 #define BLDP_ABI_VERSION 5
 
 #if defined(BLDP_BUILD)
@@ -1141,6 +1142,83 @@ BLDP_API int bldp_band_unfold_f32(int nbank, const float *const *in, int64_t nch
 BLDP_API int bldp_unfold_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
                                   int64_t ntime, const int64_t *win, int64_t nfpc, int64_t tavby,
                                   int uop, const float *prof, float *out);
+
+/* ---- dedoppler: the drift-rate sums of every channel ------------------------
+ * A narrow-band signal that moves d channels while a block of T spectra is
+ * recorded is in no single spectrum and not in the sum along a channel; it is in
+ * the sum along the sloped path.  Float32 input; additive in ABI 5.
+ *
+ * The rule, on the selected window W of shape (nc, ni, nt) (after the window's
+ * offsets, steps and direction, as every block operation takes it): T = tavby
+ * spectra make a block, nb = nt / T; D = maxdrift >= 0 gives K = 2D + 1 drifts
+ * d_k = k - D, k = 0 .. 2D, the selected channels moved between the first and the
+ * last spectrum of a block.
+ *  - Path, in integers: off(d, t) = sign(d) * floor((2|d|t + (T-1)) / (2(T-1))),
+ *    the straight line rounded to the nearest channel, halves away from zero.
+ *    off(d, 0) = 0, off(d, T-1) = d, off(-d, t) = -off(d, t); two drifts never
+ *    share a whole path.  off(5, t) at T = 16: 0 0 1 1 1 2 2 2 3 3 3 4 4 4 5 5.
+ *  - Segments: seg > 0 is the number of selected channels of a coarse channel (it
+ *    need not divide nc); selected channel c lies in segment c div seg, and a path
+ *    takes no sample outside the segment of c.  seg = 0: the whole window is one
+ *    segment.  A band is then the vcat of its banks.
+ *  - Sum: S[c, i, b, k] = sum over t of W[c + off(d_k, t), i, b*T + t], added in
+ *    Float32 in the order t = 0 .. T-1 from +0.0f; a term whose channel lies
+ *    outside the segment (or the window) is skipped.  The order is fixed: the
+ *    result is a function of the input alone, bit for bit, on any data.
+ *  - Best: best[c, i, b] and drift[c, i, b] (the signed d) come from scanning the
+ *    drifts in the order 0, -1, +1, -2, +2, ..., -D, +D with BLDP_ARG_MAX's rule:
+ *    the first NaN in scan order wins, with its payload; otherwise the first in
+ *    scan order among the isless-greatest.  A flat window answers drift = 0.
+ *
+ * Outputs: best (Float32) and drift (Int32: a C int), (nc, ni, nb), element (c, i, b) at
+ * [c + out_ld_i*i + out_ld_t*b]; sums, (nc, ni, nb, K), plane k at + out_ld_q*k
+ * (bldp_quantiles_f32's layout).  best and drift go together; that pair or sums
+ * may be NULL, not both, and a plane that is not asked for is not written.  sums
+ * is for zoom windows: at a whole high-resolution bank (16 spectra) it is K / 16
+ * times the input.
+ *
+ * BLDP_EINVAL: tavby < 2, tavby > 2^20, maxdrift < 0 or > BLDP_MAX_DRIFT (within
+ * these the path arithmetic fits 32 bits), seg < 0, outputs that overlap the
+ * input window or each other, strides that overlap; BLDP_EDIM: tavby does not
+ * divide the selected nt; BLDP_EBOUNDS as in the reduce.  Nothing is launched
+ * then.  Every (tavby, maxdrift) inside the caps runs.
+ *
+ * A workgroup takes a tile of neighbouring channels of one (IF, block), a lane a
+ * channel, with the tile's rows and a halo of maxdrift channels on each side in
+ * LDS; a lane keeps a group of drifts' sums and its running best in registers and
+ * loops over the groups, so best needs no second launch, no atomics and no
+ * workspace.  "resident": the block's rows are staged once.  "chunked" (long
+ * tavby, or large maxdrift, against the LDS): the rows are staged a chunk at a
+ * time and read again for every group.  Both add in the rule's order.
+ *
+ * bldp_dedoppler_plan_f32: info = {path (0 resident, 1 chunked), channels per
+ * tile, halo channels staged on each side, rows per staging chunk, drifts per
+ * group, groups, LDS bytes, workgroups per bank, vector loads 1 / 0, workspace
+ * bytes (0)}.  Launches nothing and needs no GPU; `in` may be null (a null
+ * pointer counts as aligned).
+ * bldp_dedoppler_f32: device pointers, asynchronous on `stream`, one launch.
+ * bldp_band_dedoppler_f32: host array of device pointers to banks of identical
+ * geometry; dense outputs, the vcat of the banks' (bank b's channels at b*nc of
+ * every row; sums (nbank*nc, ni, nb, K)); one launch.  Segments are counted from
+ * each bank's first selected channel.
+ * bldp_dedoppler_host_f32: host in, host dense outs; the window's rows are staged
+ * on device `dev` once.  Synchronous. */
+#define BLDP_MAX_DRIFT 1024
+BLDP_API int bldp_dedoppler_plan_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                                     const int64_t *win, int64_t tavby, int64_t maxdrift,
+                                     int64_t seg, int64_t info[10]);
+BLDP_API int bldp_dedoppler_f32(const float *in, int64_t nchan, int64_t nif, int64_t ntime,
+                                const int64_t *win, int64_t tavby, int64_t maxdrift, int64_t seg,
+                                float *best, int *drift, float *sums, int64_t out_ld_i,
+                                int64_t out_ld_t, int64_t out_ld_q, void *stream);
+BLDP_API int bldp_band_dedoppler_f32(int nbank, const float *const *in, int64_t nchan,
+                                     int64_t nif, int64_t ntime, const int64_t *win,
+                                     int64_t tavby, int64_t maxdrift, int64_t seg, float *best,
+                                     int *drift, float *sums, void *stream);
+BLDP_API int bldp_dedoppler_host_f32(int dev, const float *in, int64_t nchan, int64_t nif,
+                                     int64_t ntime, const int64_t *win, int64_t tavby,
+                                     int64_t maxdrift, int64_t seg, float *best, int *drift,
+                                     float *sums);
 
 /* Element types other than Float32 (what Blio maps SIGPROC nbits 8 / 16 to, and
  * what HDF5.jl returns for an integer or Float64 dataset: the reference's
