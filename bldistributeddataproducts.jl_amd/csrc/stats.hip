@@ -280,10 +280,16 @@ __device__ __forceinline__ uint32_t f2key(float x) {
 __device__ __forceinline__ float key2f(uint32_t k) {
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
-// Statistics.middle(a, b) = a/2 + b/2 (no overflow next to floatmax), two
-// roundings: no fused multiply-add
+// Statistics.middle(a, b) = a/2 + b/2 (no overflow next to floatmax), each half
+// rounded before the sum.  The products must not be contracted into a fused
+// multiply-add (tstats.hip middle): half a subnormal, or a normal below 2^-125,
+// with an odd significand is inexact, and fma(a, 0.5, b/2) keeps the exact
+// half.  hipcc contracts by default, __fmul_rn or not: the sort and select
+// kernels here held v_fmac_f32 v, 0.5, v before the pragma.
 __device__ __forceinline__ float middle(float x, float y) {
-  return __fadd_rn(__fmul_rn(x, 0.5f), __fmul_rn(y, 0.5f));
+#pragma clang fp contract(off)
+  const float hx = x * 0.5f, hy = y * 0.5f;
+  return hx + hy;
 }
 // Ranks (F-1)/2 and F/2 of a block of F: the element itself for odd F, else
 // middle() even of two equal values (a/2 + a/2 is not a for a subnormal with
